@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- variational-loss iterations/sec of the hp-VPINN hot path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One step = one full training iteration of BASELINE.json config 4 (Poisson-2D, 16x16 elements, 20x20 GLL points and
 10x10 test functions per element, MLP [2,20,20,20,1] tanh, var_form 1): Taylor-mode MLP forward at all 102 400
@@ -9,16 +9,27 @@ quadrature points, per-element projection + residual, adjoint, reverse pass, bou
 update.  Inputs are synthetic of that shape (the driver's exact right-hand side, seeded boundary points, seeded Xavier
 init) and are resident in HBM before the timed region.
 
-N > 1: `python bench.py --gpus N` re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (when it
-is not already running under it), one rank per GPU; the 256 elements shard over the ranks (strong scaling: total work
-fixed) with ONE RCCL all-reduce of the packed gradient/loss buffer per step, issued by the library inside its
+N > 1: `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N` on itself as a child process
+(when it is not already running under it), one rank per GPU; the 256 elements shard over the ranks (strong scaling: total
+work fixed) with ONE RCCL all-reduce of the packed gradient/loss buffer per step, issued by the library inside its
 iteration graphs.
 
 Timing: W untimed warm-up steps, one untimed window of K steps (captures the iteration graphs for exactly this K), further
 untimed windows until at least 0.3 s of iterations have run (clocks ramp for the first few hundred microseconds-long
-iterations: a `--steps 20` window is 1.3 ms), then 5 windows of EXACTLY K steps each -- 25 when a window is shorter than
-20 ms -- every window bracketed by barrier + synchronize on both sides and reduced with MAX over ranks; `value` = K / median
-window, min / max / all windows are in `timing`.  Rank 0 prints ONE JSON line (contract: DESIGN.md section 6).
+iterations: a `--steps 20` window is 1.3 ms).  Then the parameters are reset to the seeded initial ones with a fresh
+optimizer, and ONE window of exactly K steps is timed, bracketed by barrier + synchronize on both sides and reduced with MAX
+over ranks: `value` = K / that window, `ms_per_step` = window / K.  Rank 0 prints ONE JSON line (contract: DESIGN.md
+section 6).
+
+--dump-outputs DIR: after the timed window, rank 0 writes what its K steps computed -- the parameters (`params.npy`, the
+layout `get_params()` returns) and the whole optimizer state (`optimizer_state.npy`: parameters, Adam moments, beta
+powers, as `save_checkpoint` stores them) -- in float64.  Because the timed steps start from the seeded initial state,
+two runs with the same arguments compute the same K iterations from the same inputs.
+
+--full: everything beside the headline figure, after the timed window: more windows of K steps (5 in all, 25 when a
+window is shorter than 20 ms; min / max / median in `timing`), per-kernel device times and the roofline of the dominant
+kernel (traffic from two rocprofv3 --pmc passes of a child run), the collective alone, the L2-error tail, the scaled
+problems, the stand-alone residual kernel's roofline and the CPU baselines.  The `--no-*` options drop parts of it.
 """
 import argparse
 import json
@@ -165,6 +176,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--backend", default="auto")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters and optimizer state after the timed steps as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (more windows, kernel times and roofline, L2 error, "
+                         "scaled problems, residual roofline, CPU baselines); the --no-* options below apply to it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-residual-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the L2-error tail, the scaled problems and the alternative exchange")
@@ -178,11 +194,14 @@ def main():
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        # the driver's plain `python bench.py --gpus N`: become N ranks, one per GPU, over RCCL
+        # the driver's plain `python bench.py --gpus N`: N ranks, one per GPU, over RCCL, in child processes of a launcher
+        # (this process never touches a GPU; it waits and passes the launcher's exit status on)
+        import subprocess
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                   "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)]
-                  + sys.argv[1:])
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)]
+                             + sys.argv[1:])
+        sys.exit(rc)
 
     import torch
     rank = int(os.environ.get("RANK", 0))
@@ -243,8 +262,8 @@ def main():
         barrier(m)
         return max_over_ranks(time.perf_counter() - t0)
 
-    def timed_windows(m, warmup, steps, windows=None):
-        """-> (list of window times (s), MAX over ranks each; untimed warm-up iterations actually run)."""
+    def warm_up(m, warmup, steps):
+        """-> (time of one window of `steps` iterations (s), MAX over ranks; untimed warm-up iterations actually run)."""
         m.prepare(warmup, steps)      # torch-collective fallback: communicator warm-up + graph capture outside the timed region
         m._step(warmup, False)
         m._step(steps, False)         # untimed: captures the graphs this K needs (whole replays + one remainder graph)
@@ -253,22 +272,88 @@ def main():
         n_more = int(min(4000, max(0, np.ceil(WARM_WALL_S / max(t1, 1e-6)) - 1)))
         for _ in range(n_more):
             m._step(steps, False)
-        n_warm = warmup + (2 + n_more) * steps
-        if windows is None:
-            windows = N_WINDOWS if t1 >= SHORT_WINDOW_S else 5 * N_WINDOWS
-        return [one_window(m, steps) for _ in range(windows)], n_warm
+        return t1, warmup + (2 + n_more) * steps
+
+    def n_windows(t1):
+        return N_WINDOWS if t1 >= SHORT_WINDOW_S else 5 * N_WINDOWS
+
+    def timed_windows(m, warmup, steps, windows=None):
+        """-> (list of window times (s), MAX over ranks each; untimed warm-up iterations actually run)."""
+        t1, n_warm = warm_up(m, warmup, steps)
+        return [one_window(m, steps) for _ in range(windows or n_windows(t1))], n_warm
+
+    def dump_outputs(m, d):
+        """What the timed steps computed, as a caller of the iteration receives it: parameters and optimizer state."""
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "params.npy"), np.asarray(m.get_params(), dtype=np.float64))
+        np.save(os.path.join(d, "optimizer_state.npy"), np.asarray(m.h.get_state(), dtype=np.float64))
 
     model = poisson2d.build_model(s, LAYERS, var_form=1, init_params=theta, backend=args.backend, device=local_rank)
     if args.traffic_child:      # (under rocprofv3 --pmc: 64 iterations of the same model through the same graphs, nothing else)
         model._step(64, False)
         model.h.sync()
         return
-    wins, n_warm = timed_windows(model, args.warmup, args.steps)
-    dt = _median(wins)
-    n_its_done = n_warm + len(wins) * args.steps
+    t1, n_warm = warm_up(model, args.warmup, args.steps)
+    # the timed steps start from the seeded initial parameters with a fresh optimizer (set_params writes the same device buffers:
+    # the captured graphs stay valid), so that what they compute does not depend on how much warm-up the wall clock asked for
+    model.set_params(theta)
+    wins = [one_window(model, args.steps)]
+    dt = wins[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+    n_its_done = args.steps       # Adam iterations since the seeded start
     structure = model.h.pass_structure()      # which launch structure the timed iterations ran (SPLIT vs the split reverse kernels ...)
     variant = model.h.kernel_variant()        # ... and which kernel instantiation (quarter-tile plan or whole tiles, split factor)
     graphs = model.h.graphs_in_use() if not model._coll else bool(model._dist_graphs.get(min(args.steps, 8) if args.steps <= 16 else 8))
+    exchange = model.exchange() if world > 1 or dist is not None else "none"
+    rccl_world = None
+    if exchange == "rccl":
+        try:
+            rccl_world = model.h.rccl_info()[0]       # (ncclCommCount of the library's own communicator)
+        except Exception:  # noqa: BLE001 -- an evidence field: never take the headline line down
+            pass
+    per_rank = [{"rank": rank, "pass_structure": structure, "kernel_variant": variant, "graphs": bool(graphs), "exchange": exchange,
+                 "rccl_world": rccl_world, "device": local_rank,
+                 "elements": list(shard_range(model.Nelementx * model.Nelementy, rank, world))}]
+    out = {
+        "metric": "variational-loss iterations/sec", "value": args.steps / dt, "unit": "it/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "Poisson-2D hp-VPINN, 16x16 elements, 20x20 GLL quad/elem, 10x10 test fcns/elem, "
+                               "MLP [2,20,20,20,1] tanh, var_form 1, 320 boundary pts, TF1 Adam (BASELINE config 4)",
+                   "points": 102400, "residuals": 25600, "params": 921, "backend": model.backend(),
+                   "parallelism": "element-sharded dp%d" % world,
+                   "exchange": {"rccl": "in-library ncclAllReduce of the packed buffer, " +
+                                        ("captured in the iteration graphs" if graphs else
+                                         "EAGER launches (RCCL refused stream capture: no iteration graphs)"),
+                                "p2p": "in-library peer-mapped mailboxes over xGMI", "torch": "torch.distributed all_reduce (RCCL)",
+                                "none": "none"}[exchange],
+                   "rccl_world": rccl_world,
+                   "pass_structure": structure, "kernel_variant": variant, "build": model.h.build_info(), "per_rank": per_rank},
+        "timing": {"windows": 1, "untimed_warmup_iterations": n_warm,
+                   "value_is": "steps / ONE window of exactly `steps` iterations from the seeded initial state between "
+                               "barrier+synchronize, MAX over ranks (%.1f ms)" % (1e3 * dt)},
+    }
+    if not args.full:
+        if dist is not None:
+            allr = [None] * world
+            dist.all_gather_object(allr, per_rank[0])
+            out["config"]["per_rank"] = allr
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ================================ --full: everything beside the headline figure ================================
+    wins += [one_window(model, args.steps) for _ in range(n_windows(t1) - 1)]
+    n_its_done += (len(wins) - 1) * args.steps
+    out["timing"] = {"windows": len(wins), "window_it_per_s": [round(args.steps / w, 1) for w in wins],
+                     "min_it_per_s": args.steps / max(wins), "max_it_per_s": args.steps / min(wins),
+                     "median_it_per_s": args.steps / _median(wins), "untimed_warmup_iterations": n_warm,
+                     "value_is": "steps / the FIRST window (the timed one of the plain run); %d windows of exactly `steps` iterations "
+                                 "each between barrier+synchronize, MAX over ranks, because one window lasts %.1f ms"
+                                 % (len(wins), 1e3 * t1)}
 
     # ---- per-kernel device times (hipEvents on the stream the kernels run on), untimed extra pass ----
     nt = min(args.steps, 100)
@@ -320,13 +405,12 @@ def main():
                   "loss": min(best_loss, last_loss), "loss_last_iterate": last_loss,
                   "note": "seeded Xavier start (1234), Adam lr 1e-3; value = the lowest-loss checkpoint of the last 10 000 iterations "
                           "(tests/test_gpu_convergence.py asserts <= 1e-2 for it)"}
-    exchange = model.exchange() if world > 1 or dist is not None else "none"
-    # what the library's communicator ITSELF reports (ncclCommCount) and what its all-reduce of the packed buffer costs alone
-    # (200 eager calls between one hipEvent pair, collective): the 10-20 us DESIGN.md 7 assumes for 8 ranks becomes a measured field
-    rccl_world, collective_us = None, None
+    # what the library's communicator's all-reduce of the packed buffer costs alone (200 eager calls between one hipEvent pair,
+    # collective; rccl_world above = what the communicator ITSELF reports): the 10-20 us DESIGN.md 7 assumes for 8 ranks becomes a
+    # measured field
+    collective_us = None
     if exchange == "rccl":
         try:
-            rccl_world = model.h.rccl_info()[0]
             collective_us = model.h.rccl_time_allreduce(200)
         except Exception as e:  # noqa: BLE001 -- evidence fields: never take the headline line down
             collective_us = "failed: %s" % str(e)[:120]
@@ -383,9 +467,7 @@ def main():
             finally:
                 os.environ.pop("HPV_EXCHANGE", None)
 
-    per_rank = [{"rank": rank, "pass_structure": structure, "kernel_variant": variant, "graphs": bool(graphs), "exchange": exchange,
-                 "rccl_world": rccl_world, "collective_us": collective_us, "device": local_rank,
-                 "elements": list(shard_range(model.Nelementx * model.Nelementy, rank, world))}]
+    per_rank[0]["collective_us"] = collective_us
     if dist is not None:
         allr = [None] * world
         dist.all_gather_object(allr, per_rank[0])
@@ -434,31 +516,14 @@ def main():
                 "flops_per_launch": fl, "avg_ms": ms, "timer": kernel_timer if k == dom else "one hipEvent pair per launch"}
     # whole-iteration algorithmic HBM bytes (fused ideal): coordinates in, F in, Adam state in/out
     ideal_bytes = 8 * (2 * N_local + n_elem_local * 100 + 7 * 921)
-    out = {
-        "metric": "variational-loss iterations/sec", "value": args.steps / dt, "unit": "it/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "Poisson-2D hp-VPINN, 16x16 elements, 20x20 GLL quad/elem, 10x10 test fcns/elem, "
-                               "MLP [2,20,20,20,1] tanh, var_form 1, 320 boundary pts, TF1 Adam (BASELINE config 4)",
-                   "points": 102400, "residuals": 25600, "params": 921, "backend": model.backend(),
-                   "parallelism": "element-sharded dp%d" % world,
-                   "exchange": {"rccl": "in-library ncclAllReduce of the packed buffer, " +
-                                        ("captured in the iteration graphs" if graphs else
-                                         "EAGER launches (RCCL refused stream capture: no iteration graphs)"),
-                                "p2p": "in-library peer-mapped mailboxes over xGMI", "torch": "torch.distributed all_reduce (RCCL)",
-                                "none": "none"}[exchange],
-                   "rccl_world": rccl_world,
-                   "collective_us": (max(r["collective_us"] for r in per_rank)
-                                     if all(isinstance(r.get("collective_us"), float) for r in per_rank) else collective_us),
-                   "collective_note": "rccl_world = ncclCommCount of the library's own communicator; collective_us = ONE all-reduce of the "
-                                      "packed buffer (P + 4 doubles) alone, eager, 200 calls between one hipEvent pair, MAX over ranks; "
-                                      "null when the exchange is not the in-library RCCL one",
-                   "pass_structure": structure, "kernel_variant": variant, "build": model.h.build_info(), "per_rank": per_rank},
-        "timing": {"windows": len(wins), "window_it_per_s": [round(args.steps / w, 1) for w in wins],
-                   "min_it_per_s": args.steps / max(wins), "max_it_per_s": args.steps / min(wins),
-                   "untimed_warmup_iterations": n_warm,
-                   "value_is": "steps / median window; every window = exactly `steps` iterations between barrier+synchronize; "
-                               "%d windows because one window lasts %.1f ms" % (len(wins), 1e3 * dt)},
+    out["config"].update({
+        "per_rank": per_rank,
+        "collective_us": (max(r["collective_us"] for r in per_rank)
+                          if all(isinstance(r.get("collective_us"), float) for r in per_rank) else collective_us),
+        "collective_note": "rccl_world = ncclCommCount of the library's own communicator; collective_us = ONE all-reduce of the "
+                           "packed buffer (P + 4 doubles) alone, eager, 200 calls between one hipEvent pair, MAX over ranks; "
+                           "null when the exchange is not the in-library RCCL one"})
+    out.update({
         "loss_after": float(loss3[0]),
         "rel_l2_error": rel_l2,
         "kernel_ms": ktime, "kernel_ms_per_launch_events": ktime_per_launch_events, "kernel_timer": kernel_timer,
@@ -468,7 +533,7 @@ def main():
                               "78.6 TFLOP/s fp64 peak; the tangent pre-activations the kernel recomputes in its reverse phase "
                               "(+2/9 of the layer products) are NOT counted; traffic = PMC HBM bytes per launch "
                               "(profiles/traffic.json) against algorithmic_hbm_bytes_per_iteration = 8 (d N + N_R + 7 P)"),
-    }
+    })
     for k in kernels:
         if k != dom:
             out["roofline_other_kernel"] = roof(k)

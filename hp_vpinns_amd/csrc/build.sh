@@ -179,7 +179,7 @@ compile_one() {   # compile_one <source stem> <object> <extra flags>
 
 # job pool: at most NJ compilers at a time (27 at once on 8 cores cost 30 % more CPU time than 8 at a time), longest jobs first;
 # a job that fails leaves a marker (wait -n consumes exit statuses)
-NJ=${HPV_BUILD_JOBS:-$(nproc)}
+NJ=${HPV_BUILD_JOBS:-${MAX_JOBS:-$(nproc)}}
 rm -f .fail_*
 spawn() {   # spawn <object name> <command...>
   local name=$1; shift

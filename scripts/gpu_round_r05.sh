@@ -10,8 +10,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 REPO=$PWD
 if [ -n "$2" ]; then python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log; fi
-python bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-300 $OUT/bench.json
-python bench.py --steps 20 --warmup 5 2> $OUT/bench_driver_style.err | tail -1 > $OUT/bench_driver_style.json; cut -c1-200 $OUT/bench_driver_style.json
+python bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-300 $OUT/bench.json
+python bench.py --steps 20 --warmup 5 --full 2> $OUT/bench_driver_style.err | tail -1 > $OUT/bench_driver_style.json; cut -c1-200 $OUT/bench_driver_style.json
 cd /tmp
 BENCH="python $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-residual-roofline --no-extras --no-pmc"
 C5="python $REPO/scripts/cfg5_quick.py 200"

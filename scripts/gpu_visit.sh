@@ -6,8 +6,8 @@
 #   suite            pytest -m gpu (whole suite, per-test durations)
 #   pytest:<expr>    pytest -m gpu -k <expr>  (whole tests/ directory)
 #   file:<name>      pytest -m gpu tests/<name>
-#   bench            python bench.py  (default K / W)
-#   bench_driver     python bench.py --steps 20 --warmup 5  (the driver's call, timed)
+#   bench            python bench.py --full  (default K / W)
+#   bench_driver     python bench.py --steps 20 --warmup 5 --full  (the driver's call, timed)
 #   prof             rocprofv3 --kernel-trace --stats of the default bench (no extras) -> <out>/prof
 #   configs          scripts/config_bench.py (the five BASELINE configs)
 #   elems            scripts/elem_bench.py (other element shapes / forms)
@@ -25,8 +25,8 @@ for step in "$@"; do
     suite) timeout $T python -m pytest tests -m gpu -q --durations=60 > $OUT/pytest_gpu.log 2>&1; tail -8 $OUT/pytest_gpu.log ;;
     pytest:*) timeout $T python -m pytest tests -m gpu -q -x -k "${step#pytest:}" > $OUT/pytest_k.log 2>&1; tail -15 $OUT/pytest_k.log ;;
     file:*) n=${step#file:}; timeout $T python -m pytest tests/$n -m gpu -q --durations=15 > $OUT/pytest_${n%.py}.log 2>&1; tail -15 $OUT/pytest_${n%.py}.log ;;
-    bench) timeout $T python bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-400 $OUT/bench.json ;;
-    bench_driver) ( time timeout $T python bench.py --steps 20 --warmup 5 2> $OUT/bench_driver_style.err | tail -1 > $OUT/bench_driver_style.json ) 2> $OUT/bench_driver_style.time
+    bench) timeout $T python bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-400 $OUT/bench.json ;;
+    bench_driver) ( time timeout $T python bench.py --steps 20 --warmup 5 --full 2> $OUT/bench_driver_style.err | tail -1 > $OUT/bench_driver_style.json ) 2> $OUT/bench_driver_style.time
                   cut -c1-300 $OUT/bench_driver_style.json; cat $OUT/bench_driver_style.time ;;
     prof) ( cd /tmp && timeout $T rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $OLDPWD/bench.py --no-extras --no-cpu-baseline --no-residual-roofline --no-pmc > $OUT/prof_bench.json 2> $OUT/prof.err )
           f=$(find $OUT/prof -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && head -8 "$f" ;;

@@ -1,10 +1,12 @@
 """bench.py as the driver runs it: a subprocess, ONE parseable JSON line on stdout.
 
-  * `python bench.py --gpus 2 ...` on a one-GPU box (HPV_BENCH_ONE_GPU=1: both ranks on cuda:0, gloo group, mailbox exchange):
-    the self-re-exec under torch.distributed.run -> N ranks -> sharded model -> timed windows -> per-rank gather -> one line
-    path that the 8-GPU SCALE run depends on (the throughput of two processes sharing a GPU is meaningless and not asserted);
-  * the driver-style single-GPU call `--steps 20 --warmup 5`: short windows must be timed 25 times after a wall-clock warm-up
-    and the line must carry `roofline` and `cpu_baseline`.
+  * `python bench.py --gpus 2 --full ...` on a one-GPU box (HPV_BENCH_ONE_GPU=1: both ranks on cuda:0, gloo group, mailbox
+    exchange): the self-launch under torch.distributed.run -> N ranks -> sharded model -> timed windows -> per-rank gather -> one
+    line path that the 8-GPU SCALE run depends on (the throughput of two processes sharing a GPU is meaningless and not asserted);
+  * the driver-style single-GPU call `--steps 20 --warmup 5 --full`: short windows must be timed 25 times after a wall-clock
+    warm-up and the line must carry `roofline` and `cpu_baseline`;
+  * the plain call `--steps K --warmup W --dump-outputs DIR`: ONE timed window of exactly K steps, the headline fields only, and
+    the dumped parameters / optimizer state are those of K iterations from the seeded initial state.
 """
 import json
 import os
@@ -33,7 +35,7 @@ def _run_bench(args, extra_env=None, timeout=900):
 
 
 def test_bench_two_ranks_self_launch_on_one_gpu():
-    out = _run_bench(["--gpus", "2", "--steps", "16", "--warmup", "8", "--l2-iters", "600"], {"HPV_BENCH_ONE_GPU": "1"})
+    out = _run_bench(["--gpus", "2", "--steps", "16", "--warmup", "8", "--l2-iters", "600", "--full"], {"HPV_BENCH_ONE_GPU": "1"})
     assert out["n_gpus"] == 2 and out["steps"] == 16 and out["warmup"] == 8
     assert out["metric"].startswith("variational-loss iterations/sec") and out["unit"] == "it/s" and out["value"] > 0
     assert out["scaling"] == "strong" and out["dtype"] == "f64" and out["higher_is_better"] is True
@@ -49,9 +51,9 @@ def test_bench_two_ranks_self_launch_on_one_gpu():
 
 def test_bench_eight_ranks_self_launch_on_one_gpu():
     """The SCALE run's N = 8 call walked end to end on this one-GPU box (verdict round 5, item 1b): `python bench.py --gpus 8`
-    re-execs itself under torch.distributed.run, eight ranks own 32-element shards of config 4 (gloo group + mailbox exchange: RCCL
+    launches itself under torch.distributed.run, eight ranks own 32-element shards of config 4 (gloo group + mailbox exchange: RCCL
     refuses eight ranks on one device), the line gathers eight per-rank records and both scaled probes at N = 8."""
-    out = _run_bench(["--gpus", "8", "--steps", "16", "--warmup", "8", "--l2-iters", "400"], {"HPV_BENCH_ONE_GPU": "1"}, timeout=1500)
+    out = _run_bench(["--gpus", "8", "--steps", "16", "--warmup", "8", "--l2-iters", "400", "--full"], {"HPV_BENCH_ONE_GPU": "1"}, timeout=1500)
     assert out["n_gpus"] == 8 and out["steps"] == 16 and out["value"] > 0 and out["scaling"] == "strong"
     cfg = out["config"]
     assert cfg["parallelism"] == "element-sharded dp8" and len(cfg["per_rank"]) == 8
@@ -66,7 +68,8 @@ def test_bench_eight_ranks_self_launch_on_one_gpu():
 
 
 def test_bench_driver_style_single_gpu_line():
-    out = _run_bench(["--steps", "20", "--warmup", "5", "--l2-iters", "2000", "--residual-elems", "16384", "--cpu-iters", "1"])
+    out = _run_bench(["--steps", "20", "--warmup", "5", "--l2-iters", "2000", "--residual-elems", "16384", "--cpu-iters", "1",
+                      "--full"])
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["config"]["pass_structure"] == "whole-iteration"
     bi = out["config"]["build"]
     assert bi["test_hooks"] == "0" and bi["k_iter_fused"] in ("ok", "no-quarter-tile")
@@ -109,7 +112,8 @@ def test_bench_default_rccl_exchange_with_a_one_rank_group():
     sk.bind(("127.0.0.1", 0))
     port = sk.getsockname()[1]
     sk.close()
-    out = _run_bench(["--steps", "16", "--warmup", "8", "--l2-iters", "600", "--no-cpu-baseline", "--no-residual-roofline", "--no-pmc"],
+    out = _run_bench(["--steps", "16", "--warmup", "8", "--l2-iters", "600", "--no-cpu-baseline", "--no-residual-roofline", "--no-pmc",
+                      "--full"],
                      {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "HPV_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1",
                       "MASTER_PORT": str(port)})
     cfg = out["config"]
@@ -120,3 +124,30 @@ def test_bench_default_rccl_exchange_with_a_one_rank_group():
     # evidence fields of the collective (verdict round 5, item 1c): the communicator's own rank count, the all-reduce alone
     assert cfg["rccl_world"] == 1 and cfg["per_rank"][0]["rccl_world"] == 1
     assert isinstance(cfg["collective_us"], float) and 0.0 < cfg["collective_us"] < 200.0, cfg["collective_us"]     # (one rank: RCCL has nothing to move, ~0.05 us)
+
+
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_their_outputs(tmp_path):
+    """The plain call does what the headline needs and nothing else: one timed window of exactly `--steps` iterations, and
+    `--dump-outputs` writes what those iterations computed -- K Adam iterations from the seeded initial state, whatever the
+    wall-clock warm-up ran before them."""
+    import numpy as np
+    d = tmp_path / "out"
+    out = _run_bench(["--steps", "24", "--warmup", "6", "--dump-outputs", str(d)])
+    assert out["n_gpus"] == 1 and out["steps"] == 24 and out["warmup"] == 6 and out["value"] > 0
+    assert out["metric"].startswith("variational-loss iterations/sec") and out["unit"] == "it/s" and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and abs(out["ms_per_step"] * 1e-3 * out["value"] - 1.0) < 1e-9
+    assert out["timing"]["windows"] == 1
+    for k in ("roofline", "kernel_ms", "rel_l2_error", "cpu_baseline", "roofline_residual", "scaled_strong_64x64", "weak_scaling_probe"):
+        assert k not in out, k
+    params, state = np.load(d / "params.npy"), np.load(d / "optimizer_state.npy")
+    assert params.dtype == np.float64 and state.dtype == np.float64 and params.shape == (921,) and state.shape == (3 * 921 + 2,)
+    import bench
+    from hp_vpinns_amd.drivers import poisson2d
+    from hp_vpinns_amd.init import xavier_init
+    theta = xavier_init(bench.LAYERS, 1234)
+    m = poisson2d.build_model(poisson2d.setup(**bench.CFG4, with_test_grid=False), bench.LAYERS, var_form=1, init_params=theta)
+    m._step(24, False)
+    ref = m.get_params()
+    assert np.max(np.abs(params - ref)) <= 1e-10 * np.max(np.abs(ref)), np.max(np.abs(params - ref))
+    assert np.max(np.abs(params - theta)) > 1e-6                # (the steps did move the parameters)
+    assert np.array_equal(state[:921], params)

@@ -11,7 +11,9 @@ covers (verdict round 4, weak 1 ii; round 5, weak 1: the fraction was 1/4).
 
 The sweeps have a FIXED part (the seeds below: the same combinations every run, a regression net) and a ROTATING part: the last
 eight cases of the 2-D sweep and the last four of the others are drawn from HPV_FUZZ_SEED, by default the run's clock -- the seed is
-printed in pytest's header (tests/conftest.py) and is part of every failing assertion's message; HPV_FUZZ_SEED=<n> reproduces a run."""
+printed in pytest's header (tests/conftest.py) and is part of every failing assertion's message; HPV_FUZZ_SEED=<n> reproduces a run.
+The rotating cases' test ids name their position in the sweep (`[rotating0]` ...), not their values: the ids stay the same from run
+to run.  The rotating draws of earlier recorded runs (PAST_FUZZ_SEEDS) belong to the fixed part."""
 import os
 import time
 
@@ -31,19 +33,41 @@ def _oracle_pick(i, n_points):
     return n_points < 8000 or i % (2 if n_points < 20000 else 4) == 0
 
 
+# Seeds of earlier recorded runs of the suite: their rotating draws stay in the sweep as FIXED cases (named by their values, as they
+# were when they ran), so that a combination the suite has once been run with is never dropped from it
+PAST_FUZZ_SEEDS = (1792112344, 1792112352)
+
+
+def _sweep(fixed_seed, n, first_rotating, seed_offset, draw):
+    """Cases 0 .. first_rotating-1 drawn from `fixed_seed`, then the rotating draws (positions first_rotating .. n-1) of every seed
+    of PAST_FUZZ_SEEDS that are not already there, then those of this run (HPV_FUZZ_SEED + seed_offset).  This run's rotating
+    cases are named by their position (`rotating0`, `rotating1`, ...): the suite's test ids do not change with the seed."""
+    rng = np.random.RandomState(fixed_seed)
+    out = [draw(rng, i) for i in range(first_rotating)]
+    seen = set(out)
+    for seed in PAST_FUZZ_SEEDS:
+        rng = np.random.RandomState(seed + seed_offset)
+        for i in range(first_rotating, n):
+            v = draw(rng, i)
+            if v not in seen:
+                out.append(v)
+                seen.add(v)
+    rng = np.random.RandomState(FUZZ_SEED + seed_offset)
+    return out + [pytest.param(*draw(rng, i), id="rotating%d" % (i - first_rotating)) for i in range(first_rotating, n)]
+
+
+def _draw_2d(rng, i):
+    q = int(rng.choice([5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 22, 24]))
+    ntx, nty = int(rng.randint(1, q // 2 + 1)), int(rng.randint(1, q // 2 + 1))
+    nex, ney = int(rng.randint(1, 19)), int(rng.randint(1, 19))       # 1 ... 324 elements: SPLIT shards, full grids, a second round
+    depth = int(rng.choice([1, 2, 3, 3, 3, 4, 5, 6]))
+    width = int(rng.choice([5, 12, 20, 20, 20, 24, 30]))
+    vf = int(rng.choice([0, 1, 1, 1, 2]))
+    return (q, ntx, nty, nex, ney, depth, width, vf, _oracle_pick(i, q * q * nex * ney))
+
+
 def _cases_2d():
-    rng = np.random.RandomState(20260929)
-    out = []
-    for i in range(64):
-        if i == 56: rng = np.random.RandomState(FUZZ_SEED)          # the rotating part
-        q = int(rng.choice([5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 22, 24]))
-        ntx, nty = int(rng.randint(1, q // 2 + 1)), int(rng.randint(1, q // 2 + 1))
-        nex, ney = int(rng.randint(1, 19)), int(rng.randint(1, 19))       # 1 ... 324 elements: SPLIT shards, full grids, a second round
-        depth = int(rng.choice([1, 2, 3, 3, 3, 4, 5, 6]))
-        width = int(rng.choice([5, 12, 20, 20, 20, 24, 30]))
-        vf = int(rng.choice([0, 1, 1, 1, 2]))
-        out.append((q, ntx, nty, nex, ney, depth, width, vf, _oracle_pick(len(out), q * q * nex * ney)))
-    return out
+    return _sweep(20260929, 64, 56, 0, _draw_2d)
 
 
 def _against_oracle(m, o, n_res, what):
@@ -54,7 +78,10 @@ def _against_oracle(m, o, n_res, what):
     what = (what, "HPV_FUZZ_SEED=%d" % FUZZ_SEED)
     assert rel(l3m, l3o) < 1e-9 and rel(gm, go) < 1e-8, (what, l3m, l3o, rel(gm, go))
     if n_res:
-        assert rel(m.h.residuals(n_res), o.last["R"]) < 1e-9, what
+        # (relative to the residuals' norm, but not below 1e-4 of it: on ONE element centred on the origin with one test function per
+        #  direction, F and the projection both vanish by symmetry and the residual is round-off on both sides, ~4e-16 -- no digits to compare)
+        rm, ro = np.ravel(m.h.residuals(n_res)), np.ravel(o.last["R"])
+        assert np.linalg.norm(rm - ro) < 1e-9 * max(np.linalg.norm(ro), 1e-4), (what, rm[:4], ro[:4])
     m._step(1, False)
     o.adam_step()
     # (Adam's first update is lr * sign(g) up to eps / |g|: entries whose gradient cancels to round-off are compared through the rest)
@@ -88,14 +115,13 @@ def test_poisson2d_default_dispatch_against_the_generic_kernels(q, ntx, nty, nex
     assert rel(m.get_params(), g.get_params()) < 1e-8, v
 
 
+def _draw_1d(rng, i):
+    q, nt, ne = int(rng.choice([10, 20, 40, 60, 80])), int(rng.randint(1, 31)), int(rng.randint(1, 9))
+    return (q, nt, ne, int(rng.choice([2, 3, 4, 5])), int(rng.choice([8, 20, 20, 32])), int(rng.choice([1, 2, 3])), _oracle_pick(i, q * ne))
+
+
 def _cases_1d():
-    rng = np.random.RandomState(7)
-    out = []
-    for i in range(20):
-        if i == 16: rng = np.random.RandomState(FUZZ_SEED + 1)      # the rotating part
-        q, nt, ne = int(rng.choice([10, 20, 40, 60, 80])), int(rng.randint(1, 31)), int(rng.randint(1, 9))
-        out.append((q, nt, ne, int(rng.choice([2, 3, 4, 5])), int(rng.choice([8, 20, 20, 32])), int(rng.choice([1, 2, 3])), _oracle_pick(i, q * ne)))
-    return out
+    return _sweep(7, 20, 16, 1, _draw_1d)
 
 
 @pytest.mark.parametrize("q,nt,ne,depth,width,vf,oracle", _cases_1d())
@@ -123,14 +149,13 @@ def test_poisson1d_default_dispatch_against_the_generic_kernels(q, nt, ne, depth
     assert rel(m.get_params(), g.get_params()) < 1e-8, m.h.kernel_variant()
 
 
+def _draw_adv(rng, i):
+    q, ntx, ntt, nex, net = int(rng.choice([6, 8, 10, 12, 16, 20])), int(rng.randint(1, 6)), int(rng.randint(1, 6)), int(rng.randint(1, 9)), int(rng.randint(1, 9))
+    return (q, ntx, ntt, nex, net, int(rng.choice([2, 3, 4])), int(rng.choice([0, 1])), _oracle_pick(i, q * q * nex * net))
+
+
 def _cases_adv():
-    rng = np.random.RandomState(11)
-    out = []
-    for i in range(16):
-        if i == 12: rng = np.random.RandomState(FUZZ_SEED + 2)      # the rotating part
-        q, ntx, ntt, nex, net = int(rng.choice([6, 8, 10, 12, 16, 20])), int(rng.randint(1, 6)), int(rng.randint(1, 6)), int(rng.randint(1, 9)), int(rng.randint(1, 9))
-        out.append((q, ntx, ntt, nex, net, int(rng.choice([2, 3, 4])), int(rng.choice([0, 1])), _oracle_pick(i, q * q * nex * net)))
-    return out
+    return _sweep(11, 16, 12, 2, _draw_adv)
 
 
 @pytest.mark.parametrize("q,ntx,ntt,nex,net,depth,vf,oracle", _cases_adv())
