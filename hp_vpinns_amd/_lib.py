@@ -34,7 +34,7 @@ EXPORTS = [
     "hpv_set_collocation_shard", "hpv_rccl_unique_id", "hpv_rccl_connect", "hpv_rccl_selftest", "hpv_rccl_disconnect", "hpv_exchange_in_use",
     "hpv_rccl_available", "hpv_graphs_in_use", "hpv_updates_applied", "hpv_set_shared_element_kernels", "hpv_shared_element_kernels",
     "hpv_kernel_variant", "hpv_build_info", "hpv_rccl_abandon", "hpv_bench_residual_checksums", "hpv_rule_advice",
-    "hpv_rccl_info", "hpv_rccl_time_allreduce", "hpv_grid_plan",
+    "hpv_rccl_info", "hpv_rccl_time_allreduce", "hpv_grid_plan", "hpv_set_active_tests_2d",
 ]
 
 
@@ -143,6 +143,7 @@ def load():
     lib.hpv_backend_in_use.argtypes = [h]
     lib.hpv_pass_structure.argtypes = [h]
     lib.hpv_set_active_tests.argtypes = [h, C.POINTER(C.c_int), C.c_int]
+    lib.hpv_set_active_tests_2d.argtypes = [h, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     lib.hpv_enable_timing.argtypes = [h, C.c_int]
     lib.hpv_kernel_time_ms.argtypes = [h, C.c_int, _dp, C.POINTER(C.c_long)]
     lib.hpv_time_iteration_kernel.argtypes = [h, C.c_int, _dp]
@@ -372,6 +373,21 @@ class Handle:
             return
         a = np.ascontiguousarray(n_active, dtype=np.int32).reshape(-1)
         self._chk(self.lib.hpv_set_active_tests(self._h, a.ctypes.data_as(C.POINTER(C.c_int)), a.size))
+
+    def set_active_tests_2d(self, nax, nay=None):
+        """per-element numbers of active test functions per direction (2-D p-refinement, P2:72-73 / P3:112-113): one entry per
+        element of the WHOLE grid, flattened e = ex * ney + ey; None = all."""
+        if nax is None and nay is None:
+            self._chk(self.lib.hpv_set_active_tests_2d(self._h, None, None, 0))
+            return
+        if nax is None or nay is None:
+            raise ValueError("nax and nay are given together (or both None)")
+        a = np.ascontiguousarray(nax, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(nay, dtype=np.int32).reshape(-1)
+        if a.size != b.size:
+            raise ValueError("nax and nay must have one entry per element each")
+        ip = C.POINTER(C.c_int)
+        self._chk(self.lib.hpv_set_active_tests_2d(self._h, a.ctypes.data_as(ip), b.ctypes.data_as(ip), a.size))
 
     def residuals(self, n):
         out = np.empty(n)

@@ -665,6 +665,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->d_xerr) (void)hipFree(h->d_xerr);
     if (h->d_nupd) (void)hipFree(h->d_nupd);
     if (h->d_nact) (void)hipFree(h->d_nact);
+    if (h->d_nacty) (void)hipFree(h->d_nacty);
     for (auto& t : h->timers) for (auto e : t.ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -706,6 +707,9 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
     for (size_t i = 0; i < h->nact_all.size(); ++i)     // counts given for an earlier, larger table set
         if (h->nact_all[i] > ntx)
             return fail(h, -1, "n_active[%zu] = %d exceeds the new ntest %d (hpv_set_active_tests(NULL) drops the counts)", i, h->nact_all[i], ntx);
+    for (size_t i = 0; i < h->nacty_all.size(); ++i)    // ... and the second direction's (hpv_set_active_tests_2d)
+        if (h->nacty_all[i] > nty)
+            return fail(h, -1, "nay[%zu] = %d exceeds the new nty %d (hpv_set_active_tests_2d(NULL, NULL) drops the counts)", i, h->nacty_all[i], nty);
     const int qx = h->qx, qy = h->qy;
     std::vector<double> wtx((size_t)3 * ntx * qx), wty((size_t)3 * nty * qy);
     const double* tx[3] = {phix, dphix, d2phix};
@@ -793,6 +797,7 @@ int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* g
     if ((rc = dalloc(h, &h->d_jac, jac.size()))) return rc;
     if (ne > 0 && (rc = upload(h, h->d_jac, jac.data(), jac.size()))) return rc;
     if ((rc = dalloc(h, &h->d_R, (size_t)ne * h->ntx * h->nty))) return rc;
+    // (per-element counts switch the row-split projection off -- set_proj_split below -- but its buffers are sized without them)
     h->proj_split = project_row_split(h->pd, ne, h->cfg.backend == HPV_BACKEND_GENERIC);
     // (the tall-element kernel shares an element among up to 64 workgroups, each with its own loss / d-epsilon / partial-sum slot)
     const bool tall = h->pd.qx == 80 && h->pd.qy == 80 && h->pd.ntx == 5 && h->pd.nty == 5 && h->cfg.backend != HPV_BACKEND_GENERIC && ne <= 128;
@@ -823,11 +828,22 @@ int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* g
         if ((rc = hpv_set_rhs(h, F.data(), F.size()))) return rc;
     } else if (h->d_F) { (void)hipFree(h->d_F); h->d_F = nullptr; }
     if (!h->nact_all.empty()) {   // ... and the active test counts
-        std::vector<int> na = h->nact_all;
-        if ((rc = hpv_set_active_tests(h, na.data(), (int)na.size()))) return rc;
+        std::vector<int> na = h->nact_all, nay = h->nacty_all;
+        if (!nay.empty()) { if ((rc = hpv_set_active_tests_2d(h, na.data(), nay.data(), (int)na.size()))) return rc; }
+        else if ((rc = hpv_set_active_tests(h, na.data(), (int)na.size()))) return rc;
     }
     if (h->mfma_edge) { hpv_mfma_destroy(h->mfma_edge); h->mfma_edge = nullptr; }
     return 0;
+}
+
+// the device copies of the per-element counts go; the row-split projection (which ignores counts) is on again where it applies
+static void drop_device_counts(hpv_ctx* h) {
+    h->nacty_all.clear();
+    if (h->d_nact) { (void)hipFree(h->d_nact); h->d_nact = nullptr; }
+    if (h->d_nacty) { (void)hipFree(h->d_nacty); h->d_nacty = nullptr; }
+    h->pd.nact = nullptr;
+    h->pd.nacty = nullptr;
+    if (h->have_elems) h->proj_split = project_row_split(h->pd, h->n_elem, h->cfg.backend == HPV_BACKEND_GENERIC);
 }
 
 // p-refinement of the 1-D driver: element e uses only its first n_active[e] test functions (P1:66-67: Ntest_element =
@@ -837,11 +853,10 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n) {
     drop_graph(h);
     if (!n_active) {
         h->nact_all.clear();
-        if (h->d_nact) { (void)hipFree(h->d_nact); h->d_nact = nullptr; }
-        h->pd.nact = nullptr;
+        drop_device_counts(h);
         return 0;
     }
-    if (h->dim != 1) return fail(h, -1, "per-element test-function counts exist in the 1-D problem only (P2:414 / P3:411 reshape F_ext_total)");
+    if (h->dim != 1) return fail(h, -1, "per-element test-function counts of a 2-D problem go through hpv_set_active_tests_2d (one pair per element)");
     if (!h->have_tables) return fail(h, -3, "call hpv_set_tables first");
     for (int i = 0; i < n; ++i)
         if (n_active[i] < 1 || n_active[i] > h->ntx) return fail(h, -1, "n_active[%d] = %d is outside 1..%d", i, n_active[i], h->ntx);
@@ -857,6 +872,49 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n) {
         }
     }
     if (n_active != h->nact_all.data()) h->nact_all.assign(n_active, n_active + n);
+    return 0;
+}
+
+// p-refinement of the 2-D drivers: element e = ex * ney + ey projects onto its first nax[e] x nay[e] test functions (P2:72-73,
+// P3:112-113: Ntest_elementx = N_testfcn[0][ex], Ntest_elementy = N_testfcn[1][ey]; one PAIR per element here, a superset of that
+// product).  n = elements of the whole grid; the owned range is sliced here and again after hpv_set_elements.
+int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n) {
+    if (!h) return -1;
+    drop_graph(h);
+    if (!nax && !nay) {
+        h->nact_all.clear();
+        drop_device_counts(h);
+        return 0;
+    }
+    if (!nax || !nay) return fail(h, -1, "nax and nay are given together (or both NULL)");
+    if (h->dim != 2) return fail(h, -1, "hpv_set_active_tests_2d is for the 2-D problems (1-D: hpv_set_active_tests)");
+    if (h->cfg.scheme != HPV_SCHEME_VPINN) return fail(h, -1, "test-function counts belong to the variational scheme");
+    if (!h->have_tables) return fail(h, -3, "call hpv_set_tables first");
+    if (n < 1) return fail(h, -1, "bad number of counts %d", n);
+    for (int i = 0; i < n; ++i) {
+        if (nax[i] < 1 || nax[i] > h->ntx) return fail(h, -1, "nax[%d] = %d is outside 1..%d", i, nax[i], h->ntx);
+        if (nay[i] < 1 || nay[i] > h->nty) return fail(h, -1, "nay[%d] = %d is outside 1..%d", i, nay[i], h->nty);
+    }
+    if (h->have_elems) {
+        if (n != h->nex * h->ney) return fail(h, -1, "nax / nay have %d entries, expected %d", n, h->nex * h->ney);
+        if (h->d_nact) { (void)hipFree(h->d_nact); h->d_nact = nullptr; }
+        if (h->d_nacty) { (void)hipFree(h->d_nacty); h->d_nacty = nullptr; }
+        h->pd.nact = nullptr;
+        h->pd.nacty = nullptr;
+        if (h->n_elem > 0) {
+            const size_t bytes = (size_t)h->n_elem * sizeof(int);
+            HIPCHK(h, hipMalloc((void**)&h->d_nact, bytes));
+            HIPCHK(h, hipMalloc((void**)&h->d_nacty, bytes));
+            HIPCHK(h, hipMemcpyAsync(h->d_nact, nax + h->e_begin, bytes, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->d_nacty, nay + h->e_begin, bytes, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            h->pd.nact = h->d_nact;
+            h->pd.nacty = h->d_nacty;
+            h->proj_split = 1;      // (the row-split projection of tall elements knows no counts: one workgroup per element)
+        }
+    }
+    if (nax != h->nact_all.data()) h->nact_all.assign(nax, nax + n);
+    if (nay != h->nacty_all.data()) h->nacty_all.assign(nay, nay + n);
     return 0;
 }
 

@@ -67,6 +67,8 @@ struct hpv_ctx {
     bool have_F = false;
     std::vector<int> nact_all;     // active test functions per element of the whole grid (empty: all); see hpv_set_active_tests
     int* d_nact = nullptr;         // ... of the owned elements
+    std::vector<int> nacty_all;    // 2-D: the second direction's counts (nact_all then holds the x counts); see hpv_set_active_tests_2d
+    int* d_nacty = nullptr;
     Batch var, data, edge, pred;
     // host copies of the point sets; the device batches are (re)assembled lazily (assemble_batches)
     std::vector<double> Xq_host;   // [dim][Nq] quadrature points of the owned elements

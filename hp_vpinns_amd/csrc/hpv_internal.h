@@ -49,9 +49,14 @@ struct ProjDesc {
     int edge;        // Poisson-1D var_form 3 boundary term (P1:90)
     // p-refinement of the 1-D driver (P1:66-67, 268-281: F_ext_total[e] may be shorter in some elements): number of ACTIVE test
     // functions per owned element (device pointer, nullptr = all ntx); the residual rows beyond it are zero and the element's
-    // mean runs over the active ones.  Only the general projections (k_project, project_element_wg) honour it; the
-    // specialised 2-D kernels are bypassed when it is set.
+    // mean runs over the active ones.  The general projections (k_project, project_element_wg) and the 1-D tile kernel honour
+    // it; of the specialised 2-D kernels only k_iter_fused does (with `nacty` below), the others are bypassed when it is set.
     const int* nact;
+    // p-refinement of the 2-D drivers (P2:72-73, P3:112-113: Ntest_elementx = N_testfcn[0][ex], Ntest_elementy = N_testfcn[1][ey]):
+    // the second direction's count per owned element (device pointer; nullptr = all nty -- always so in 1-D).  Set together with
+    // `nact`, which then holds the x counts: element e keeps the residuals (k, r) with r < nact[e] and k < nacty[e], and its mean
+    // runs over nact[e] * nacty[e] of them.  Honoured by the general projections and by k_iter_fused (kernels_fused.hip).
+    const int* nacty;
 };
 
 static inline size_t hpv_proj_lds_bytes(const ProjDesc& pd) {

@@ -360,11 +360,12 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
     }
     const int nax = PRE ? (int)red[48 + HPV_MAXT + 1] : (pd.nact ? pd.nact[e] : NTX);   // active test functions (p-refinement, P1:67)
     const bool counted = pd.nact != nullptr;     // (per-element counts, P1:66-67: 1-D, rnx = NTX)
-    const double NRa = counted ? (double)(nax * NTY) : (double)rnr;
+    const int nay = pd.nacty ? pd.nacty[e] : NTY;        // ... and of the second direction (2-D: P2:72-73, P3:112-113)
+    const double NRa = counted ? (double)(nax * nay) : (double)rnr;
     double sq = 0.0;
     for (int o = tid; o < NR; o += PW_BLOCK) {
         const int k_ = o / NTX, r_ = o % NTX;
-        const double u = r_ < nax ? U[o] : 0.0;
+        const double u = (r_ < nax && k_ < nay) ? U[o] : 0.0;
         U[o] = u;                                         // (each entry is read and written by its own thread only)
         if (k_ < rny && r_ < rnx) R[e * rnr + k_ * rnx + r_] = u;
         sq = fma(u, u, sq);

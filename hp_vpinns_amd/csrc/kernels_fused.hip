@@ -747,6 +747,16 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     // =============================================================================================
     {
         const double* G = lds + M::CH;
+        // per-element test-function counts (p-refinement of the 2-D drivers, P2:72-73 / P3:112-113): THIS element's pair, requested here
+        // and used behind the two contractions -- scalar registers (e is workgroup-uniform), nothing lives across the phases.  The
+        // tables, F, R and their strides keep the run's rnx x rny; residuals beyond the pair are zero, the mean runs over the pair.
+        int nax_e = FZ_NTX, nay_e = FZ_NTY;
+        double nr_e = (double)rnr;
+        if (pa.pd.nact) {
+            nax_e = __builtin_amdgcn_readfirstlane(pa.pd.nact[e]);
+            nay_e = __builtin_amdgcn_readfirstlane(pa.pd.nacty[e]);
+            nr_e = (double)(nax_e * nay_e);
+        }
         // T_t[j][r] = sum_i AX_t[r][i] G_t[j][i]
         for (int o = tid; o < 2 * FZ_QY * FZ_NTX; o += FZ_BLOCK) {
             const int t = o / (FZ_QY * FZ_NTX), j = (o / FZ_NTX) % FZ_QY, r = o % FZ_NTX;
@@ -770,18 +780,21 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         }
         __syncthreads();
         double sq = 0.0;
-        const double sc = 2.0 / (double)rnr;
+        const double sc = 2.0 / nr_e;
         [[maybe_unused]] double deps = 0.0;      // GEN: this thread's share of d loss_e / d eps
         if (tid < FZ_NR) {
+            const bool act = ro_r < nax_e && ro_k < nay_e;      // (without counts: every residual of the instantiation)
             double u;
             if constexpr (GEN) {
                 // (UP holds the terms WITHOUT their factor eps: U = m_0 UP_0 + m_1 UP_1 - F, and a term that carries eps as a factor
                 //  contributes (2/NR) U UP_t to d loss_e / d eps -- P3:171)
                 const double u0 = lds[M::UP + tid], u1 = lds[M::UP + FZ_NR + tid];
                 u = fma(gm0, u0, gm1 * u1) - pF;
+                if (!act) u = 0.0;
                 deps = sc * u * fma(ge0, u0, ge1 * u1);
             } else {
                 u = (lds[M::UP + tid] + lds[M::UP + FZ_NR + tid]) - pF;
+                if (!act) u = 0.0;
             }
             lds[M::U + tid] = u;
             if (ro_on) pa.R[ro_idx] = u;
@@ -792,7 +805,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             if (lane == 0) lds[M::RED + wv] = sq;
         }
         __syncthreads();
-        if (tid == 0) pa.loss_e[e] = (lds[M::RED] + lds[M::RED + 1]) / (double)rnr;
+        if (tid == 0) pa.loss_e[e] = (lds[M::RED] + lds[M::RED + 1]) / nr_e;
         // adjoint: S_t[k][i] = (2/NR) c_t sum_r AX_t[r][i] U[k][r];  Gbar_t[j][i] = sum_k BY_t[k][j] S_t[k][i]
         for (int o = tid; o < 2 * FZ_NTY * FZ_QX; o += FZ_BLOCK) {
             const int t = o / (FZ_NTY * FZ_QX), kk = (o / FZ_QX) % FZ_NTY, i = o % FZ_QX;
@@ -2012,7 +2025,11 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
 #ifdef HPV_FZ_NO_EXTRA_SHAPES     // csrc/build.sh: the AGPR guard tripped in an instantiation of a shape other than 20x20 / 10x10
     if (!q20 && !small) return fz_no(5);
 #endif
-    if (pd.edge || pd.nact || pd.nterms < 1 || pd.nterms > 2) return fz_no(6);
+    if (pd.edge || pd.nterms < 1 || pd.nterms > 2) return fz_no(6);
+    // per-element test-function counts (hpv_set_active_tests_2d): k_iter_fused honours them in every structure -- one workgroup per
+    // element, the element loop, SPLIT (every partner projects the whole element) -- and says so in its name; k_iter_small does not
+    const bool counted = pd.nact != nullptr;
+    if (counted && (small || !pd.nacty)) return fz_no(34);
     // one-hot (Poisson-2D var_form 1, the headline instantiations): term t integrates exactly channel 1 + t with weight 1, no epsilon.
     // Every other form of these channel sets (round 6): the general instantiations (k_iter_fused<.., NT2, GEN>)
     bool onehot = !pd.has_eps && pd.nterms == 2 && nd.nT2 == 0;
@@ -2183,6 +2200,7 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
     if (split > 1 || n_tail > 0) m->split_used = true;
     char shp[64] = "";
     if (!base_shape || gen) snprintf(shp, sizeof shp, ",%dx%d/%dx%d%s", pd.qx, pd.qy, pd.ntx, pd.nty, gen ? (nd.nT2 ? ",NT2=1,GEN" : ",GEN") : "");
+    if (counted) snprintf(shp + strlen(shp), sizeof shp - strlen(shp), ",NACT");
     if (split > 1) snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=true,QT=false,GS=%s%s> split=%d", m->L, gs ? "true" : "false", shp, split);
     else snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=false,QT=%s,GS=%s%s>%s", m->L, (plan == 2 || plan == 4) ? "true" : "false",
                   gs ? "true" : "false", shp, multi ? " elements-per-workgroup>1" : "");

@@ -363,11 +363,12 @@ __global__ void __launch_bounds__(256) k_project(ProjDesc pd, const double* __re
             U[idx] += ce * (uR * edge_dphi[2 * idx + 1] - uL * edge_dphi[2 * idx]);
         __syncthreads();
     }
-    const int nax = pd.nact ? pd.nact[e] : ntx;          // active test functions of this element (P1:67)
-    const double NRa = (double)(nax * nty);
+    const int nax = pd.nact ? pd.nact[e] : ntx;          // active test functions of this element (P1:67; P2:72-73, P3:112-113)
+    const int nay = pd.nacty ? pd.nacty[e] : nty;
+    const double NRa = (double)(nax * nay);
     double sq = 0.0;
     for (int idx = tid; idx < NR; idx += nthr) {
-        const double u = (idx % ntx) < nax ? U[idx] : 0.0;
+        const double u = ((idx % ntx) < nax && (idx / ntx) < nay) ? U[idx] : 0.0;
         U[idx] = u;
         R[e * NR + idx] = u;
         sq += u * u;

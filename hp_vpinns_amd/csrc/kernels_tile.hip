@@ -684,6 +684,7 @@ bool hpv_mfma_iter_tile(HpvMfma* m, const double* theta, const double* X, double
     const bool shape2d = pd.qx == 10 && pd.qy == 10 && pd.ntx >= 1 && pd.ntx <= 5 && pd.nty >= 1 && pd.nty <= 5 && nd.act == HPV_ACT_TANH &&
                          (key == 200 || key == 220 || key == 221 || key == 222) && m->L <= 3;
     if (!shape1d && !shape2d) { TL_WHY(2); return false; }
+    if (shape2d && pd.nact) { TL_WHY(6); return false; }      // per-element counts of a 2-D grid: k_iter_fused or the general projections
     // (thousands of small 2-D elements: the separate launches stream, one workgroup per element does not -- scripts/grid_sweep.py)
     if (shape2d && n_elem > hpv_elem_resident_max(2, 10, m->n_cus) && !m->iter_fused_force) { TL_WHY(5); return false; }
     const int waves = shape1d ? 6 : 8, nq = pd.qx * pd.qy, tpe = (nq + 15) / 16;

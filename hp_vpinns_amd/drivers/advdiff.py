@@ -61,7 +61,12 @@ def setup(N_el_x=1, N_el_t=1, N_test_x=5, N_test_t=5, N_quad=10, N_bound=80, NPf
     delta_x, delta_t = 2 / N_el_x, T / N_el_t                    # P3:404-410
     grid_x = np.asarray([-1 + i * delta_x for i in range(N_el_x + 1)])
     grid_t = np.asarray([0 + i * delta_t for i in range(N_el_t + 1)])
-    N_testfcn_total = [N_el_x * [N_test_x], N_el_t * [N_test_t]]
+    # N_test_x / N_test_t: an integer (the reference, P3:48-51) or one entry per element column / row (p-refinement, P3:112-113)
+    nax = [int(N_test_x)] * N_el_x if np.isscalar(N_test_x) else [int(v) for v in N_test_x]
+    nat = [int(N_test_t)] * N_el_t if np.isscalar(N_test_t) else [int(v) for v in N_test_t]
+    if len(nax) != N_el_x or len(nat) != N_el_t:
+        raise ValueError("N_test_x / N_test_t given as lists need one entry per element column / row")
+    N_testfcn_total = [nax, nat]
     out = {}
     if with_test_grid:                                           # P3:448-458 (x fastest)
         xtest = np.linspace(-1, 1, 256)

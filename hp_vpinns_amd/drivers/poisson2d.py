@@ -53,7 +53,15 @@ def setup(N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10, N_bound=80, N_r
     delta_x, delta_y = 2 / NE_x, 2 / NE_y
     grid_x = np.asarray([-1 + i * delta_x for i in range(NE_x + 1)])
     grid_y = np.asarray([-1 + i * delta_y for i in range(NE_y + 1)])
-    N_testfcn_total = [NE_x * [N_test_x], NE_y * [N_test_y]]
+    # N_test_x / N_test_y: an integer (the reference, P2:283-286) or one entry per element column / row -- the p-refinement the
+    # class bodies read per element (P2:72-73) and the commented-out list of P2:377 hints at
+    ragged = not (np.isscalar(N_test_x) and np.isscalar(N_test_y))
+    nax = [int(N_test_x)] * NE_x if np.isscalar(N_test_x) else [int(v) for v in N_test_x]
+    nay = [int(N_test_y)] * NE_y if np.isscalar(N_test_y) else [int(v) for v in N_test_y]
+    if len(nax) != NE_x or len(nay) != NE_y:
+        raise ValueError("N_test_x / N_test_y given as lists need one entry per element column / row")
+    N_testfcn_total = [nax, nay]
+    N_test_x, N_test_y = max(nax), max(nay)                      # (the family is nested: every element's block is a corner of this one)
     tx, ty = Test_fcn(N_test_x, X_quad), Test_fcn(N_test_y, X_quad)      # (Nt, Q)
     ax, by = tx * WX_quad, ty * WX_quad
     F_ext_total = np.empty((NE_x, NE_y, N_test_y, N_test_x))
@@ -67,6 +75,12 @@ def setup(N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10, N_bound=80, N_r
             jacobian = ((grid_x[ex + 1] - grid_x[ex]) / 2) * ((grid_y[ey + 1] - grid_y[ey]) / 2)
             fq = f_ext(xq[None, :], yq[:, None])                 # [j (y)][i (x)]
             F_ext_total[ex, ey] = jacobian * (by @ fq @ ax.T)    # [k][r]
+    if ragged:      # what the reference class indexes with [ex, ey]: an (NE_x, NE_y) array of (N_test_y[ey], N_test_x[ex]) blocks
+        blocks = np.empty((NE_x, NE_y), dtype=object)
+        for ex in range(NE_x):
+            for ey in range(NE_y):
+                blocks[ex, ey] = F_ext_total[ex, ey][:nay[ey], :nax[ex]].copy()
+        F_ext_total = blocks
     out = dict(X_u_train=X_u_train, u_train=u_train, X_f_train=X_f_train, f_train=f_train,
                XY_quad_train=XY_quad_train, WXY_quad_train=WXY_quad_train, F_ext_total=F_ext_total,
                grid_x=grid_x, grid_y=grid_y, N_testfcn_total=N_testfcn_total)

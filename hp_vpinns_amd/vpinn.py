@@ -147,12 +147,41 @@ def _resolve(value, name, ns, default, kinds):
 _NUM = (int, float, np.integer, np.floating)
 
 
-def _uniform(lst, what):
-    vals = [int(v) for v in np.ravel(lst)]
-    if len(set(vals)) != 1:
-        raise ValueError(f"{what} must be the same in every element (the reference's F_ext_total "
-                         "reshape, P2:414, requires it too)")
-    return vals[0]
+def _counts_2d(N_testfcn):
+    """The reference's N_testfcn = [[per element column], [per element row]] (read per element at P2:72-73 / P3:112-113) ->
+    (counts per column, counts per row, the pair of every element flattened e = ex * ney + ey, whether any count differs)."""
+    nax = np.array([int(v) for v in np.ravel(N_testfcn[0])], dtype=np.int32)
+    nay = np.array([int(v) for v in np.ravel(N_testfcn[1])], dtype=np.int32)
+    if nax.size < 1 or nay.size < 1 or nax.min() < 1 or nay.min() < 1:
+        raise ValueError("N_testfcn needs at least one test function per direction in every element")
+    ragged = bool(np.any(nax != nax.max()) or np.any(nay != nay.max()))
+    return nax, nay, np.repeat(nax, nay.size), np.tile(nay, nax.size), ragged
+
+
+def _dense_rhs_2d(F, nax, nay):
+    """F_exact_total of the 2-D class as the dense (nex, ney, max nty, max ntx) array hpv_set_rhs takes.  Given as that array
+    (entries beyond an element's counts are ignored by the library), or as what the reference class indexes with [ex, ey]: an
+    (nex, ney) object array / nested list of (nty_ey, ntx_ex) blocks, padded with zeros here."""
+    nex, ney, ntx, nty = nax.size, nay.size, int(nax.max()), int(nay.max())
+    try:
+        Fd = np.asarray(F, dtype=np.float64)
+    except (ValueError, TypeError):      # ragged blocks / an object array of blocks
+        Fd = None
+    if Fd is not None and Fd.ndim != 2:
+        if Fd.shape != (nex, ney, nty, ntx):
+            raise ValueError(f"F_exact_total has shape {Fd.shape}, expected {(nex, ney, nty, ntx)} (P2:414)")
+        return Fd
+    if len(F) != nex or any(len(F[ex]) != ney for ex in range(nex)):
+        raise ValueError(f"F_exact_total must hold one block per element: {nex} x {ney}")
+    out = np.zeros((nex, ney, nty, ntx))
+    for ex in range(nex):
+        for ey in range(ney):
+            b = np.asarray(F[ex][ey], dtype=np.float64)
+            if b.shape != (nay[ey], nax[ex]):
+                raise ValueError(f"F_exact_total[{ex}][{ey}] has shape {b.shape}, but N_testfcn gives that element "
+                                 f"{(int(nay[ey]), int(nax[ex]))} test functions (y, x)")
+            out[ex, ey, :nay[ey], :nax[ex]] = b
+    return out
 
 
 def _next_chunk(it, nIter, every=10):
@@ -718,18 +747,17 @@ class VPINN2D(_VPINNBase):
         self.utrain = np.asarray(u_train, dtype=np.float64)
         self.xf_train, self.ftrain = X_f_train, f_train
         self.U_ext_total = U_exact_total                   # stored, never used (P2:47)
-        self.F_ext_total = np.asarray(F_exact_total, dtype=np.float64)
         self.Nelementx, self.Nelementy = np.size(N_testfcn[0]), np.size(N_testfcn[1])   # P2:43-44
-        self.Ntestx = _uniform(N_testfcn[0], "N_test_x")
-        self.Ntesty = _uniform(N_testfcn[1], "N_test_y")
+        # the counts may differ from element column to column and row to row (p-refinement; the class reads them per element,
+        # P2:72-73): tables, rule padding and F are built for the maxima, the pairs are handed to the library
+        nax, nay, self._nax_e, self._nay_e, ragged = _counts_2d(N_testfcn)
+        self.Ntestx, self.Ntesty = int(nax.max()), int(nay.max())     # P2:45-46 (the reference reads element 0; equal when uniform)
+        self.F_ext_total = _dense_rhs_2d(F_exact_total, nax, nay)
         self.gridx, self.gridy = np.asarray(gridx, dtype=np.float64), np.asarray(gridy, dtype=np.float64)
         self.X_test, self.utest = X_test, u_test
         self.var_form = var_form
         self._loss_his_arg = loss_his
         self.loss_his = [] if loss_his is None else loss_his
-        if self.F_ext_total.shape != (self.Nelementx, self.Nelementy, self.Ntesty, self.Ntestx):
-            raise ValueError(f"F_exact_total has shape {self.F_ext_total.shape}, expected "
-                             f"{(self.Nelementx, self.Nelementy, self.Ntesty, self.Ntestx)} (P2:414)")
         self._create(layers, var_form, LR, lossb_weight, 1.0, init_params, seed, backend, device,
                      scheme=_lib.SCHEME_PINN if scheme == "PINNs" else _lib.SCHEME_VPINN)
 
@@ -759,6 +787,8 @@ class VPINN2D(_VPINNBase):
                 eb, ee = shard_range(self.Nelementx * self.Nelementy, self.rank, self.world)
                 self.h.set_elements(self.gridx, self.gridy, eb, ee)
                 self.h.set_rhs(self.F_ext_total.reshape(-1))
+                if ragged:
+                    self.h.set_active_tests_2d(self._nax_e, self._nay_e)
             if self.rank == 0:
                 self.h.set_data(self.X_u_train, self.utrain.reshape(-1))
         self._populate = populate
@@ -814,8 +844,9 @@ class VPINNAdvDiff(_VPINNBase):
         self.u = np.asarray(u_train, dtype=np.float64)
         self.XT_f_train = XT_f_train
         self.Nelementx, self.Nelementt = np.size(N_testfcn[0]), np.size(N_testfcn[1])
-        self.Ntestx = _uniform(N_testfcn[0], "N_test_x")
-        self.Ntestt = _uniform(N_testfcn[1], "N_test_t")
+        # (the counts may differ per element column / row: P3:112-113; see VPINN2D)
+        nax, nat, self._nax_e, self._nat_e, ragged = _counts_2d(N_testfcn)
+        self.Ntestx, self.Ntestt = int(nax.max()), int(nat.max())
         self.grid_x, self.grid_t = np.asarray(grid_x, dtype=np.float64), np.asarray(grid_t, dtype=np.float64)
         self.XT_test, self.utest = XT_test, u_test
         self.var_form, self.V = var_form, V
@@ -838,6 +869,8 @@ class VPINNAdvDiff(_VPINNBase):
             eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)
             self.h.set_elements(self.grid_x, self.grid_t, eb, ee)
             self.h.set_rhs(None)                               # zero right-hand side (P3:180)
+            if ragged:
+                self.h.set_active_tests_2d(self._nax_e, self._nat_e)
             if self.rank == 0:
                 self.h.set_data(self.XT_u_train, self.u.reshape(-1))
         self._populate = populate

@@ -84,9 +84,23 @@ int hpv_set_rhs(hpv_handle h, const double* F, size_t n);
 /* p-refinement of the 1-D driver: element e projects onto its first n_active[e] <= ntest test functions only and its loss
  * is the mean over those (P1:66-67: Ntest_element = len(F_ext_total[e]); the driver builds F_ext_total from the per-element
  * list N_testfcn_total, P1:268-281).  n = nex (all elements of the grid); rows of F beyond n_active[e] are ignored and the
- * residuals returned for them are zero.  NULL restores "all ntest in every element".  1-D only: the 2-D and AdvDiff drivers
- * reshape F_ext_total into a dense array (P2:414, P3:411), which forbids ragged counts in the reference too. */
+ * residuals returned for them are zero.  NULL restores "all ntest in every element".  1-D only: 2-D handles are refused
+ * here and take their counts through hpv_set_active_tests_2d below. */
 int hpv_set_active_tests(hpv_handle h, const int* n_active, int n);
+
+/* p-refinement of the 2-D drivers (Poisson-2D, AdvDiff; variational scheme): the reference classes read the number of test
+ * functions per element column and per element row -- Ntest_elementx = N_testfcn[0][ex], Ntest_elementy = N_testfcn[1][ey]
+ * (P2:72-73, P3:112-113) -- build that element's tables from them (P2:85-88, P3:127-130) and take its reduce_mean over exactly
+ * those residuals (P2:118-120).  Only the Poisson-2D DRIVER's np.reshape of F_ext_total (P2:414) asks for equal counts; the
+ * AdvDiff right-hand side is zero (P3:180).
+ * n = nex*ney: the counts of ALL elements of the grid, indexed by the flattened element e = ex*ney + ey, 1 <= nax[e] <= ntx and
+ * 1 <= nay[e] <= nty -- one PAIR per element, a superset of the reference's column x row product.  Element e projects onto its
+ * first nax[e] x nay[e] test functions (the family is nested: the first rows of a larger table are the smaller table) and its
+ * loss is the mean over those nax[e]*nay[e] residuals; rows and columns of F beyond the counts are ignored, the residuals
+ * hpv_get_residuals returns for them are exactly 0 (layout [ne][nty][ntx] as ever).  The owned range [e_begin, e_end) is sliced
+ * inside and the counts are re-applied after hpv_set_elements / hpv_set_tables.  NULL, NULL restores "all ntx x nty everywhere"
+ * bit for bit.  Refused for 1-D handles, the strong-form PINN scheme, a wrong n and counts out of range. */
+int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n);
 
 /* Boundary / data points of lossb (P1:98, P2:122, P3:184): X is [n][dim] row-major, u is [n].
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
