@@ -38,14 +38,15 @@ EXPORTS = [
 ]
 
 
-def rule_advice(device, dim, q, ntx, nty, n_elem_shard, exact_counts=False, n_hidden=0):
+def rule_advice(device, pde, var_form, n_hidden, max_width, q, ntx, nty, n_elem_shard):
     """hpv_rule_advice: (q_dev, nt_dev) -- the instantiated rule a shard's rule should be zero-weight padded to (q_dev == q: leave it
-    alone) and, in 1-D, the test-function count the device tables should have.  The limits are the launch functions' own."""
+    alone) and, in 1-D, the test-function count the device tables should have, for problem `pde` in form `var_form` under a network of
+    `n_hidden` hidden layers at most `max_width` wide.  The answer is the dispatch's own plan."""
     qd, nd = C.c_int(0), C.c_int(0)
-    rc = load().hpv_rule_advice(int(device), int(dim), int(q), int(ntx), int(nty), int(n_elem_shard), 1 if exact_counts else 0, int(n_hidden),
-                                C.byref(qd), C.byref(nd))
+    rc = load().hpv_rule_advice(int(device), int(pde), int(var_form), int(n_hidden), int(max_width), int(q), int(ntx), int(nty),
+                                int(n_elem_shard), C.byref(qd), C.byref(nd))
     if rc:
-        raise HpvError(f"hpv_rule_advice({dim}, {q}, {ntx}, {nty}, {n_elem_shard}) returned {rc}")
+        raise HpvError(f"hpv_rule_advice({pde}, {var_form}, {n_hidden}, {max_width}, {q}, {ntx}, {nty}, {n_elem_shard}) returned {rc}")
     return qd.value, nd.value
 
 
@@ -181,7 +182,7 @@ def load():
     lib.hpv_kernel_variant.argtypes = [h, C.c_char_p, C.c_size_t]
     lib.hpv_build_info.argtypes = []
     lib.hpv_grid_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_long]
-    lib.hpv_rule_advice.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.hpv_rule_advice.argtypes = [C.c_int] * 8 + [C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:

@@ -530,6 +530,43 @@ extern "C" {
 
 const char* hpv_last_error(hpv_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+// channel selection + integrand terms per (pde, var_form); returns what is wrong with the pair, or nullptr
+static const char* form_terms(int pde, int vf, double V, ProjDesc& pd, int& nT1, int& nT2, bool& mixed) {
+    pd = ProjDesc{};
+    nT1 = nT2 = 0;
+    mixed = false;
+    auto term = [&](int dx, int dy, int eps_mult) -> TermDesc& {
+        TermDesc& t = pd.t[pd.nterms++];
+        t = TermDesc{}; t.dx = dx; t.dy = dy; t.eps_mult = eps_mult; return t;
+    };
+    if (pde == HPV_PDE_POISSON1D) {
+        if (vf == 1) { nT1 = 1; nT2 = 1; term(0, 0, 0).a0[2] = 1.0; }            // P1:83-84  -J int u'' phi
+        else if (vf == 2) { nT1 = 1; term(1, 0, 0).a0[1] = 1.0; }                // P1:86-87  int u' phi'
+        else if (vf == 3) { term(2, 0, 0).a0[0] = 1.0; pd.edge = 1; }            // P1:89-91
+        else return "Poisson-1D var_form must be 1, 2 or 3";
+    } else if (pde == HPV_PDE_POISSON2D) {
+        if (vf == 0) {                                                           // P2:91, 93-96: integrand u_xx + u_yy
+            // ONE mixed second tangent (NetDesc::t2w = {1, 1}) instead of the two channels u_xx, u_yy: 4 channels through the
+            // forward, the tangent recompute and the reverse pass instead of 5 (second-order channels propagate linearly)
+            nT1 = 2; nT2 = 1; mixed = true; term(0, 0, 0).a0[3] = 1.0;
+        }
+        else if (vf == 1) { nT1 = 2; term(1, 0, 0).a0[1] = 1.0; term(0, 1, 0).a0[2] = 1.0; }            // P2:98-105
+        else if (vf == 2) { term(2, 0, 0).a0[0] = 1.0; term(0, 2, 0).a0[0] = 1.0; }                     // P2:108-115
+        else return "Poisson-2D var_form must be 0, 1 or 2";
+    } else if (pde == HPV_PDE_ADVDIFF) {
+        pd.has_eps = 1;
+        if (vf == 0) {                                                           // P3:161-167
+            nT1 = 2; nT2 = 1;  // channels u, u_x, u_t, u_xx
+            TermDesc& t = term(0, 0, 0); t.a0[1] = V; t.a0[2] = 1.0; t.a1[3] = -1.0;
+        } else if (vf == 1) {                                                    // P3:169-174
+            nT1 = 2;
+            TermDesc& t = term(0, 0, 0); t.a0[1] = V; t.a0[2] = 1.0;
+            term(1, 0, 1).a0[1] = 1.0;
+        } else return "AdvDiff var_form must be 0 or 1";
+    } else return "unknown pde";
+    return nullptr;
+}
+
 int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     if (!out || !cfg) return fail(nullptr, -1, "null argument");
     *out = nullptr;
@@ -559,42 +596,12 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     { const char* ng = getenv("HPV_NO_GRAPH"); h->use_graph = !(ng && ng[0] == '1'); }
     { const char* nd = getenv("HPV_NO_DEFERRED_ADAM"); h->defer_ok = !(nd && nd[0] == '1'); }
 
-    // channel selection + integrand terms per (pde, var_form)
     int t1[2] = {0, 1}, t2[2] = {0, 1};
     ProjDesc& pd = h->pd;
-    pd = ProjDesc{};
     int nT1 = 0, nT2 = 0;
     bool mixed = false;
-    const int vf = cfg->var_form;
-    auto term = [&](int dx, int dy, int eps_mult) -> TermDesc& {
-        TermDesc& t = pd.t[pd.nterms++];
-        t = TermDesc{}; t.dx = dx; t.dy = dy; t.eps_mult = eps_mult; return t;
-    };
-    if (cfg->pde == HPV_PDE_POISSON1D) {
-        if (vf == 1) { nT1 = 1; nT2 = 1; term(0, 0, 0).a0[2] = 1.0; }            // P1:83-84  -J int u'' phi
-        else if (vf == 2) { nT1 = 1; term(1, 0, 0).a0[1] = 1.0; }                // P1:86-87  int u' phi'
-        else if (vf == 3) { term(2, 0, 0).a0[0] = 1.0; pd.edge = 1; }            // P1:89-91
-        else { delete h; return fail(nullptr, -1, "Poisson-1D var_form must be 1, 2 or 3"); }
-    } else if (cfg->pde == HPV_PDE_POISSON2D) {
-        if (vf == 0) {                                                           // P2:91, 93-96: integrand u_xx + u_yy
-            // ONE mixed second tangent (NetDesc::t2w = {1, 1}) instead of the two channels u_xx, u_yy: 4 channels through the
-            // forward, the tangent recompute and the reverse pass instead of 5 (second-order channels propagate linearly)
-            nT1 = 2; nT2 = 1; mixed = true; term(0, 0, 0).a0[3] = 1.0;
-        }
-        else if (vf == 1) { nT1 = 2; term(1, 0, 0).a0[1] = 1.0; term(0, 1, 0).a0[2] = 1.0; }            // P2:98-105
-        else if (vf == 2) { term(2, 0, 0).a0[0] = 1.0; term(0, 2, 0).a0[0] = 1.0; }                     // P2:108-115
-        else { delete h; return fail(nullptr, -1, "Poisson-2D var_form must be 0, 1 or 2"); }
-    } else {
-        h->has_eps = 1;
-        if (vf == 0) {                                                           // P3:161-167
-            nT1 = 2; nT2 = 1;  // channels u, u_x, u_t, u_xx
-            TermDesc& t = term(0, 0, 0); t.a0[1] = cfg->V; t.a0[2] = 1.0; t.a1[3] = -1.0;
-        } else if (vf == 1) {                                                    // P3:169-174
-            nT1 = 2;
-            TermDesc& t = term(0, 0, 0); t.a0[1] = cfg->V; t.a0[2] = 1.0;
-            term(1, 0, 1).a0[1] = 1.0;
-        } else { delete h; return fail(nullptr, -1, "AdvDiff var_form must be 0 or 1"); }
-    }
+    if (const char* bad = form_terms(cfg->pde, cfg->var_form, cfg->V, pd, nT1, nT2, mixed)) { delete h; return fail(nullptr, -1, "%s", bad); }
+    h->has_eps = pd.has_eps;
     h->nd_var = make_netdesc(*cfg, nT1, t1, nT2, t2);
     h->nd_eval = h->nd_var;
     if (mixed) {
@@ -610,7 +617,6 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
         h->nd_pinn.t2w[0] = 1.0; h->nd_pinn.t2w[1] = 1.0;
     } else if (cfg->scheme != HPV_SCHEME_VPINN) { delete h; return fail(nullptr, -1, "unknown scheme %d", cfg->scheme); }
     pd.C = h->nd_var.C;
-    pd.has_eps = h->has_eps;
     h->P = h->nd_var.P;
     h->Ptot = h->P + h->has_eps;
 
@@ -1464,42 +1470,54 @@ const char* hpv_build_info(void) {
     });
     return info.c_str();
 }
-int hpv_rule_advice(int device, int dim, int q, int ntx, int nty, long n_elem_shard, int exact_counts, int n_hidden, int* q_dev, int* nt_dev) {
-    if (!q_dev || !nt_dev || (dim != 1 && dim != 2) || q < 1 || ntx < 1 || n_elem_shard < 0) return -1;
-    *q_dev = q; *nt_dev = ntx;
-    int n_cus = 256;
+static int device_cus(int device) {      // 256 when no device can be queried
     hipDeviceProp_t prop;
-    if (device >= 0 && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
-    else (void)hipGetLastError();
-    if (dim == 1) {                                   // kernels_tile.hip: 80 points / 60 test functions (P1:237-238)
-        if (q > 80 || ntx > 60) return 0;
+    if (device >= 0 && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) return prop.multiProcessorCount;
+    (void)hipGetLastError();
+    return 256;
+}
+int hpv_rule_advice(int device, int pde, int var_form, int n_hidden, int max_width, int q, int ntx, int nty, long n_elem_shard, int* q_dev, int* nt_dev) {
+    ProjDesc pd;
+    NetDesc nd{};
+    bool mixed;
+    if (!q_dev || !nt_dev || q < 1 || ntx < 1 || n_elem_shard < 0 || form_terms(pde, var_form, 1.0, pd, nd.nT1, nd.nT2, mixed)) return -1;
+    *q_dev = q; *nt_dev = ntx;
+    const int n_cus = device_cus(device);
+    const bool net20 = max_width <= 20 && n_hidden >= 2;       // the element-resident kernels are written for 20-wide layers
+    if (pde == HPV_PDE_POISSON1D) {                   // kernels_tile.hip: 80 points / 60 test functions (P1:237-238), var_form 1 / 2, 2-4 hidden layers
+        if (var_form == 3 || !net20 || n_hidden > 4 || q > 80 || ntx > 60) return 0;
         if (q == 80) { *nt_dev = 60; return 0; }      // fewer test functions: the first 60, per-element counts
         if (n_elem_shard <= hpv_rule1d_pad_max(q, n_cus) && n_elem_shard <= hpv_elem_resident_max(1, 80, n_cus)) { *q_dev = 80; *nt_dev = 60; }
         return 0;
     }
-    static const int rules[4][2] = {{10, 5}, {12, 6}, {16, 8}, {20, 10}};     // kernels_fused.hip (k_iter_small, FZ_SHAPES)
-    for (const auto& r : rules) {
-        const bool counts_ok = exact_counts ? (ntx == r[1] && nty == r[1]) : (ntx <= r[1] && nty <= r[1]);
-        if (q <= r[0] && counts_ok) {
-            // (pad only while ONE WORKGROUP PER ELEMENT of that rule's kernel would take the shard -- the plan evaluated with the
-            //  network's depth and the element loop as built, exactly as launch_iter_fused evaluates it: where the loop (plan 2) or
-            //  the separate launches (plan 0) take the grid, the padded points cost more than the structure saves; advisor, round 5)
-            const int Lh = n_hidden > 0 ? n_hidden : 3;
-            const bool takes = r[0] == 10 ? n_elem_shard <= hpv_elem_resident_max(2, 10, n_cus)
-                                          : (hpv_fused_grid_plan(r[0], Lh, n_elem_shard, n_cus, hpv_fused_loop_built()) | 2) == 3;      // plans 1 and 3
-            if (q < r[0] && takes) *q_dev = r[0];
-            break;
-        }
+    if (pde == HPV_PDE_ADVDIFF && q <= 10) {          // kernels_tile.hip: 10x10 points, exactly 5x5 test functions (no run-time counts)
+        if (net20 && n_hidden <= 3 && ntx == 5 && nty == 5 && n_elem_shard <= hpv_elem_resident_max(2, 10, n_cus)) *q_dev = 10;
+        return 0;
     }
+    // k_iter_small / k_iter_fused: pad only while ONE WORKGROUP PER ELEMENT of the next rule's kernel takes the shard -- where the element
+    // loop (plan 2) or the separate launches (declined) take the grid, the padded points cost more than the structure saves
+    nd.d = 2; nd.act = HPV_ACT_TANH;                  // the 2-D classes' networks (P2:165, P3:226)
+    FusedShard in;
+    in.nd = &nd; in.L = n_hidden; in.n_cus = n_cus; in.n_elem = n_elem_shard;
+    in.H = max_width < 20 ? 20 : max_width;           // (narrower networks get the 20-wide answer, as they always have: DESIGN.md 8)
+    in.loop_any_form = true;                          // (the general forms never run the loop, yet the advice has always planned with it: DESIGN.md 8)
+    int q_rule;
+    const FusedPlan p = hpv_fused_plan_rule(in, pd, q, ntx, nty, &q_rule);
+    if (!p.declined && (p.gplan == 1 || p.gplan == 3)) *q_dev = q_rule;
     return 0;
 }
 int hpv_grid_plan(int device, int q, int n_hidden, long n_elem_shard) {
-    if ((q != 12 && q != 16 && q != 20) || n_hidden < 2 || n_hidden > 3 || n_elem_shard < 1) return -1;
-    int n_cus = 256;
-    hipDeviceProp_t prop;
-    if (device >= 0 && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cus = prop.multiProcessorCount;
-    else (void)hipGetLastError();
-    return hpv_fused_grid_plan(q, n_hidden, n_elem_shard, n_cus, hpv_fused_loop_built());
+    ProjDesc pd;
+    NetDesc nd{};
+    bool mixed;
+    (void)form_terms(HPV_PDE_POISSON2D, 1, 1.0, pd, nd.nT1, nd.nT2, mixed);
+    nd.d = 2; nd.act = HPV_ACT_TANH;
+    FusedShard in;
+    in.nd = &nd; in.H = 20; in.L = n_hidden; in.n_cus = device_cus(device); in.n_elem = n_elem_shard;
+    int q_rule;
+    const FusedPlan p = hpv_fused_plan_rule(in, pd, q, 1, 1, &q_rule);
+    if (q_rule != q || p.small || n_hidden < 2 || n_hidden > 3 || n_elem_shard < 1) return -1;
+    return p.declined ? 0 : p.gplan;
 }
 int hpv_updates_applied(hpv_handle h, long long* n) {
     if (!h || !n) return -1;

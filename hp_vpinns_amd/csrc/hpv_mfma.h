@@ -13,7 +13,7 @@ HPV_WIDE_WIDTHS(HPV_WIDE_DECL)
 #undef HPV_WIDE_DECL
 
 // Largest shard (elements) the element-resident whole-iteration kernel of a rule takes before the separate launches amortise the
-// per-element launch-once phases better; ONE definition for the launch functions (kernels_fused.hip, kernels_tile.hip) and for
+// per-element launch-once phases better; ONE definition for the plans (kernels_fused.hip, kernels_tile.hip) and through them for
 // hpv_rule_advice (the Python classes pad a smaller rule onto an instantiated one only while the kernel would take the shard).
 // q = points per direction of the instantiated rule, dim = 1 | 2.  Measured: scripts/elem_bench.py, scripts/grid_sweep.py,
 // scripts/rule1d_sweep.py (profiles/).
@@ -26,9 +26,7 @@ inline long hpv_elem_resident_max(int dim, int q, int n_cus) {
 }
 // How the whole-iteration kernel k_iter_fused takes a shard of n_elem elements of its 2-D rules (q = 12, 16, 20 points per direction):
 // 0 not at all (the separate launches), 1 one workgroup per element, 2 the element loop (gridDim = CUs workgroups walk the elements).
-// ONE definition for the dispatch (kernels_fused.hip) and for hpv_rule_advice (a smaller rule is padded onto an instantiated one only
-// while the kernel would take the shard).  Numbers behind it: profiles/r05_multi_element.md.
-bool hpv_fused_loop_built();      // kernels_fused.hip: the element loop (MULTI) survived the build guard
+// Evaluated in ONE place, hpv_fused_plan_shard below.  Numbers behind it: profiles/r05_multi_element.md.
 // 3 (round 6): the full rounds with one workgroup per element + the ragged tail (n_elem % n_cus elements, at most half a round) in a
 // second launch in SPLIT mode, 2 - 8 workgroups per element -- 1 600 elements of the config-4 shape: 6 rounds + a 64-element tail
 // instead of 7 rounds.  20x20-point elements from two full rounds on (see below).
@@ -62,9 +60,9 @@ int hpv_test_hook_split_skip();
 // Returns nullptr (and a reason) when the network shape is not covered by the fast path.
 HpvMfma* hpv_mfma_create(const NetDesc& nd, long N, std::string* why, bool need_store = true);
 void hpv_mfma_destroy(HpvMfma* m);
-int hpv_mfma_grad_rows(HpvMfma* m);
+int hpv_mfma_grad_rows(const HpvMfma* m);
 double* hpv_mfma_activation_store(HpvMfma* m);
-size_t hpv_mfma_activation_store_doubles(HpvMfma* m);
+size_t hpv_mfma_activation_store_doubles(const HpvMfma* m);
 // Boundary/data term evaluated inside the forward kernel for the data tiles of a merged batch.
 struct MfmaDataTerm {
     long data_off;        // first data point (multiple of 16)
@@ -89,6 +87,39 @@ bool hpv_mfma_backward_fused(HpvMfma* m, const double* theta, const double* X, c
 struct MfmaPendingAdam { AdamArgs ad; const double* g; int Ptot; };
 bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
                          const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaPendingAdam* pre = nullptr);
+// The decision behind it, in two halves that launch nothing and write nothing (kernels_fused.hip).  hpv_mfma_iter_fused plans, then
+// launches what the plan names; hpv_rule_advice / hpv_grid_plan ask the first half, which needs no handle.
+struct MfmaArgs;
+typedef void (*FusedLauncher)(const MfmaArgs&, int blocks, hipStream_t);
+// What the shape / form / grid half reads: the dispatch fills it from the handle, the advice with a fresh handle's defaults.
+struct FusedShard {
+    const NetDesc* nd = nullptr;                 // channel set and activation
+    int H = 0, L = 0, n_cus = 256;               // uniform hidden width, hidden layers, compute units
+    long n_elem = 0;
+    bool enabled = true, one_force = false;      // HPV_FUSE: the kernel is not switched off / =i: one workgroup per element on every grid
+    bool loop_store = true;                      // the activation store the element loop spills into exists
+    bool loop_off = false, loop_force = false;   // HPV_FUSE=1 / =m
+    bool loop_any_form = false;                  // the grid plan counts on the element loop for the general forms too (the advice: DESIGN.md 8)
+    bool tail_ok = true;                         // a ragged tail may run as a second launch in SPLIT mode
+    bool eps_ptr = true, pre = false;            // a trainable epsilon has its device pointer; a deferred update rides along
+};
+struct FusedPlan {
+    int declined = 0;             // the check at which the kernel declines the pass (0: it takes it) -- what HPV_TRACE_DISPATCH=1 prints
+    bool small = false;           // k_iter_small (10x10 points) instead of k_iter_fused
+    bool gen = false, counted = false, gs = false, pre = false;      // general form, per-element counts, GS, the update prologue
+    int nT2 = 0;
+    int gplan = 0;                // hpv_fused_grid_plan: 1 one workgroup per element | 2 the element loop | 3 full rounds + a SPLIT tail
+    int plan = 1;                 // instantiation: 0 SPLIT | 1 whole tiles | 2 quarter tiles | 3 / 4 = 1 / 2 inside the element loop
+    int split = 1, tsplit = 1;    // workgroups per element of the main / the tail launch
+    long n_main = 0, n_tail = 0, blocks = 0, rows_all = 0;      // elements of the two launches, workgroups of the first, gradient rows of both
+    FusedLauncher launch = nullptr, launch_tail = nullptr;       // resolved before anything is enqueued
+};
+FusedPlan hpv_fused_plan_shard(const FusedShard& in, const ProjDesc& pd);      // checks 1-15, 18, 33, 34
+FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTerm* dt, long n_elem, bool pre);
+// hpv_fused_plan_shard for the smallest instantiated rule that holds q points and ntx x nty test functions per direction (*q_rule; 0 and
+// declined when none does), with the whole-tile instantiation looked up: not declined and gplan 1 or 3 = one workgroup per element of
+// that rule's kernel takes the shard.  pd carries the form, in everything else.
+FusedPlan hpv_fused_plan_rule(const FusedShard& in, ProjDesc pd, int q, int ntx, int nty, int* q_rule);
 // The same for small elements of any channel set (kernels_tile.hip): one tile per wave, the tile's saved state in registers.
 // fin (optional): everything the finalize step needs; when the grid is ONE workgroup the kernel runs it itself and *fin_done
 // is set (the caller then skips k_finalize).

@@ -1857,17 +1857,19 @@ static void launch_iter_fused(const MfmaArgs& a, int blocks, hipStream_t s) {
     }
     hipLaunchKernelGGL((k_iter_fused<L, SPLIT, QT, GS, QX_, QY_, NTX_, NTY_, MULTI, NT2, GEN>), dim3(blocks), dim3(FZ_BLOCK), bytes, s, a);
 }
+// Instantiation lookups: plan 0 = SPLIT, 1 = whole tiles, 2 = quarter tiles (shapes with 0 / 1 mod 4 tiles), 3 / 4 = 1 / 2 walking several
+// elements per workgroup (MULTI: grids larger than the chip).  nullptr: that (shape, depth, plan, channel set, GS) is not instantiated
+// -- or compiled out by the build guard (csrc/build.sh).  The plan (hpv_fused_plan) asks BEFORE anything is enqueued.
 // The general forms (GEN: term weights, trainable epsilon; NT2 = 1: the mixed second tangent) are instantiated in a translation unit
-// of their own (kernels_fused_gen.hip = this file with HPV_FZ_GEN_TU): plan 0 = SPLIT, 1 = whole tiles, 2 = quarter tiles.
-// false: that (shape, depth, plan, channel set) is not instantiated -- or compiled out by the build guard (csrc/build.sh).
-bool hpv_fused_launch_gen(const ProjDesc& pd, int L, int plan, int nt2, const MfmaArgs& a, int blocks, hipStream_t s);
+// of their own (kernels_fused_gen.hip = this file with HPV_FZ_GEN_TU).
+FusedLauncher hpv_fused_launcher_gen(const ProjDesc& pd, int L, int plan, int nt2);
 const char* hpv_fused_gen_build_state();
 #ifdef HPV_FZ_GEN_TU
 template <int QX_, int QY_, int NTX_, int NTY_>
-static bool launch_iter_fused_gen_shape(int L, int plan, int nt2, const MfmaArgs& a, int blocks, hipStream_t s) {
+static FusedLauncher fused_launcher_gen_shape(int L, int plan, int nt2) {
     constexpr int TPE = QX_ * QY_ / 16;
-    constexpr bool HAS_QT = (TPE % 4) <= 1 && TPE >= 8;
-    constexpr bool HAS_DQ = HAS_QT && TPE % 4 == 0;            // four channels: the data-quarter plan only
+    [[maybe_unused]] constexpr bool HAS_QT = (TPE % 4) <= 1 && TPE >= 8;
+    [[maybe_unused]] constexpr bool HAS_DQ = HAS_QT && TPE % 4 == 0;            // four channels: the data-quarter plan only
     // (20x20 points keep four tiles per wave in the stash -- ABASE = 256 - 4 x 2 x 5 L: room for the fourth channel's registers with two
     //  hidden layers, a77 of 176, not with three, a159 of 136: three layers run the tight plan (FzPlan), whole tiles on whole elements only)
 #ifdef HPV_FZ_GEN_NO_TIGHT
@@ -1875,49 +1877,40 @@ static bool launch_iter_fused_gen_shape(int L, int plan, int nt2, const MfmaArgs
 #else
     constexpr bool HAS_TIGHT = true;
 #endif
-    const bool has_nt2 = QX_ != 20 || L == 2 || (HAS_TIGHT && plan <= 1);
-    if (L != 2 && L != 3) return false;
-#define FZ_GG(L_, SPLIT_, QT_, NT2_) launch_iter_fused<L_, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true>(a, blocks, s)
+    [[maybe_unused]] const bool has_nt2 = QX_ != 20 || L == 2 || (HAS_TIGHT && plan <= 1);
+    if (L != 2 && L != 3) return nullptr;
+#define FZ_GG(SPLIT_, QT_, NT2_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true> \
+                                         : &launch_iter_fused<3, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
+#define FZ_GG2(SPLIT_, QT_, NT2_) (&launch_iter_fused<2, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
     if (nt2 == 0) {
-        if (plan == 0) { if (L == 2) FZ_GG(2, true, false, 0); else FZ_GG(3, true, false, 0); }
-        else if (plan == 1) { if (L == 2) FZ_GG(2, false, false, 0); else FZ_GG(3, false, false, 0); }
-        else if (plan == 2) {
-#ifdef HPV_FZ_GEN_NO_QT
-            return false;
-#else
-            if constexpr (HAS_QT) { if (L == 2) FZ_GG(2, false, true, 0); else FZ_GG(3, false, true, 0); } else return false;
+        if (plan == 0) return FZ_GG(true, false, 0);
+        if (plan == 1) return FZ_GG(false, false, 0);
+#ifndef HPV_FZ_GEN_NO_QT
+        if constexpr (HAS_QT) if (plan == 2) return FZ_GG(false, true, 0);
 #endif
-        } else return false;
-        return true;
+        return nullptr;
     }
-#ifdef HPV_FZ_GEN_NO_NT2
-    return false;
-#else
+#ifndef HPV_FZ_GEN_NO_NT2
     if (has_nt2) {
-        if (plan == 0) { if (L == 2) FZ_GG(2, true, false, 1); else if constexpr (QX_ != 20 || HAS_TIGHT) FZ_GG(3, true, false, 1); }
-        else if (plan == 1) { if (L == 2) FZ_GG(2, false, false, 1); else if constexpr (QX_ != 20 || HAS_TIGHT) FZ_GG(3, false, false, 1); }
-        else if (plan == 2) {
-#ifdef HPV_FZ_GEN_NO_QT
-            return false;
-#else
-            if constexpr (HAS_DQ) { if (L == 2) FZ_GG(2, false, true, 1); else FZ_GG(3, false, true, 1); } else return false;
+        if (plan == 0) { if constexpr (QX_ != 20 || HAS_TIGHT) return FZ_GG(true, false, 1); else return L == 2 ? FZ_GG2(true, false, 1) : nullptr; }
+        if (plan == 1) { if constexpr (QX_ != 20 || HAS_TIGHT) return FZ_GG(false, false, 1); else return L == 2 ? FZ_GG2(false, false, 1) : nullptr; }
+#ifndef HPV_FZ_GEN_NO_QT
+        if constexpr (HAS_DQ) if (plan == 2) return FZ_GG(false, true, 1);
 #endif
-        } else return false;
-        return true;
-    } else return false;
+    }
 #endif
+    return nullptr;
+#undef FZ_GG2
 #undef FZ_GG
 }
-bool hpv_fused_launch_gen(const ProjDesc& pd, int L, int plan, int nt2, const MfmaArgs& a, int blocks, hipStream_t s) {
-#ifdef HPV_FZ_GEN_TRIPPED
-    return false;
-#else
+FusedLauncher hpv_fused_launcher_gen(const ProjDesc& pd, int L, int plan, int nt2) {
+#ifndef HPV_FZ_GEN_TRIPPED
 #define FZ_TRY(A_, B_, C_, D_) \
-    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return launch_iter_fused_gen_shape<A_, B_, C_, D_>(L, plan, nt2, a, blocks, s);
+    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return fused_launcher_gen_shape<A_, B_, C_, D_>(L, plan, nt2);
     FZ_SHAPES(FZ_TRY)
 #undef FZ_TRY
-    return false;
 #endif
+    return nullptr;
 }
 const char* hpv_fused_gen_build_state() {
 #if defined(HPV_FZ_GEN_TRIPPED)
@@ -1937,52 +1930,41 @@ const char* hpv_fused_gen_build_state() {
 #endif
 }
 #else    // ---- everything below: the main translation unit ----
-// One element shape: plan 0 = SPLIT, 1 = whole tiles, 2 = quarter tiles (shapes with 1 mod 4 tiles).  false: not instantiated.
-// (GS: the saved values travel through the activation store instead of AGPRs / LDS + recompute; HPV_FUSED_GSTASH=1 opts in; built
-//  for the 20x20 / 10x10 shape only)
-// plan 3 / 4 = plan 1 / 2 walking several elements per workgroup (MULTI: grids larger than the chip)
+// One element shape of the one-hot form.  (GS: the saved values travel through the activation store instead of AGPRs / LDS + recompute;
+// HPV_FUSED_GSTASH=1 opts in; built for the 20x20 / 10x10 shape only)
 template <int QX_, int QY_, int NTX_, int NTY_>
-static bool launch_iter_fused_shape(int L, int plan, bool gs, const MfmaArgs& a, int blocks, hipStream_t s) {
+static FusedLauncher fused_launcher_shape(int L, int plan, bool gs) {
 #ifdef HPV_EXPERIMENTS      // GS (measured slower: 67.8 against 60.6 us, profiles/r04_notes.md 6) is instantiated in libhpvpinn_testhooks.so only
     constexpr bool HAS_GS = QX_ == 20;
 #else
     constexpr bool HAS_GS = false;
 #endif
     constexpr bool HAS_QT = ((QX_ * QY_ / 16) % 4) <= 1 && QX_ * QY_ / 16 >= 8;     // (0 mod 4: the data-quarter plan)
-#define FZ_GO(L_, SPLIT_, QT_, GS_) launch_iter_fused<L_, SPLIT_, QT_, GS_, QX_, QY_, NTX_, NTY_>(a, blocks, s)
-    if (L != 2 && L != 3) return false;
-    if (gs) {
-        if constexpr (HAS_GS) {
-            if (plan == 0) { if (L == 2) FZ_GO(2, true, false, true); else FZ_GO(3, true, false, true); }
-            else if (plan == 1) { if (L == 2) FZ_GO(2, false, false, true); else FZ_GO(3, false, false, true); }
-            else { if (L == 2) FZ_GO(2, false, true, true); else FZ_GO(3, false, true, true); }
-            return true;
-        } else return false;
-    }
-#define FZ_GOM(L_, QT_) launch_iter_fused<L_, false, QT_, false, QX_, QY_, NTX_, NTY_, true>(a, blocks, s)
-    if (plan == 0) { if (L == 2) FZ_GO(2, true, false, false); else FZ_GO(3, true, false, false); }
-    else if (plan == 1) { if (L == 2) FZ_GO(2, false, false, false); else FZ_GO(3, false, false, false); }
+#define FZ_GO(SPLIT_, QT_, GS_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, GS_, QX_, QY_, NTX_, NTY_> : &launch_iter_fused<3, SPLIT_, QT_, GS_, QX_, QY_, NTX_, NTY_>)
     // (MULTI with three hidden layers on 20x20 points is not instantiated: inside the element loop the compiler parks the reverse
-    //  loop's accumulators in a104..a117 -- inside the stash, base a106, while later tiles' values are still there; fz_multi_built)
-    else if (plan == 3) { if (L == 2) FZ_GOM(2, false); else if constexpr (QX_ != 20) FZ_GOM(3, false); else return false; }
-    else if (plan == 4) {
-        if constexpr (HAS_QT) { if (L == 2) FZ_GOM(2, true); else if constexpr (QX_ != 20) FZ_GOM(3, true); else return false; }
-        else return false;
+    //  loop's accumulators in a104..a117 -- inside the stash, base a106, while later tiles' values are still there)
+#define FZ_GOM(QT_) { if (L == 2) return &launch_iter_fused<2, false, QT_, false, QX_, QY_, NTX_, NTY_, true>; \
+                      if constexpr (QX_ != 20) return &launch_iter_fused<3, false, QT_, false, QX_, QY_, NTX_, NTY_, true>; \
+                      return nullptr; }
+    if (L != 2 && L != 3) return nullptr;
+    if (gs) {
+        if constexpr (HAS_GS) return plan == 0 ? FZ_GO(true, false, true) : plan == 1 ? FZ_GO(false, false, true) : FZ_GO(false, true, true);
+        return nullptr;
     }
-    else {
-        if constexpr (HAS_QT) { if (L == 2) FZ_GO(2, false, true, false); else FZ_GO(3, false, true, false); }
-        else return false;
-    }
+    if (plan == 0) return FZ_GO(true, false, false);
+    if (plan == 1) return FZ_GO(false, false, false);
+    if (plan == 3) FZ_GOM(false)
+    if constexpr (HAS_QT) { if (plan == 4) FZ_GOM(true) return FZ_GO(false, true, false); }
+    return nullptr;
 #undef FZ_GOM
 #undef FZ_GO
-    return true;
 }
-static bool launch_iter_fused_any(const ProjDesc& pd, int L, int plan, bool gs, const MfmaArgs& a, int blocks, hipStream_t s) {
+static FusedLauncher fused_launcher(const ProjDesc& pd, int L, int plan, bool gs) {
 #define FZ_TRY(A_, B_, C_, D_) \
-    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return launch_iter_fused_shape<A_, B_, C_, D_>(L, plan, gs, a, blocks, s);
+    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return fused_launcher_shape<A_, B_, C_, D_>(L, plan, gs);
     FZ_SHAPES(FZ_TRY)
 #undef FZ_TRY
-    return false;
+    return nullptr;
 }
 static bool fused_shape_ok(const ProjDesc& pd) {
 #define FZ_TRY(A_, B_, C_, D_) if (pd.qx == A_ && pd.qy == B_ && pd.ntx >= 1 && pd.ntx <= C_ && pd.nty >= 1 && pd.nty <= D_) return true;
@@ -2002,60 +1984,52 @@ static void launch_iter_small(const MfmaArgs& a, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((k_iter_small<L>), dim3(blocks), dim3(SM_BLOCK), bytes, s, a);
 }
 
-// Whole training pass (forward, projection, reverse) of a shard of 20x20 / 10x10 elements in one launch.  Returns false
-// when the shape / variational form / shard is not covered; the caller then runs the separate kernels.
-// (libhpvpinn_testhooks.so: HPV_TRACE_DISPATCH=1 names the line at which the whole-iteration kernel declines a pass)
-#ifdef HPV_EXPERIMENTS
-#define fz_no(ID) (getenv("HPV_TRACE_DISPATCH") ? (fprintf(stderr, "hpv_mfma_iter_fused: declined at check %d (line %d)\n", ID, __LINE__), false) : false)
-#else
-#define fz_no(ID) false
-#endif
-bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                         const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaPendingAdam* pre) {
-    const ProjDesc& pd = pa.pd;
-    const NetDesc& nd = m->nd;
-    if (!m->iter_fused_ok) return fz_no(1);
-    if (m->H != MF_H) return fz_no(2);      // written for 20-wide layers (other widths: kernels_wide.hip)
-    if (!(nd.d == 2 && nd.nT1 == 2 && nd.nT2 <= 1 && nd.act == HPV_ACT_TANH) || m->L < 2 || m->L > 3) return fz_no(3);
-    const bool small = pd.qx == SM_QX && pd.qy == SM_QY && pd.ntx >= 1 && pd.ntx <= SM_NTX && pd.nty >= 1 && pd.nty <= SM_NTY;
-    if (!fused_shape_ok(pd) && !small) return fz_no(4);
-    const int NQ = pd.qx * pd.qy, TPE = NQ / 16;              // points and 16-point tiles of an element
-    const bool has_qt = TPE % 4 <= 1 && TPE >= 8, q20 = pd.qx == 20 && pd.qy == 20;
-    const bool base_shape = q20 && pd.ntx == 10 && pd.nty == 10;           // BASELINE config 4 itself
+// ---- the plan: does the whole-iteration kernel take this pass, and in which structure.  Launches nothing, writes nothing. ----
+#define FZ_NO(ID) do { p.declined = ID; return p; } while (0)
+// The half the network, the variational form and the size of the shard decide.
+FusedPlan hpv_fused_plan_shard(const FusedShard& in, const ProjDesc& pd) {
+    FusedPlan p;
+    const NetDesc& nd = *in.nd;
+    if (!in.enabled) FZ_NO(1);
+    if (in.H != MF_H) FZ_NO(2);      // written for 20-wide layers (other widths: kernels_wide.hip)
+    if (!(nd.d == 2 && nd.nT1 == 2 && nd.nT2 <= 1 && nd.act == HPV_ACT_TANH) || in.L < 2 || in.L > 3) FZ_NO(3);
+    p.small = pd.qx == SM_QX && pd.qy == SM_QY && pd.ntx >= 1 && pd.ntx <= SM_NTX && pd.nty >= 1 && pd.nty <= SM_NTY;
+    if (!fused_shape_ok(pd) && !p.small) FZ_NO(4);
+    const bool q20 = pd.qx == 20 && pd.qy == 20;
 #ifdef HPV_FZ_NO_EXTRA_SHAPES     // csrc/build.sh: the AGPR guard tripped in an instantiation of a shape other than 20x20 / 10x10
-    if (!q20 && !small) return fz_no(5);
+    if (!q20 && !p.small) FZ_NO(5);
 #endif
-    if (pd.edge || pd.nterms < 1 || pd.nterms > 2) return fz_no(6);
+    if (pd.edge || pd.nterms < 1 || pd.nterms > 2) FZ_NO(6);
     // per-element test-function counts (hpv_set_active_tests_2d): k_iter_fused honours them in every structure -- one workgroup per
     // element, the element loop, SPLIT (every partner projects the whole element) -- and says so in its name; k_iter_small does not
-    const bool counted = pd.nact != nullptr;
-    if (counted && (small || !pd.nacty)) return fz_no(34);
+    p.counted = pd.nact != nullptr;
+    if (p.counted && (p.small || !pd.nacty)) FZ_NO(34);
     // one-hot (Poisson-2D var_form 1, the headline instantiations): term t integrates exactly channel 1 + t with weight 1, no epsilon.
     // Every other form of these channel sets (round 6): the general instantiations (k_iter_fused<.., NT2, GEN>)
     bool onehot = !pd.has_eps && pd.nterms == 2 && nd.nT2 == 0;
     for (int t = 0; t < 2 && onehot; ++t)
         for (int ch = 0; ch < HPV_MAXC; ++ch)
             if (pd.t[t].a0[ch] != (ch == 1 + t ? 1.0 : 0.0) || pd.t[t].a1[ch] != 0.0 || pd.t[t].eps_mult) onehot = false;
-    const bool gen = !onehot;
-    const int C = 3 + nd.nT2;
-    if (gen) {
-        if (small) return fz_no(7);                            // (10x10 points: kernels_tile.hip)
+    p.gen = !onehot;
+    p.nT2 = nd.nT2;
+    if (p.gen) {
+        if (p.small) FZ_NO(7);                            // (10x10 points: kernels_tile.hip)
         for (int t = 0; t < pd.nterms; ++t) {
-            if (pd.t[t].a0[0] != 0.0 || pd.t[t].a1[0] != 0.0) return fz_no(8);       // the value channel is not integrated here
-            for (int ch = C; ch < HPV_MAXC; ++ch) if (pd.t[t].a0[ch] != 0.0 || pd.t[t].a1[ch] != 0.0) return fz_no(9);
+            if (pd.t[t].a0[0] != 0.0 || pd.t[t].a1[0] != 0.0) FZ_NO(8);       // the value channel is not integrated here
+            for (int ch = 3 + nd.nT2; ch < HPV_MAXC; ++ch) if (pd.t[t].a0[ch] != 0.0 || pd.t[t].a1[ch] != 0.0) FZ_NO(9);
             // two terms fill both LDS arrays: none is left for dG / d eps of a term whose WEIGHTS depend on epsilon
-            if (pd.nterms == 2) for (int ch = 0; ch < HPV_MAXC; ++ch) if (pd.t[t].a1[ch] != 0.0) return fz_no(10);
+            if (pd.nterms == 2) for (int ch = 0; ch < HPV_MAXC; ++ch) if (pd.t[t].a1[ch] != 0.0) FZ_NO(10);
         }
-        if (pd.has_eps && !pa.eps_ptr) return fz_no(11);
-        if (pre && pd.has_eps) return fz_no(12);                // the deferred-update prologue forms the network parameters only
+        if (pd.has_eps && !in.eps_ptr) FZ_NO(11);
+        if (in.pre && pd.has_eps) FZ_NO(12);                // the deferred-update prologue forms the network parameters only
     }
-    if (n_elem <= 0) return fz_no(13);
+    if (in.n_elem <= 0) FZ_NO(13);
     // the tight plan (four channels, three hidden layers, 20x20 points: whole tiles 7 + 7 + 6 + 6) gains 12 % on one round of elements, 5 % on
     // two (552 elements: 196.3 against 207.1 us) and nothing from six on (1 600: 516.0 against 513.8 -- the separate launches amortise
     // to 82 us per 256 elements there): profiles/r06_tight_plan.txt
-    if (gen && nd.nT2 == 1 && q20 && m->L == 3 && n_elem > 5L * m->n_cus && !m->iter_fused_force) return fz_no(33);
+    if (p.gen && nd.nT2 == 1 && q20 && in.L == 3 && in.n_elem > 5L * in.n_cus && !in.one_force) FZ_NO(33);
 #ifdef HPV_AGPR_GUARD_TRIPPED     // csrc/build.sh: the compiler's registers reached the hand-managed AGPR range of k_iter_fused
-    if (!small) return fz_no(14);
+    if (!p.small) FZ_NO(14);
 #endif
     // shapes other than the headline one: one workgroup per element pays the launch-once phases (staging, projection, epilogue:
     // ~7 us) per element -- on grids of many small elements the separate launches amortise them better (scripts/elem_bench.py:
@@ -2071,66 +2045,126 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
 #endif
     // (plan 3, round 6: the full rounds with one workgroup per element and, in a SECOND launch, the ragged tail's elements shared by
     //  2 - 8 workgroups each (SPLIT) -- needs the exchange machinery of the split mode)
-    const bool tail_ok = m->xerr && m->xg && m->xiter && m->iter_split_ok && !pre;
-    int gplan = small ? 1 : hpv_fused_grid_plan(pd.qx, m->L, n_elem, m->n_cus, !gen && multi_built && m->base.ACTS != nullptr, m->multi_off, m->multi_force && !gen, m->iter_fused_force, tail_ok);
-    if (gplan == 0) return fz_no(15);
-    const bool multi = gplan == 2;
-    long n_tail = 0;
-    int tsplit = 1;
-    if (gplan == 3) {
-        n_tail = n_elem % m->n_cus;
-        while (tsplit < 8 && n_tail * tsplit * 2 <= m->n_cus) tsplit *= 2;
-        const long data_tiles = m->ntiles - n_elem * TPE;
-        if (tsplit < 2 || n_tail > m->xsync_elems || (size_t)n_tail * 2 * NQ * 2 > m->xg_words || data_tiles > n_tail * tsplit) {
+    p.gplan = p.small ? 1 : hpv_fused_grid_plan(pd.qx, in.L, in.n_elem, in.n_cus, (!p.gen || in.loop_any_form) && multi_built && in.loop_store,
+                                                 in.loop_off, in.loop_force && !p.gen, in.one_force, in.tail_ok);
+    if (p.gplan == 0) FZ_NO(15);
+    // thousands of small elements: one workgroup per element pays staging / projection / epilogue per element, the separate
+    // launches stream (scripts/grid_sweep.py: 1 024 elements 80.8 against 77.5 us, 4 096 elements 292 against 273)
+    if (p.small && in.n_elem > hpv_elem_resident_max(2, SM_QX, in.n_cus) && !in.one_force) FZ_NO(18);
+    return p;
+}
+// The whole plan: + what the handle's buffers, the batch layout and the instantiations of this build decide.
+FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTerm* dt, long n_elem, bool pre) {
+    const ProjDesc& pd = pa.pd;
+    const bool xchg = m.xerr && m.xg && m.xiter && m.iter_split_ok;      // the exchange machinery of the split mode
+    FusedShard in;
+    in.nd = &m.nd; in.H = m.H; in.L = m.L; in.n_cus = m.n_cus; in.n_elem = n_elem;
+    in.enabled = m.iter_fused_ok; in.one_force = m.iter_fused_force;
+    in.loop_store = m.base.ACTS != nullptr; in.loop_off = m.multi_off; in.loop_force = m.multi_force;
+    in.tail_ok = xchg && !pre; in.eps_ptr = pa.eps_ptr != nullptr; in.pre = pre;
+    FusedPlan p = hpv_fused_plan_shard(in, pd);
+    if (p.declined) return p;
+    p.pre = pre;
+    const int NQ = pd.qx * pd.qy, TPE = NQ / 16;              // points and 16-point tiles of an element
+    const bool multi = p.gplan == 2;
+    const auto launcher = [&](int plan, bool gs) { return p.gen ? hpv_fused_launcher_gen(pd, m.L, plan, p.nT2) : fused_launcher(pd, m.L, plan, gs); };
+    if (p.gplan == 3) {
+        p.n_tail = n_elem % m.n_cus;
+        while (p.tsplit < 8 && p.n_tail * p.tsplit * 2 <= m.n_cus) p.tsplit *= 2;
+        const long data_tiles = m.ntiles - n_elem * TPE;
+        p.launch_tail = launcher(0, false);
+        if (p.tsplit < 2 || p.n_tail > m.xsync_elems || (size_t)p.n_tail * 2 * NQ * 2 > m.xg_words || data_tiles > p.n_tail * p.tsplit || !p.launch_tail) {
             // (the tail cannot run in split mode: whole rounds as before)
-            const long rounds = (n_elem + m->n_cus - 1) / m->n_cus;
-            if (n_elem * 100 < rounds * m->n_cus * 80) return fz_no(16);
-            n_tail = 0; gplan = 1;
+            const long rounds = (n_elem + m.n_cus - 1) / m.n_cus;
+            if (n_elem * 100 < rounds * m.n_cus * 80) FZ_NO(16);
+            p.n_tail = 0; p.tsplit = 1; p.launch_tail = nullptr; p.gplan = 1;
         }
     }
-    const long n_main = n_elem - n_tail;
-    if (pre && (small || multi || nd.P > FZ_PRE_PER_THREAD * FZ_BLOCK)) return fz_no(17);       // the deferred-update prologue exists in the one-workgroup-per-element / SPLIT instantiations
-    if (small) {
-        // thousands of small elements: one workgroup per element pays staging / projection / epilogue per element, the separate
-        // launches stream (scripts/grid_sweep.py: 1 024 elements 80.8 against 77.5 us, 4 096 elements 292 against 273)
-        if (n_elem > hpv_elem_resident_max(2, SM_QX, m->n_cus) && !m->iter_fused_force) return fz_no(18);
+    p.n_main = n_elem - p.n_tail;
+    if (pre && (p.small || multi || m.nd.P > FZ_PRE_PER_THREAD * FZ_BLOCK)) FZ_NO(17);       // the deferred-update prologue exists in the one-workgroup-per-element / SPLIT instantiations
+    const bool has_data = dt && dt->n_data > 0;
+    if (p.small) {
         // batch layout [element points | pad to 16 | data points]; at most one boundary/data tile per workgroup
         const long npad = (n_elem * SM_NQ + 15) / 16 * 16;
-        const bool has_data = dt && dt->n_data > 0;
-        if (has_data ? dt->data_off != npad : (m->N != npad && m->N != n_elem * SM_NQ)) return fz_no(19);
-        if (has_data && m->ntiles - npad / 16 > n_elem) return fz_no(20);
-        if (n_elem > hpv_mfma_grad_rows(m) && n_elem > m->max_rows) return fz_no(21);
-        MfmaArgs a = m->base;
-        a.theta = theta; a.X = X; a.GPART = GPART;
-        a.OUT = const_cast<double*>(pa.OUT);   // (only written by the -DHPV_FZ_TIMING build)
-        a.data_off = -1;
-        if (has_data) {
-            a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-            a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-        }
-        a.proj_n_elem = n_elem;
-        a.proj_split = 1;
-        a.pa = pa;
-        m->last_split = false;
-        if (pd.ntx == SM_NTX && pd.nty == SM_NTY) snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d>", m->L);
-        else snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d,10x10/%dx%d>", m->L, pd.ntx, pd.nty);
-        if (m->L == 2) launch_iter_small<2>(a, (int)n_elem, s); else launch_iter_small<3>(a, (int)n_elem, s);
-        if (rows) *rows = (int)n_elem;
-        return true;
+        if (has_data ? dt->data_off != npad : (m.N != npad && m.N != n_elem * SM_NQ)) FZ_NO(19);
+        if (has_data && m.ntiles - npad / 16 > n_elem) FZ_NO(20);
+        if (n_elem > hpv_mfma_grad_rows(&m) && n_elem > m.max_rows) FZ_NO(21);
+        p.blocks = p.rows_all = n_elem;
+        p.launch = m.L == 2 ? &launch_iter_small<2> : &launch_iter_small<3>;
+        return p;
     }
     // small shards (the multi-GPU runs of config 4): an element is shared by 2 / 4 / 8 workgroups so that every CU works; the
     // partners meet at a barrier in device memory, which needs all of them resident: at most one workgroup per CU
-    int split = 1;
-    if (n_elem * 2 <= m->n_cus && !m->iter_fused_force) {
-        if (!m->xerr || !m->xg || !m->xiter || !m->iter_split_ok) return fz_no(22);
-        while (split < 8 && n_elem * split * 2 <= m->n_cus) split *= 2;
-        if (n_elem * split > m->n_cus || n_elem > m->xsync_elems || (size_t)n_elem * 2 * NQ * 2 > m->xg_words) return fz_no(23);
+    if (n_elem * 2 <= m.n_cus && !m.iter_fused_force) {
+        if (!xchg) FZ_NO(22);
+        while (p.split < 8 && n_elem * p.split * 2 <= m.n_cus) p.split *= 2;
+        if (n_elem * p.split > m.n_cus || n_elem > m.xsync_elems || (size_t)n_elem * 2 * NQ * 2 > m.xg_words) FZ_NO(23);
     }
-    const long blocks = multi ? (long)m->n_cus : n_main * split;
-    const long rest = m->ntiles - n_elem * TPE;                  // pad + boundary/data tiles: at most one per workgroup
-    if (rest < 0 || (n_tail == 0 && rest > blocks)) return fz_no(24);
-    const long rows_all = blocks + n_tail * tsplit;
-    if (rows_all > hpv_mfma_grad_rows(m) && rows_all > m->max_rows) return fz_no(25);
+    p.blocks = multi ? (long)m.n_cus : p.n_main * p.split;
+    const long rest = m.ntiles - n_elem * TPE;                  // pad + boundary/data tiles: at most one per workgroup
+    if (rest < 0 || (p.n_tail == 0 && rest > p.blocks)) FZ_NO(24);
+    p.rows_all = p.blocks + p.n_tail * p.tsplit;
+    if (p.rows_all > hpv_mfma_grad_rows(&m) && p.rows_all > m.max_rows) FZ_NO(25);
+    if (!has_data && rest > 0) FZ_NO(26);    // tiles behind the elements but no data term: not a layout this kernel knows
+    // GS is opt-in (HPV_FUSED_GSTASH=1): measured 67.8 against 60.6 us at config 4 -- the reverse phase does shrink (73.1 k -> 60.9 k
+    // cycles) but the forward phase pays for its stores (42.9 k -> 49.4 k: the four waves' bursts share one 64 B/clk path), and with
+    // 220 MB of extra traffic per iteration the chip clocks 10 % lower (1.94 against 2.16 GHz); profiles/r04_notes.md
+#ifdef HPV_EXPERIMENTS
+    const char* ge = getenv("HPV_FUSED_GSTASH");
+    p.gs = pd.qx == 20 && pd.qy == 20 && m.base.ACTS != nullptr && ge && ge[0] == '1';
+#endif
+    // the prologue is paid per WORKGROUP: worth it only where every workgroup is resident at once (one round); on larger grids the caller's
+    // k_adam launch in front of the pass is cheaper (4 096 elements: +12.3 us against +4.5)
+    if (pre && (p.gs || p.blocks > (long)m.n_cus)) FZ_NO(27);
+    // MULTI spills 45 doubles per lane into the activation store: [workgroup][wave][slot][64] -- it must hold that (it is sized for
+    // the separate launches' slots of every tile: far larger on any grid that takes this branch)
+    if (multi && (size_t)p.blocks * FZ_WAVES * 64 * 48 > hpv_mfma_activation_store_doubles(&m)) FZ_NO(28);
+    p.plan = 2;
+    if (p.split > 1) p.plan = 0;
+#ifdef HPV_AGPR_GUARD_TRIPPED_QT                    // csrc/build.sh: the compiler's registers reached the stash of the QT instantiation
+    else if (!p.gs) p.plan = 1;
+#endif
+    else if (!(TPE % 4 <= 1 && TPE >= 8) || getenv("HPV_NO_QUARTER_TILE")) p.plan = 1;      // (A/B switch: whole tiles only, read per launch / capture)
+    if (p.gen && p.plan == 2 && p.nT2 == 1 && TPE % 4 != 0) p.plan = 1;    // four channels: the packed quarter has room for the data points only
+    if (multi) p.plan += 2;                                                // plans 3 / 4: several elements per workgroup
+    if (p.gen && (p.gs || multi)) FZ_NO(29);
+    p.launch = launcher(p.plan, p.gs);
+    if (!p.launch && p.gen && p.plan == 2) p.launch = launcher(p.plan = 1, false);      // (a quarter-tile instantiation the build guard compiled out: whole tiles)
+    if (!p.launch) FZ_NO(p.gen ? 30 : 31);
+    return p;
+}
+FusedPlan hpv_fused_plan_rule(const FusedShard& in, ProjDesc pd, int q, int ntx, int nty, int* q_rule) {
+    static const int rules[][4] = {
+#define FZ_ROW(A_, B_, C_, D_) {A_, B_, C_, D_},
+        FZ_SHAPES(FZ_ROW) {SM_QX, SM_QY, SM_NTX, SM_NTY}};
+#undef FZ_ROW
+    const int* fit = nullptr;
+    for (const auto& r : rules)
+        if (r[0] == r[1] && q <= r[0] && ntx <= r[2] && nty <= r[3] && (!fit || r[0] < fit[0])) fit = r;
+    FusedPlan p;
+    *q_rule = fit ? fit[0] : 0;
+    if (!fit) FZ_NO(4);
+    pd.qx = pd.qy = fit[0]; pd.ntx = ntx; pd.nty = nty;
+    p = hpv_fused_plan_shard(in, pd);
+    if (!p.declined && !p.small && !(p.gen ? hpv_fused_launcher_gen(pd, in.L, 1, p.nT2) : fused_launcher(pd, in.L, 1, false))) FZ_NO(p.gen ? 30 : 31);
+    return p;
+}
+#undef FZ_NO
+
+// Whole training pass (forward, projection, reverse) of a shard of 20x20 / 10x10 elements in one launch.  Returns false
+// when the shape / variational form / shard is not covered (hpv_fused_plan; nothing has been launched then); the caller then runs the
+// separate kernels.  (libhpvpinn_testhooks.so: HPV_TRACE_DISPATCH=1 names the check at which the plan declines a pass)
+bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
+                         const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaPendingAdam* pre) {
+    const FusedPlan p = hpv_fused_plan(*m, pa, dt, n_elem, pre != nullptr);
+    if (p.declined) {
+#ifdef HPV_EXPERIMENTS
+        if (getenv("HPV_TRACE_DISPATCH")) fprintf(stderr, "hpv_mfma_iter_fused: declined at check %d\n", p.declined);
+#endif
+        return false;
+    }
+    const ProjDesc& pd = pa.pd;
+    const int TPE = pd.qx * pd.qy / 16;
     MfmaArgs a = m->base;
     a.theta = theta; a.X = X; a.GPART = GPART;
     a.OUT = const_cast<double*>(pa.OUT);   // SPLIT: the partners' channel exchange; otherwise only written by the -DHPV_FZ_TIMING build
@@ -2138,78 +2172,50 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
     if (dt && dt->n_data > 0) {
         a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
         a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    } else if (rest > 0) {
-        return fz_no(26);    // tiles behind the elements but no data term: not a layout this kernel knows
     }
-    a.proj_n_elem = n_main;
-    a.proj_split = split;
-    a.elem0 = 0;
-    a.data_tile0 = n_elem * TPE;
-    // (a ragged tail: the boundary / data tiles ride in the tail's launch -- this one sees a batch that ends behind its elements)
-    if (n_tail > 0) a.ntiles = n_main * TPE;
-    if (pre) { a.pre_g = pre->g; a.pre_Ptot = pre->Ptot; a.pre_ad = pre->ad; }
-    a.xerr = m->xerr;
-    a.xdebug_skip = m->xdebug_skip;
-    a.xg = m->xg;
-    a.xiter = m->xiter;
+    a.proj_n_elem = p.n_main;
+    a.proj_split = p.split;
     a.pa = pa;
-    // GS is opt-in (HPV_FUSED_GSTASH=1): measured 67.8 against 60.6 us at config 4 -- the reverse phase does shrink (73.1 k -> 60.9 k
-    // cycles) but the forward phase pays for its stores (42.9 k -> 49.4 k: the four waves' bursts share one 64 B/clk path), and with
-    // 220 MB of extra traffic per iteration the chip clocks 10 % lower (1.94 against 2.16 GHz); profiles/r04_notes.md
-#ifdef HPV_EXPERIMENTS
-    const char* ge = getenv("HPV_FUSED_GSTASH");
-    const bool gs = q20 && a.ACTS != nullptr && ge && ge[0] == '1';
-#else
-    constexpr bool gs = false;
-#endif
-    // the prologue is paid per WORKGROUP: worth it only where every workgroup is resident at once (one round); on larger grids the caller's
-    // k_adam launch in front of the pass is cheaper (4 096 elements: +12.3 us against +4.5)
-    if (pre && (gs || blocks > (long)m->n_cus)) return fz_no(27);
-    // MULTI spills 45 doubles per lane into the activation store: [workgroup][wave][slot][64] -- it must hold that (it is sized for
-    // the separate launches' slots of every tile: far larger on any grid that takes this branch)
-    if (multi && (size_t)blocks * FZ_WAVES * 64 * 48 > hpv_mfma_activation_store_doubles(m)) return fz_no(28);
-    int plan = 2;
-    if (split > 1) plan = 0;
-#ifdef HPV_AGPR_GUARD_TRIPPED_QT                    // csrc/build.sh: the compiler's registers reached the stash of the QT instantiation
-    else if (!gs) plan = 1;
-#endif
-    else if (!has_qt || getenv("HPV_NO_QUARTER_TILE")) plan = 1;      // (A/B switch: whole tiles only, read per launch / capture)
-    if (gen && plan == 2 && nd.nT2 == 1 && TPE % 4 != 0) plan = 1;    // four channels: the packed quarter has room for the data points only
-    if (multi) plan += 2;                                              // plans 3 / 4: several elements per workgroup
-    if (gen) {
-        if (gs || multi) return fz_no(29);
-        if (!hpv_fused_launch_gen(pd, m->L, plan, nd.nT2, a, (int)blocks, s)) {
-            // (a quarter-tile instantiation the build guard compiled out: whole tiles)
-            if (plan != 2 || !hpv_fused_launch_gen(pd, m->L, plan = 1, nd.nT2, a, (int)blocks, s)) return fz_no(30);
-        }
-    } else
-    if (!launch_iter_fused_any(pd, m->L, plan, gs, a, (int)blocks, s)) return fz_no(31);
-    if (n_tail > 0) {
+    if (!p.small) {
+        a.elem0 = 0;
+        a.data_tile0 = n_elem * TPE;
+        // (a ragged tail: the boundary / data tiles ride in the tail's launch -- this one sees a batch that ends behind its elements)
+        if (p.n_tail > 0) a.ntiles = p.n_main * TPE;
+        if (pre) { a.pre_g = pre->g; a.pre_Ptot = pre->Ptot; a.pre_ad = pre->ad; }
+        a.xerr = m->xerr;
+        a.xdebug_skip = m->xdebug_skip;
+        a.xg = m->xg;
+        a.xiter = m->xiter;
+        m->pre_used = pre != nullptr;
+    }
+    p.launch(a, (int)p.blocks, s);
+    if (p.n_tail > 0) {
         // the ragged tail: elements n_main .. n_elem - 1, tsplit workgroups each, gradient rows behind the first launch's
         MfmaArgs b = a;
         b.ntiles = m->ntiles;
-        b.proj_n_elem = n_tail;
-        b.proj_split = tsplit;
-        b.elem0 = n_main;
-        b.GPART = GPART + blocks * (long)nd.P;
-        const bool ok = gen ? hpv_fused_launch_gen(pd, m->L, 0, nd.nT2, b, (int)(n_tail * tsplit), s)
-                            : launch_iter_fused_any(pd, m->L, 0, false, b, (int)(n_tail * tsplit), s);
-        if (!ok) return fz_no(32);      // (cannot happen for an instantiated shape: plan 0 exists wherever plans 1 / 2 do)
+        b.proj_n_elem = p.n_tail;
+        b.proj_split = p.tsplit;
+        b.elem0 = p.n_main;
+        b.GPART = GPART + p.blocks * (long)m->nd.P;
+        p.launch_tail(b, (int)(p.n_tail * p.tsplit), s);
     }
-    m->last_split = split > 1 || n_tail > 0;
-    if (split > 1 || n_tail > 0) m->split_used = true;
+    m->last_split = p.split > 1 || p.n_tail > 0;
+    if (m->last_split) m->split_used = true;
     char shp[64] = "";
-    if (!base_shape || gen) snprintf(shp, sizeof shp, ",%dx%d/%dx%d%s", pd.qx, pd.qy, pd.ntx, pd.nty, gen ? (nd.nT2 ? ",NT2=1,GEN" : ",GEN") : "");
-    if (counted) snprintf(shp + strlen(shp), sizeof shp - strlen(shp), ",NACT");
-    if (split > 1) snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=true,QT=false,GS=%s%s> split=%d", m->L, gs ? "true" : "false", shp, split);
-    else snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=false,QT=%s,GS=%s%s>%s", m->L, (plan == 2 || plan == 4) ? "true" : "false",
-                  gs ? "true" : "false", shp, multi ? " elements-per-workgroup>1" : "");
-    if (n_tail > 0) {
+    const bool base_shape = pd.qx == 20 && pd.qy == 20 && pd.ntx == 10 && pd.nty == 10;           // BASELINE config 4 itself
+    if (!base_shape || p.gen) snprintf(shp, sizeof shp, ",%dx%d/%dx%d%s", pd.qx, pd.qy, pd.ntx, pd.nty, p.gen ? (p.nT2 ? ",NT2=1,GEN" : ",GEN") : "");
+    if (p.counted) snprintf(shp + strlen(shp), sizeof shp - strlen(shp), ",NACT");
+    const char* gs = p.gs ? "true" : "false";
+    if (p.small && pd.ntx == SM_NTX && pd.nty == SM_NTY) snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d>", m->L);
+    else if (p.small) snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d,10x10/%dx%d>", m->L, pd.ntx, pd.nty);
+    else if (p.split > 1) snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=true,QT=false,GS=%s%s> split=%d", m->L, gs, shp, p.split);
+    else snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=false,QT=%s,GS=%s%s>%s", m->L, (p.plan == 2 || p.plan == 4) ? "true" : "false",
+                  gs, shp, p.plan >= 3 ? " elements-per-workgroup>1" : "");
+    if (p.n_tail > 0) {
         const size_t l = strlen(m->variant);
-        snprintf(m->variant + l, sizeof m->variant - l, " + SPLIT=true split=%d on the last %ld elements", tsplit, n_tail);
+        snprintf(m->variant + l, sizeof m->variant - l, " + SPLIT=true split=%d on the last %ld elements", p.tsplit, p.n_tail);
     }
-    m->pre_used = pre != nullptr;
-    if (rows) *rows = (int)rows_all;
+    if (rows) *rows = (int)p.rows_all;
     return true;
 }
 
@@ -2229,15 +2235,5 @@ void hpv_mfma_set_split_ok(HpvMfma* m, bool on) {
     if (!m) return;
     const char* e = getenv("HPV_FUSE");
     m->iter_split_ok = on && !(e && e[0] == 's');
-}
-
-// the element loop (MULTI instantiations) is in this build (csrc/build.sh compiles them out when their AGPR guard trips); read by
-// hpv_rule_advice so that its plan is the dispatch's
-bool hpv_fused_loop_built() {
-#ifdef HPV_FZ_NO_MULTI
-    return false;
-#else
-    return true;
-#endif
 }
 #endif   // HPV_FZ_GEN_TU

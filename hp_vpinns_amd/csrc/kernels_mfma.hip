@@ -801,7 +801,7 @@ void hpv_mfma_destroy(HpvMfma* m) {
     delete m;
 }
 
-int hpv_mfma_grad_rows(HpvMfma* m) { return m->bwd_blocks; }
+int hpv_mfma_grad_rows(const HpvMfma* m) { return m->bwd_blocks; }
 const char* hpv_mfma_variant(HpvMfma* m, int which) {
     if (!m) return "";
     return which == 0 ? m->variant : (which == 1 ? m->vfwd : (which == 2 ? m->vbwd : m->vbwd_fused));
@@ -809,7 +809,7 @@ const char* hpv_mfma_variant(HpvMfma* m, int which) {
 unsigned int* hpv_mfma_xiter(HpvMfma* m) { return m ? m->xiter : nullptr; }
 bool hpv_mfma_prefers_elem(HpvMfma* m) { return m && m->prefer_elem; }
 double* hpv_mfma_activation_store(HpvMfma* m) { return m ? m->ACTS : nullptr; }
-size_t hpv_mfma_activation_store_doubles(HpvMfma* m) { return m && m->ACTS ? (size_t)m->ntiles * m->L * m->ns * m->ks * 64 : 0; }   // (the timing builds park their stamps there)
+size_t hpv_mfma_activation_store_doubles(const HpvMfma* m) { return m && m->ACTS ? (size_t)m->ntiles * m->L * m->ns * m->ks * 64 : 0; }   // (the timing builds park their stamps there)
 // Workgroups per element of the fused reverse kernel: one when the shard has an element for every CU, more for the
 // small shards of a multi-GPU run (each workgroup walks 1/split of the element's 25 tiles).
 static int fused_split(HpvMfma* m, long n_elem) {

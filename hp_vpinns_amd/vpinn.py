@@ -66,9 +66,9 @@ def _tensor_rule(X_quad, W_quad):
     return xi, wx, yi, wy
 
 
-# Quadrature rules the element-resident whole-iteration kernels are instantiated for, and the shard sizes up to which each of
-# them runs one workgroup per element, live in the LIBRARY (csrc/hpv_mfma.h: hpv_elem_resident_max, hpv_rule1d_pad_max -- the
-# same functions gate the launches); `_lib.rule_advice` (hpv_rule_advice) answers for this rank's shard on this rank's device.
+# Quadrature rules the element-resident whole-iteration kernels are instantiated for, the forms and networks they take and the shard
+# sizes up to which each of them runs one workgroup per element live in the LIBRARY (csrc/hpv_mfma.h, the plan of the dispatch itself);
+# `_lib.rule_advice` (hpv_rule_advice) answers for this problem and this rank's shard on this rank's device.
 
 
 def _pad_rule(xi, w, q_dev):
@@ -82,26 +82,13 @@ def _pad_rule(xi, w, q_dev):
     return np.concatenate([xi, np.full(n, xi[-1])]), np.concatenate([w, np.zeros(n)])
 
 
-def _device_rule_2d(xi, wx, yi, wy, ntx, nty, n_elem_shard, device=0, exact_counts=False, only=None, n_hidden=0, reject=()):
-    """The (possibly padded) 2-D rule for the device, as the library advises for a shard of `n_elem_shard` elements on `device`;
-    `exact_counts`: only instantiations with exactly these test-function counts; `only`: accept this device rule alone;
-    `reject`: device rules whose whole-iteration kernel does not take this variational form."""
-    if xi.size != yi.size or os.environ.get("HPV_NO_RULE_PADDING"):
+def _device_rule_2d(xi, wx, yi, wy, ntx, nty, n_elem_shard, pde, var_form, hidden, device=0, backend="auto"):
+    """The (possibly padded) 2-D rule for the device, as the library advises for problem `pde` in form `var_form` under a network of
+    `hidden` layer widths and a shard of `n_elem_shard` elements on `device`."""
+    if xi.size != yi.size or backend == "generic" or os.environ.get("HPV_NO_RULE_PADDING"):
         return xi, wx, yi, wy
-    q_dev, _ = _lib.rule_advice(device, 2, xi.size, ntx, nty, n_elem_shard, exact_counts, n_hidden)
-    if q_dev > xi.size and (only is None or q_dev == only) and q_dev not in reject:
-        xi, wx = _pad_rule(xi, wx, q_dev)
-        yi, wy = _pad_rule(yi, wy, q_dev)
-    return xi, wx, yi, wy
-
-
-def _n_cus(device):
-    """Compute units of the device (the tight plan of the whole-iteration kernel is dispatched up to five rounds of elements)."""
-    try:
-        import torch
-        return int(torch.cuda.get_device_properties(device).multi_processor_count)
-    except Exception:      # pragma: no cover - no device: the constructors fail later, loudly
-        return 256
+    q_dev, _ = _lib.rule_advice(device, pde, var_form, len(hidden), max(hidden), xi.size, ntx, nty, n_elem_shard)
+    return _pad_rule(xi, wx, q_dev) + _pad_rule(yi, wy, q_dev)
 
 
 def _caller_globals(depth=2):
@@ -660,15 +647,13 @@ class VPINN1D(_VPINNBase):
         #     h-refined grid of 10 k elements x 10 points must NOT run 8x the points and 12x the test functions).
         # Everywhere else (generic backend, var_form 3, wider / deeper networks) the device sees the problem as it is.
         hidden = self.layers[1:-1]
-        tile_ok = (backend != "generic" and var_form in (1, 2) and max(hidden) <= 20 and 2 <= len(hidden) <= 4
-                   and self.xquad.size <= 80 and self.N_test <= 60)
         pad_rule = False
-        if tile_ok:
+        if backend != "generic":
             eb, ee = shard_range(self.Nelement, self.rank, self.world)
-            q_dev, nt_dev = _lib.rule_advice(self.device, 1, self.xquad.size, self.N_test, 1, ee - eb)
-            pad_rule = q_dev > self.xquad.size and not os.environ.get("HPV_NO_RULE_PADDING")
-            if os.environ.get("HPV_FORCE_RULE_PADDING") and self.xquad.size < 80:     # (measurement knob: scripts/rule1d_sweep.py)
-                pad_rule, nt_dev = True, 60
+            force = bool(os.environ.get("HPV_FORCE_RULE_PADDING"))     # (measurement knob, scripts/rule1d_sweep.py: the advice for ONE element)
+            q_dev, nt_dev = _lib.rule_advice(self.device, self._pde, var_form, len(hidden), max(hidden), self.xquad.size, self.N_test, 1,
+                                             1 if force else ee - eb)
+            pad_rule = q_dev > self.xquad.size and (force or not os.environ.get("HPV_NO_RULE_PADDING"))
             if pad_rule or self.xquad.size == 80:
                 self._N_test_dev = nt_dev
 
@@ -773,15 +758,11 @@ class VPINN2D(_VPINNBase):
                 self.h.set_collocation(Xf[cb:ce], ff[cb:ce], n_total=Xf.shape[0])
             else:
                 xi, wx, yi, wy = _tensor_rule(X_quad, W_quad)
-                hidden = self.layers[1:-1]
-                if backend != "generic" and var_form in (0, 1) and max(hidden) <= 20 and 2 <= len(hidden) <= 3:
-                    eb, ee = shard_range(self.Nelementx * self.Nelementy, self.rank, self.world)
-                    # (var_form 0 runs on the FOUR-channel instantiations of the whole-iteration kernel: 12x12, 16x16 and 20x20 points; with
-                    #  three hidden layers 20x20 is the tight plan, dispatched up to five rounds of elements -- 18 / 19-point rules padded onto it
-                    #  95.2 / 96.1 -> 84.8 / 85.2 us, 17 points level: scripts/pad_probe.py; the 10x10 kernel takes the two one-hot terms of
-                    #  var_form 1 alone)
-                    rej = () if var_form == 1 else ((10, 20) if (len(hidden) == 3 and ee - eb > 5 * _n_cus(self.device)) else (10,))
-                    xi, wx, yi, wy = _device_rule_2d(xi, wx, yi, wy, self.Ntestx, self.Ntesty, ee - eb, self.device, n_hidden=len(hidden), reject=rej)
+                # (var_form 1 runs on the one-hot instantiations of the whole-iteration kernel, var_form 0 on the FOUR-channel ones: 12x12, 16x16 and
+                #  20x20 points -- 18 / 19-point rules padded onto 20x20 95.2 / 96.1 -> 84.8 / 85.2 us, 17 points level: scripts/pad_probe.py)
+                eb, ee = shard_range(self.Nelementx * self.Nelementy, self.rank, self.world)
+                xi, wx, yi, wy = _device_rule_2d(xi, wx, yi, wy, self.Ntestx, self.Ntesty, ee - eb, self._pde, var_form, self.layers[1:-1],
+                                                 self.device, backend)
                 self.h.set_quadrature(xi, wx, yi, wy)
                 self.h.set_tables(tables_1d(self.Ntestx, xi), tables_1d(self.Ntesty, yi))
                 eb, ee = shard_range(self.Nelementx * self.Nelementy, self.rank, self.world)
@@ -854,16 +835,11 @@ class VPINNAdvDiff(_VPINNBase):
 
         def populate():
             xi, wx, ti, wt = _tensor_rule(XT_quad, W_quad)
-            hidden = self.layers[1:-1]
-            if backend != "generic" and max(hidden) <= 20 and 2 <= len(hidden) <= 3 and xi.size < 10:     # (the 10x10 / 5x5 tile kernel)
-                eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)
-                xi, wx, ti, wt = _device_rule_2d(xi, wx, ti, wt, self.Ntestx, self.Ntestt, ee - eb, self.device, exact_counts=True, only=10)
-            elif backend != "generic" and max(hidden) <= 20 and 2 <= len(hidden) <= 3 and 10 < xi.size < 20:
-                # rules between the instantiated ones onto the whole-iteration kernel's general forms (round 6): var_form 1 has three
-                # channels (every shape), var_form 0 four (12x12, 16x16, 20x20 -- with three hidden layers the tight plan, up to five rounds of elements)
-                eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)
-                rej = (10,) if (var_form == 1 or len(hidden) == 2 or ee - eb <= 5 * _n_cus(self.device)) else (10, 20)
-                xi, wx, ti, wt = _device_rule_2d(xi, wx, ti, wt, self.Ntestx, self.Ntestt, ee - eb, self.device, n_hidden=len(hidden), reject=rej)
+            # rules below 10 points onto the 10x10 / 5x5 tile kernel, rules between the instantiated ones onto the whole-iteration kernel's
+            # general forms (round 6): var_form 1 has three channels (every shape), var_form 0 four (12x12, 16x16, 20x20)
+            eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)
+            xi, wx, ti, wt = _device_rule_2d(xi, wx, ti, wt, self.Ntestx, self.Ntestt, ee - eb, self._pde, var_form, self.layers[1:-1],
+                                             self.device, backend)
             self.h.set_quadrature(xi, wx, ti, wt)
             self.h.set_tables(tables_1d(self.Ntestx, xi), tables_1d(self.Ntestt, ti))
             eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)

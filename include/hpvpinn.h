@@ -246,21 +246,21 @@ int hpv_updates_applied(hpv_handle h, long long* n);
 int hpv_shared_element_kernels(hpv_handle h);
 int hpv_set_shared_element_kernels(hpv_handle h, int on);
 /* N_quad is a free hyper-parameter (P1:237, P2:282, P3:47); the element-resident kernels are instantiated for a few rules and
- * take a SMALLER rule padded with zero-weight points (exact: the tables are w * phi).  Whether that pays depends on the shard and
- * on the device, so the library decides: for a shard of n_elem_shard elements with q points per direction and ntx x nty test
- * functions (dim = 1: nty ignored) on `device` (its CU count; 256 when no device can be queried), *q_dev = the rule to hand to
- * hpv_set_quadrature (== q: leave the rule alone) and *nt_dev = the test-function count to hand to hpv_set_tables in 1-D (the
- * 80-point kernel takes 60 functions and per-element counts; == ntx otherwise).  exact_counts != 0: only an instantiation with
- * exactly these counts (forms whose kernel has no run-time counts).  n_hidden = the network's hidden layers (0: unknown -> three,
- * the reference's depth): the plan is evaluated exactly as the dispatch will evaluate it, and a rule is padded only where ONE
- * WORKGROUP PER ELEMENT will run -- not where the element loop or the separate launches take the grid (on many rounds the padded
- * points cost more than the structure saves).  No handle needed; the same limits gate the launch functions. */
-int hpv_rule_advice(int device, int dim, int q, int ntx, int nty, long n_elem_shard, int exact_counts, int n_hidden, int* q_dev, int* nt_dev);
+ * take a SMALLER rule padded with zero-weight points (exact: the tables are w * phi).  Whether that pays depends on the problem, the
+ * shard and the device, so the library decides, with the plan its own dispatch follows: for problem `pde` in variational form
+ * `var_form` under a network of n_hidden hidden layers, the widest max_width neurons, and a shard of n_elem_shard elements with q
+ * points per direction and ntx x nty test functions (1-D: nty ignored) on `device` (its CU count; 256 when no device can be queried),
+ * *q_dev = the rule to hand to hpv_set_quadrature (== q: leave the rule alone) and *nt_dev = the test-function count to hand to
+ * hpv_set_tables in 1-D (the 80-point kernel takes 60 functions and per-element counts; == ntx otherwise).  A rule is padded only
+ * where an element-resident kernel of this build takes that form, network and rule and ONE WORKGROUP PER ELEMENT will run -- not
+ * where the element loop or the separate launches take the grid (on many rounds the padded points cost more than the structure
+ * saves).  No handle needed; < 0: bad arguments (an unknown pde / var_form pair among them). */
+int hpv_rule_advice(int device, int pde, int var_form, int n_hidden, int max_width, int q, int ntx, int nty, long n_elem_shard, int* q_dev, int* nt_dev);
 /* How the whole-iteration kernel takes a shard of n_elem_shard elements of one of its 2-D rules (q = 12, 16, 20 points per
  * direction; N_el_x, N_el_y are free: P2:282-283, P3:44-45) under a network of n_hidden hidden layers on `device`: 0 = not at all
  * (the separate launches), 1 = one workgroup per element, 2 = the element loop (CUs workgroups walk the elements), 3 = the full
  * rounds with one workgroup per element + the ragged tail (n mod CUs elements) shared by 2 - 8 workgroups each in a second launch.
- * The dispatch's own function (csrc/hpv_mfma.h, hpv_fused_grid_plan) with this build's instantiations; < 0: bad arguments. */
+ * The dispatch's own plan (csrc/hpv_mfma.h, hpv_fused_plan_shard) with this build's instantiations; < 0: bad arguments. */
 int hpv_grid_plan(int device, int q, int n_hidden, long n_elem_shard);
 /* The network value and its input-derivative channels at the owned quadrature points, [C][n_owned*qx*qy]
  * (channel order: u, then d/dx, d/dy (d/dt), then the second derivatives the variational form integrates) --

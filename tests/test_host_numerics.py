@@ -215,7 +215,10 @@ def test_zero_weight_padding_of_quadrature_rules():
     # the tables the kernels contract with are w * phi: the padded columns vanish whatever phi is there
     t0, tp = tables_1d(7, x), tables_1d(7, xp)
     assert tp.shape == (3, 7, 16) and np.array_equal(tp[..., :14], t0) and np.all(np.isfinite(tp))
-    sel = lambda q, ntx, nty, ne, **k: _device_rule_2d(*(GaussLobattoJacobiWeights(q, 0, 0) * 2), ntx, nty, ne, **k)[0].size
+    from hp_vpinns_amd._lib import PDE_ADVDIFF, PDE_POISSON1D, PDE_POISSON2D, rule_advice
+    # (the advice knows the problem: Poisson-2D var_form 1 under three 20-wide hidden layers unless said otherwise)
+    sel = lambda q, ntx, nty, ne, pde=PDE_POISSON2D, var_form=1, n_hidden=3: _device_rule_2d(
+        *(GaussLobattoJacobiWeights(q, 0, 0) * 2), ntx, nty, ne, pde, var_form, [20] * n_hidden)[0].size
     assert [sel(q, q // 2, q // 2, 256) for q in (6, 10, 11, 12, 14, 16, 18, 20, 22)] == [10, 10, 12, 12, 16, 16, 20, 20, 22]
     assert sel(14, 9, 3, 256) == 20 and sel(14, 11, 3, 256) == 14          # the test-function counts must fit the instantiation too
     assert sel(7, 4, 4, 2048) == 7 and sel(14, 7, 7, 2048) == 14 and sel(18, 9, 9, 4096) == 20     # grids the kernel leaves to the separate launches
@@ -225,18 +228,35 @@ def test_zero_weight_padding_of_quadrature_rules():
     # rounds under two hidden layers, so 1 024 elements are padded there
     assert sel(14, 7, 7, 1024, n_hidden=3) == 14 and sel(14, 7, 7, 768, n_hidden=3) == 16 and sel(14, 7, 7, 1024, n_hidden=2) == 16
     assert sel(14, 7, 7, 1536, n_hidden=2) == 14
-    assert sel(8, 5, 5, 64, exact_counts=True, only=10) == 10 and sel(8, 4, 5, 64, exact_counts=True, only=10) == 8
-    assert sel(11, 6, 6, 64, exact_counts=True, only=10) == 11                # (an instantiation the caller did not ask for)
+    # AdvDiff below 10 points: the 10x10 / 5x5 tile kernel, which has no run-time counts
+    assert sel(8, 5, 5, 64, pde=PDE_ADVDIFF, var_form=0) == 10 and sel(8, 4, 5, 64, pde=PDE_ADVDIFF, var_form=0) == 8
+    assert sel(8, 6, 6, 64, pde=PDE_ADVDIFF, var_form=0) == 8                # (never onto 12x12 / 6x6 from there: an instantiation that form's class never asked for)
+    assert sel(11, 6, 6, 64, pde=PDE_ADVDIFF, var_form=0) == 12              # (beyond 10 points: the general forms of the whole-iteration kernel)
     # 1-D: the 80 / 60 tile kernel takes a smaller rule only on shards where one workgroup per element pays (hpv_rule1d_pad_max)
-    from hp_vpinns_amd._lib import rule_advice
-    assert rule_advice(0, 1, 80, 60, 1, 16) == (80, 60) and rule_advice(0, 1, 80, 12, 1, 16) == (80, 60)
-    assert rule_advice(0, 1, 40, 20, 1, 16) == (80, 60) and rule_advice(0, 1, 10, 5, 1, 256) == (80, 60)
-    assert rule_advice(0, 1, 10, 5, 1, 10000) == (10, 5)                     # h-refinement: 10 k elements of 10 points stay as they are
-    assert rule_advice(0, 1, 40, 20, 1, 257) == (40, 20) and rule_advice(0, 1, 60, 30, 1, 512) == (80, 60) and rule_advice(0, 1, 60, 30, 1, 513) == (60, 30)
-    assert rule_advice(0, 1, 90, 20, 1, 4) == (90, 20) and rule_advice(0, 1, 60, 61, 1, 4) == (60, 61)
+    adv1 = lambda q, nt, ne: rule_advice(0, PDE_POISSON1D, 1, 3, 20, q, nt, 1, ne)
+    assert adv1(80, 60, 16) == (80, 60) and adv1(80, 12, 16) == (80, 60)
+    assert adv1(40, 20, 16) == (80, 60) and adv1(10, 5, 256) == (80, 60)
+    assert adv1(10, 5, 10000) == (10, 5)                     # h-refinement: 10 k elements of 10 points stay as they are
+    assert adv1(40, 20, 257) == (40, 20) and adv1(60, 30, 512) == (80, 60) and adv1(60, 30, 513) == (60, 30)
+    assert adv1(90, 20, 4) == (90, 20) and adv1(60, 61, 4) == (60, 61)
     xa, _ = GaussLobattoJacobiWeights(12, 0, 0)
     xb, wb = GaussLobattoJacobiWeights(14, 0, 0)
-    assert _device_rule_2d(xa, _, xb, wb, 5, 5, 64)[0].size == 12           # different rules per direction: left alone
+    assert _device_rule_2d(xa, _, xb, wb, 5, 5, 64, PDE_POISSON2D, 1, [20] * 3)[0].size == 12           # different rules per direction: left alone
+
+
+def test_rule_advice_answers_as_the_classes_and_the_library_did_together():
+    """hpv_rule_advice is the dispatch's own plan and knows the problem (form, depth, width).  Before that the decision was spread over
+    the library and the three classes of vpinn.py (gates on form / depth / width in front of the call, rejected answers behind it);
+    tests/golden/make_rule_advice_table.py restates that and recorded it, with the library of that commit, over a sweep that straddles
+    every threshold (256 compute units).  EVERY row must come out of the single call alike."""
+    import os
+    from hp_vpinns_amd._lib import rule_advice
+    t = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rule_advice_parent.npz"))
+    rows, want = t["rows"], np.stack([t["q_dev"], t["nt_dev"]], axis=1)
+    assert rows.shape[0] == want.shape[0] > 50000
+    got = np.array([rule_advice(-1, *(int(v) for v in r)) for r in rows])
+    bad = np.nonzero(np.any(got != want, axis=1))[0]
+    assert bad.size == 0, [(rows[i].tolist(), got[i].tolist(), want[i].tolist()) for i in bad[:10]]
 
 
 def test_grid_plan_of_the_whole_iteration_kernel():
