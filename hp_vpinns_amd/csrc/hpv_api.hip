@@ -231,16 +231,22 @@ AdamArgs adam_args(hpv_ctx* h) {
 
 int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam);
 
-// the boundary / data term as the merged kernels see it, and the projection arguments of the quadrature batch (one definition for
-// enqueue_pass and the stand-alone timing of the iteration kernel)
+// the boundary / data term as the merged kernels see it, the projection arguments of the quadrature batch (edge: with the element-edge
+// batch's pointers, for the stand-alone projection kernels that integrate that term) and the pass over that batch as the MFMA launch
+// functions take it (one definition for enqueue_pass and the stand-alone timing of the iteration kernel)
 static MfmaDataTerm pass_data_term(hpv_ctx* h, bool backward) {
     return MfmaDataTerm{h->data_off, h->merged ? h->n_data : 0, h->d_udata, h->var.GBAR, h->d_data_part,
                         h->n_data > 0 ? -2.0 * h->cfg.lossb_weight / (double)h->n_data : 0.0, backward ? 1 : 0};
 }
-static ProjArgs pass_proj_args(hpv_ctx* h, bool backward) {
+static ProjArgs pass_proj_args(hpv_ctx* h, bool backward, bool edge = false) {
     const double* eps_ptr = h->has_eps ? h->d_theta + h->P : nullptr;
-    return ProjArgs{h->pd, h->var.OUT, h->var.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr,
-                    h->d_loss_e, h->d_deps_e, h->var.N, backward ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
+    ProjArgs pa{h->pd, h->var.OUT, h->var.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr,
+                h->d_loss_e, h->d_deps_e, h->var.N, backward ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
+    if (edge) { pa.edge_u = h->edge.OUT; pa.edge_dphi = h->d_edge_dphi; pa.edge_coef = h->d_edge_coef; pa.edge_gbar = h->edge.GBAR; }
+    return pa;
+}
+static MfmaPass pass_mfma(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa) {
+    return MfmaPass{h->d_theta, h->var.X, h->var.GBAR, h->var.GPART, &h->var.rows, h->stream, &dt, &pa, h->n_elem};
 }
 
 // ---- one pass over both loss terms ------------------------------------------------------------------------------------------
@@ -257,35 +263,29 @@ struct PassPlan {
 // takes a deferred update `pend` into its prologue), k_iter_tile (one tile per wave: 1-D rules, 10x10 points; a one-workgroup grid
 // finishes the iteration itself), k_iter_elem (any instantiated shape / channel set; first with HPV_FUSE=e), k_iter_tall (80x80
 // points).  Timed as the reverse-pass class.  false: nothing was launched.
-static bool pass_whole_iteration(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa, bool fuse_adam, bool& pend, PassPlan& pl) {
+static bool pass_whole_iteration(hpv_ctx* h, const MfmaPass& p, bool fuse_adam, bool& pend, PassPlan& pl) {
     HpvMfma* m = h->mfma;
-    Batch& v = h->var;
     int structure = -1;
     tstart(h, 2);
-    auto fused = [&](const MfmaPendingAdam* pre) {
-        return hpv_mfma_iter_fused(m, h->d_theta, v.X, v.GPART, &v.rows, h->stream, &dt, pa, h->n_elem, pre);
-    };
-    auto elem = [&] { return hpv_mfma_iter_elem(m, h->d_theta, v.X, v.GPART, &v.rows, h->stream, &dt, pa, h->n_elem); };
     if (pend) {      // the deferred update rides in k_iter_fused's prologue -- or is applied here, before anything else is launched
         const MfmaPendingAdam pre{adam_args(h), h->d_RB, h->Ptot};
-        if (fused(&pre)) { pl.pend_taken = true; structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2; }
+        if (hpv_mfma_iter_fused(m, p, &pre)) { pl.pend_taken = true; structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2; }
         else launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream);
         pend = false;
     }
-    if (structure < 0 && hpv_mfma_prefers_elem(m) && elem()) structure = 6;      // HPV_FUSE=e (A/B runs): the generic element-resident kernel first
-    if (structure < 0 && fused(nullptr)) structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2;
+    if (structure < 0 && hpv_mfma_prefers_elem(m) && hpv_mfma_iter_elem(m, p)) structure = 6;      // HPV_FUSE=e (A/B runs): the generic element-resident kernel first
+    if (structure < 0 && hpv_mfma_iter_fused(m, p)) structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2;
     if (structure < 0) {
         MfmaFinalize fin{adam_args(h), h->d_RB, h->cfg.lossb_weight, h->n_data, (h->n_data + 15) / 16, h->has_eps, adam_state_doubles(h->P) / 2};
         if (!fuse_adam) fin.ad.theta = nullptr;
         fin.n_iters = fuse_adam ? h->persist_want : 1;
         fin.iters_done = &h->persist_done;
-        if (hpv_mfma_iter_tile(m, h->d_theta, v.X, v.GPART, &v.rows, h->stream, &dt, pa, h->n_elem, h->merged ? &fin : nullptr, &pl.fin_done)) structure = 4;
+        if (hpv_mfma_iter_tile(m, p, h->merged ? &fin : nullptr, &pl.fin_done)) structure = 4;
     }
-    if (structure < 0 && elem()) structure = 6;
+    if (structure < 0 && hpv_mfma_iter_elem(m, p)) structure = 6;
     if (structure < 0) {
         const int ts = hpv_mfma_tall_split(m, h->pd, h->n_elem);
-        if (ts > 1 && h->n_elem * ts <= h->n_red_alloc &&
-            hpv_mfma_iter_tall(m, h->d_theta, v.X, v.GPART, &v.rows, h->stream, &dt, pa, h->n_elem)) { structure = 5; pl.n_loss = h->n_elem * ts; }
+        if (ts > 1 && h->n_elem * ts <= h->n_red_alloc && hpv_mfma_iter_tall(m, p)) { structure = 5; pl.n_loss = h->n_elem * ts; }
     }
     if (structure < 0) return false;     // (nothing was launched; the caller re-records the start event)
     tstop(h, 2);
@@ -298,18 +298,17 @@ static bool pass_whole_iteration(hpv_ctx* h, const MfmaDataTerm& dt, const ProjA
 // (2) / (3) The variational term as separate launches: forward (+ edge batch) -> projection -> reverse; on the MFMA path the
 // projection rides inside the reverse kernel where that applies (element-block mode), otherwise it is the fastest projection
 // kernel that takes the shape.
-static void pass_separate(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa, bool backward, bool use_mfma) {
+static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_mfma) {
     Batch& v = h->var;
-    const double* eps_ptr = pa.eps_ptr;
     tstart(h, 0);
-    if (use_mfma) hpv_mfma_forward(h->mfma, h->d_theta, v.X, v.OUT, backward ? 1 : 0, h->stream, &dt);
+    if (use_mfma) hpv_mfma_forward(h->mfma, h->d_theta, v.X, v.OUT, backward ? 1 : 0, h->stream, p.dt);
     else run_fwd(h, v, nullptr, backward ? 1 : 0);
     tstop(h, 0);
     if (h->pd.edge) run_fwd(h, h->edge, h->mfma_edge, backward ? 1 : 0);
     bool bfused = false;
     if (backward && use_mfma) {
         tstart(h, 2);   // timed as the reverse-pass class (the projection is ~1 % of its flops)
-        bfused = hpv_mfma_backward_fused(h->mfma, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream, pa, h->n_elem);
+        bfused = hpv_mfma_backward_fused(h->mfma, p);
         if (bfused) tstop(h, 2);
     }
     if (backward) h->pass_structure = bfused ? 1 : 0;
@@ -318,22 +317,17 @@ static void pass_separate(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa
         tstart(h, 1);
         // (the specialised kernels need GBAR's unused channels pre-zeroed: true for every batch, see alloc_batch)
         const bool special = h->cfg.backend != HPV_BACKEND_GENERIC;
-        auto wg = [&](double* upart) {
-            return launch_project_wg(h->pd, v.OUT, v.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr, h->d_loss_e, h->d_deps_e,
-                                     v.N, h->n_elem, backward ? 1 : 0, h->edge.OUT, h->d_edge_dphi, h->d_edge_coef, h->edge.GBAR, h->stream, upart);
-        };
+        const ProjArgs pj = pass_proj_args(h, backward, true);
         // few elements (at most two per CU) of a 2-D shape: one workgroup per element before "a lane owns a line"
         bool small_grid = h->dim == 2 && h->n_elem <= 512 && h->proj_split == 1 && !h->pd.nact;
 #ifdef HPV_EXPERIMENTS
         if (getenv("HPV_PJ_WG_SMALL")) small_grid = false;      // (A/B: "a lane owns a line" on small grids too)
 #endif
         const char* pname = "k_project";
-        if (special && small_grid && wg(nullptr)) pname = "k_project_wg";
-        else if (special && launch_project_tp(h->pd, v.OUT, v.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr, h->d_loss_e,
-                                              h->d_deps_e, v.N, h->n_elem, backward ? 1 : 0, h->stream)) pname = "k_project_tp";
-        else if (special && wg(h->d_upart)) pname = h->proj_split > 1 ? "k_project_rows" : "k_project_wg";
-        else launch_project(h->pd, v.OUT, v.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr, h->d_loss_e, h->d_deps_e, v.N,
-                            h->n_elem, backward ? 1 : 0, h->edge.OUT, h->d_edge_dphi, h->d_edge_coef, h->edge.GBAR, h->stream);
+        if (special && small_grid && launch_project_wg(pj, h->n_elem, h->stream)) pname = "k_project_wg";
+        else if (special && launch_project_tp(pj, h->n_elem, h->stream)) pname = "k_project_tp";
+        else if (special && launch_project_wg(pj, h->n_elem, h->stream, h->d_upart)) pname = h->proj_split > 1 ? "k_project_rows" : "k_project_wg";
+        else launch_project(pj, h->n_elem, h->stream);
         tstop(h, 1);
         if (backward) {
             snprintf(h->variant, sizeof h->variant, "%s + %s<%dx%d/%dx%d> + %s", use_mfma ? hpv_mfma_variant(h->mfma, 1) : "k_mlp_fwd_generic", pname,
@@ -378,7 +372,8 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
     if (h->var.N > 0) {
         const MfmaDataTerm dt = pass_data_term(h, backward);
         const ProjArgs pa = pass_proj_args(h, backward);
-        if (!(backward && use_mfma && pass_whole_iteration(h, dt, pa, fuse_adam, pend, pl))) pass_separate(h, dt, pa, backward, use_mfma);
+        const MfmaPass p = pass_mfma(h, dt, pa);
+        if (!(backward && use_mfma && pass_whole_iteration(h, p, fuse_adam, pend, pl))) pass_separate(h, p, backward, use_mfma);
     }
     // --- boundary / data term: inside the quadrature batch (one partial per 16-point data tile), or its own small batch ---
     int ndp = 0;
@@ -1220,13 +1215,14 @@ int hpv_time_iteration_kernel(hpv_handle h, int reps, double* avg_ms) {
     if (h->pass_structure != 2) return fail(h, -4, "the handle's iteration is not ONE whole-iteration launch without an in-kernel exchange");
     const MfmaDataTerm dt = pass_data_term(h, true);
     const ProjArgs pa = pass_proj_args(h, true);
+    const MfmaPass p = pass_mfma(h, dt, pa);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(h, hipEventCreate(&e0));
     HIPCHK(h, hipEventCreate(&e1));
     bool ok = true;
     (void)hipEventRecord(e0, h->stream);
     for (int i = 0; i < reps && ok; ++i)
-        ok = hpv_mfma_iter_fused(h->mfma, h->d_theta, h->var.X, h->var.GPART, &h->var.rows, h->stream, &dt, pa, h->n_elem);
+        ok = hpv_mfma_iter_fused(h->mfma, p);
     (void)hipEventRecord(e1, h->stream);
     hipError_t e = hipStreamSynchronize(h->stream);
     float ms = 0.0f;
@@ -1339,10 +1335,10 @@ int hpv_assemble_rhs(hpv_handle h, const double* f_quad, size_t n, double* F_out
         ProjDesc pd{};
         pd.nterms = 1; pd.t[0].dx = 0; pd.t[0].dy = 0; pd.t[0].a0[0] = 1.0;
         pd.qx = h->qx; pd.qy = h->qy; pd.ntx = h->ntx; pd.nty = h->nty; pd.C = 1;
-        if (h->cfg.backend == HPV_BACKEND_GENERIC ||
-            !launch_project_tp(pd, d_f, nullptr, d_F, nullptr, h->d_jac, ne, h->d_wtx, h->d_wty, nullptr, d_le, nullptr, ne * NQ, ne, 0, h->stream))
-            launch_project(pd, d_f, nullptr, d_F, nullptr, h->d_jac, ne, h->d_wtx, h->d_wty, nullptr, d_le, nullptr, ne * NQ, ne, 0,
-                           nullptr, nullptr, nullptr, nullptr, h->stream);
+        ProjArgs pa{};      // residual only: no adjoint, no epsilon, no right-hand side to subtract
+        pa.pd = pd; pa.OUT = d_f; pa.R = d_F; pa.coef = h->d_jac; pa.coef_stride = ne; pa.wtx = h->d_wtx; pa.wty = h->d_wty;
+        pa.loss_e = d_le; pa.N = ne * NQ;
+        if (h->cfg.backend == HPV_BACKEND_GENERIC || !launch_project_tp(pa, ne, h->stream)) launch_project(pa, ne, h->stream);
         hipError_t e = hipMemcpyAsync(F_out, d_F, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(h, -2, "hpv_assemble_rhs failed: %s", hipGetErrorString(e));

@@ -86,10 +86,9 @@ static int bench_residual_impl(hpv_handle h, long n_elem, int reps, int do_adjoi
         ProjDesc p2 = pd; p2.edge = 0;
         hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipMemset(GB, 0, (size_t)C * N * sizeof(double));
+        const ProjArgs pa{p2, OUT, GB, R, F, coef, n_elem, h->d_wtx, h->d_wty, eps_ptr, le, de, N, do_adjoint ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
         auto go = [&]() {
-            if (h->cfg.backend == HPV_BACKEND_GENERIC ||
-                !launch_project_tp(p2, OUT, GB, R, F, coef, n_elem, h->d_wtx, h->d_wty, eps_ptr, le, de, N, n_elem, do_adjoint ? 1 : 0, h->stream))
-                launch_project(p2, OUT, GB, R, F, coef, n_elem, h->d_wtx, h->d_wty, eps_ptr, le, de, N, n_elem, do_adjoint ? 1 : 0, nullptr, nullptr, nullptr, nullptr, h->stream);
+            if (h->cfg.backend == HPV_BACKEND_GENERIC || !launch_project_tp(pa, n_elem, h->stream)) launch_project(pa, n_elem, h->stream);
         };
         go();
         (void)hipEventRecord(e0, h->stream);

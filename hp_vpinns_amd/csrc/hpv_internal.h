@@ -59,6 +59,28 @@ struct ProjDesc {
     const int* nacty;
 };
 
+// All arguments of one projection launch (plain pointers; passed by value in the kernarg segment).
+struct ProjArgs {
+    ProjDesc pd;
+    const double* OUT;
+    double* GBAR;
+    double* R;
+    const double* F;
+    const double* coef;
+    long coef_stride;
+    const double* wtx;
+    const double* wty;
+    const double* eps_ptr;
+    double* loss_e;
+    double* deps_e;
+    long N;
+    int do_adjoint;
+    const double* edge_u;
+    const double* edge_dphi;
+    const double* edge_coef;
+    double* edge_gbar;
+};
+
 static inline size_t hpv_proj_lds_bytes(const ProjDesc& pd) {
     size_t nq = (size_t)pd.qx * pd.qy, nr = (size_t)pd.ntx * pd.nty;
     return (nq + (size_t)pd.qy * pd.ntx + nr + (size_t)pd.nterms * nr + (size_t)pd.nterms * pd.nty * pd.qx + 256) *
@@ -127,10 +149,7 @@ void launch_mlp_fwd_generic(const NetDesc& nd, const double* theta, const double
 void launch_mlp_bwd_generic(const NetDesc& nd, const double* theta, const double* X, const double* ACT,
                             const double* GBAR, double* GPART, int rows, long N, hipStream_t s);
 int mlp_bwd_generic_rows(long N);
-void launch_project(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                    long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                    double* deps_e, long N, long n_elem, int do_adjoint, const double* edge_u, const double* edge_dphi,
-                    const double* edge_coef, double* edge_gbar, hipStream_t s);
+void launch_project(const ProjArgs& pa, long n_elem, hipStream_t s);
 void launch_data_loss(const double* U, const double* Ud, double* GBAR, double scale_grad, double* part, int n,
                       hipStream_t s);
 void launch_finalize(const double* GPART_v, int rows_v, const double* GPART_b, int rows_b, const double* GPART_e,
@@ -144,14 +163,9 @@ int adam_state_doubles(int P);
 void launch_debug_act(int act, const double* x, int n, double* a, double* a1, double* ref, hipStream_t s);
 void launch_gll_rule(int Q, double* x, double* w, hipStream_t s);
 void launch_test_tables(int ntest, int q, const double* xi, double* tab, hipStream_t s);
-bool launch_project_tp(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                       long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                       double* deps_e, long N, long n_elem, int do_adjoint, hipStream_t s);
+bool launch_project_tp(const ProjArgs& pa, long n_elem, hipStream_t s);
 int pinn_residual_parts(int n);
 void launch_pinn_residual(const double* OUT, const double* f, double* GBAR, double* part, long N, int n, long n_total,
                           int write_gbar, hipStream_t s);
-bool launch_project_wg(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                       long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                       double* deps_e, long N, long n_elem, int do_adjoint, const double* edge_u, const double* edge_dphi,
-                       const double* edge_coef, double* edge_gbar, hipStream_t s, double* upart = nullptr);
+bool launch_project_wg(const ProjArgs& pa, long n_elem, hipStream_t s, double* upart = nullptr);
 int project_row_split(const ProjDesc& pd, long n_elem, int backend_generic);   // workgroups per element of the row-split projection

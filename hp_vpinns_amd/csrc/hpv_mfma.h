@@ -77,16 +77,34 @@ void hpv_mfma_forward(HpvMfma* m, const double* theta, const double* X, double* 
                       const MfmaDataTerm* dt = nullptr);
 void hpv_mfma_backward(HpvMfma* m, const double* theta, const double* X, const double* GBAR, double* GPART, int* rows,
                        hipStream_t s);
-struct ProjArgs;
-bool hpv_mfma_backward_fused(HpvMfma* m, const double* theta, const double* X, const double* GBAR, double* GPART, int* rows,
-                             hipStream_t s, const ProjArgs& pa, long n_elem);
+// One pass over the quadrature batch of a shard, as every launch function below that carries the projection takes it: filled once
+// by the caller, handed to each kernel of its cascade.  The functions return false when they do not cover the pass; nothing has
+// been launched then and neither the handle nor *rows has been written.
+struct MfmaPass {
+    const double* theta;
+    const double* X;
+    const double* GBAR;       // read by the separate reverse kernel only (the whole-iteration kernels keep the adjoint in pa->GBAR)
+    double* GPART;
+    int* rows;                // out (optional): gradient rows the launch writes
+    hipStream_t s;
+    const MfmaDataTerm* dt;   // nullptr or n_data == 0: no boundary / data tiles in the batch
+    const ProjArgs* pa;
+    long n_elem;
+};
+// Workgroups per element of a shard too small to give every CU an element: the largest power of two <= max that keeps
+// n_elem * s <= CUs (all partners resident at once).  ONE rule for every kernel that shares elements and for hpv_mfma_max_rows.
+inline int hpv_elem_split(long n_elem, int n_cus, int max) {
+    int s = 1;
+    while (s < max && n_elem * s * 2 <= n_cus) s *= 2;
+    return s;
+}
+bool hpv_mfma_backward_fused(HpvMfma* m, const MfmaPass& p);
 // Element-resident whole-iteration kernel (kernels_fused.hip): forward, projection and reverse pass of the shard in ONE
 // launch, no activation store.  Returns false when not applicable (shape, variational form, small shard).
 // pre (optional): a deferred TF1-Adam update the kernel is to compute WITH (MfmaArgs::pre_g) -- only k_iter_fused takes it; when the
 // function returns false nothing has been launched and the caller applies the update itself (k_adam) before it goes on.
 struct MfmaPendingAdam { AdamArgs ad; const double* g; int Ptot; };
-bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                         const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaPendingAdam* pre = nullptr);
+bool hpv_mfma_iter_fused(HpvMfma* m, const MfmaPass& p, const MfmaPendingAdam* pre = nullptr);
 // The decision behind it, in two halves that launch nothing and write nothing (kernels_fused.hip).  hpv_mfma_iter_fused plans, then
 // launches what the plan names; hpv_rule_advice / hpv_grid_plan ask the first half, which needs no handle.
 struct MfmaArgs;
@@ -131,13 +149,10 @@ struct MfmaFinalize {
     int n_iters = 1;              // iterations the caller wants back to back (a one-workgroup grid may run them in ONE persistent launch)
     int* iters_done = nullptr;    // out: iterations this launch performs (1, or n_iters on the persistent path)
 };
-bool hpv_mfma_iter_tile(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaFinalize* fin = nullptr,
-                        bool* fin_done = nullptr);
+bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin = nullptr, bool* fin_done = nullptr);
 // The same for ANY instantiated tensor-product element shape and 2-D channel set (kernels_elem.hip): several tiles per wave, s of
 // every tile in registers, tangents recomputed in the reverse phase.
-bool hpv_mfma_iter_elem(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem);
+bool hpv_mfma_iter_elem(HpvMfma* m, const MfmaPass& p);
 // Split whole-iteration kernels (SPLIT mode of k_iter_fused, k_iter_tall): the handle's sticky failure flag (device int, owned
 // by the caller) that a timed-out exchange sets; without one those modes are not used.  hpv_mfma_split_used: such a launch
 // happened since creation.
@@ -148,10 +163,8 @@ void hpv_mfma_set_split_ok(HpvMfma* m, bool on);
 bool hpv_mfma_split_used(HpvMfma* m);
 // Tall elements (80x80 points, 5x5 test functions: BASELINE config 5) split over `split` workgroups each (kernels_tall.hip);
 // hpv_mfma_tall_split: workgroups per element (0 = not applicable), loss_e / deps_e then hold n_elem * split entries.
-struct ProjDesc;
 int hpv_mfma_tall_split(HpvMfma* m, const ProjDesc& pd, long n_elem);
-bool hpv_mfma_iter_tall(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem);
+bool hpv_mfma_iter_tall(HpvMfma* m, const MfmaPass& p);
 // Names of the kernel instantiations (hpv_kernel_variant): which = 0 the whole-iteration kernel most recently launched, 1 the
 // separate forward kernel, 2 the separate reverse kernel, 3 the reverse kernel with the projection fused in
 const char* hpv_mfma_variant(HpvMfma* m, int which);

@@ -93,7 +93,6 @@ struct HpvMfma {
     void (*bwd_fused)(const MfmaArgs&, int, hipStream_t) = nullptr; // projection + reverse, element-block mode
     int occ_fwd = 1, occ_bwd = 1;   // resident 256-thread blocks per CU
     int n_cus = 256;                // compute units of the device
-    bool pre_used = false;          // the last k_iter_fused launch carried a deferred TF1-Adam update in its prologue
     bool multi_off = false, multi_force = false;   // HPV_FUSE=1 / m at creation: k_iter_fused's element loop never / on every grid larger than the chip
     int max_rows = 0;               // gradient rows the caller allocated (>= every launch mode's row count)
     // A/B switches read at creation (HPV_FUSE): default = the element-resident whole-iteration kernel where it applies,
@@ -115,6 +114,25 @@ struct HpvMfma {
     char variant[160] = "";                // whole-iteration kernel instantiation most recently launched through this object (hpv_kernel_variant)
     char vfwd[96] = "", vbwd[96] = "", vbwd_fused[128] = "";   // the separate forward / reverse kernels of this object
 };
+
+// The argument block of a pass as every kernel that takes an MfmaPass sees it: the handle's base arguments, the pass's pointers, the
+// boundary / data term (data_off = -1: none), the element-block fields and the projection arguments.  xchg: the kernel shares elements
+// between workgroups and gets the handle's exchange state.  Every other field stays as the base has it (zero); OUT and the kernel's own
+// extras are the caller's.
+inline MfmaArgs hpv_mfma_pass_args(const HpvMfma& m, const MfmaPass& p, long proj_n_elem, int proj_split, bool xchg = false) {
+    MfmaArgs a = m.base;
+    a.theta = p.theta; a.X = p.X; a.GPART = p.GPART;
+    a.data_off = -1;
+    if (p.dt && p.dt->n_data > 0) {
+        a.data_off = p.dt->data_off; a.ud = p.dt->ud; a.gbar0 = p.dt->gbar0; a.data_part = p.dt->data_part;
+        a.data_scale = p.dt->scale; a.data_write_gbar = p.dt->write_gbar;
+    }
+    a.proj_n_elem = proj_n_elem;
+    a.proj_split = proj_split;
+    if (p.pa) a.pa = *p.pa;
+    if (xchg) { a.xerr = m.xerr; a.xdebug_skip = m.xdebug_skip; a.xg = m.xg; a.xiter = m.xiter; }
+    return a;
+}
 
 // FAST (sin only): the caller has checked |z| <= HPV_SINCOS_MAX for the whole wave (act_wave_needs_safe below)
 template <int ACT, bool FAST = false>
@@ -209,8 +227,10 @@ __device__ __forceinline__ double row_sum16(double v) {
 
 
 // kernels_elem.hip: the generic element-resident whole-iteration kernel, one translation unit per element shape
-// (= ELEM_SHAPES of csrc/build.sh); false: that (H, channel set, depth) is not instantiated or its LDS does not fit
+// (= ELEM_SHAPES of csrc/build.sh); the lookup yields nullptr where that (H, channel set, depth, waves) is not instantiated or its
+// LDS does not fit; the launcher returns false (nothing enqueued) when the runtime refuses the kernel's LDS size
+typedef bool (*ElemLauncher)(const MfmaArgs& a, int blocks, hipStream_t s);
 #define HPV_ELEM_SHAPES(X) X(16, 16, 8, 8) X(20, 20, 10, 10) X(12, 12, 6, 6)
-#define HPV_ELEM_DECL(qx, qy, ntx, nty) bool hpv_elem_launch_##qx##qy##_##ntx##_##nty(int H, int key, int L, const MfmaArgs& a, int blocks, hipStream_t s);
+#define HPV_ELEM_DECL(qx, qy, ntx, nty) ElemLauncher hpv_elem_launcher_##qx##qy##_##ntx##_##nty(int H, int key, int L, int waves);
 HPV_ELEM_SHAPES(HPV_ELEM_DECL)
 #undef HPV_ELEM_DECL

@@ -53,28 +53,6 @@ __device__ __forceinline__ void pj_wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// All arguments of one projection launch (plain pointers; passed by value in the kernarg segment).
-struct ProjArgs {
-    ProjDesc pd;
-    const double* OUT;
-    double* GBAR;
-    double* R;
-    const double* F;
-    const double* coef;
-    long coef_stride;
-    const double* wtx;
-    const double* wty;
-    const double* eps_ptr;
-    double* loss_e;
-    double* deps_e;
-    long N;
-    int do_adjoint;
-    const double* edge_u;
-    const double* edge_dphi;
-    const double* edge_coef;
-    double* edge_gbar;
-};
-
 // lanes per output of a contraction of length K with n_out outputs on `block` threads: the largest power of two
 // (<= 64, <= K) that still gives every output its own lane group in one pass
 constexpr int pj_splitk(int n_out, int K, int block) {

@@ -354,11 +354,11 @@ __global__ void __launch_bounds__(WAVES * 64, 1) k_iter_elem(MfmaArgs g) {
 // ------------------------------------------------------------------------------------------------
 // Wavefronts per workgroup: 4 (one per SIMD, 512 registers each) or 8 (two per SIMD, 256 registers each: half the tiles per wave,
 // the two waves of a SIMD cover each other's LDS / MFMA-result latencies).  (The A/B switch HPV_ELEM_WAVES is gone since round 6.)
+// false: the runtime refused the kernel's LDS size; nothing has been enqueued.
 template <int D, int NT1, int NT2, int ACT, int L, int H, int QX, int QY, int NTX, int NTY, int EL_WAVES>
 static bool launch_iter_elem_w(const MfmaArgs& a, int blocks, hipStream_t s) {
     using M = ElLds<D, NT1, NT2, L, H, QX, QY, NTX, NTY, EL_WAVES>;
     constexpr size_t bytes = (size_t)M::TOTAL * sizeof(double);
-    if (bytes > 160 * 1024) return false;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)k_iter_elem<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, EL_WAVES>,
@@ -371,29 +371,35 @@ static bool launch_iter_elem_w(const MfmaArgs& a, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((k_iter_elem<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, EL_WAVES>), dim3(blocks), dim3(EL_WAVES * 64), bytes, s, a);
     return true;
 }
+// The lookups: the launcher of an instantiation, nullptr where there is none or its LDS does not fit the CU.
+template <int D, int NT1, int NT2, int ACT, int L, int H, int QX, int QY, int NTX, int NTY, int EL_WAVES>
+static ElemLauncher elem_launcher_w() {
+    const size_t bytes = (size_t)ElLds<D, NT1, NT2, L, H, QX, QY, NTX, NTY, EL_WAVES>::TOTAL * sizeof(double);
+    return bytes > 160 * 1024 ? nullptr : &launch_iter_elem_w<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, EL_WAVES>;
+}
 template <int D, int NT1, int NT2, int ACT, int L, int H, int QX, int QY, int NTX, int NTY>
-static bool launch_iter_elem(const MfmaArgs& a, int blocks, hipStream_t s) {
+static ElemLauncher elem_launcher(int waves) {
     constexpr int TPE = (QX * QY + 15) / 16;
     if constexpr (H <= 24 && TPE >= 8) {      // (wider layers need more than 256 registers per wave in the reverse phase)
-        if (a.elem_waves == 8) return launch_iter_elem_w<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, 8>(a, blocks, s);
+        if (waves == 8) return elem_launcher_w<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, 8>();
     }
-    return launch_iter_elem_w<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, 4>(a, blocks, s);
+    return elem_launcher_w<D, NT1, NT2, ACT, L, H, QX, QY, NTX, NTY, 4>();
 }
 
 template <int H, int QX, int QY, int NTX, int NTY>
-static bool launch_iter_elem_key(int key, int L, const MfmaArgs& a, int blocks, hipStream_t s) {
+static ElemLauncher elem_launcher_key(int key, int L, int waves) {
 #define EL_CASE(K, N1, N2)                                                                                              \
     if (key == K) {                                                                                                     \
-        if (L == 2) return launch_iter_elem<2, N1, N2, HPV_ACT_TANH, 2, H, QX, QY, NTX, NTY>(a, blocks, s);              \
-        if (L == 3) return launch_iter_elem<2, N1, N2, HPV_ACT_TANH, 3, H, QX, QY, NTX, NTY>(a, blocks, s);              \
-        return false;                                                                                                   \
+        if (L == 2) return elem_launcher<2, N1, N2, HPV_ACT_TANH, 2, H, QX, QY, NTX, NTY>(waves);                        \
+        if (L == 3) return elem_launcher<2, N1, N2, HPV_ACT_TANH, 3, H, QX, QY, NTX, NTY>(waves);                        \
+        return nullptr;                                                                                                 \
     }
     EL_CASE(220, 2, 0)
     EL_CASE(222, 2, 2)
     EL_CASE(221, 2, 1)
     EL_CASE(200, 0, 0)
 #undef EL_CASE
-    return false;
+    return nullptr;
 }
 
 // One translation unit per element shape (csrc/build.sh compiles this file once per entry of ELEM_SHAPES with
@@ -403,8 +409,8 @@ static bool launch_iter_elem_key(int key, int L, const MfmaArgs& a, int blocks, 
 #endif
 #define EL_CAT5_(a, b, c, d, e) a##b##c##_##d##_##e
 #define EL_CAT5(a, b, c, d, e) EL_CAT5_(a, b, c, d, e)
-bool EL_CAT5(hpv_elem_launch_, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY)(int H, int key, int L, const MfmaArgs& a, int blocks, hipStream_t s) {
-    if (H == 20) return launch_iter_elem_key<20, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY>(key, L, a, blocks, s);
-    if (H == 32) return launch_iter_elem_key<32, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY>(key, L, a, blocks, s);
-    return false;
+ElemLauncher EL_CAT5(hpv_elem_launcher_, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY)(int H, int key, int L, int waves) {
+    if (H == 20) return elem_launcher_key<20, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY>(key, L, waves);
+    if (H == 32) return elem_launcher_key<32, HPV_ELEM_QX, HPV_ELEM_QY, HPV_ELEM_NTX, HPV_ELEM_NTY>(key, L, waves);
+    return nullptr;
 }

@@ -2070,7 +2070,7 @@ FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTer
     const auto launcher = [&](int plan, bool gs) { return p.gen ? hpv_fused_launcher_gen(pd, m.L, plan, p.nT2) : fused_launcher(pd, m.L, plan, gs); };
     if (p.gplan == 3) {
         p.n_tail = n_elem % m.n_cus;
-        while (p.tsplit < 8 && p.n_tail * p.tsplit * 2 <= m.n_cus) p.tsplit *= 2;
+        p.tsplit = hpv_elem_split(p.n_tail, m.n_cus, 8);
         const long data_tiles = m.ntiles - n_elem * TPE;
         p.launch_tail = launcher(0, false);
         if (p.tsplit < 2 || p.n_tail > m.xsync_elems || (size_t)p.n_tail * 2 * NQ * 2 > m.xg_words || data_tiles > p.n_tail * p.tsplit || !p.launch_tail) {
@@ -2097,7 +2097,7 @@ FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTer
     // partners meet at a barrier in device memory, which needs all of them resident: at most one workgroup per CU
     if (n_elem * 2 <= m.n_cus && !m.iter_fused_force) {
         if (!xchg) FZ_NO(22);
-        while (p.split < 8 && n_elem * p.split * 2 <= m.n_cus) p.split *= 2;
+        p.split = hpv_elem_split(n_elem, m.n_cus, 8);
         if (n_elem * p.split > m.n_cus || n_elem > m.xsync_elems || (size_t)n_elem * 2 * NQ * 2 > m.xg_words) FZ_NO(23);
     }
     p.blocks = multi ? (long)m.n_cus : p.n_main * p.split;
@@ -2154,9 +2154,11 @@ FusedPlan hpv_fused_plan_rule(const FusedShard& in, ProjDesc pd, int q, int ntx,
 // Whole training pass (forward, projection, reverse) of a shard of 20x20 / 10x10 elements in one launch.  Returns false
 // when the shape / variational form / shard is not covered (hpv_fused_plan; nothing has been launched then); the caller then runs the
 // separate kernels.  (libhpvpinn_testhooks.so: HPV_TRACE_DISPATCH=1 names the check at which the plan declines a pass)
-bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                         const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaPendingAdam* pre) {
-    const FusedPlan p = hpv_fused_plan(*m, pa, dt, n_elem, pre != nullptr);
+bool hpv_mfma_iter_fused(HpvMfma* m, const MfmaPass& ps, const MfmaPendingAdam* pre) {
+    const ProjArgs& pa = *ps.pa;
+    const long n_elem = ps.n_elem;
+    hipStream_t s = ps.s;
+    const FusedPlan p = hpv_fused_plan(*m, pa, ps.dt, n_elem, pre != nullptr);
     if (p.declined) {
 #ifdef HPV_EXPERIMENTS
         if (getenv("HPV_TRACE_DISPATCH")) fprintf(stderr, "hpv_mfma_iter_fused: declined at check %d\n", p.declined);
@@ -2165,28 +2167,14 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
     }
     const ProjDesc& pd = pa.pd;
     const int TPE = pd.qx * pd.qy / 16;
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.GPART = GPART;
+    MfmaArgs a = hpv_mfma_pass_args(*m, ps, p.n_main, p.split, !p.small);
     a.OUT = const_cast<double*>(pa.OUT);   // SPLIT: the partners' channel exchange; otherwise only written by the -DHPV_FZ_TIMING build
-    a.data_off = -1;
-    if (dt && dt->n_data > 0) {
-        a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-        a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    }
-    a.proj_n_elem = p.n_main;
-    a.proj_split = p.split;
-    a.pa = pa;
     if (!p.small) {
         a.elem0 = 0;
         a.data_tile0 = n_elem * TPE;
         // (a ragged tail: the boundary / data tiles ride in the tail's launch -- this one sees a batch that ends behind its elements)
         if (p.n_tail > 0) a.ntiles = p.n_main * TPE;
         if (pre) { a.pre_g = pre->g; a.pre_Ptot = pre->Ptot; a.pre_ad = pre->ad; }
-        a.xerr = m->xerr;
-        a.xdebug_skip = m->xdebug_skip;
-        a.xg = m->xg;
-        a.xiter = m->xiter;
-        m->pre_used = pre != nullptr;
     }
     p.launch(a, (int)p.blocks, s);
     if (p.n_tail > 0) {
@@ -2196,7 +2184,7 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
         b.proj_n_elem = p.n_tail;
         b.proj_split = p.tsplit;
         b.elem0 = p.n_main;
-        b.GPART = GPART + p.blocks * (long)m->nd.P;
+        b.GPART = ps.GPART + p.blocks * (long)m->nd.P;
         p.launch_tail(b, (int)(p.n_tail * p.tsplit), s);
     }
     m->last_split = p.split > 1 || p.n_tail > 0;
@@ -2215,7 +2203,7 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const double* theta, const double* X, doubl
         const size_t l = strlen(m->variant);
         snprintf(m->variant + l, sizeof m->variant - l, " + SPLIT=true split=%d on the last %ld elements", p.tsplit, p.n_tail);
     }
-    if (rows) *rows = (int)p.rows_all;
+    if (ps.rows) *ps.rows = (int)p.rows_all;
     return true;
 }
 

@@ -435,14 +435,11 @@ __global__ void __launch_bounds__(256) k_project(ProjDesc pd, const double* __re
     }
 }
 
-void launch_project(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                    long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                    double* deps_e, long N, long n_elem, int do_adjoint, const double* edge_u, const double* edge_dphi,
-                    const double* edge_coef, double* edge_gbar, hipStream_t s) {
+void launch_project(const ProjArgs& pa, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
-    size_t lds = hpv_proj_lds_bytes(pd);
-    hipLaunchKernelGGL(k_project, dim3((unsigned)n_elem), dim3(256), lds, s, pd, OUT, GBAR, R, F, coef, coef_stride, wtx,
-                       wty, eps_ptr, loss_e, deps_e, N, do_adjoint, edge_u, edge_dphi, edge_coef, edge_gbar);
+    hipLaunchKernelGGL(k_project, dim3((unsigned)n_elem), dim3(256), hpv_proj_lds_bytes(pa.pd), s, pa.pd, pa.OUT, pa.GBAR, pa.R, pa.F,
+                       pa.coef, pa.coef_stride, pa.wtx, pa.wty, pa.eps_ptr, pa.loss_e, pa.deps_e, pa.N, pa.do_adjoint, pa.edge_u,
+                       pa.edge_dphi, pa.edge_coef, pa.edge_gbar);
 }
 
 // ------------------------------------------------------------------------------------------------

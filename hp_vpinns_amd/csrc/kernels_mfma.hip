@@ -810,24 +810,19 @@ unsigned int* hpv_mfma_xiter(HpvMfma* m) { return m ? m->xiter : nullptr; }
 bool hpv_mfma_prefers_elem(HpvMfma* m) { return m && m->prefer_elem; }
 double* hpv_mfma_activation_store(HpvMfma* m) { return m ? m->ACTS : nullptr; }
 size_t hpv_mfma_activation_store_doubles(const HpvMfma* m) { return m && m->ACTS ? (size_t)m->ntiles * m->L * m->ns * m->ks * 64 : 0; }   // (the timing builds park their stamps there)
-// Workgroups per element of the fused reverse kernel: one when the shard has an element for every CU, more for the
-// small shards of a multi-GPU run (each workgroup walks 1/split of the element's 25 tiles).
-static int fused_split(HpvMfma* m, long n_elem) {
-    int split = 1;
-    while (split < 8 && n_elem * split * 2 <= m->n_cus) split *= 2;
-    return split;
-}
 // rows the caller must allocate: the element-block mode writes one row per workgroup
 int hpv_mfma_max_rows(HpvMfma* m, long n_elem, long n_data_tiles) {
     int r = hpv_mfma_grad_rows(m);
     // kernels_elem.hip: one row per element plus one per 8 .. 16 boundary / data tiles no element wave has a free slot for
     if (n_elem + n_data_tiles / 8 + 2 > r && n_elem <= 65536) r = (int)(n_elem + n_data_tiles / 8 + 2);
-    const long fused_rows = n_elem * fused_split(m, n_elem);
+    // the fused reverse kernel: one workgroup per element when the shard has an element for every CU, up to 8 for the small shards of a
+    // multi-GPU run (hpv_elem_split; each workgroup walks 1 / split of the element's 25 tiles)
+    const long fused_rows = n_elem * hpv_elem_split(n_elem, m->n_cus, 8);
     if (m->bwd_fused && fused_rows > r && fused_rows <= 65536) r = (int)fused_rows;
     if (n_elem > r && n_elem <= 65536) r = (int)n_elem;      // the whole-iteration kernel writes one row per element
     // SPLIT mode of the whole-iteration kernel: 2 - 8 workgroups per element while they fit the chip (three-channel sets have the fused
     // reverse kernel's count above; the four-channel sets of the general forms do not)
-    if (n_elem * 2 <= m->n_cus) { long sp = 1; while (sp < 8 && n_elem * sp * 2 <= m->n_cus) sp *= 2; if (n_elem * sp > r) r = (int)(n_elem * sp); }
+    if (n_elem * 2 <= m->n_cus && fused_rows > r) r = (int)fused_rows;
     // ... and, on a grid larger than the chip with a ragged last round, up to 8 rows per element of the tail (at most half a round of elements)
     if (n_elem > m->n_cus && n_elem + m->n_cus > r && n_elem <= 65536) r = (int)(n_elem + m->n_cus);
     if (n_elem * 64 > r && n_elem * 64 <= m->n_cus) r = (int)(n_elem * 64);   // tall-element kernel: up to 64 workgroups per element
@@ -839,13 +834,8 @@ int hpv_mfma_max_rows(HpvMfma* m, long n_elem, long n_data_tiles) {
 
 void hpv_mfma_forward(HpvMfma* m, const double* theta, const double* X, double* OUT, int save_act, hipStream_t s,
                       const MfmaDataTerm* dt) {
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.OUT = OUT; a.save_act = (save_act && m->store_s_only) ? 2 : save_act;
-    a.data_off = -1;
-    if (dt && dt->n_data > 0) {
-        a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-        a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    }
+    MfmaArgs a = hpv_mfma_pass_args(*m, MfmaPass{theta, X, nullptr, nullptr, nullptr, s, dt, nullptr, 0}, 0, 0);
+    a.OUT = OUT; a.save_act = (save_act && m->store_s_only) ? 2 : save_act;
     m->fwd(a, m->fwd_blocks, s);
 }
 
@@ -859,9 +849,11 @@ void hpv_mfma_backward(HpvMfma* m, const double* theta, const double* X, const d
 
 // Whole training pass of a shard of elements of any instantiated shape in one launch (kernels_elem.hip).  Returns false when the
 // shape / channel set / width / layout is not covered; the caller then runs the separate kernels.
-bool hpv_mfma_iter_elem(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem) {
+bool hpv_mfma_iter_elem(HpvMfma* m, const MfmaPass& p) {
+    const ProjArgs& pa = *p.pa;
     const ProjDesc& pd = pa.pd;
+    const MfmaDataTerm* dt = p.dt;
+    const long n_elem = p.n_elem;
     const NetDesc& nd = m->nd;
     if (!m->iter_fused_ok || pd.edge || pd.nact || n_elem <= 0 || m->L < 2 || m->L > 3 || nd.d != 2 || nd.act != HPV_ACT_TANH) return false;
     const int key = nd.d * 100 + nd.nT1 * 10 + nd.nT2;
@@ -888,39 +880,30 @@ bool hpv_mfma_iter_elem(HpvMfma* m, const double* theta, const double* X, double
     const long left = n_dt - n_elem * nfree;
     const long blocks = n_elem + (left > 0 ? (left + slots - 1) / slots : 0);
     if (blocks > hpv_mfma_grad_rows(m) && blocks > m->max_rows) return false;
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.GPART = GPART;
-    a.OUT = const_cast<double*>(pa.OUT);
-    a.data_off = -1;
-    if (has_data) {
-        a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-        a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    }
-    a.proj_n_elem = n_elem;
-    a.proj_split = 1;
-    a.pa = pa;
-    a.elem_waves = waves;
-    bool ok = false, known = false;
-#define HPV_ELEM_TRY(A_, B_, C_, D_)                                                           \
-    if (!known && pd.qx == A_ && pd.qy == B_ && pd.ntx >= 1 && pd.ntx <= C_ && pd.nty >= 1 && pd.nty <= D_) {                 \
-        known = true;                                                                          \
-        ok = hpv_elem_launch_##A_##B_##_##C_##_##D_(m->H, key, m->L, a, (int)blocks, s);         \
-    }
-    HPV_ELEM_SHAPES(HPV_ELEM_TRY)
+    ElemLauncher launch;
+#define HPV_ELEM_TRY(A_, B_, C_, D_)                                                                                    \
+    if (pd.qx == A_ && pd.qy == B_ && pd.ntx >= 1 && pd.ntx <= C_ && pd.nty >= 1 && pd.nty <= D_)                        \
+        launch = hpv_elem_launcher_##A_##B_##_##C_##_##D_(m->H, key, m->L, waves);                                        \
+    else
+    HPV_ELEM_SHAPES(HPV_ELEM_TRY) launch = nullptr;
 #undef HPV_ELEM_TRY
-    if (!ok) return false;
+    if (!launch) return false;
+    MfmaArgs a = hpv_mfma_pass_args(*m, p, n_elem, 1);
+    a.OUT = const_cast<double*>(pa.OUT);
+    a.elem_waves = waves;
+    if (!launch(a, (int)blocks, p.s)) return false;
     m->last_split = false;
     snprintf(m->variant, sizeof m->variant, "k_iter_elem<D=2,NT1=%d,NT2=%d,tanh,L=%d,H=%d,%dx%d/%dx%d,waves=%d,tiles/wave=%d>", nd.nT1, nd.nT2,
              m->L, m->H, pd.qx, pd.qy, pd.ntx, pd.nty, waves, tpw);
-    if (rows) *rows = (int)blocks;
+    if (p.rows) *p.rows = (int)blocks;
     return true;
 }
 
 // Reverse pass with the per-element projection fused in front (element-block mode).  Returns false when not
 // applicable; the caller then launches projection and reverse pass separately.
-bool hpv_mfma_backward_fused(HpvMfma* m, const double* theta, const double* X, const double* GBAR, double* GPART, int* rows,
-                             hipStream_t s, const ProjArgs& pa, long n_elem) {
-    const ProjDesc& pd = pa.pd;
+bool hpv_mfma_backward_fused(HpvMfma* m, const MfmaPass& p) {
+    const ProjDesc& pd = p.pa->pd;
+    const long n_elem = p.n_elem;
     if (!m->bwd_fused || !m->fuse_bwd || pd.edge || pd.nact || n_elem <= 0) return false;
     if (!(pd.qx == 20 && pd.qy == 20 && pd.ntx >= 1 && pd.ntx <= 10 && pd.nty >= 1 && pd.nty <= 10)) return false;   // (counts: run-time values)
     // (element-block mode = whole elements in rounds of one workgroup per CU: on a ragged grid larger than the chip the three separate
@@ -931,17 +914,17 @@ bool hpv_mfma_backward_fused(HpvMfma* m, const double* theta, const double* X, c
     }
     const long tpe = (20 * 20) / 16;
     const long rest = m->ntiles - n_elem * tpe;                 // pad + data tiles: at most one per workgroup
-    const int split = fused_split(m, n_elem);
+    const int split = hpv_elem_split(n_elem, m->n_cus, 8);
     const long blocks = n_elem * split;
     if (rest < 0 || rest > blocks) return false;
     if (blocks > hpv_mfma_grad_rows(m) && blocks > m->max_rows) return false;
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.GBAR = GBAR; a.GPART = GPART;
+    MfmaArgs a = m->base;      // (no data term in the reverse kernel: data_off stays as the base has it)
+    a.theta = p.theta; a.X = p.X; a.GBAR = p.GBAR; a.GPART = p.GPART;
     a.proj_n_elem = n_elem;
     a.proj_split = split;
-    a.pa = pa;
-    m->bwd_fused(a, (int)blocks, s);
-    if (rows) *rows = (int)blocks;
+    a.pa = *p.pa;
+    m->bwd_fused(a, (int)blocks, p.s);
+    if (p.rows) *p.rows = (int)blocks;
     return true;
 }
 

@@ -684,8 +684,7 @@ __global__ void __launch_bounds__(256, 1) k_residual_dma(ProjDesc pd, int ch0, i
 }
 
 template <int QX, int QY, int NTX, int NTY>
-static bool launch_residual_dma(const ProjDesc& pd, const ActiveCh& ac, const double* OUT, double* R, const double* F, const double* coef,
-                                long coef_stride, const double* wtx, const double* wty, double* loss_e, long N, long n_elem, hipStream_t s) {
+static bool launch_residual_dma(const ProjArgs& pa, const ActiveCh& ac, long n_elem, hipStream_t s) {
     constexpr int NB = 6;
     using M = RdLds<QX, QY, NTX, NTY, NB>;
     constexpr size_t lds = (size_t)M::TOTAL * sizeof(double);
@@ -700,8 +699,8 @@ static bool launch_residual_dma(const ProjDesc& pd, const ActiveCh& ac, const do
     }
     const long nbatch = (n_elem + NB - 1) / NB;
     const unsigned blocks = (unsigned)std::min<long>(nbatch, 256);          // one resident workgroup per CU, each streams its batches
-    hipLaunchKernelGGL((k_residual_dma<QX, QY, NTX, NTY, NB>), dim3(blocks), dim3(256), lds, s, pd, ac.id[0], ac.id[1], OUT, R, F, coef,
-                       coef_stride, wtx, wty, loss_e, N, n_elem);
+    hipLaunchKernelGGL((k_residual_dma<QX, QY, NTX, NTY, NB>), dim3(blocks), dim3(256), lds, s, pa.pd, ac.id[0], ac.id[1], pa.OUT, pa.R,
+                       pa.F, pa.coef, pa.coef_stride, pa.wtx, pa.wty, pa.loss_e, pa.N, n_elem);
     return true;
 }
 
@@ -858,8 +857,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) k_residual_wdma(ProjDesc pd, in
 }
 
 template <int QX, int QY, int NTX, int NTY>
-static bool launch_residual_wdma(const ProjDesc& pd, const ActiveCh& ac, const double* OUT, double* R, const double* F, const double* coef,
-                                 long coef_stride, const double* wtx, const double* wty, double* loss_e, long N, long n_elem, hipStream_t s) {
+static bool launch_residual_wdma(const ProjArgs& pa, const ActiveCh& ac, long n_elem, hipStream_t s) {
     constexpr int WAVES = 5, EPW = 64 / QX, NQ = QX * QY, NR = NTX * NTY;
     constexpr int NG = (EPW * NQ / 2 + 63) / 64, NF = (EPW * NR / 2 + 63) / 64;
     constexpr int WAVE_D = (2 * NG * 128 + NF * 128 + EPW * NTY * (QX + 1) + 64 + 1) / 2 * 2;
@@ -875,14 +873,13 @@ static bool launch_residual_wdma(const ProjDesc& pd, const ActiveCh& ac, const d
     }
     const long ngroups = (n_elem + EPW - 1) / EPW;
     const unsigned blocks = (unsigned)std::min<long>((ngroups + WAVES - 1) / WAVES, 256);
-    hipLaunchKernelGGL((k_residual_wdma<QX, QY, NTX, NTY, WAVES>), dim3(blocks), dim3(WAVES * 64), lds, s, pd, ac.id[0], ac.id[1], OUT, R, F,
-                       coef, coef_stride, wtx, wty, loss_e, N, n_elem);
+    hipLaunchKernelGGL((k_residual_wdma<QX, QY, NTX, NTY, WAVES>), dim3(blocks), dim3(WAVES * 64), lds, s, pa.pd, ac.id[0], ac.id[1], pa.OUT,
+                       pa.R, pa.F, pa.coef, pa.coef_stride, pa.wtx, pa.wty, pa.loss_e, pa.N, n_elem);
     return true;
 }
 
 template <int QX, int QY, int NTX, int NTY>
-static bool launch_residual_stream(const ProjDesc& pd, const ActiveCh& ac, const double* OUT, double* R, const double* F, const double* coef,
-                                   long coef_stride, const double* wtx, const double* wty, double* loss_e, long N, long n_elem, hipStream_t s) {
+static bool launch_residual_stream(const ProjArgs& pa, const ActiveCh& ac, long n_elem, hipStream_t s) {
     constexpr int NB = 6;
     using M = RsLds<QX, QY, NTX, NTY, NB>;
     constexpr size_t lds = (size_t)M::TOTAL * sizeof(double);
@@ -896,17 +893,15 @@ static bool launch_residual_stream(const ProjDesc& pd, const ActiveCh& ac, const
     }
     const long nbatch = (n_elem + NB - 1) / NB;
     const unsigned blocks = (unsigned)std::min<long>(nbatch, 512);          // two resident workgroups per CU, each streams its batches
-    hipLaunchKernelGGL((k_residual_stream<QX, QY, NTX, NTY, NB>), dim3(blocks), dim3(256), lds, s, pd, ac.id[0], ac.id[1], OUT, R, F, coef,
-                       coef_stride, wtx, wty, loss_e, N, n_elem);
+    hipLaunchKernelGGL((k_residual_stream<QX, QY, NTX, NTY, NB>), dim3(blocks), dim3(256), lds, s, pa.pd, ac.id[0], ac.id[1], pa.OUT, pa.R,
+                       pa.F, pa.coef, pa.coef_stride, pa.wtx, pa.wty, pa.loss_e, pa.N, n_elem);
     return true;
 }
 
 #endif  // HPV_EXPERIMENTS
 
 template <int QX, int QY, int NTX, int NTY, int NA, bool EPS, int PJ_WAVES, bool OH = false, bool PIPE = false>
-static void launch_tp3(const ProjDesc& pd, const ActiveCh& ac, const double* OUT, double* GBAR, double* R, const double* F,
-                       const double* coef, long coef_stride, const double* wtx, const double* wty, const double* eps_ptr,
-                       double* loss_e, double* deps_e, long N, long n_elem, int do_adjoint, long ngroups, hipStream_t s) {
+static void launch_tp3(const ProjArgs& pa, const ActiveCh& ac, long n_elem, long ngroups, hipStream_t s) {
     constexpr int LPE = QX > QY ? QX : QY;
     constexpr int EPW = 64 / LPE;
     constexpr int WAVE_DOUBLES = EPW * NTY * (QX + 1) + 64;
@@ -932,13 +927,13 @@ static void launch_tp3(const ProjDesc& pd, const ActiveCh& ac, const double* OUT
         }
     }
     hipLaunchKernelGGL((k_project_tp<QX, QY, NTX, NTY, NA, EPS, PJ_WAVES, OH, PIPE>), dim3((unsigned)blocks), dim3(PJ_WAVES * 64), lds, s,
-                       pd, ac, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e, deps_e, N, n_elem, do_adjoint);
+                       pa.pd, ac, pa.OUT, pa.GBAR, pa.R, pa.F, pa.coef, pa.coef_stride, pa.wtx, pa.wty, pa.eps_ptr, pa.loss_e, pa.deps_e, pa.N, n_elem,
+                       pa.do_adjoint);
 }
 
 template <int QX, int QY, int NTX, int NTY, int NA, bool EPS>
-static bool launch_tp2(const ProjDesc& pd, const ActiveCh& ac, const double* OUT, double* GBAR, double* R, const double* F,
-                       const double* coef, long coef_stride, const double* wtx, const double* wty, const double* eps_ptr,
-                       double* loss_e, double* deps_e, long N, long n_elem, int do_adjoint, hipStream_t s) {
+static bool launch_tp2(const ProjArgs& pa, const ActiveCh& ac, long n_elem, hipStream_t s) {
+    const ProjDesc& pd = pa.pd;
     constexpr int LPE = QX > QY ? QX : QY;
     constexpr int EPW = 64 / LPE;
     const long ngroups = (n_elem + EPW - 1) / EPW;
@@ -950,9 +945,7 @@ static bool launch_tp2(const ProjDesc& pd, const ActiveCh& ac, const double* OUT
     for (int t = 0; t < pd.nterms && onehot; ++t)
         for (int a = 0; a < NA; ++a)
             if (a != t && (pd.t[t].a0[ac.id[a]] != 0.0 || pd.t[t].a1[ac.id[a]] != 0.0)) onehot = false;
-#define HPV_GO(W_, OH_, PIPE_)                                                                                           \
-    launch_tp3<QX, QY, NTX, NTY, NA, EPS, W_, OH_, PIPE_>(pd, ac, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e, deps_e, \
-                                                          N, n_elem, do_adjoint, ngroups, s)
+#define HPV_GO(W_, OH_, PIPE_) launch_tp3<QX, QY, NTX, NTY, NA, EPS, W_, OH_, PIPE_>(pa, ac, n_elem, ngroups, s)
     if constexpr (!EPS && NA >= 2) {
         if (onehot) {
 #ifdef HPV_EXPERIMENTS
@@ -964,18 +957,18 @@ static bool launch_tp2(const ProjDesc& pd, const ActiveCh& ac, const double* OUT
                 // large batches, residual only: the LDS-DMA stream (HPV_PJ_DMA=1: A/B switch)
                 const bool dma_on = getenv("HPV_PJ_DMA") && getenv("HPV_PJ_DMA")[0] == '1';
                 const bool wdma_on = getenv("HPV_PJ_DMA") && getenv("HPV_PJ_DMA")[0] == '2';       // per-wave loader + consumer
-                if (!do_adjoint && wdma_on && n_elem >= 4096 && N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
+                if (!pa.do_adjoint && wdma_on && n_elem >= 4096 && pa.N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
                     pd.t[1].a1[ac.id[1]] == 0.0 && !pd.t[0].eps_mult && !pd.t[1].eps_mult &&
-                    launch_residual_wdma<QX, QY, NTX, NTY>(pd, ac, OUT, R, F, coef, coef_stride, wtx, wty, loss_e, N, n_elem, s))
+                    launch_residual_wdma<QX, QY, NTX, NTY>(pa, ac, n_elem, s))
                     return true;
-                if (!do_adjoint && dma_on && n_elem >= 4096 && N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
+                if (!pa.do_adjoint && dma_on && n_elem >= 4096 && pa.N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
                     pd.t[1].a1[ac.id[1]] == 0.0 && !pd.t[0].eps_mult && !pd.t[1].eps_mult &&
-                    launch_residual_dma<QX, QY, NTX, NTY>(pd, ac, OUT, R, F, coef, coef_stride, wtx, wty, loss_e, N, n_elem, s))
+                    launch_residual_dma<QX, QY, NTX, NTY>(pa, ac, n_elem, s))
                     return true;
                 // large batches, residual only, unit channel weights: the streaming kernel (LDS-staged, register double-buffered)
-                if (!do_adjoint && !no_stream && n_elem >= 4096 && N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
+                if (!pa.do_adjoint && !no_stream && n_elem >= 4096 && pa.N == n_elem * (long)(QX * QY) && pd.t[0].a1[ac.id[0]] == 0.0 &&
                     pd.t[1].a1[ac.id[1]] == 0.0 && !pd.t[0].eps_mult && !pd.t[1].eps_mult &&
-                    launch_residual_stream<QX, QY, NTX, NTY>(pd, ac, OUT, R, F, coef, coef_stride, wtx, wty, loss_e, N, n_elem, s))
+                    launch_residual_stream<QX, QY, NTX, NTY>(pa, ac, n_elem, s))
                     return true;
             }
             if (ngroups <= 1024) HPV_GO(1, true, false);
@@ -993,9 +986,8 @@ static bool launch_tp2(const ProjDesc& pd, const ActiveCh& ac, const double* OUT
 }
 
 template <int QX, int QY, int NTX, int NTY>
-static bool launch_tp(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                      long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                      double* deps_e, long N, long n_elem, int do_adjoint, hipStream_t s) {
+static bool launch_tp(const ProjArgs& pa, long n_elem, hipStream_t s) {
+    const ProjDesc& pd = pa.pd;
     ActiveCh ac{};
     for (int ch = 0; ch < pd.C; ++ch) {
         bool used = false;
@@ -1004,8 +996,7 @@ static bool launch_tp(const ProjDesc& pd, const double* OUT, double* GBAR, doubl
     }
 #define HPV_NA(NA_, EPS_)                                                                                              \
     if (ac.n == NA_ && (pd.has_eps != 0) == EPS_)                                                                      \
-        return launch_tp2<QX, QY, NTX, NTY, NA_, EPS_>(pd, ac, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e,   \
-                                                       deps_e, N, n_elem, do_adjoint, s);
+        return launch_tp2<QX, QY, NTX, NTY, NA_, EPS_>(pa, ac, n_elem, s);
     HPV_NA(1, false) HPV_NA(2, false) HPV_NA(2, true) HPV_NA(3, true)
 #undef HPV_NA
     return false;
@@ -1026,18 +1017,13 @@ __global__ void __launch_bounds__(PW_BLOCK) k_project_wg(ProjArgs pa) {
 }
 
 template <int QX, int QY, int NTX, int NTY>
-static bool launch_wg(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                      long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                      double* deps_e, long N, long n_elem, int do_adjoint, const double* edge_u, const double* edge_dphi,
-                      const double* edge_coef, double* edge_gbar, hipStream_t s) {
+static bool launch_wg(const ProjArgs& pa, long n_elem, hipStream_t s) {
     constexpr size_t lds = (size_t)project_wg_lds_doubles<QX, QY, NTX, NTY>() * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {   // > 64 KB of dynamic LDS needs the opt-in
         (void)hipFuncSetAttribute((const void*)k_project_wg<QX, QY, NTX, NTY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    ProjArgs pa{pd, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e, deps_e, N, do_adjoint, edge_u, edge_dphi,
-                edge_coef, edge_gbar};
     hipLaunchKernelGGL((k_project_wg<QX, QY, NTX, NTY>), dim3((unsigned)n_elem), dim3(PW_BLOCK), lds, s, pa);
     return true;
 }
@@ -1063,21 +1049,18 @@ static void launch_rows(const ProjArgs& pa, long n_elem, double* upart, hipStrea
     hipLaunchKernelGGL((k_project_rows_adj<QX, QY, NTX, NTY>), dim3(blocks), dim3(PJ_RBLOCK), lds, s, pa, upart);
 }
 
-bool launch_project_wg(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                       long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                       double* deps_e, long N, long n_elem, int do_adjoint, const double* edge_u, const double* edge_dphi,
-                       const double* edge_coef, double* edge_gbar, hipStream_t s, double* upart) {
+bool launch_project_wg(const ProjArgs& pa, long n_elem, hipStream_t s, double* upart) {
+    const ProjDesc& pd = pa.pd;
     if (n_elem <= 0) return false;
     if (upart && !pd.nact && project_row_split(pd, n_elem, 0) > 1) {   // few tall elements: PJ_SPLIT workgroups per element, two phases
-        ProjArgs pa{pd, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e, deps_e, N, do_adjoint, nullptr, nullptr,
-                    nullptr, nullptr};
-        launch_rows<80, 80, 5, 5>(pa, n_elem, upart, s);
+        ProjArgs rows = pa;      // (the row-split kernels take no element-edge term)
+        rows.edge_u = rows.edge_dphi = rows.edge_coef = nullptr; rows.edge_gbar = nullptr;
+        launch_rows<80, 80, 5, 5>(rows, n_elem, upart, s);
         return true;
     }
 #define HPV_WG(QX_, QY_, NTX_, NTY_, EXACT_)                                                                              \
     if (pd.qx == QX_ && pd.qy == QY_ && (EXACT_ ? pd.ntx == NTX_ && pd.nty == NTY_ : pd.ntx >= 1 && pd.ntx <= NTX_ && pd.nty >= 1 && pd.nty <= NTY_))   \
-        return launch_wg<QX_, QY_, NTX_, NTY_>(pd, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e, deps_e, N, \
-                                               n_elem, do_adjoint, edge_u, edge_dphi, edge_coef, edge_gbar, s);
+        return launch_wg<QX_, QY_, NTX_, NTY_>(pa, n_elem, s);
     HPV_WG(80, 1, 60, 1, true)     // Poisson-1D reference rule: N_Quad = 80, N_testfcn = 60 (P1:237-238; BASELINE configs 1, 2)
     HPV_WG(80, 80, 5, 5, true)     // AdvDiff with the 80-point rule per direction (BASELINE config 5)
     // small grids of the 2-D shapes (round 4): one 1024-thread workgroup per element spreads a few hundred elements over all CUs,
@@ -1099,15 +1082,13 @@ bool launch_project_wg(const ProjDesc& pd, const double* OUT, double* GBAR, doub
 }
 
 // Returns false when the element shape has no specialised instantiation (caller falls back to k_project).
-bool launch_project_tp(const ProjDesc& pd, const double* OUT, double* GBAR, double* R, const double* F, const double* coef,
-                       long coef_stride, const double* wtx, const double* wty, const double* eps_ptr, double* loss_e,
-                       double* deps_e, long N, long n_elem, int do_adjoint, hipStream_t s) {
+bool launch_project_tp(const ProjArgs& pa, long n_elem, hipStream_t s) {
+    const ProjDesc& pd = pa.pd;
     if (pd.nact) return false;   // per-element active test counts: the general projections only
     if (pd.edge || n_elem <= 0) return false;
 #define HPV_TP(QX_, QY_, NTX_, NTY_)                                                                              \
     if (pd.qx == QX_ && pd.qy == QY_ && pd.ntx == NTX_ && pd.nty == NTY_)                                          \
-        return launch_tp<QX_, QY_, NTX_, NTY_>(pd, OUT, GBAR, R, F, coef, coef_stride, wtx, wty, eps_ptr, loss_e,  \
-                                               deps_e, N, n_elem, do_adjoint, s);
+        return launch_tp<QX_, QY_, NTX_, NTY_>(pa, n_elem, s);
     HPV_TP(20, 20, 10, 10)   // BASELINE config 4
     HPV_TP(10, 10, 5, 5)     // BASELINE config 3, the Poisson-2D and AdvDiff reference defaults (P2:282-286, P3:47-51)
 #undef HPV_TP

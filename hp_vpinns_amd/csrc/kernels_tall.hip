@@ -967,12 +967,23 @@ static void launch_iter_tall_q(const MfmaArgs& a, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((k_iter_tall<NT1, NT2, L, QX, QY, NTX, NTY, QT>), dim3(blocks), dim3(TA_BLOCK), bytes, s, a);
 }
 
+typedef void (*TallLauncher)(const MfmaArgs&, int blocks, hipStream_t);
 template <int NT1, int NT2, int L, int QX, int QY, int NTX, int NTY>
-static void launch_iter_tall(const MfmaArgs& a, int blocks, hipStream_t s) {
+static TallLauncher tall_launcher_q(bool qt) {
 #ifndef HPV_AGPR_GUARD_TRIPPED_QT     // csrc/build.sh: only the quarter-tile instantiations reached their hand-managed AGPR range
-    if (a.tall_qt) { launch_iter_tall_q<NT1, NT2, L, QX, QY, NTX, NTY, true>(a, blocks, s); return; }
+    if (qt) return &launch_iter_tall_q<NT1, NT2, L, QX, QY, NTX, NTY, true>;
 #endif
-    launch_iter_tall_q<NT1, NT2, L, QX, QY, NTX, NTY, false>(a, blocks, s);
+    return &launch_iter_tall_q<NT1, NT2, L, QX, QY, NTX, NTY, false>;
+}
+// The lookup: the launcher of the instantiation for a channel set and depth, nullptr where there is none.
+static TallLauncher tall_launcher(int nT2, int L, bool qt) {
+    switch (nT2 * 10 + L) {
+        case 12: return tall_launcher_q<2, 1, 2, 80, 80, 5, 5>(qt);
+        case 13: return tall_launcher_q<2, 1, 3, 80, 80, 5, 5>(qt);
+        case 2: return tall_launcher_q<2, 0, 2, 80, 80, 5, 5>(qt);
+        case 3: return tall_launcher_q<2, 0, 3, 80, 80, 5, 5>(qt);
+        default: return nullptr;
+    }
 }
 
 const char* hpv_tall_build_state() {
@@ -997,8 +1008,7 @@ int hpv_mfma_tall_split(HpvMfma* m, const ProjDesc& pd, long n_elem) {
     if (!(pd.qx == 80 && pd.qy == 80 && pd.ntx == 5 && pd.nty == 5) || pd.edge || pd.nact || pd.nterms < 1) return 0;
     if (n_elem <= 0 || n_elem > m->xsync_elems) return 0;
     const int tpe = 80 * 80 / 16;
-    int split = 1;
-    while (split < 64 && n_elem * split * 2 <= m->n_cus) split *= 2;
+    const int split = hpv_elem_split(n_elem, m->n_cus, 64);
     if (n_elem * split > m->n_cus) return 0;                                   // all partners must be resident: one workgroup per CU
     if ((tpe + split - 1) / split > TA_WAVES * TA_MAXT - 1) return 0;          // (one slot per workgroup stays free for a data tile)
     return split;
@@ -1006,63 +1016,40 @@ int hpv_mfma_tall_split(HpvMfma* m, const ProjDesc& pd, long n_elem) {
 
 // Whole training pass (forward, projection, reverse) of a shard of tall elements in one launch.  Returns false when the shape /
 // variational form / shard is not covered; the caller then runs the separate kernels.
-bool hpv_mfma_iter_tall(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem) {
-    const int split = hpv_mfma_tall_split(m, pa.pd, n_elem);
+bool hpv_mfma_iter_tall(HpvMfma* m, const MfmaPass& p) {
+    const long n_elem = p.n_elem;
+    const int split = hpv_mfma_tall_split(m, p.pa->pd, n_elem);
     if (split < 2) return false;
     const long blocks = n_elem * split;
     const long rest = m->ntiles - n_elem * (80 * 80 / 16);           // boundary/data tiles: at most one per workgroup
     if (rest < 0 || rest > blocks) return false;
     if (blocks > hpv_mfma_grad_rows(m) && blocks > m->max_rows) return false;
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.GPART = GPART;
-    a.data_off = -1;
-    if (dt && dt->n_data > 0) {
-        a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-        a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    } else if (rest > 0) {
-        return false;
+    if (!(p.dt && p.dt->n_data > 0) && rest > 0) return false;
+    // quarter-tile plan: every workgroup's tile count must be 0 or 1 mod 4 (its one extra tile is cut in four), its whole tiles
+    // must leave a stash slot for the quarter, and the workgroups without a 13th element tile must suffice for the data tiles
+    const int tpe = 80 * 80 / 16, lg = __builtin_ctz(split);
+    bool qt = getenv("HPV_NO_QUARTER_TILE") == nullptr;
+    long n0 = 0;
+    for (int p_ = 0; p_ < split; ++p_) {
+        const int n = (((p_ + 1) * tpe) >> lg) - ((p_ * tpe) >> lg);
+        if (n % TA_WAVES > 1 || n / TA_WAVES + 1 > TA_MAXT) qt = false;
+        if (n % TA_WAVES == 0) ++n0;
     }
-    a.proj_n_elem = n_elem;
-    a.proj_split = split;
-    {
-        // quarter-tile plan: every workgroup's tile count must be 0 or 1 mod 4 (its one extra tile is cut in four), its whole tiles
-        // must leave a stash slot for the quarter, and the workgroups without a 13th element tile must suffice for the data tiles
-        const int tpe = 80 * 80 / 16, lg = __builtin_ctz(split);
-        bool qt = getenv("HPV_NO_QUARTER_TILE") == nullptr;
-        long n0 = 0;
-        for (int p_ = 0; p_ < split; ++p_) {
-            const int n = (((p_ + 1) * tpe) >> lg) - ((p_ * tpe) >> lg);
-            if (n % TA_WAVES > 1 || n / TA_WAVES + 1 > TA_MAXT) qt = false;
-            if (n % TA_WAVES == 0) ++n0;
-        }
-        if (rest > n0 * n_elem) qt = false;
-        a.tall_qt = qt ? 1 : 0;
-    }
-    a.xerr = m->xerr;
-    a.xdebug_skip = m->xdebug_skip;
-    a.xg = m->xg;
-    a.xiter = m->xiter;
-    a.pa = pa;
+    if (rest > n0 * n_elem) qt = false;
+    const TallLauncher launch = tall_launcher(m->nd.nT2, m->L, qt);
+    if (!launch) return false;
+    MfmaArgs a = hpv_mfma_pass_args(*m, p, n_elem, split, true);
+    a.tall_qt = qt ? 1 : 0;
+    launch(a, (int)blocks, p.s);
     m->last_split = true;
     m->split_used = true;
-    {
 #ifdef HPV_AGPR_GUARD_TRIPPED_QT
-        const bool qt_run = false;
+    const bool qt_run = false;
 #else
-        const bool qt_run = a.tall_qt != 0;
+    const bool qt_run = qt;
 #endif
-        snprintf(m->variant, sizeof m->variant, "k_iter_tall<NT1=2,NT2=%d,L=%d,80,80,5,5,QT=%s> split=%d", m->nd.nT2, m->L,
-                 qt_run ? "true" : "false", split);
-    }
-    const int key = m->nd.nT2 * 10 + m->L;
-    switch (key) {
-        case 12: launch_iter_tall<2, 1, 2, 80, 80, 5, 5>(a, (int)blocks, s); break;
-        case 13: launch_iter_tall<2, 1, 3, 80, 80, 5, 5>(a, (int)blocks, s); break;
-        case 2: launch_iter_tall<2, 0, 2, 80, 80, 5, 5>(a, (int)blocks, s); break;
-        case 3: launch_iter_tall<2, 0, 3, 80, 80, 5, 5>(a, (int)blocks, s); break;
-        default: return false;
-    }
-    if (rows) *rows = (int)blocks;
+    snprintf(m->variant, sizeof m->variant, "k_iter_tall<NT1=2,NT2=%d,L=%d,80,80,5,5,QT=%s> split=%d", m->nd.nT2, m->L,
+             qt_run ? "true" : "false", split);
+    if (p.rows) *p.rows = (int)blocks;
     return true;
 }

@@ -610,27 +610,20 @@ __global__ void __launch_bounds__(WAVES * 64, 1) k_iter_tile_persist(MfmaArgs g)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+#ifdef HPV_EXPERIMENTS
+static bool tile_debug() { static const bool dbg = getenv("HPV_TILE_DEBUG") != nullptr; return dbg; }
+#else
+static constexpr bool tile_debug() { return false; }
+#endif
+// false: the runtime refused the kernel's LDS size; nothing has been enqueued.  (PERSIST: -DHPV_EXPERIMENTS builds, the 1-D rule only)
 template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES, bool PERSIST = false>
 static bool launch_iter_tile(const MfmaArgs& a, int blocks, hipStream_t s) {
-#ifdef HPV_EXPERIMENTS
-    if constexpr (!PERSIST && QY == 1) {      // persistent loop: instantiated for the 1-D rule (config 1)
-        if (a.persist_iters > 1) return launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES, true>(a, blocks, s);
-    }
-#else
+#ifndef HPV_EXPERIMENTS
     static_assert(!PERSIST, "the persistent launch exists in -DHPV_EXPERIMENTS builds only");
 #endif
     static_assert(!PERSIST || QY == 1, "the persistent launch is instantiated for the 1-D rule only");
     using M = TlLds<L, WAVES, QX, QY, NTX, NTY, D>;
     const size_t bytes = (size_t)M::total(a.P) * sizeof(double);
-#ifdef HPV_EXPERIMENTS
-    static const bool dbg = getenv("HPV_TILE_DEBUG") != nullptr;
-#else
-    constexpr bool dbg = false;
-#endif
-    if (bytes + (PERSIST ? sizeof(MfmaArgs) + 64 : 0) > 160 * 1024) {
-        if (dbg) fprintf(stderr, "hpv_mfma_iter_tile: %zu bytes of LDS needed\n", bytes);
-        return false;
-    }
     static bool attr_set = false;
     if (!attr_set) {
         const void* kfn;
@@ -642,7 +635,7 @@ static bool launch_iter_tile(const MfmaArgs& a, int blocks, hipStream_t s) {
         const hipError_t e = hipFuncSetAttribute(kfn,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) {
-            if (dbg) fprintf(stderr, "hpv_mfma_iter_tile: hipFuncSetAttribute(%zu bytes): %s\n", bytes, hipGetErrorString(e));
+            if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: hipFuncSetAttribute(%zu bytes): %s\n", bytes, hipGetErrorString(e));
             (void)hipGetLastError();
             return false;
         }
@@ -656,27 +649,42 @@ static bool launch_iter_tile(const MfmaArgs& a, int blocks, hipStream_t s) {
     return true;
 }
 
-template <int D, int NT1, int NT2, int ACT, int QX, int QY, int NTX, int NTY, int WAVES, int MAXL>
-static bool launch_iter_tile_L(int L, const MfmaArgs& a, int blocks, hipStream_t s) {
-    if (L == 2) return launch_iter_tile<D, NT1, NT2, ACT, 2, QX, QY, NTX, NTY, WAVES>(a, blocks, s);
-    if (L == 3) return launch_iter_tile<D, NT1, NT2, ACT, 3, QX, QY, NTX, NTY, WAVES>(a, blocks, s);
-    if constexpr (MAXL >= 4) {
-        if (L == 4) return launch_iter_tile<D, NT1, NT2, ACT, 4, QX, QY, NTX, NTY, WAVES>(a, blocks, s);
+// The lookups: the launcher of an instantiation (nullptr: there is none) and the LDS it needs for P parameters -- dynamic bytes, and
+// what the persistent launch keeps in static LDS on top.
+typedef bool (*TileLauncher)(const MfmaArgs&, int blocks, hipStream_t);
+struct TileKernel { TileLauncher launch = nullptr; size_t bytes = 0, fixed = 0; };
+template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
+static TileKernel tile_kernel(int P, bool persist) {
+    const size_t bytes = (size_t)TlLds<L, WAVES, QX, QY, NTX, NTY, D>::total(P) * sizeof(double);
+#ifdef HPV_EXPERIMENTS
+    if constexpr (QY == 1) {      // persistent loop: instantiated for the 1-D rule (config 1)
+        if (persist) return {&launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES, true>, bytes, sizeof(MfmaArgs) + 64};
     }
-    return false;
+#endif
+    return {&launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>, bytes, 0};
+}
+template <int D, int NT1, int NT2, int ACT, int QX, int QY, int NTX, int NTY, int WAVES, int MAXL>
+static TileKernel tile_kernel_L(int L, int P, bool persist) {
+    if (L == 2) return tile_kernel<D, NT1, NT2, ACT, 2, QX, QY, NTX, NTY, WAVES>(P, persist);
+    if (L == 3) return tile_kernel<D, NT1, NT2, ACT, 3, QX, QY, NTX, NTY, WAVES>(P, persist);
+    if constexpr (MAXL >= 4) {
+        if (L == 4) return tile_kernel<D, NT1, NT2, ACT, 4, QX, QY, NTX, NTY, WAVES>(P, persist);
+    }
+    return {};
 }
 
 // Whole training pass (forward, projection, reverse) of a shard of small elements in one launch.  Returns false when the
 // element shape / channel set / layout is not covered; the caller then runs the separate kernels.
 #ifdef HPV_EXPERIMENTS
-#define TL_WHY(K) do { static const bool dbg_ = getenv("HPV_TILE_DEBUG") != nullptr; if (dbg_) fprintf(stderr, "hpv_mfma_iter_tile: not applicable (check %d)\n", K); } while (0)
+#define TL_WHY(K) do { if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: not applicable (check %d)\n", K); } while (0)
 #else
 #define TL_WHY(K) do { } while (0)
 #endif
-bool hpv_mfma_iter_tile(HpvMfma* m, const double* theta, const double* X, double* GPART, int* rows, hipStream_t s,
-                        const MfmaDataTerm* dt, const ProjArgs& pa, long n_elem, const MfmaFinalize* fin, bool* fin_done) {
-    if (fin_done) *fin_done = false;
+bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin, bool* fin_done) {
+    const ProjArgs& pa = *p.pa;
     const ProjDesc& pd = pa.pd;
+    const MfmaDataTerm* dt = p.dt;
+    const long n_elem = p.n_elem;
     const NetDesc& nd = m->nd;
     if (!m->iter_fused_ok || pd.edge || n_elem <= 0 || m->L < 2 || m->L > 4 || m->H != MF_H) { TL_WHY(1); return false; }
     const int key = nd.d * 100 + nd.nT1 * 10 + nd.nT2;
@@ -696,25 +704,12 @@ bool hpv_mfma_iter_tile(HpvMfma* m, const double* theta, const double* X, double
     const long left = n_dt - n_elem * (waves - tpe);
     const long blocks = n_elem + (left > 0 ? (left + waves - 1) / waves : 0);
     if (blocks > hpv_mfma_grad_rows(m) && blocks > m->max_rows) { TL_WHY(4); return false; }
-    MfmaArgs a = m->base;
-    a.theta = theta; a.X = X; a.GPART = GPART;
-    a.OUT = const_cast<double*>(pa.OUT);
-    a.data_off = -1;
-    if (has_data) {
-        a.data_off = dt->data_off; a.ud = dt->ud; a.gbar0 = dt->gbar0; a.data_part = dt->data_part;
-        a.data_scale = dt->scale; a.data_write_gbar = dt->write_gbar;
-    }
-    a.proj_n_elem = n_elem;
-    a.proj_split = 1;
-    a.pa = pa;
 #ifdef HPV_EXPERIMENTS
     const bool fin_off = getenv("HPV_NO_INKERNEL_FINALIZE") != nullptr;            // (A/B switch of libhpvpinn_testhooks.so, read per launch / capture)
 #else
     constexpr bool fin_off = false;
 #endif
     const bool fin_here = fin && blocks == 1 && n_elem == 1 && !fin_off;
-    a.fin_mode = 0;
-    a.persist_iters = 1;
     // persistent loop (k_iter_tile<.., PERSIST>): only where the kernel finishes the iteration itself AND applies the update
     // (opt-in, HPV_PERSIST=1: measured 24.6 us per iteration against 24.0 for one launch per iteration -- see tile_body)
 #ifdef HPV_EXPERIMENTS
@@ -722,28 +717,38 @@ bool hpv_mfma_iter_tile(HpvMfma* m, const double* theta, const double* X, double
 #else
     constexpr bool persist_off = true;
 #endif
-    if (fin_here && fin->ad.theta && fin->n_iters > 1 && shape1d && !persist_off) a.persist_iters = fin->n_iters;
+    const bool persist = fin_here && fin->ad.theta && fin->n_iters > 1 && shape1d && !persist_off;
+    TileKernel k;
+    if (shape1d) {
+        if (key == 111) k = tile_kernel_L<1, 1, 1, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P, persist);
+        else k = tile_kernel_L<1, 1, 0, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P, persist);
+    } else {
+        if (key == 221) k = tile_kernel_L<2, 2, 1, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
+        else if (key == 222) k = tile_kernel_L<2, 2, 2, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
+        else if (key == 200) k = tile_kernel_L<2, 0, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
+        else k = tile_kernel_L<2, 2, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
+    }
+    if (!k.launch) return false;
+    if (k.bytes + k.fixed > 160 * 1024) {
+        if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: %zu bytes of LDS needed\n", k.bytes);
+        return false;
+    }
+    MfmaArgs a = hpv_mfma_pass_args(*m, p, n_elem, 1);
+    a.OUT = const_cast<double*>(pa.OUT);
+    a.fin_mode = 0;
+    a.persist_iters = persist ? fin->n_iters : 1;
     if (fin_here) {
         a.fin_mode = fin->ad.theta ? 2 : 1;
         a.fin_ad = fin->ad; a.fin_RB = fin->RB; a.fin_lossb_weight = fin->lossb_weight;
         a.fin_n_data = fin->n_data; a.fin_n_data_part = fin->n_data_part; a.fin_has_eps = fin->has_eps; a.fin_ncopies = fin->ncopies;
     }
+    if (!k.launch(a, (int)blocks, p.s)) return false;
     m->last_split = false;
     snprintf(m->variant, sizeof m->variant, "k_iter_tile<D=%d,NT1=%d,NT2=%d,%s,L=%d,%dx%d/%dx%d,waves=%d>%s%s", nd.d, nd.nT1, nd.nT2,
              nd.act == HPV_ACT_SIN ? "sin" : "tanh", m->L, pd.qx, pd.qy, pd.ntx, pd.nty, waves, fin_here ? " +finalize" : "",
-             (fin_here && fin->ad.theta && fin->n_iters > 1 && shape1d && !persist_off) ? " persistent" : "");
-    bool ok = false;
-    if (shape1d) {
-        if (key == 111) ok = launch_iter_tile_L<1, 1, 1, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, a, (int)blocks, s);
-        else ok = launch_iter_tile_L<1, 1, 0, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, a, (int)blocks, s);
-    } else {
-        if (key == 221) ok = launch_iter_tile_L<2, 2, 1, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, a, (int)blocks, s);
-        else if (key == 222) ok = launch_iter_tile_L<2, 2, 2, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, a, (int)blocks, s);
-        else if (key == 200) ok = launch_iter_tile_L<2, 0, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, a, (int)blocks, s);
-        else ok = launch_iter_tile_L<2, 2, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, a, (int)blocks, s);
-    }
-    if (ok && rows) *rows = (int)blocks;
-    if (ok && fin_done) *fin_done = fin_here;
-    if (ok && fin && fin->iters_done) *fin->iters_done = a.persist_iters;
-    return ok;
+             persist ? " persistent" : "");
+    if (p.rows) *p.rows = (int)blocks;
+    if (fin_done) *fin_done = fin_here;
+    if (fin && fin->iters_done) *fin->iters_done = a.persist_iters;
+    return true;
 }
