@@ -6,13 +6,15 @@
 
 // ---- explicit AGPR stash -------------------------------------------------------------------------------------------
 // At one wave per SIMD a wave owns 512 registers: 256 architectural VGPRs + 256 accumulation registers (AGPRs).  The s
-// values of the wave's tiles 1..6 (6 x L x 5 doubles per lane) are parked in the TOP AGPRs a[FZ_ABASE..255] by hand
-// (v_accvgpr_write/read through inline asm): left to the register allocator, the same values end up behind PHI copies
-// that move hundreds of registers per tile.  The compiler does not know these registers hold live values -- it only sees
-// that a255 is clobbered, which makes the kernel descriptor reserve all 256 AGPRs -- so csrc/build.sh runs
-// scripts/check_agpr.py on the generated assembly: if compiler-generated code touches a[FZ_ABASE..255] the library is built WITHOUT
-// that kernel / instantiation (-DHPV_AGPR_GUARD_TRIPPED[_QT], reported by hpv_build_info); the build FAILS when the check itself
-// cannot run (symbol renamed, no assembly).
+// values of the wave's tiles 1..6 (6 x L x 5 doubles per lane) are parked in the TOP AGPRs a[ABASE..255] by hand (ABASE: a
+// constexpr of each kernel; v_accvgpr_write/read through inline asm): left to the register allocator, the same values end up
+// behind PHI copies that move hundreds of registers per tile.  The compiler does not know these registers hold live values -- it
+// only sees that a255 is clobbered, which makes the kernel descriptor reserve all 256 AGPRs -- so csrc/build.sh runs
+// scripts/check_agpr.py on the generated assembly.  The register numbers below are inline-asm immediates and print in hexadecimal
+// there, the compiler's own in decimal: the check reads each instantiation's range from the lowest hexadecimal one -- nothing
+// restates ABASE -- and if compiler-generated code reaches it the library is built WITHOUT that kernel / instantiation (the table in
+// check_agpr.py: -DHPV_AGPR_GUARD_TRIPPED[_QT], reported by hpv_build_info, ...); the build FAILS when the check itself cannot run
+// (symbol renamed, no assembly).
 template <int IDX>
 __device__ __forceinline__ void acc_put(double v) {
     const int lo = __double2loint(v), hi = __double2hiint(v);

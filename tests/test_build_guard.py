@@ -57,67 +57,164 @@ def test_guard_tells_a_trip_from_a_check_that_could_not_run(tmp_path):
     assert nofile.returncode == 2 and "cannot read" in nofile.stderr
 
 
-def test_margins_of_the_built_kernels():
-    """The hand-managed AGPR ranges of the library as BUILT here: every guarded instantiation keeps at least 6 registers between the
-    compiler's high-water mark and the stash (verdict round 4, item 5: a two-register margin would let a compiler point release
-    move the headline kernel to its fallback plan silently).  Reads the assembly csrc/build.sh leaves beside the objects; skipped
-    when the library was built elsewhere."""
-    import re
+def _guard():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_agpr", os.path.join(ROOT, "scripts", "check_agpr.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+GUARDED = {"kernels_fused.s": ("k_iter_fused", 28), "kernels_fused_gen.s": ("k_iter_fused", 32), "kernels_tall.s": ("k_iter_tall", 8)}
+
+
+def _built(stems):
+    """{file: the scanner's records of the functions with one of `stems`} of the assembly csrc/build.sh leaves beside the objects."""
     import pytest
     csrc = os.path.join(ROOT, "hp_vpinns_amd", "csrc")
-    S20, S16, S12, T = "ELi20ELi20ELi10ELi10E", "ELi16ELi16ELi8ELi8E", "ELi12ELi12ELi6ELi6E", "ELi80ELi80ELi5ELi5"
-    guarded = {"kernels_fused.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20, 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20, 106),
-                                   ("k_iter_fusedILi3ELb1ELb0ELb0" + S20, 106), ("k_iter_fusedILi2ELb0ELb1ELb0" + S20, 156),
-                                   ("k_iter_fusedILi3ELb0ELb1ELb0" + S16, 166), ("k_iter_fusedILi3ELb0ELb1ELb0" + S12, 226)],
-               # round 6, the general forms (template tail <.., MULTI = false, NT2, GEN = true>): three channels on the one-hot kernels' stash,
-               # four channels with one more tile per wave in LDS (the stash starts 2 L x 5 registers higher)
-               "kernels_fused_gen.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106),
-                                       ("k_iter_fusedILi3ELb1ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi0ELb1E", 166),
-                                       ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi1ELb1E", 196), ("k_iter_fusedILi3ELb1ELb0ELb0" + S16 + "Lb0ELi1ELb1E", 196),
-                                       ("k_iter_fusedILi2ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 176),
-                                       # the tight plan (FzPlan): three of the first stash place's fifteen doubles in registers, twelve in LDS
-                                       ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 160)],
-               "kernels_tall.s": [("k_iter_tallILi2ELi1ELi3" + T + "ELb0", 136), ("k_iter_tallILi2ELi1ELi3" + T + "ELb1", 166),
-                                  ("k_iter_tallILi2ELi0ELi3" + T + "ELb1", 166)]}
-    if not all(os.path.exists(os.path.join(csrc, f)) for f in guarded):
+    if not all(os.path.exists(os.path.join(csrc, f)) for f in GUARDED):
         pytest.skip("no assembly beside the objects (library built elsewhere)")
-    script = os.path.join(ROOT, "scripts", "check_agpr.py")
-    for f, ks in guarded.items():
-        for key, base in ks:
-            r = subprocess.run([sys.executable, script, os.path.join(csrc, f), key, str(base)], capture_output=True, text=True)
-            assert r.returncode == 0, r.stdout + r.stderr
-            hi = int(re.search(r"AGPR a(\d+),", r.stdout).group(1))
-            assert base - hi >= 6, (key, hi, base)
+    g = _guard()
+    return {f: g.scan(os.path.join(csrc, f), lambda name, stem: stem in stems) for f in GUARDED}
+
+
+def test_margins_of_the_built_kernels():
+    """The hand-managed AGPR ranges of the library as BUILT here: every instantiation that hand-manages registers keeps at least 6
+    registers between the compiler's high-water mark and the stash (verdict round 4, item 5: a two-register margin would let a
+    compiler point release move the headline kernel to its fallback plan silently), and the range the guard derives from the
+    assembly starts where the kernels' constexprs (ABASE / LBASE) put it.  Reads the assembly csrc/build.sh leaves beside the
+    objects; skipped when the library was built elsewhere."""
+    S20, S16, S12, T = "ELi20ELi20ELi10ELi10E", "ELi16ELi16ELi8ELi8E", "ELi12ELi12ELi6ELi6E", "ELi80ELi80ELi5ELi5"
+    # (name up to and including MULTI = false: the element-loop instantiations of the same shapes have ranges of their own)
+    expected = {"kernels_fused.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20 + "Lb0E", 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0E", 106),
+                                    ("k_iter_fusedILi3ELb1ELb0ELb0" + S20 + "Lb0E", 106), ("k_iter_fusedILi2ELb0ELb1ELb0" + S20 + "Lb0E", 156),
+                                    ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0E", 166), ("k_iter_fusedILi3ELb0ELb1ELb0" + S12 + "Lb0E", 226)],
+                # round 6, the general forms (template tail <.., MULTI = false, NT2, GEN = true>): three channels on the one-hot kernels' stash,
+                # four channels with one more tile per wave in LDS (the stash starts 2 L x 5 registers higher)
+                "kernels_fused_gen.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106),
+                                        ("k_iter_fusedILi3ELb1ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi0ELb1E", 166),
+                                        ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi1ELb1E", 196), ("k_iter_fusedILi3ELb1ELb0ELb0" + S16 + "Lb0ELi1ELb1E", 196),
+                                        ("k_iter_fusedILi2ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 176),
+                                        # the tight plan (FzPlan): three of the first stash place's fifteen doubles in registers, twelve in LDS
+                                        ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 160)],
+                "kernels_tall.s": [("k_iter_tallILi2ELi1ELi3" + T + "ELb0", 136), ("k_iter_tallILi2ELi1ELi3" + T + "ELb1", 166),
+                                   ("k_iter_tallILi2ELi0ELi3" + T + "ELb1", 166)]}
+    for f, fns in _built(("k_iter_fused", "k_iter_tall")).items():
+        assert len(fns) >= GUARDED[f][1] and all(fn.stem == GUARDED[f][0] for fn in fns), (f, len(fns))
+        for key, base in expected[f]:
+            hit = [fn for fn in fns if key in fn.name]
+            assert len(hit) == 1 and hit[0].base == base, (key, base, [(fn.name, fn.base) for fn in hit])
+        for fn in fns:
+            assert fn.base == 256 or fn.base - fn.hi >= 6, (fn.name, fn.hi, fn.base)
 
 
 def test_no_whole_iteration_kernel_spills_to_scratch():
     """Round 6: one more pointer kept alive across the phases of k_iter_fused<.., NT2 = 1> sent the register allocator to scratch
     memory -- 420 - 540 scratch accesses per instantiation, correct results, 148 instead of 58 us per iteration, and nothing said so.
-    check_agpr.py now counts them (exit 3, build.sh fails); here: NO instantiation of the hand-scheduled whole-iteration kernels in
+    check_agpr.py now counts them (build.sh fails); here: NO instantiation of the hand-scheduled whole-iteration kernels in
     the assembly csrc/build.sh left beside the objects touches scratch memory."""
-    import re
-    import pytest
-    csrc = os.path.join(ROOT, "hp_vpinns_amd", "csrc")
-    files = ["kernels_fused.s", "kernels_fused_gen.s", "kernels_tall.s"]
-    if not all(os.path.exists(os.path.join(csrc, f)) for f in files):
-        pytest.skip("no assembly beside the objects (library built elsewhere)")
-    n_kernels, spills = 0, {}
-    for f in files:
-        lines = open(os.path.join(csrc, f)).read().split("\n")
-        name = None
-        for l in lines:
-            m = re.match(r"^(_Z\d+k_iter_(fused|tall|small)\w+):", l)
-            if m:
-                name, n_kernels = m.group(1), n_kernels + 1
-            elif l.startswith(".Lfunc_end"):
-                name = None
-            elif name and re.search(r"\bscratch_(load|store)_", l.split(";")[0]):
-                spills[name] = spills.get(name, 0) + 1
-    assert n_kernels >= 40, n_kernels
+    fns = [fn for fs in _built(("k_iter_fused", "k_iter_tall", "k_iter_small")).values() for fn in fs]
+    assert len(fns) >= 40, len(fns)
+    spills = {fn.name: fn.spills for fn in fns if fn.spills}
     # (k_iter_small<3> -- eight waves of 256 registers, config 3 -- has carried seven spilled quad-words since round 3: 14 accesses
     #  outside its tile loops; anything beyond that, or any other kernel, is a regression)
     known = {k: v for k, v in spills.items() if "k_iter_smallILi3E" in k and v <= 16}
     assert spills == known, {k: v for k, v in spills.items() if k not in known}
+
+
+def _fused(L, SPLIT, QT, QX, MULTI=0, NT2=0, GEN=0, GS=0):
+    return "_Z12k_iter_fusedILi%dELb%dELb%dELb%dELi%dELi%dELi%dELi%dELb%dELi%dELb%dEEv9FusedArgs" % (L, SPLIT, QT, GS, QX, QX, QX // 2, QX // 2, MULTI, NT2, GEN)
+
+
+def _tall(L, QT):
+    return "_Z11k_iter_tallILi2ELi1ELi%dELi80ELi80ELi5ELi5ELb%dEEv8TallArgs" % (L, QT)
+
+
+def _plan(tmp_path, unit, fns):
+    """--plan on synthetic assembly: fns = [(mangled name, highest compiler register, lowest hand-managed register or None, spills)]."""
+    body = "\t.text\n"
+    for i, (name, hi, base, spills) in enumerate(fns):
+        body += "%s:\n\tv_accvgpr_read_b32 v9, a%d\n\ts_endpgm\n" % (name, hi)
+        if base is not None:
+            body += "\tv_accvgpr_write_b32 a[0x%x], v1\n\tv_accvgpr_write_b32 a[0xfe:0xff], v1\n" % base
+        body += "\tscratch_load_dword v1, off, off\n" * spills + "\ts_endpgm\n.Lfunc_end%d:\n" % i
+    f = tmp_path / (unit + ".s")
+    f.write_text(body)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_agpr.py"), "--plan", unit, str(f)], capture_output=True, text=True)
+    return r.returncode, set(r.stdout.split()), r.stderr
+
+
+def test_trip_policy(tmp_path):
+    """What a trip compiles out (the table of scripts/check_agpr.py), per group of instantiations: real mangled names, the base read
+    from a hex-printed operand, one compiler register at or above it.  clear = every group present and clear: no flag."""
+    D = "-DHPV_"
+    # (name, hand-managed base): one function per group, bases as derived from the library's assembly
+    fused = {"20": (_fused(3, 0, 0, 20), 106), "20s": (_fused(2, 1, 0, 20), 156), "20q": (_fused(3, 0, 1, 20), 106),
+             "16": (_fused(3, 1, 0, 16), 166), "12q": (_fused(2, 0, 1, 12), 236),
+             "m20": (_fused(2, 0, 0, 20, MULTI=1), 156), "m16q": (_fused(3, 0, 1, 16, MULTI=1), 166), "m12": (_fused(2, 0, 0, 12, MULTI=1), 190)}
+    gen = {"3": (_fused(3, 0, 0, 20, GEN=1), 106), "3s16": (_fused(2, 1, 0, 16, GEN=1), 196), "3q": (_fused(3, 0, 1, 12, GEN=1), 226),
+           "4": (_fused(3, 1, 0, 16, NT2=1, GEN=1), 196), "4_20": (_fused(2, 0, 0, 20, NT2=1, GEN=1), 176), "4q": (_fused(2, 0, 1, 16, NT2=1, GEN=1), 216),
+           "tight": (_fused(3, 0, 0, 20, NT2=1, GEN=1), 160), "4_12": (_fused(3, 0, 0, 12, NT2=1, GEN=1), None)}
+    tall = {"w3": (_tall(3, 0), 136), "w2": (_tall(2, 0), 176), "q3": (_tall(3, 1), 166), "q2": (_tall(2, 1), 196)}
+    cases = [("kernels_fused", fused, [], []),
+             ("kernels_fused", fused, ["20"], ["AGPR_GUARD_TRIPPED"]),
+             ("kernels_fused", fused, ["20s"], ["AGPR_GUARD_TRIPPED"]),
+             ("kernels_fused", fused, ["20s", "20q", "16", "m12"], ["AGPR_GUARD_TRIPPED"]),               # nothing else is evaluated
+             ("kernels_fused", fused, ["20q"], ["AGPR_GUARD_TRIPPED_QT"]),
+             ("kernels_fused", fused, ["16"], ["FZ_NO_EXTRA_SHAPES"]),
+             ("kernels_fused", fused, ["12q"], ["FZ_NO_EXTRA_SHAPES"]),
+             ("kernels_fused", fused, ["m20"], ["FZ_NO_MULTI"]),
+             ("kernels_fused", fused, ["m16q"], ["FZ_NO_MULTI"]),
+             ("kernels_fused", fused, ["m12"], ["FZ_NO_MULTI"]),
+             ("kernels_fused", fused, ["20q", "12q", "m16q"], ["AGPR_GUARD_TRIPPED_QT", "FZ_NO_EXTRA_SHAPES", "FZ_NO_MULTI"]),   # independent of one another
+             ("kernels_fused_gen", gen, [], []),
+             ("kernels_fused_gen", gen, ["3"], ["FZ_GEN_TRIPPED"]),
+             ("kernels_fused_gen", gen, ["3s16"], ["FZ_GEN_TRIPPED"]),
+             ("kernels_fused_gen", gen, ["3s16", "3q", "4", "4q", "tight"], ["FZ_GEN_TRIPPED"]),          # nothing else is evaluated
+             ("kernels_fused_gen", gen, ["3q"], ["FZ_GEN_NO_QT"]),
+             ("kernels_fused_gen", gen, ["4q"], ["FZ_GEN_NO_QT"]),
+             ("kernels_fused_gen", gen, ["4"], ["FZ_GEN_NO_NT2", "FZ_GEN_NO_TIGHT"]),                     # NO_NT2 implies NO_TIGHT
+             ("kernels_fused_gen", gen, ["4_20"], ["FZ_GEN_NO_NT2", "FZ_GEN_NO_TIGHT"]),
+             ("kernels_fused_gen", gen, ["4", "4q", "tight"], ["FZ_GEN_NO_NT2", "FZ_GEN_NO_TIGHT"]),      # ... and silences the four-channel QT functions
+             ("kernels_fused_gen", gen, ["4", "3q"], ["FZ_GEN_NO_NT2", "FZ_GEN_NO_QT", "FZ_GEN_NO_TIGHT"]),
+             ("kernels_fused_gen", gen, ["tight"], ["FZ_GEN_NO_TIGHT"]),
+             ("kernels_fused_gen", gen, ["tight", "4q"], ["FZ_GEN_NO_QT", "FZ_GEN_NO_TIGHT"]),
+             ("kernels_tall", tall, [], []),
+             ("kernels_tall", tall, ["w3"], ["AGPR_GUARD_TRIPPED"]),
+             ("kernels_tall", tall, ["w2", "q3"], ["AGPR_GUARD_TRIPPED"]),                                # nothing else is evaluated
+             ("kernels_tall", tall, ["q3"], ["AGPR_GUARD_TRIPPED_QT"]),
+             ("kernels_tall", tall, ["q2"], ["AGPR_GUARD_TRIPPED_QT"])]
+    for unit, group, trips, want in cases:
+        # a tripping function's compiler register sits AT its base (even cases) or above it (odd ones), a clear one's just below;
+        # a function that hand-manages nothing (base None -> 256) never trips, whatever the compiler uses
+        fns = [(name, 255 if base is None else base + len(trips) % 2 if k in trips else base - 1, base, 0) for k, (name, base) in group.items()]
+        rc, flags, err = _plan(tmp_path, unit, fns)
+        assert rc == 0 and flags == {D + w for w in want}, (unit, trips, rc, flags, err)
+        assert err.count("build.sh: WARNING") == len(want) and err.count("check_agpr: _Z") == len(fns), err
+        assert all("hand-managed range starts at a%d\n" % (256 if base is None else base) in err for _, base in group.values()), err
+
+
+def test_plan_fails_when_it_cannot_check(tmp_path):
+    """Exit 2 (build.sh FAILS) when no function carries the kernel's name any more, the template arguments changed, the file is
+    missing, or a guarded kernel spills; k_iter_small (not hand-scheduled: 14 known scratch accesses) is not the guard's business."""
+    ok = (_fused(3, 0, 0, 20), 90, 106, 0)
+    small = ("_Z12k_iter_smallILi3EEv9FusedArgs", 250, None, 14)
+    assert _plan(tmp_path, "kernels_fused", [ok, small])[:2] == (0, set())
+    rc, flags, err = _plan(tmp_path, "kernels_fused", [(ok[0].replace("k_iter_fused", "k_iter_fuzed"), 90, 106, 0), small])
+    assert rc == 2 and not flags and "no k_iter_fused function" in err
+    rc, flags, err = _plan(tmp_path, "kernels_tall", [ok])
+    assert rc == 2 and "no k_iter_tall function" in err
+    rc, flags, err = _plan(tmp_path, "kernels_fused", [ok, (ok[0].replace("Lb0ELi0ELb0EEv", "Lb0ELi0EEv"), 90, 106, 0)])
+    assert rc == 2 and not flags and "template arguments" in err
+    rc, flags, err = _plan(tmp_path, "kernels_fused", [ok, (_fused(2, 0, 0, 16), 90, 196, 3)])
+    assert rc == 2 and not flags and "spills" in err
+    script = os.path.join(ROOT, "scripts", "check_agpr.py")
+    r = subprocess.run([sys.executable, script, "--plan", "kernels_fused", str(tmp_path / "missing.s")], capture_output=True, text=True)
+    assert r.returncode == 2 and not r.stdout.strip() and "cannot read" in r.stderr
+    f = tmp_path / "k.s"
+    f.write_text(ok[0] + ":\n\tv_accvgpr_read_b32 v9, a90\n\ts_endpgm\n")
+    r = subprocess.run([sys.executable, script, "--plan", "kernels_fused", str(f)], capture_output=True, text=True)
+    assert r.returncode == 2 and "no function end marker" in r.stderr
 
 
 def test_guard_reports_spills(tmp_path):
