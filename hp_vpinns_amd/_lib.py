@@ -291,9 +291,10 @@ class Handle:
         self._chk(self.lib.hpv_set_rhs(self._h, _p(F), 0 if F is None else F.size))
 
     def set_collocation(self, X, f, n_total=None):
-        """X, f: this handle's collocation points; n_total: their number over all shards (default: these are all)."""
-        X, f = _points(X, self.layers[0], "collocation points"), _c(f).reshape(-1)
-        if f.size != X.shape[0]:
+        """X, f: this handle's collocation points; n_total: their number over all shards (default: these are all).  f None: zero
+        right-hand side (AdvDiff only; the library refuses it for the Poisson problems)."""
+        X, f = _points(X, self.layers[0], "collocation points"), (None if f is None else _c(f).reshape(-1))
+        if f is not None and f.size != X.shape[0]:
             raise ValueError("one right-hand-side value per collocation point")
         self._chk(self.lib.hpv_set_collocation_shard(self._h, _p(X), _p(f), X.shape[0],
                                                      X.shape[0] if n_total is None else int(n_total)))

@@ -406,7 +406,9 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
     return 0;
 }
 
-// scheme == 'PINNs' (P2:128-129): loss = w*lossb + lossp, lossp = mean((u_xx+u_yy-f)^2) at the collocation points
+// scheme == 'PINNs' (P2:128-129; the same switch for the other two problems): loss = w*lossb + lossp, lossp = mean(r^2) at the
+// collocation points with the problem's strong-form residual r (k_pinn_residual); AdvDiff: the partials of d lossp / d epsilon ride
+// where the variational path puts its own (deps_e of k_finalize -> the packed buffer's slot [P])
 int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->n_col <= 0) return fail(h, -3, "hpv_set_collocation has not been called");
@@ -433,8 +435,10 @@ int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
         if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) return rc;
     }
     run_fwd(h, h->colloc, h->mfma_colloc, backward ? 1 : 0);
-    launch_pinn_residual(h->colloc.OUT, h->d_fcol, h->colloc.GBAR, h->d_col_part, h->colloc.N, h->n_col, h->n_col_total,
-                         backward ? 1 : 0, h->stream);
+    const int nparts = pinn_residual_parts(h->n_col);
+    launch_pinn_residual(h->cfg.pde, PinnArgs{h->colloc.OUT, h->d_fcol, h->colloc.GBAR, h->d_col_part, h->d_col_part + 64,
+                                              h->has_eps ? h->d_theta + h->P : nullptr, h->cfg.V, h->colloc.N, h->n_col,
+                                              h->n_col_total, backward ? 1 : 0}, h->stream);
     if (backward) run_bwd(h, h->colloc, h->mfma_colloc);
     int ndp = 0;
     if (h->n_data > 0) {
@@ -446,8 +450,8 @@ int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
     }
     const AdamArgs ad = adam_args(h);
     launch_finalize(backward ? h->colloc.GPART : nullptr, h->colloc.rows, backward && h->n_data > 0 ? h->data.GPART : nullptr,
-                    h->data.rows, nullptr, 0, h->d_col_part, pinn_residual_parts(h->n_col), nullptr, h->d_data_part, ndp,
-                    h->cfg.lossb_weight, h->n_data, h->P, 0, h->d_RB, backward ? 1 : 0, (backward && fuse_adam) ? &ad : nullptr,
+                    h->data.rows, nullptr, 0, h->d_col_part, nparts, h->has_eps ? h->d_col_part + 64 : nullptr, h->d_data_part, ndp,
+                    h->cfg.lossb_weight, h->n_data, h->P, h->has_eps, h->d_RB, backward ? 1 : 0, (backward && fuse_adam) ? &ad : nullptr,
                     h->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, -2, "kernel launch failed: %s", hipGetErrorString(e));
@@ -606,10 +610,11 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     }
     h->nd_val = make_netdesc(*cfg, 0, t1, 0, t2);
     if (cfg->scheme == HPV_SCHEME_PINN) {
-        if (cfg->pde != HPV_PDE_POISSON2D) { delete h; return fail(nullptr, -1, "scheme PINNs is the Poisson-2D branch (P2:128-129)"); }
-        // (u_xx + u_yy as ONE mixed second tangent, NetDesc::t2w: four channels instead of five through forward and reverse -- P2:187-194)
-        h->nd_pinn = make_netdesc(*cfg, 2, t1, 1, t2);
-        h->nd_pinn.t2w[0] = 1.0; h->nd_pinn.t2w[1] = 1.0;
+        // channels of the strong-form residual (k_pinn_residual): 1-D [u, u_x, u_xx] (P1:150-155); AdvDiff [u, u_x, u_t, u_xx]
+        // (P3:247-253; t2w = {1, 0}); 2-D u_xx + u_yy as ONE mixed second tangent, NetDesc::t2w: four channels instead of five
+        // through forward and reverse (P2:187-194)
+        h->nd_pinn = make_netdesc(*cfg, dim, t1, 1, t2);
+        if (cfg->pde == HPV_PDE_POISSON2D) { h->nd_pinn.t2w[0] = 1.0; h->nd_pinn.t2w[1] = 1.0; }
     } else if (cfg->scheme != HPV_SCHEME_VPINN) { delete h; return fail(nullptr, -1, "unknown scheme %d", cfg->scheme); }
     pd.C = h->nd_var.C;
     h->P = h->nd_var.P;
@@ -955,15 +960,17 @@ int hpv_set_collocation(hpv_handle h, const double* X, const double* f, int n) {
 int hpv_set_collocation_shard(hpv_handle h, const double* X, const double* f, int n, long n_total) {
     if (!h) return -1;
     if (h->cfg.scheme != HPV_SCHEME_PINN) return fail(h, -1, "collocation points belong to scheme PINNs");
-    if (n < 1 || !X || !f || n_total < n) return fail(h, -1, "bad collocation arguments");
+    // f == NULL: zero right-hand side, AdvDiff only (P3:186 squares net_f itself; hpv_set_rhs does the same for the variational form)
+    if (n < 1 || !X || (!f && h->cfg.pde != HPV_PDE_ADVDIFF) || n_total < n) return fail(h, -1, "bad collocation arguments");
     drop_graph(h);
     int rc;
     if (h->mfma_colloc) { hpv_mfma_destroy(h->mfma_colloc); h->mfma_colloc = nullptr; }
     if ((rc = alloc_batch(h, h->colloc, h->nd_pinn, n, true))) return rc;
     if ((rc = upload_points(h, h->colloc, X, n, h->dim))) return rc;
     if ((rc = dalloc(h, &h->d_fcol, (size_t)n))) return rc;
-    if ((rc = upload(h, h->d_fcol, f, (size_t)n))) return rc;
-    if ((rc = dalloc(h, &h->d_col_part, 64))) return rc;
+    if (f) { if ((rc = upload(h, h->d_fcol, f, (size_t)n))) return rc; }
+    else HIPCHK(h, hipMemsetAsync(h->d_fcol, 0, (size_t)n * sizeof(double), h->stream));
+    if ((rc = dalloc(h, &h->d_col_part, 128))) return rc;      // [0..63] r^2 partials, [64..127] d epsilon partials
     h->n_col = n;
     h->n_col_total = n_total;
     return 0;

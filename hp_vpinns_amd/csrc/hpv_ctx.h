@@ -101,11 +101,12 @@ struct hpv_ctx {
     HpvMfma* mfma_eval = nullptr;
     double* d_eval_out = nullptr;
     long eval_N = 0;
-    // strong-form PINN branch (scheme == PINNs): collocation batch: u, u_x, u_y and the Laplacian as one mixed second tangent (four channels)
+    // strong-form PINN branch (scheme == PINNs): collocation batch with the channels of the problem's residual (k_pinn_residual) -- 1-D
+    // u, u_x, u_xx; 2-D u, u_x, u_y and the Laplacian as one mixed second tangent; AdvDiff u, u_x, u_t, u_xx
     NetDesc nd_pinn{};
     Batch colloc;
     HpvMfma* mfma_colloc = nullptr;
-    double *d_fcol = nullptr, *d_col_part = nullptr;
+    double *d_fcol = nullptr, *d_col_part = nullptr;      // d_col_part: [64] r^2 partials, then [64] d epsilon partials
     int n_col = 0;
     long n_col_total = 0;      // collocation points of ALL shards (the mean of P2:124 runs over them)
     double* d_jac = nullptr;   // |J_e| of the owned elements (RHS assembly, hpv_assemble_rhs)

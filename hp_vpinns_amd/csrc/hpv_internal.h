@@ -165,7 +165,20 @@ void launch_gll_rule(int Q, double* x, double* w, hipStream_t s);
 void launch_test_tables(int ntest, int q, const double* xi, double* tab, hipStream_t s);
 bool launch_project_tp(const ProjArgs& pa, long n_elem, hipStream_t s);
 int pinn_residual_parts(int n);
-void launch_pinn_residual(const double* OUT, const double* f, double* GBAR, double* part, long N, int n, long n_total,
-                          int write_gbar, hipStream_t s);
+// All arguments of the strong-form residual launch (k_pinn_residual, kernels_generic.hip).
+struct PinnArgs {
+    const double* OUT;       // [C][N] channels of the collocation batch
+    const double* f;         // [n] right-hand side at the points
+    double* GBAR;            // [C][N] adjoints, every row written (write_gbar)
+    double* part;            // [pinn_residual_parts(n)] per-block sums of r^2 / n_total
+    double* deps_part;       // [pinn_residual_parts(n)] per-block sums of d lossp / d epsilon (AdvDiff only)
+    const double* eps_ptr;   // theta + P on the device (AdvDiff only)
+    double V;                // advection speed (AdvDiff only)
+    long N;
+    int n;                   // points of THIS shard
+    long n_total;            // points of all shards: the mean runs over them
+    int write_gbar;
+};
+void launch_pinn_residual(int pde, const PinnArgs& a, hipStream_t s);
 bool launch_project_wg(const ProjArgs& pa, long n_elem, hipStream_t s, double* upart = nullptr);
 int project_row_split(const ProjDesc& pd, long n_elem, int backend_generic);   // workgroups per element of the row-split projection

@@ -822,28 +822,65 @@ void launch_debug_act(int act, const double* x, int n, double* a, double* a1, do
 }
 
 // ------------------------------------------------------------------------------------------------
-// Strong-form PINN residual of the 2-D Poisson problem (P2:187-194): r = u_xx + u_yy - f at the
-// collocation points; lossp = mean(r^2) (P2:124).  Channels: [u, u_x, u_y, u_xx + u_yy] (the Laplacian as one mixed second tangent).
+// Strong-form PINN residual at the collocation points; lossp = mean(r^2) (P2:124, P3:186), per problem:
+//   Poisson-1D  channels [u, u_x, u_xx]:          r = -u_xx - f                       (net_f, P1:150-155, against f_train as P2:124)
+//   Poisson-2D  channels [u, u_x, u_y, u_xx+u_yy] (the Laplacian as one mixed second tangent): r = u_xx + u_yy - f   (P2:187-194)
+//   AdvDiff     channels [u, u_x, u_t, u_xx]:     r = u_t + V u_x - epsilon u_xx - f  (net_f, P3:247-253; f = 0 there)
+// epsilon is read from the device parameter vector (the Adam update moves it between launches).  The kernel writes EVERY adjoint
+// row of its n points -- d lossp / d channel where the residual touches the channel, zero elsewhere (the value channel among them)
+// -- so the reverse pass never depends on what an earlier pass left in GBAR.  GBAR is [C][N] with N == n: the last 16-point tile
+// has no storage beyond n (the reverse kernels substitute zero adjoints there themselves).  Per block: part = sum r^2 / n_total
+// and, for AdvDiff, deps_part = sum d lossp / d epsilon = sum sc r (-u_xx); k_finalize adds them up in block order.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_pinn_residual(const double* __restrict__ OUT, const double* __restrict__ f,
-                                                      double* __restrict__ GBAR, double* __restrict__ part, long N,
-                                                      int n, long n_total, int write_gbar) {
+template <int PDE>
+__global__ void __launch_bounds__(256) k_pinn_residual(PinnArgs a) {
     // n points of THIS shard; the mean of P2:124 runs over the n_total collocation points of all shards
     __shared__ double red[16];
-    double sq = 0.0;
-    const double sc = 2.0 / (double)n_total;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-        const double r = OUT[3 * N + p] - f[p];
+    const double* __restrict__ OUT = a.OUT;
+    const double* __restrict__ f = a.f;
+    double* __restrict__ GBAR = a.GBAR;
+    const long N = a.N;
+    double sq = 0.0, de = 0.0;
+    const double sc = 2.0 / (double)a.n_total;
+    const double eps = PDE == HPV_PDE_ADVDIFF ? *a.eps_ptr : 0.0;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < a.n; p += gridDim.x * blockDim.x) {
+        double r;
+        if constexpr (PDE == HPV_PDE_POISSON1D) r = -OUT[2 * N + p] - f[p];
+        else if constexpr (PDE == HPV_PDE_POISSON2D) r = OUT[3 * N + p] - f[p];
+        else {
+            const double uxx = OUT[3 * N + p];
+            r = OUT[2 * N + p] + a.V * OUT[N + p] - eps * uxx - f[p];
+            de += r * uxx;
+        }
         sq += r * r;
-        if (write_gbar) GBAR[3 * N + p] = sc * r;
+        if (!a.write_gbar) continue;
+        GBAR[p] = 0.0;
+        if constexpr (PDE == HPV_PDE_POISSON1D) {
+            GBAR[N + p] = 0.0;
+            GBAR[2 * N + p] = -(sc * r);
+        } else if constexpr (PDE == HPV_PDE_POISSON2D) {
+            GBAR[N + p] = 0.0;
+            GBAR[2 * N + p] = 0.0;
+            GBAR[3 * N + p] = sc * r;
+        } else {
+            GBAR[N + p] = sc * a.V * r;
+            GBAR[2 * N + p] = sc * r;
+            GBAR[3 * N + p] = -(sc * eps * r);
+        }
     }
     sq = block_sum(sq, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = sq / (double)n_total;
+    if (PDE == HPV_PDE_ADVDIFF) de = block_sum(de, red);
+    if (threadIdx.x == 0) {
+        a.part[blockIdx.x] = sq / (double)a.n_total;
+        if (PDE == HPV_PDE_ADVDIFF) a.deps_part[blockIdx.x] = -(sc * de);
+    }
 }
 int pinn_residual_parts(int n) { int b = (n + 255) / 256; return b > 64 ? 64 : (b < 1 ? 1 : b); }
-void launch_pinn_residual(const double* OUT, const double* f, double* GBAR, double* part, long N, int n, long n_total,
-                          int write_gbar, hipStream_t s) {
-    hipLaunchKernelGGL(k_pinn_residual, dim3(pinn_residual_parts(n)), dim3(256), 0, s, OUT, f, GBAR, part, N, n, n_total, write_gbar);
+void launch_pinn_residual(int pde, const PinnArgs& a, hipStream_t s) {
+    const dim3 grid(pinn_residual_parts(a.n)), block(256);
+    if (pde == HPV_PDE_POISSON1D) hipLaunchKernelGGL(k_pinn_residual<HPV_PDE_POISSON1D>, grid, block, 0, s, a);
+    else if (pde == HPV_PDE_POISSON2D) hipLaunchKernelGGL(k_pinn_residual<HPV_PDE_POISSON2D>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_pinn_residual<HPV_PDE_ADVDIFF>, grid, block, 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -114,11 +114,12 @@ def export_mat(path, s, u_record, u_records_iterhis, total_record, total_time_tr
 
 
 def run(LR=0.001, Opt_Niter=1500 + 1, Opt_tresh=2e-11, var_form=0, Net_layer=None, N_el_x=1, N_el_t=1, N_test_x=5,
-        N_test_t=5, N_quad=10, N_bound=80, init_params=None, backend="auto", verbose=True, mat_path=None):
-    """P3:31-54 hyper-parameters (reference defaults) -> identified epsilon, prediction, L2 error."""
+        N_test_t=5, N_quad=10, N_bound=80, init_params=None, backend="auto", verbose=True, mat_path=None, scheme="VPINNs"):
+    """P3:31-54 hyper-parameters (reference defaults) -> identified epsilon, prediction, L2 error.  scheme 'PINNs' trains on the
+    strong-form residual u_t + V u_x - epsilon u_xx at the NPf collocation points of P3:387-391 instead of the variational one."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P3:46
     s = setup(N_el_x, N_el_t, N_test_x, N_test_t, N_quad, N_bound)
-    model = build_model(s, Net_layer, var_form, LR, init_params, backend)
+    model = build_model(s, Net_layer, var_form, LR, init_params, backend, scheme=scheme)
     error_record, total_record, u_record, u_his, t_train = model.train(Opt_Niter, Opt_tresh)   # P3:493-494
     if mat_path is not None:                                                    # P3:500-508
         export_mat(mat_path, s, u_record, u_his, total_record, t_train)
@@ -139,6 +140,7 @@ if __name__ == "__main__":
     ap.add_argument("--width", type=int, default=5)
     ap.add_argument("--var-form", type=int, default=0)
     ap.add_argument("--mat", default=None, help="write the reference's <case>_record.mat here (P3:500-508)")
+    ap.add_argument("--scheme", default="VPINNs", choices=("VPINNs", "PINNs"))
     a = ap.parse_args()
     run(Opt_Niter=a.iters, N_el_x=a.elements_x, N_quad=a.quad, var_form=a.var_form, Net_layer=[2] + [a.width] * 3 + [1],
-        mat_path=a.mat)
+        mat_path=a.mat, scheme=a.scheme)

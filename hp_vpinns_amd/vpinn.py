@@ -171,6 +171,21 @@ def _dense_rhs_2d(F, nax, nay):
     return out
 
 
+def _check_scheme(scheme, X_f, f=None, need_f=False):
+    """The `scheme` switch of P2:125-129 as the 1-D and AdvDiff classes take it: an explicit keyword (P1 and P3 have no such module
+    global, so it is never looked up in the caller's).  Raises before any library call."""
+    if scheme not in ("VPINNs", "PINNs"):
+        raise ValueError("scheme is either 'PINNs' or 'VPINNs' (P2:269)")
+    if scheme == "PINNs":
+        if X_f is None or np.size(X_f) == 0:
+            raise ValueError("scheme 'PINNs' needs collocation points")
+        if need_f and f is None:
+            raise ValueError("scheme 'PINNs' needs f_train, the right-hand side at the collocation points")
+        if need_f and np.size(f) != np.shape(X_f)[0]:
+            raise ValueError("f_train needs one value per collocation point")
+    return scheme
+
+
 def _next_chunk(it, nIter, every=10):
     """Iterations `it .. it+n-1` run back to back on the device; `rec` says whether the last of
     them is a recording iteration (it % every == 0, P1:210 / P3:314)."""
@@ -602,6 +617,17 @@ class _VPINNBase:
         X = np.asarray(X, dtype=np.float64)
         return self.h.predict(X)[:, None]
 
+    def _set_collocation_shard(self, X_f, f):
+        """Strong-form branch, multi-GPU: the collocation points shard over the ranks in contiguous blocks (lossp is a mean of
+        independent point-wise terms), the boundary term stays on rank 0, one all-reduce of the packed buffer per iteration.
+        f None: zero right-hand side (AdvDiff)."""
+        Xf = np.asarray(X_f, dtype=np.float64)
+        ff = None if f is None else np.asarray(f, dtype=np.float64).reshape(-1)
+        if Xf.shape[0] < self.world:
+            raise ValueError("fewer collocation points than ranks")
+        cb, ce = shard_range(Xf.shape[0], self.rank, self.world)
+        self.h.set_collocation(Xf[cb:ce], None if ff is None else ff[cb:ce], n_total=Xf.shape[0])
+
 
 class VPINN1D(_VPINNBase):
     """Poisson 1-D hp-VPINN (reference P1:30-224; constructor P1:31-32, call site P1:333-334)."""
@@ -610,7 +636,10 @@ class VPINN1D(_VPINNBase):
 
     def __init__(self, X_u_train, u_train, X_quad, W_quad, F_exact_total, grid, X_test, u_test, layers,
                  X_f_train=None, f_train=None, *, var_form=None, lossb_weight=None, LR=None, init_params=None,
-                 seed=1234, backend="auto", device=None, total_record=None, module_globals=None):
+                 seed=1234, backend="auto", device=None, total_record=None, module_globals=None, scheme="VPINNs"):
+        # scheme 'PINNs' (an extension: P1 has no such switch; it follows P2:124-129): the variational term is replaced by
+        # lossp = mean((-u_xx - f_train)^2) at X_f_train (net_f, P1:150-155), loss = lossb_weight * lossb + lossp
+        self.scheme = _check_scheme(scheme, X_f_train, f_train, need_f=True)
         ns = module_globals if module_globals is not None else _caller_globals()
         self._module_globals = module_globals
         var_form = _resolve(var_form, "var_form", ns, 1, (int, np.integer))              # P1:234 (read at P1:82-91)
@@ -636,7 +665,8 @@ class VPINN1D(_VPINNBase):
         self.total_record = [] if total_record is None else total_record
         if self.grid.size != self.Nelement + 1:
             raise ValueError("grid must have Nelement+1 entries")
-        self._create(layers, var_form, LR, lossb_weight, 1.0, init_params, seed, backend, device)
+        self._create(layers, var_form, LR, lossb_weight, 1.0, init_params, seed, backend, device,
+                     scheme=_lib.SCHEME_PINN if scheme == "PINNs" else _lib.SCHEME_VPINN)
 
         # The element-resident 1-D kernel (csrc/kernels_tile.hip) is instantiated for the reference's own rule, 80 points and 60 test
         # functions (P1:237-238), for var_forms 1 / 2 on 20-wide networks of 2-4 hidden layers.  Where THAT kernel can run:
@@ -648,7 +678,7 @@ class VPINN1D(_VPINNBase):
         # Everywhere else (generic backend, var_form 3, wider / deeper networks) the device sees the problem as it is.
         hidden = self.layers[1:-1]
         pad_rule = False
-        if backend != "generic":
+        if backend != "generic" and scheme == "VPINNs":
             eb, ee = shard_range(self.Nelement, self.rank, self.world)
             force = bool(os.environ.get("HPV_FORCE_RULE_PADDING"))     # (measurement knob, scripts/rule1d_sweep.py: the advice for ONE element)
             q_dev, nt_dev = _lib.rule_advice(self.device, self._pde, var_form, len(hidden), max(hidden), self.xquad.size, self.N_test, 1,
@@ -658,6 +688,11 @@ class VPINN1D(_VPINNBase):
                 self._N_test_dev = nt_dev
 
         def populate():
+            if scheme == "PINNs":
+                self._set_collocation_shard(X_f_train, f_train)
+                if self.rank == 0:
+                    self.h.set_data(self.x, self.u.reshape(-1))
+                return
             xi, wq = self.xquad.reshape(-1), self.wquad.reshape(-1)
             if pad_rule:
                 xi, wq = _pad_rule(xi, wq, 80)
@@ -689,7 +724,8 @@ class VPINN1D(_VPINNBase):
     def train(self, nIter, tresh):
         """P1:201-224.  The loss is read back every 10 iterations, AFTER that iteration's update,
         appended to `total_record` as [it, loss]; early exit when loss < tresh.  `total_record` is the list handed to the
-        constructor, else the caller's module-level `total_record` as it exists now (P1:335 creates it after P1:333)."""
+        constructor, else the caller's module-level `total_record` as it exists now (P1:335 creates it after P1:333).
+        (scheme 'PINNs': the Lossv column of the progress line is lossp.)"""
         self.total_record = self._history("total_record", self._total_record_arg, _caller_globals())
         start_time = time.time()
         it = 0
@@ -749,13 +785,7 @@ class VPINN2D(_VPINNBase):
         def populate():
             if scheme == "PINNs":
                 # strong-form branch (P2:128-129): loss = 10 lossb + mean((u_xx+u_yy-f)^2) at X_f_train
-                # multi-GPU: the collocation points shard over the ranks in contiguous blocks (lossp is a mean of independent
-                # point-wise terms), the boundary term stays on rank 0, one all-reduce of the packed buffer per iteration
-                Xf, ff = np.asarray(X_f_train, dtype=np.float64), np.asarray(f_train, dtype=np.float64).reshape(-1)
-                if Xf.shape[0] < self.world:
-                    raise ValueError("fewer collocation points than ranks")
-                cb, ce = shard_range(Xf.shape[0], self.rank, self.world)
-                self.h.set_collocation(Xf[cb:ce], ff[cb:ce], n_total=Xf.shape[0])
+                self._set_collocation_shard(X_f_train, f_train)
             else:
                 xi, wx, yi, wy = _tensor_rule(X_quad, W_quad)
                 # (var_form 1 runs on the one-hot instantiations of the whole-iteration kernel, var_form 0 on the FOUR-channel ones: 12x12, 16x16 and
@@ -814,7 +844,12 @@ class VPINNAdvDiff(_VPINNBase):
 
     def __init__(self, XT_u_train, u_train, XT_f_train, XT_quad, W_quad, T_quad, WT_quad, grid_x, grid_t,
                  N_testfcn, XT_test, u_test, layers, lb=None, ub=None, *, var_form=None, LR=None, V=None,
-                 lossb_weight=10, init_params=None, seed=1234, backend="auto", device=None, module_globals=None):
+                 lossb_weight=10, init_params=None, seed=1234, backend="auto", device=None, module_globals=None,
+                 scheme="VPINNs"):
+        # scheme 'PINNs' (an extension: P3 builds lossp at P3:186 but never trains on it; the switch follows P2:124-129): the
+        # variational term is replaced by lossp = mean((u_t + V u_x - epsilon u_xx)^2) at XT_f_train (net_f, P3:247-253),
+        # loss = lossb + lossp with lossb = 10 * mean(...) (P3:184); epsilon stays trainable
+        self.scheme = _check_scheme(scheme, XT_f_train)
         ns = module_globals if module_globals is not None else _caller_globals()
         self._module_globals = module_globals
         var_form = _resolve(var_form, "var_form", ns, 0, (int, np.integer))              # P3:38 (read at P3:161-174)
@@ -831,9 +866,15 @@ class VPINNAdvDiff(_VPINNBase):
         self.grid_x, self.grid_t = np.asarray(grid_x, dtype=np.float64), np.asarray(grid_t, dtype=np.float64)
         self.XT_test, self.utest = XT_test, u_test
         self.var_form, self.V = var_form, V
-        self._create(layers, var_form, LR, lossb_weight, V, init_params, seed, backend, device)
+        self._create(layers, var_form, LR, lossb_weight, V, init_params, seed, backend, device,
+                     scheme=_lib.SCHEME_PINN if scheme == "PINNs" else _lib.SCHEME_VPINN)
 
         def populate():
+            if scheme == "PINNs":
+                self._set_collocation_shard(XT_f_train, None)      # zero right-hand side (P3:186)
+                if self.rank == 0:
+                    self.h.set_data(self.XT_u_train, self.u.reshape(-1))
+                return
             xi, wx, ti, wt = _tensor_rule(XT_quad, W_quad)
             # rules below 10 points onto the 10x10 / 5x5 tile kernel, rules between the instantiated ones onto the whole-iteration kernel's
             # general forms (round 6): var_form 1 has three channels (every shape), var_form 0 four (12x12, 16x16, 20x20)
@@ -862,7 +903,7 @@ class VPINNAdvDiff(_VPINNBase):
 
     def train(self, nIter, tresh):
         """P3:291-341 -- returns (error_records, total_records, u_records, u_records_iterhis,
-        total_time_train) like the reference."""
+        total_time_train) like the reference.  (scheme 'PINNs': the Lossv column of the progress line is lossp.)"""
         total_time_train, min_loss = 0.0, 1e16
         total_records, u_records_iterhis, u_records = [], [], None
         loss_value, start_time = None, time.time()

@@ -47,7 +47,7 @@ typedef struct hpv_config {
     double V;                     /* advection speed, P3:43                                           */
     int device;                   /* HIP device ordinal                                               */
     int backend;                  /* HPV_BACKEND_*                                                    */
-    int scheme;                   /* HPV_SCHEME_VPINN (default) or HPV_SCHEME_PINN (P2:126-129)       */
+    int scheme;                   /* HPV_SCHEME_VPINN (default) or HPV_SCHEME_PINN (P2:126-129; every pde) */
 } hpv_config;
 
 /* Construction = the graph-build part of VPINN.__init__ (P1:31-107, P2:28-136, P3:60-197). */
@@ -106,8 +106,15 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
 int hpv_set_data(hpv_handle h, const double* X, const double* u, int n);
 
-/* Collocation points of the strong-form PINN branch (`scheme == 'PINNs'`, P2:124-129,
- * 187-194): lossp = mean((u_xx + u_yy - f)^2) over X_f [n][2] replaces the variational term.  Poisson-2D only. */
+/* Collocation points of the strong-form PINN branch (`scheme == 'PINNs'`, P2:124-129): lossp = mean(r^2)
+ * over the points X [n][dim] replaces the variational term, loss = lossb_weight * lossb + lossp (P2:129).  Residual per problem:
+ *   Poisson-1D  r = -u_xx - f                        (net_f, P1:150-155, against f_train as P2:124)
+ *   Poisson-2D  r = u_xx + u_yy - f                  (P2:187-194)
+ *   AdvDiff     r = u_t + V u_x - epsilon u_xx - f   (net_f, P3:247-253, lossp P3:186; columns of X are (x, t), V = cfg.V)
+ * The reference offers the switch in P2 only; the other two follow P2:124-129.  f is [n]; NULL means a zero right-hand side and
+ * is accepted for AdvDiff only (as hpv_set_rhs does for its variational form).  AdvDiff: epsilon stays the trainable last
+ * parameter, read on the device at every pass; d lossp / d epsilon = (2 / n_total) sum r (-u_xx) lands in the packed buffer's
+ * d-epsilon slot like the variational path's. */
 int hpv_set_collocation(hpv_handle h, const double* X, const double* f, int n);
 /* One rank's shard of the collocation set (multi-GPU PINN branch): n points here, n_total over all ranks -- lossp is the
  * mean over all n_total points (P2:124), the partial sums are made global by the iteration's all-reduce. */
