@@ -161,7 +161,6 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     static_assert(C % TRG == 0, "whole transpose passes");
     static_assert(NPART == 0 || !QT, "the tight plan: whole tiles");
     using M = FzLds<L, QX_, QY_, NTX_, NTY_, MULTI, C, TRG, NPART>;
-    static_assert(!GEN || (M::AX == M::TR && 4 <= M::TR_WAVE), "the d-epsilon partials live in wave 0's part of the transpose region (it reads them back itself)");
     constexpr int LH = L > 1 ? L - 1 : 1;
     constexpr int NSV = L * MF_KS;                 // saved doubles per lane and tile
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -746,7 +745,6 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     // phase P: projection of the element from LDS (two one-hot terms: term t integrates channel 1 + t)
     // =============================================================================================
     {
-        const double* G = lds + M::CH;
         // per-element test-function counts (p-refinement of the 2-D drivers, P2:72-73 / P3:112-113): THIS element's pair, requested here
         // and used behind the two contractions -- scalar registers (e is workgroup-uniform), nothing lives across the phases.  The
         // tables, F, R and their strides keep the run's rnx x rny; residuals beyond the pair are zero, the mean runs over the pair.
@@ -757,90 +755,230 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             nay_e = __builtin_amdgcn_readfirstlane(pa.pd.nacty[e]);
             nr_e = (double)(nax_e * nay_e);
         }
-        // T_t[j][r] = sum_i AX_t[r][i] G_t[j][i]
-        for (int o = tid; o < 2 * FZ_QY * FZ_NTX; o += FZ_BLOCK) {
-            const int t = o / (FZ_QY * FZ_NTX), j = (o / FZ_NTX) % FZ_QY, r = o % FZ_NTX;
-            const double* ax = lds + M::AX + (t * FZ_NTX + r) * FZ_QX;
-            const double* gr = G + t * FZ_NQ + j * FZ_QX;
-            double acc = 0.0;
+        // The four-channel forms on 16x16 points keep the scalar contractions (one output per thread, five barriers): with the matrix form
+        // below they measured 1.2 - 1.4 us per iteration SLOWER (profiles/proj_phase_mfma.md); every other instantiation takes the matrix form.
+        constexpr bool PJ_SCALAR = NT2 > 0 && FZ_NQ == 256;
+        if constexpr (PJ_SCALAR) {
+            static_assert(!GEN || (M::AX == M::TR && 4 <= M::TR_WAVE), "the d-epsilon partials live in wave 0's part of the transpose region (it reads them back itself)");
+            // T_t[j][r] = sum_i AX_t[r][i] G_t[j][i]
+            for (int o = tid; o < 2 * FZ_QY * FZ_NTX; o += FZ_BLOCK) {
+                const int t = o / (FZ_QY * FZ_NTX), j = (o / FZ_NTX) % FZ_QY, r = o % FZ_NTX;
+                const double* ax = lds + M::AX + (t * FZ_NTX + r) * FZ_QX;
+                const double* gr = lds + M::CH + t * FZ_NQ + j * FZ_QX;
+                double acc = 0.0;
 #pragma unroll
-            for (int i = 0; i < FZ_QX; ++i) acc = fma(ax[i], gr[i], acc);
-            lds[M::T + o] = acc;
-        }
-        __syncthreads();
-        // per-term partial of U[k][r] = c_t sum_j BY_t[k][j] T_t[j][r]
-        if (tid < 2 * FZ_NR) {
-            const int t = tid / FZ_NR, o = tid % FZ_NR, kk = o / FZ_NTX, r = o % FZ_NTX;
-            const double* by = lds + M::BY + (t * FZ_NTY + kk) * FZ_QY;
-            const double* tt = lds + M::T + t * FZ_QY * FZ_NTX + r;
-            double acc = 0.0;
+                for (int i = 0; i < FZ_QX; ++i) acc = fma(ax[i], gr[i], acc);
+                lds[M::T + o] = acc;
+            }
+            __syncthreads();
+            // per-term partial of U[k][r] = c_t sum_j BY_t[k][j] T_t[j][r]
+            if (tid < 2 * FZ_NR) {
+                const int t = tid / FZ_NR, o = tid % FZ_NR, kk = o / FZ_NTX, r = o % FZ_NTX;
+                const double* by = lds + M::BY + (t * FZ_NTY + kk) * FZ_QY;
+                const double* tt = lds + M::T + t * FZ_QY * FZ_NTX + r;
+                double acc = 0.0;
 #pragma unroll
-            for (int j = 0; j < FZ_QY; ++j) acc = fma(by[j], tt[j * FZ_NTX], acc);
-            lds[M::UP + tid] = (t == 0 ? pc0 : pc1) * acc;
-        }
-        __syncthreads();
-        double sq = 0.0;
-        const double sc = 2.0 / nr_e;
-        [[maybe_unused]] double deps = 0.0;      // GEN: this thread's share of d loss_e / d eps
-        if (tid < FZ_NR) {
-            const bool act = ro_r < nax_e && ro_k < nay_e;      // (without counts: every residual of the instantiation)
-            double u;
+                for (int j = 0; j < FZ_QY; ++j) acc = fma(by[j], tt[j * FZ_NTX], acc);
+                lds[M::UP + tid] = (t == 0 ? pc0 : pc1) * acc;
+            }
+            __syncthreads();
+            double sq = 0.0;
+            const double sc = 2.0 / nr_e;
+            [[maybe_unused]] double deps = 0.0;      // GEN: this thread's share of d loss_e / d eps
+            if (tid < FZ_NR) {
+                const bool act = ro_r < nax_e && ro_k < nay_e;      // (without counts: every residual of the instantiation)
+                double u;
+                if constexpr (GEN) {
+                    // (UP holds the terms WITHOUT their factor eps: U = m_0 UP_0 + m_1 UP_1 - F, and a term that carries eps as a factor
+                    //  contributes (2/NR) U UP_t to d loss_e / d eps -- P3:171)
+                    const double u0 = lds[M::UP + tid], u1 = lds[M::UP + FZ_NR + tid];
+                    u = fma(gm0, u0, gm1 * u1) - pF;
+                    if (!act) u = 0.0;
+                    deps = sc * u * fma(ge0, u0, ge1 * u1);
+                } else {
+                    u = (lds[M::UP + tid] + lds[M::UP + FZ_NR + tid]) - pF;
+                    if (!act) u = 0.0;
+                }
+                lds[M::U + tid] = u;
+                if (ro_on) pa.R[ro_idx] = u;
+                sq = u * u;
+            }
+            if (wv < 2) {
+                sq = pj_wave_sum_dpp(sq);
+                if (lane == 0) lds[M::RED + wv] = sq;
+            }
+            __syncthreads();
+            if (tid == 0) pa.loss_e[e] = (lds[M::RED] + lds[M::RED + 1]) / nr_e;
+            // adjoint: S_t[k][i] = (2/NR) c_t sum_r AX_t[r][i] U[k][r];  Gbar_t[j][i] = sum_k BY_t[k][j] S_t[k][i]
+            for (int o = tid; o < 2 * FZ_NTY * FZ_QX; o += FZ_BLOCK) {
+                const int t = o / (FZ_NTY * FZ_QX), kk = (o / FZ_QX) % FZ_NTY, i = o % FZ_QX;
+                const double* ax = lds + M::AX + t * FZ_NTX * FZ_QX + i;
+                const double* ur = lds + M::U + kk * FZ_NTX;
+                double acc = 0.0;
+#pragma unroll
+                for (int r = 0; r < FZ_NTX; ++r) acc = fma(ax[r * FZ_QX], ur[r], acc);
+                if constexpr (GEN) lds[M::S + o] = acc * sc * (t == 0 ? pc0 * gm0 : pc1 * gm1);
+                else lds[M::S + o] = acc * sc * (t == 0 ? pc0 : pc1);
+            }
+            __syncthreads();
+            // (GEN, one term: only array 0 gets an adjoint; array 1 holds E = dG_0 / d eps, which meets it here: d eps += Gbar_0 E)
+            const int n_adj = (GEN && !gtwo) ? FZ_NQ : 2 * FZ_NQ;
+            for (int o = tid; o < n_adj; o += FZ_BLOCK) {
+                const int t = o / FZ_NQ, j = (o / FZ_QX) % FZ_QY, i = o % FZ_QX;
+                const double* by = lds + M::BY + t * FZ_NTY * FZ_QY + j;
+                const double* sr = lds + M::S + t * FZ_NTY * FZ_QX + i;
+                double acc = 0.0;
+#pragma unroll
+                for (int kk = 0; kk < FZ_NTY; ++kk) acc = fma(by[kk * FZ_QY], sr[kk * FZ_QX], acc);
+                if constexpr (GEN) { if (!gtwo) deps = fma(acc, lds[M::CH + FZ_NQ + o], deps); }
+                lds[M::CH + o] = acc;
+            }
             if constexpr (GEN) {
-                // (UP holds the terms WITHOUT their factor eps: U = m_0 UP_0 + m_1 UP_1 - F, and a term that carries eps as a factor
-                //  contributes (2/NR) U UP_t to d loss_e / d eps -- P3:171)
-                const double u0 = lds[M::UP + tid], u1 = lds[M::UP + FZ_NR + tid];
-                u = fma(gm0, u0, gm1 * u1) - pF;
-                if (!act) u = 0.0;
-                deps = sc * u * fma(ge0, u0, ge1 * u1);
-            } else {
-                u = (lds[M::UP + tid] + lds[M::UP + FZ_NR + tid]) - pF;
-                if (!act) u = 0.0;
+                if (pa.pd.has_eps) {      // (kernel-uniform)
+                    // (into the head of the x-tables: their last reader was the S step, two barriers back; wave 0's own transpose tiles later)
+                    deps = pj_wave_sum_dpp(deps);
+                    if (lane == 0) lds[M::AX + wv] = deps;
+                }
             }
-            lds[M::U + tid] = u;
-            if (ro_on) pa.R[ro_idx] = u;
-            sq = u * u;
-        }
-        if (wv < 2) {
-            sq = pj_wave_sum_dpp(sq);
-            if (lane == 0) lds[M::RED + wv] = sq;
-        }
-        __syncthreads();
-        if (tid == 0) pa.loss_e[e] = (lds[M::RED] + lds[M::RED + 1]) / nr_e;
-        // adjoint: S_t[k][i] = (2/NR) c_t sum_r AX_t[r][i] U[k][r];  Gbar_t[j][i] = sum_k BY_t[k][j] S_t[k][i]
-        for (int o = tid; o < 2 * FZ_NTY * FZ_QX; o += FZ_BLOCK) {
-            const int t = o / (FZ_NTY * FZ_QX), kk = (o / FZ_QX) % FZ_NTY, i = o % FZ_QX;
-            const double* ax = lds + M::AX + t * FZ_NTX * FZ_QX + i;
-            const double* ur = lds + M::U + kk * FZ_NTX;
-            double acc = 0.0;
-#pragma unroll
-            for (int r = 0; r < FZ_NTX; ++r) acc = fma(ax[r * FZ_QX], ur[r], acc);
-            if constexpr (GEN) lds[M::S + o] = acc * sc * (t == 0 ? pc0 * gm0 : pc1 * gm1);
-            else lds[M::S + o] = acc * sc * (t == 0 ? pc0 : pc1);
-        }
-        __syncthreads();
-        // (GEN, one term: only array 0 gets an adjoint; array 1 holds E = dG_0 / d eps, which meets it here: d eps += Gbar_0 E)
-        const int n_adj = (GEN && !gtwo) ? FZ_NQ : 2 * FZ_NQ;
-        for (int o = tid; o < n_adj; o += FZ_BLOCK) {
-            const int t = o / FZ_NQ, j = (o / FZ_QX) % FZ_QY, i = o % FZ_QX;
-            const double* by = lds + M::BY + t * FZ_NTY * FZ_QY + j;
-            const double* sr = lds + M::S + t * FZ_NTY * FZ_QX + i;
-            double acc = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < FZ_NTY; ++kk) acc = fma(by[kk * FZ_QY], sr[kk * FZ_QX], acc);
-            if constexpr (GEN) { if (!gtwo) deps = fma(acc, lds[M::CH + FZ_NQ + o], deps); }
-            lds[M::CH + o] = acc;
-        }
-        if constexpr (GEN) {
-            if (pa.pd.has_eps) {      // (kernel-uniform)
-                // (into the head of the x-tables: their last reader was the S step, two barriers back; wave 0's own transpose tiles later)
-                deps = pj_wave_sum_dpp(deps);
-                if (lane == 0) lds[M::AX + wv] = deps;
+            __syncthreads();
+            if constexpr (GEN) {
+                // (the partials sit in wave 0's own part of the transpose region -- static_assert at the top: it reads them before it writes there)
+                if (pa.pd.has_eps && tid == 0) pa.deps_e[e] = (lds[M::AX] + lds[M::AX + 1]) + (lds[M::AX + 2] + lds[M::AX + 3]);
             }
-        }
-        __syncthreads();
-        if constexpr (GEN) {
-            // (the partials sit in wave 0's own part of the transpose region -- static_assert at the top: it reads them before it writes there)
-            if (pa.pd.has_eps && tid == 0) pa.deps_e[e] = (lds[M::AX] + lds[M::AX + 1]) + (lds[M::AX + 2] + lds[M::AX + 3]);
+        } else {
+            // The four contractions run on the matrix pipe (v_mfma_f64_16x16x4_f64; every dimension in zero-padded 16-wide tiles), in two
+            // chains that hand the intermediate from one product to the next IN REGISTERS: the D fragment of a product -- lane (q, pt),
+            // register v = D[row q + 4 v][column pt] -- is the B fragment of k-step v of a product that sums over D's rows.  Out-of-range
+            // operand lanes read a valid address (row / column 0: a broadcast) and are replaced by 0: padding rows and columns are exact zeros.
+            constexpr int PJ_NJT = (FZ_QY + 15) / 16, PJ_NIT = (FZ_QX + 15) / 16;       // 16-wide tiles of the point directions
+            constexpr int PJ_KX = FZ_QX / 4, PJ_KR = (FZ_NTX + 3) / 4, PJ_KK = (FZ_NTY + 3) / 4;      // k-steps over i, r, k
+            static_assert(FZ_QX % 4 == 0 && FZ_QY % 4 == 0 && FZ_NTX <= 16 && FZ_NTY <= 16, "projection tiles: whole k-steps over the points, one tile of test functions");
+            static_assert(2 * PJ_NJT * FZ_NR <= 2 * FZ_QY * FZ_NTX, "the partial sums of U fit the T array (T itself stays in registers)");
+            // chain 1, one (term, j-tile) per wave:  T_t[j][r] = sum_i G_t[j][i] AX_t[r][i]  (rows j, columns r), then this j-tile's part of
+            // UP_t[k][r] = sum_j BY_t[k][j] T_t[j][r] -> lds[M::T + (t * NJT + jt) * NR + k * NTX + r]
+            for (int u = wv; u < 2 * PJ_NJT; u += FZ_WAVES) {
+                const int t = u / PJ_NJT, jt = u % PJ_NJT;
+                const bool jon = jt * 16 + pt < FZ_QY, ron = pt < FZ_NTX, kon = pt < FZ_NTY;
+                const double* gr = lds + M::CH + t * FZ_NQ + (jon ? jt * 16 + pt : 0) * FZ_QX + q;
+                const double* ax = lds + M::AX + (t * FZ_NTX + (ron ? pt : 0)) * FZ_QX + q;
+                const double* by = lds + M::BY + (t * FZ_NTY + (kon ? pt : 0)) * FZ_QY + jt * 16 + q;
+                double ga[PJ_KX], xa[PJ_KX], ya[4];
+#pragma unroll
+                for (int s = 0; s < PJ_KX; ++s) { ga[s] = gr[4 * s]; xa[s] = ax[4 * s]; }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) ya[v] = by[jt * 16 + 4 * v < FZ_QY ? 4 * v : 0];
+                v4d tt = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < PJ_KX; ++s)
+                    tt = __builtin_amdgcn_mfma_f64_16x16x4f64(jon ? ga[s] : 0.0, ron ? xa[s] : 0.0, tt, 0, 0, 0);
+                v4d up = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (jt * 16 + 4 * v < FZ_QY)      // (wave-uniform: the 4-wide remainder tile has one k-step)
+                        up = __builtin_amdgcn_mfma_f64_16x16x4f64(kon ? ya[v] : 0.0, tt[v], up, 0, 0, 0);
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (q + 4 * v < FZ_NTY && ron) lds[M::T + u * FZ_NR + (q + 4 * v) * FZ_NTX + pt] = up[v];
+            }
+            pj_lds_barrier();
+            double sq = 0.0;
+            const double sc = 2.0 / nr_e;
+            [[maybe_unused]] double deps = 0.0;      // GEN: this thread's share of d loss_e / d eps
+            // U[k][r] = c_0 UP_0 + c_1 UP_1 - F: the terms' j-tile parts are added here
+            auto up_t = [&](int t) -> double {
+                double a = lds[M::T + t * PJ_NJT * FZ_NR + tid];
+#pragma unroll
+                for (int jt = 1; jt < PJ_NJT; ++jt) a += lds[M::T + (t * PJ_NJT + jt) * FZ_NR + tid];
+                return a;
+            };
+            if (tid < FZ_NR) {
+                const bool act = ro_r < nax_e && ro_k < nay_e;      // (without counts: every residual of the instantiation)
+                double u;
+                if constexpr (GEN) {
+                    // (UP holds the terms WITHOUT their factor eps: U = m_0 UP_0 + m_1 UP_1 - F, and a term that carries eps as a factor
+                    //  contributes (2/NR) U UP_t to d loss_e / d eps -- P3:171)
+                    const double u0 = pc0 * up_t(0), u1 = pc1 * up_t(1);
+                    u = fma(gm0, u0, gm1 * u1) - pF;
+                    if (!act) u = 0.0;
+                    deps = sc * u * fma(ge0, u0, ge1 * u1);
+                } else {
+                    u = (pc0 * up_t(0) + pc1 * up_t(1)) - pF;
+                    if (!act) u = 0.0;
+                }
+                lds[M::U + tid] = u;
+                if (ro_on) pa.R[ro_idx] = u;
+                sq = u * u;
+            }
+            if (wv < 2) {
+                sq = pj_wave_sum_dpp(sq);
+                if (lane == 0) lds[M::RED + wv] = sq;
+            }
+            pj_lds_barrier();
+            if (tid == 0) pa.loss_e[e] = (lds[M::RED] + lds[M::RED + 1]) / nr_e;
+            // chain 2, one (term, i-tile) per wave -- the adjoint:  S_t[k][i] = (2/NR) c_t sum_r U[k][r] AX_t[r][i]  (rows k, columns i), then
+            // Gbar_t[j][i] = sum_k BY_t[k][j] S_t[k][i] for every j-tile, into the channel array
+            // (GEN, one term: only array 0 gets an adjoint; array 1 holds E = dG_0 / d eps, which meets it here: d eps += Gbar_0 E)
+            const int n_adj = (GEN && !gtwo) ? PJ_NIT : 2 * PJ_NIT;
+            for (int u = wv; u < n_adj; u += FZ_WAVES) {
+                const int t = u / PJ_NIT, it = u % PJ_NIT;
+                const int i = it * 16 + pt;
+                const bool ion = i < FZ_QX, kon = pt < FZ_NTY;
+                const double* ur = lds + M::U + (kon ? pt : 0) * FZ_NTX;
+                const double* ax = lds + M::AX + t * FZ_NTX * FZ_QX + (ion ? i : 0);
+                double ua[PJ_KR], xa[PJ_KR];
+#pragma unroll
+                for (int s = 0; s < PJ_KR; ++s) {
+                    const int rc = 4 * s + q < FZ_NTX ? 4 * s + q : 0;
+                    ua[s] = ur[rc]; xa[s] = ax[rc * FZ_QX];
+                }
+                v4d ss = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < PJ_KR; ++s) {
+                    const bool ron = 4 * s + q < FZ_NTX;
+                    ss = __builtin_amdgcn_mfma_f64_16x16x4f64((kon && ron) ? ua[s] : 0.0, (ron && ion) ? xa[s] : 0.0, ss, 0, 0, 0);
+                }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    if constexpr (GEN) ss[v] = ss[v] * sc * (t == 0 ? pc0 * gm0 : pc1 * gm1);
+                    else ss[v] = ss[v] * sc * (t == 0 ? pc0 : pc1);
+                }
+#pragma unroll
+                for (int jt = 0; jt < PJ_NJT; ++jt) {
+                    const int j = jt * 16 + pt;
+                    const bool jon = j < FZ_QY;
+                    const double* by = lds + M::BY + t * FZ_NTY * FZ_QY + (jon ? j : 0);
+                    v4d gg = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int v = 0; v < PJ_KK; ++v) {
+                        const bool k4 = 4 * v + q < FZ_NTY;
+                        const double b = by[(k4 ? 4 * v + q : 0) * FZ_QY];
+                        gg = __builtin_amdgcn_mfma_f64_16x16x4f64((k4 && jon) ? b : 0.0, ss[v], gg, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const int jo = jt * 16 + q + 4 * v;
+                        if (jo < FZ_QY && ion) {
+                            const int o = jo * FZ_QX + i;
+                            if constexpr (GEN) { if (!gtwo) deps = fma(gg[v], lds[M::CH + FZ_NQ + o], deps); }
+                            lds[M::CH + t * FZ_NQ + o] = gg[v];
+                        }
+                    }
+                }
+            }
+            if constexpr (GEN) {
+                if (pa.pd.has_eps) {      // (kernel-uniform)
+                    // (into the UP array, which this phase no longer uses: the tables are still being read by waves in chain 2)
+                    deps = pj_wave_sum_dpp(deps);
+                    if (lane == 0) lds[M::UP + wv] = deps;
+                }
+            }
+            __syncthreads();
+            if constexpr (GEN) {
+                // (the partials sit in ONE wave's part of the transpose region; a thread of that wave adds them up: it reads them before it writes there)
+                constexpr int PJ_DW = (M::UP - M::TR) / M::TR_WAVE;
+                static_assert(PJ_DW < FZ_WAVES && M::UP + FZ_WAVES - M::TR <= (PJ_DW + 1) * M::TR_WAVE, "the d-epsilon partials live in one wave's part of the transpose region");
+                if (pa.pd.has_eps && tid == PJ_DW * 64) pa.deps_e[e] = (lds[M::UP] + lds[M::UP + 1]) + (lds[M::UP + 2] + lds[M::UP + 3]);
+            }
         }
     }
 
