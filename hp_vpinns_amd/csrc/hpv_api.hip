@@ -439,7 +439,13 @@ int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
     launch_pinn_residual(h->cfg.pde, PinnArgs{h->colloc.OUT, h->d_fcol, h->colloc.GBAR, h->d_col_part, h->d_col_part + 64,
                                               h->has_eps ? h->d_theta + h->P : nullptr, h->cfg.V, h->colloc.N, h->n_col,
                                               h->n_col_total, backward ? 1 : 0}, h->stream);
-    if (backward) run_bwd(h, h->colloc, h->mfma_colloc);
+    if (backward) {
+        run_bwd(h, h->colloc, h->mfma_colloc);
+        // (hpv_kernel_variant: the layer kernels of the collocation batch -- recorded after their launches, as pass_separate does)
+        HpvMfma* mc = h->mfma_colloc;
+        snprintf(h->variant, sizeof h->variant, "%s + k_pinn_residual + %s", mc ? hpv_mfma_variant(mc, 1) : "k_mlp_fwd_generic",
+                 mc ? hpv_mfma_variant(mc, 2) : "k_mlp_bwd_generic");
+    }
     int ndp = 0;
     if (h->n_data > 0) {
         run_fwd(h, h->data, h->mfma_data, backward ? 1 : 0);

@@ -28,16 +28,26 @@ struct WideFwdLds {
     static constexpr int W1 = BI + LH * H;               // first-layer rows, first bias, head weights  [D + 2][H]
     static constexpr int TOTAL = W1 + (D + 2) * H;
 };
-template <int H, int L, int D>
+template <int H, int L, int D, int WAVES = WF_WAVES>
 struct WideBwdLds {
     using W = WD<H>;
     static constexpr int LH = L - 1;
     static constexpr int TAB = 0;                               // per-wave transpose pair (one channel at a time) [WAVES][2][H][17]; epilogue: exchange
-    static constexpr int FR = TAB + WF_WAVES * 2 * W::TR;       // reverse fragments        [LH][FRAG]
+    static constexpr int FR = TAB + WAVES * 2 * W::TR;          // reverse fragments        [LH][FRAG]
     static constexpr int W1 = FR + LH * W::FRAG;                // first-layer rows, head weights  [D + 1][H]
     static constexpr int TOTAL = W1 + (D + 1) * H;
-    static_assert(WF_WAVES * 2 * W::TR >= WF_WAVES * 256, "the epilogue exchanges one accumulator (4 doubles per lane) per wave through the transpose region");
+    static_assert(2 * W::TR >= 256 && 2 * W::TR >= (L + D + 1) * H + 1, "the epilogue exchanges one accumulator (4 doubles per lane) and the per-neuron sums of one wave through that wave's transpose region");
 };
+// Wavefronts per workgroup of the reverse kernel: WF_WAVES where the map fits the 160 KB of a CU, else the most that do.  Only the
+// deepest 64-wide network needs it: three layers of reverse fragments are 96 KB, four waves' transpose pairs 68 KB -- 169 472 B
+// with the first-layer rows; with three waves 152 064 B.  (The tile loop strides by the waves of the grid: any count is correct.)
+constexpr size_t WIDE_LDS_MAX = 160 * 1024;
+template <int H, int L, int D>
+constexpr int wide_bwd_waves() {
+    if ((size_t)WideBwdLds<H, L, D, WF_WAVES>::TOTAL * sizeof(double) <= WIDE_LDS_MAX) return WF_WAVES;
+    if ((size_t)WideBwdLds<H, L, D, 3>::TOTAL * sizeof(double) <= WIDE_LDS_MAX) return 3;
+    return 2;      // (not checked here: pick_wide asserts at compile time that the map of every shape it instantiates fits)
+}
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -196,10 +206,11 @@ __global__ void __launch_bounds__(WF_BLOCK, (H <= 32 ? 2 : 1)) k_fwd_wide(MfmaAr
 // ------------------------------------------------------------------------------------------------
 // reverse
 // ------------------------------------------------------------------------------------------------
-template <int D, int NT1, int NT2, int ACT, int L, int H>
-__global__ void __launch_bounds__(WF_BLOCK, 1) k_bwd_wide(MfmaArgs g) {
+template <int D, int NT1, int NT2, int ACT, int L, int H, int WAVES = wide_bwd_waves<H, L, D>()>
+__global__ void __launch_bounds__(WAVES * 64, 1) k_bwd_wide(MfmaArgs g) {
     using W = WD<H>;
-    using M = WideBwdLds<H, L, D>;
+    using M = WideBwdLds<H, L, D, WAVES>;
+    constexpr int BT = WAVES * 64;
     constexpr int KS = W::KS, C = 1 + NT1 + NT2, LH = L > 1 ? L - 1 : 1;
     constexpr int NS = SlotCount<ACT, NT1, NT2>::value;
     constexpr int SZC = 1 + (ACT == HPV_ACT_SIN ? 1 : 0), SZCC = SZC + NT1;
@@ -210,8 +221,8 @@ __global__ void __launch_bounds__(WF_BLOCK, 1) k_bwd_wide(MfmaArgs g) {
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
     const double* __restrict__ th = g.theta;
 #pragma unroll
-    for (int i = 1; i < L; ++i) wide_stage_layer<H, false, WF_BLOCK>(th, g.woff[i], lds + M::FR + (i - 1) * W::FRAG, tid);
-    for (int f = tid; f < (D + 1) * H; f += WF_BLOCK) {
+    for (int i = 1; i < L; ++i) wide_stage_layer<H, false, BT>(th, g.woff[i], lds + M::FR + (i - 1) * W::FRAG, tid);
+    for (int f = tid; f < (D + 1) * H; f += BT) {
         const int c = f / H, j = f - c * H;
         lds[M::W1 + f] = th[(c < D ? g.woff[0] + c * H : g.woff[L]) + j];
     }
@@ -358,7 +369,7 @@ __global__ void __launch_bounds__(WF_BLOCK, 1) k_bwd_wide(MfmaArgs g) {
 
     // ---- epilogue: per-wave partials -> (LDS exchange, one accumulator group at a time) -> one gradient row per workgroup ----
     // (per-wave rows in LDS, as k_bwd_mfma keeps them, do not fit: 4 x P doubles is 100 KB at H = 40 and 400 KB at H = 64)
-    wide_epilogue<H, L, D, WF_WAVES>(lds + M::TAB, dW, db, dW1, dWo, dbo, g.GPART + (long)blockIdx.x * g.P, g.woff, g.boff);
+    wide_epilogue<H, L, D, WAVES>(lds + M::TAB, dW, db, dW1, dWo, dbo, g.GPART + (long)blockIdx.x * g.P, g.woff, g.boff);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -559,7 +570,7 @@ __global__ void __launch_bounds__(WF_BLOCK, 1) k_bwd_wide_rc(MfmaArgs g) {
 // ------------------------------------------------------------------------------------------------
 template <typename K>
 static bool wide_set_lds(K kernel, size_t bytes) {
-    if (bytes > 160 * 1024) return false;
+    if (bytes > WIDE_LDS_MAX) return false;
     if (bytes <= 64 * 1024) return true;
     const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -578,8 +589,9 @@ static void run_fwd_wide(const MfmaArgs& a, int blocks, hipStream_t s) {
 }
 template <int D, int NT1, int NT2, int ACT, int L, int H>
 static void run_bwd_wide(const MfmaArgs& a, int blocks, hipStream_t s) {
-    constexpr size_t bytes = (size_t)WideBwdLds<H, L, D>::TOTAL * sizeof(double);
-    hipLaunchKernelGGL((k_bwd_wide<D, NT1, NT2, ACT, L, H>), dim3(blocks), dim3(WF_BLOCK), bytes, s, a);
+    constexpr int BW = wide_bwd_waves<H, L, D>();
+    constexpr size_t bytes = (size_t)WideBwdLds<H, L, D, BW>::TOTAL * sizeof(double);
+    hipLaunchKernelGGL((k_bwd_wide<D, NT1, NT2, ACT, L, H>), dim3(blocks), dim3(BW * 64), bytes, s, a);
 }
 
 template <int D, int NT1, int NT2, int ACT, int L, int H>
@@ -590,7 +602,9 @@ static void run_bwd_wide_rc(const MfmaArgs& a, int blocks, hipStream_t s) {
 
 template <int D, int NT1, int NT2, int ACT, int L, int H>
 static bool pick_wide(HpvMfma* m) {
-    constexpr size_t fb = (size_t)WideFwdLds<H, L, D>::TOTAL * sizeof(double), bb = (size_t)WideBwdLds<H, L, D>::TOTAL * sizeof(double);
+    constexpr int BW = wide_bwd_waves<H, L, D>();
+    constexpr size_t fb = (size_t)WideFwdLds<H, L, D>::TOTAL * sizeof(double), bb = (size_t)WideBwdLds<H, L, D, BW>::TOTAL * sizeof(double);
+    static_assert(fb <= WIDE_LDS_MAX && bb <= WIDE_LDS_MAX, "an instantiated (H, L) does not fit the LDS of a CU: it could never launch");
     if (!wide_set_lds(k_fwd_wide<D, NT1, NT2, ACT, L, H, 1>, fb) ||
         !wide_set_lds(k_bwd_wide<D, NT1, NT2, ACT, L, H>, bb))
         return false;
@@ -615,7 +629,7 @@ static bool pick_wide(HpvMfma* m) {
     m->bwd_fused = nullptr;
     int of = 1, ob = 1;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, k_fwd_wide<D, NT1, NT2, ACT, L, H, 1>, WF_BLOCK, fb);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, k_bwd_wide<D, NT1, NT2, ACT, L, H>, WF_BLOCK, bb);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, k_bwd_wide<D, NT1, NT2, ACT, L, H>, BW * 64, bb);
     m->occ_fwd = of > 0 ? of : 1;
     m->occ_bwd = ob > 0 ? ob : 1;
     const char* an = ACT == HPV_ACT_SIN ? "sin" : "tanh";

@@ -231,7 +231,9 @@ int hpv_pass_structure(hpv_handle h);
 /* The kernel INSTANTIATION(s) of that pass by name, e.g. "k_iter_fused<L=3,SPLIT=false,QT=true>" (quarter-tile plan) vs
  * "k_iter_fused<L=3,SPLIT=false,QT=false>" (7/6/6/6 whole tiles: HPV_NO_QUARTER_TILE=1, or the build's AGPR guard tripped),
  * "k_iter_tall<..,QT=true> split=32", "k_iter_tile<..>", "k_fwd_mfma<..> + k_project_tp<20x20/10x10> + k_bwd_mfma<..>",
- * "k_mlp_fwd_generic + k_project<..> + k_mlp_bwd_generic" -- so that a green test run says which code it exercised. */
+ * "k_mlp_fwd_generic + k_project<..> + k_mlp_bwd_generic"; a strong-form pass (HPV_SCHEME_PINN) reports the layer kernels of its
+ * collocation batch, "k_fwd_wide<..> + k_pinn_residual + k_bwd_wide<..>" (not the value-only pair that the boundary / data batch runs
+ * beside it, in either scheme) -- so that a green test run says which code it exercised. */
 int hpv_kernel_variant(hpv_handle h, char* buf, size_t n);
 /* How this library was built: "k_iter_fused=ok|no-quarter-tile|absent;k_iter_tall=ok|no-quarter-tile|absent;test_hooks=0|1"
  * (csrc/build.sh compiles a whole-iteration kernel out when the compiler's registers reach its hand-managed AGPR range;

@@ -32,13 +32,14 @@ def warp(grid, rng):
     return out
 
 
-def generic_theta(layers, seed, extra=()):
-    """xavier_init plus 0.3 N(0,1) on every weight and every bias; the trailing extras (epsilon) as given."""
+def generic_theta(layers, seed, extra=(), scale=0.3):
+    """xavier_init plus `scale` N(0,1) on every weight and every bias; the trailing extras (epsilon) as given.  (0.3 on a 64-wide
+    tanh layer saturates it: tests/shape_matrix.py passes a smaller scale at the wider layers.)"""
     from hp_vpinns_amd.init import n_params, xavier_init
     layers = [int(v) for v in layers]
     th = xavier_init(layers, seed, extra=extra)
     n = n_params(layers)
-    th[:n] += 0.3 * np.random.default_rng(seed + 100003).standard_normal(n)
+    th[:n] += scale * np.random.default_rng(seed + 100003).standard_normal(n)
     return th
 
 
