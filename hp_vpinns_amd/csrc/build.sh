@@ -1,14 +1,14 @@
 #!/bin/bash
 # Build libhpvpinn.so for gfx950 in-tree (hipcc cross-compiles without a GPU), every stale object in parallel.
 #   ../libhpvpinn.so            the product
-#   ../libhpvpinn_testhooks.so  the same sources with -DHPV_TEST_HOOKS -DHPV_EXPERIMENTS: the fault-injection knobs of the tests
-#                               (HPV_DEBUG_SPLIT_SKIP: a partner workgroup stays away from an in-kernel exchange) and every
-#                               measured-slower kernel variant kept as evidence (HPV_PERSIST, HPV_PJ_PIPE / _STREAM / _DMA / _GRID /
-#                               _OCC_PAD, HPV_FUSED_GSTASH, HPV_WIDE_RC, HPV_TILE_DEBUG) exist ONLY there -- the product library
-#                               neither reads those variables nor carries the kernels (tests/test_cabi.py greps the binary)
-# From scratch on 8 cores: ~85 s (round 4: 150 s).  What it took: the experiments out of the product objects, one compilation
-# instead of two for the AGPR-guarded files (the guard reads the assembly -save-temps leaves behind), the width-generic kernels as
-# one translation unit per width AND input dimension (the 64-wide unit alone was 94 s), longest jobs started first.
+#   ../libhpvpinn_testhooks.so  the same sources with -DHPV_TEST_HOOKS: the fault-injection knobs of the tests (HPV_DEBUG_SPLIT_SKIP:
+#                               a partner workgroup stays away from an in-kernel exchange; HPV_TEST_RCCL_*), the A/B switches between
+#                               product paths (HPV_NO_INKERNEL_FINALIZE, HPV_PJ_WG_SMALL) and the dispatch trace (HPV_TRACE_DISPATCH)
+#                               exist ONLY there -- the product library does not read those variables (tests/test_cabi.py greps the
+#                               binary)
+# What keeps the build short: one compilation instead of two for the AGPR-guarded files (the guard reads the assembly -save-temps
+# leaves behind), the width-generic kernels as one translation unit per width AND input dimension (the 64-wide unit alone was 94 s),
+# longest jobs started first, and only the sources whose text depends on HPV_TEST_HOOKS compiled a second time.
 set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
@@ -16,12 +16,12 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $HP
 SRCS="kernels_mfma kernels_fused kernels_fused_gen kernels_project kernels_tile kernels_tall kernels_generic hpv_api hpv_exchange hpv_bench"
 ELEM_SHAPES="20,20,10,10 16,16,8,8 12,12,6,6"             # kernels_elem.hip: one object per element shape (= HPV_ELEM_SHAPES of hpv_mfma_dev.h)
 WIDE_WIDTHS="64 32 48 24 40"                            # kernels_wide.hip: one object per hidden width and dimension (= HPV_WIDE_WIDTHS of hpv_mfma.h)
-HOOKED="kernels_fused kernels_project kernels_tile kernels_tall hpv_api hpv_exchange"   # the sources that contain test hooks / experiments (built twice)
-WIDE_HOOKED="24_d2"                                     # width_dimension units whose experiment (HPV_WIDE_RC) is built into the test-hooks library
-TH_FLAGS="-DHPV_TEST_HOOKS -DHPV_EXPERIMENTS"
+# the sources whose text depends on HPV_TEST_HOOKS, their own or through HPV_XDEBUG_SKIP of hpv_mfma_dev.h (built twice)
+HOOKED="kernels_fused kernels_fused_gen kernels_tile kernels_tall hpv_api hpv_exchange"
+TH_FLAGS="-DHPV_TEST_HOOKS"
 CHK="python3 ../../scripts/check_agpr.py"
 # objects are cached by mtime; a change of flags must invalidate them (.flags remembers what the objects were built with)
-if [ "$(cat .flags 2>/dev/null)" != "$FLAGS|$HPV_FUSED_EXTRA|v2" ]; then rm -f *.o; echo "$FLAGS|$HPV_FUSED_EXTRA|v2" > .flags; fi
+if [ "$(cat .flags 2>/dev/null)" != "$FLAGS|$HPV_FUSED_EXTRA|v3" ]; then rm -f *.o; echo "$FLAGS|$HPV_FUSED_EXTRA|v3" > .flags; fi
 
 stale() {   # stale <object> <source>: the object is missing or older than its source / any header
   [ ! -f "$1" ] && return 0
@@ -90,12 +90,6 @@ done
 for f in $HOOKED; do
   if stale $f.th.o $f.hip; then spawn $f.th.o compile_one $f $f.th.o "$TH_FLAGS"; fi
 done
-for wd in $WIDE_HOOKED; do
-  o=kernels_wide_$wd.th.o
-  if stale $o kernels_wide.hip; then
-    spawn $o $HIPCC $FLAGS -DHPV_WIDE_H=${wd%_d*} -DHPV_WIDE_D=${wd#*_d} $TH_FLAGS -c kernels_wide.hip -o $o
-  fi
-done
 wait
 if ls .fail_* >/dev/null 2>&1; then rm -f .fail_*; exit 1; fi
 
@@ -107,8 +101,7 @@ for f in $SRCS; do
 done
 for w in $WIDE_WIDTHS; do
   for d in 1 2; do
-    OBJS="$OBJS kernels_wide_${w}_d$d.o"
-    case " $WIDE_HOOKED " in *" ${w}_d$d "*) TOBJS="$TOBJS kernels_wide_${w}_d$d.th.o";; *) TOBJS="$TOBJS kernels_wide_${w}_d$d.o";; esac
+    OBJS="$OBJS kernels_wide_${w}_d$d.o"; TOBJS="$TOBJS kernels_wide_${w}_d$d.o"
   done
 done
 for sh in $ELEM_SHAPES; do o=kernels_elem_${sh//,/_}.o; OBJS="$OBJS $o"; TOBJS="$TOBJS $o"; done

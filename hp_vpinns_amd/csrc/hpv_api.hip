@@ -278,8 +278,6 @@ static bool pass_whole_iteration(hpv_ctx* h, const MfmaPass& p, bool fuse_adam, 
     if (structure < 0) {
         MfmaFinalize fin{adam_args(h), h->d_RB, h->cfg.lossb_weight, h->n_data, (h->n_data + 15) / 16, h->has_eps, adam_state_doubles(h->P) / 2};
         if (!fuse_adam) fin.ad.theta = nullptr;
-        fin.n_iters = fuse_adam ? h->persist_want : 1;
-        fin.iters_done = &h->persist_done;
         if (hpv_mfma_iter_tile(m, p, h->merged ? &fin : nullptr, &pl.fin_done)) structure = 4;
     }
     if (structure < 0 && hpv_mfma_iter_elem(m, p)) structure = 6;
@@ -320,7 +318,7 @@ static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use
         const ProjArgs pj = pass_proj_args(h, backward, true);
         // few elements (at most two per CU) of a 2-D shape: one workgroup per element before "a lane owns a line"
         bool small_grid = h->dim == 2 && h->n_elem <= 512 && h->proj_split == 1 && !h->pd.nact;
-#ifdef HPV_EXPERIMENTS
+#ifdef HPV_TEST_HOOKS
         if (getenv("HPV_PJ_WG_SMALL")) small_grid = false;      // (A/B: "a lane owns a line" on small grids too)
 #endif
         const char* pname = "k_project";
@@ -393,7 +391,6 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
         (void)hipStreamWaitEvent(smain, h->ev_join, 0);
     }
     const AdamArgs ad = adam_args(h);
-    if (backward && fuse_adam) h->persist_seen = pl.fin_done;
     if (!pl.fin_done)
         launch_finalize(backward && h->var.N > 0 ? h->var.GPART : nullptr, h->var.rows,
                         backward && h->n_data > 0 && !h->merged ? h->data.GPART : nullptr, h->data.rows,
@@ -1058,31 +1055,6 @@ int hpv_loss_and_grad(hpv_handle h, double* loss3, double* grad) {
 // n_iters training iterations enqueued on the handle's stream (graph replays where possible), no synchronisation
 static int enqueue_iterations(hpv_ctx* h, int n_iters) {
     int rc;
-    // one-workgroup grids whose kernel finishes the iteration itself: the remaining iterations in ONE persistent launch
-    // (k_iter_tile<.., PERSIST>; no graph needed -- there is one launch)
-#ifdef HPV_EXPERIMENTS
-    const bool persist_on = getenv("HPV_PERSIST") && getenv("HPV_PERSIST")[0] == '1';     // opt-in (kernels_tile.hip, tile_body)
-#else
-    constexpr bool persist_on = false;      // (measured no faster: the persistent launch exists in libhpvpinn_testhooks.so only)
-#endif
-    if (persist_on && !h->persist_probed && n_iters > 1 && !h->rccl_on && !h->p2p_on && h->cfg.scheme == HPV_SCHEME_VPINN) {
-        // (the first training pass of a handle tells whether its grid is one such workgroup: one eager iteration)
-        if ((rc = enqueue_pass(h, true, true))) return rc;
-        h->persist_probed = true;
-        h->nupd_host += 1;
-        n_iters -= 1;
-    }
-    if (persist_on && h->persist_seen && n_iters > 1 && !h->rccl_on && !h->p2p_on && !h->timing && h->cfg.scheme == HPV_SCHEME_VPINN) {
-        h->persist_want = n_iters;
-        h->persist_done = 1;
-        rc = enqueue_pass(h, true, true);
-        h->persist_want = 1;
-        if (rc) return rc;
-        const int did = h->persist_seen ? h->persist_done : 1;
-        h->nupd_host += did;
-        if (did >= n_iters) return 0;
-        n_iters -= did;
-    }
     if (h->use_graph && h->own_stream && !h->timing && n_iters > 0 && h->cfg.scheme == HPV_SCHEME_VPINN) {
         if ((rc = check_ready(h))) return rc;
         // n = a * HPV_GRAPH_ITERS + r: a replays of the K-iteration graph and ONE replay of an r-iteration graph (captured
@@ -1466,12 +1438,6 @@ const char* hpv_build_info(void) {
         info = std::string("k_iter_fused=") + hpv_fused_build_state() + ";k_iter_fused_gen=" + hpv_fused_gen_build_state() +
                ";k_iter_tall=" + hpv_tall_build_state() + ";test_hooks=";
 #ifdef HPV_TEST_HOOKS
-        info += "1";
-#else
-        info += "0";
-#endif
-        info += ";experiments=";
-#ifdef HPV_EXPERIMENTS
         info += "1";
 #else
         info += "0";

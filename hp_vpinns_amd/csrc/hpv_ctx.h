@@ -113,10 +113,6 @@ struct hpv_ctx {
     // in-library exchange of the packed buffer between the ranks of a node (hpv_p2p_*)
     P2PArgs pp{};
     bool p2p_on = false;
-    // one-workgroup grids (config 1): hpv_step asks for `persist_want` iterations in one launch; the tile kernel says how many it ran
-    int persist_want = 1, persist_done = 1;
-    bool persist_probed = false;
-    bool persist_seen = false;   // the most recent training pass ended inside the tile kernel (in-kernel finalize): persistent launches possible
     int pass_structure = -1;   // see hpv_pass_structure
     char variant[320] = "";    // see hpv_kernel_variant
     double* d_inbox = nullptr;

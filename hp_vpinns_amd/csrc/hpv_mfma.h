@@ -124,7 +124,7 @@ struct FusedShard {
 struct FusedPlan {
     int declined = 0;             // the check at which the kernel declines the pass (0: it takes it) -- what HPV_TRACE_DISPATCH=1 prints
     bool small = false;           // k_iter_small (10x10 points) instead of k_iter_fused
-    bool gen = false, counted = false, gs = false, pre = false;      // general form, per-element counts, GS, the update prologue
+    bool gen = false, counted = false, pre = false;      // general form, per-element counts, the update prologue
     int nT2 = 0;
     int gplan = 0;                // hpv_fused_grid_plan: 1 one workgroup per element | 2 the element loop | 3 full rounds + a SPLIT tail
     int plan = 1;                 // instantiation: 0 SPLIT | 1 whole tiles | 2 quarter tiles | 3 / 4 = 1 / 2 inside the element loop
@@ -146,8 +146,6 @@ struct MfmaFinalize {
     double* RB;
     double lossb_weight;
     int n_data, n_data_part, has_eps, ncopies;
-    int n_iters = 1;              // iterations the caller wants back to back (a one-workgroup grid may run them in ONE persistent launch)
-    int* iters_done = nullptr;    // out: iterations this launch performs (1, or n_iters on the persistent path)
 };
 bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin = nullptr, bool* fin_done = nullptr);
 // The same for ANY instantiated tensor-product element shape and 2-D channel set (kernels_elem.hip): several tiles per wave, s of

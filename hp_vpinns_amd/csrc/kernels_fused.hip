@@ -71,8 +71,6 @@ struct FzLds {
     static constexpr int W1O = WRB + LH * MF_KS * 16;      // [4][5][64]   W1[0][4s+q], W1[1][4s+q], Wo[4s+q], b1[4s+q]
     static constexpr int CH = W1O + 4 * MF_KS * 64;        // [2][400]     u_x, u_y of the element -> their adjoints
     static constexpr int PK = CH + 2 * FZ_NQ;              // [6][L*5][64] parked s: slot w = tile 0 of wave w, slots 4, 5 = tile 1 of waves 0, 1
-    static constexpr int XS = PK;                          // GS (slots 0..3 of PK are free then): [x | y | u_d][400 + 16] coordinates of the element and of the data tile
-    static constexpr int XLD = FZ_NQ + 16;
     // (four channels: the compiler needs ~60 registers more -- one more tile of every wave is parked here: slots 4..7 = tile 1 of wave
     //  w - 4, slots 8, 9 = the quarter tiles' s (QT) or tile 2 of waves 0, 1 (whole tiles: the two waves that may own FZ_MAXT tiles))
     static constexpr int PKS = C_ > FZ_C ? 10 : 6;
@@ -92,7 +90,6 @@ struct FzLds {
     static constexpr int S = U + FZ_NR;                    // [2][NTY][QX]
     static constexpr int RED = S + 2 * FZ_NTY * FZ_QX;     // [16]
     static_assert(RED + 16 - TR <= FZ_WAVES * TR_WAVE, "projection scratch fits the transpose region");
-    static_assert(3 * XLD <= 4 * L * MF_KS * 64, "the staged coordinates fit the parking slots the GS plan leaves free");
     static constexpr int EPI = NPART_ > 0 ? PK : TR;       // the epilogue's rows [4][P]
     static constexpr int total(int P) { return NPART_ > 0 ? TR + TRSZ : TR + (TRSZ > FZ_WAVES * P ? TRSZ : FZ_WAVES * P) + (MULTI ? NTABS : 0); }
 };
@@ -121,13 +118,7 @@ struct FzPlan {
 // fragments), the channels of a point meet through DPP row shifts in the element-wise steps, and the boundary / data points
 // ride in the slots that would be idle, so no wave owns a seventh tile any more.
 //
-// GS (round 4, opt-in: measured slower, see launch_iter_fused_L): what the reverse pass needs of a whole tile -- s of every hidden layer AND the tangent pre-activations z_x, z_y of the
-// layers >= 2 (35 doubles per lane at L = 3) -- travels through device memory instead of being parked in AGPRs / LDS and recomputed:
-// the forward pass stores it (16-byte lane-contiguous stores into the handle's activation store, [tile][pair][lane][2]), the
-// reverse pass requests tile k + 1's while it works on tile k.  The kernel is bound by the fp64 datapath and leaves 8 TB/s of HBM
-// (and the 256 MB memory-side cache, which holds the whole 110 MB) idle; the recompute was 1 600 of a reverse tile's 7 650 datapath
-// cycles plus the AGPR shuffles around it.  Every workgroup reads back only what its own waves wrote (same CU, same L2): no fences.
-typedef double v2d __attribute__((ext_vector_type(2)));
+// (the saved values through device memory instead of the register stash: tried in round 4, measured slower -- profiles/r04_notes.md 6)
 //
 // MULTI (round 5): grids with more elements than CUs.  One workgroup per element pays the launch-once phases -- weight staging, the
 // epilogue's cross-wave reduction and gradient row, the dispatch of a fresh workgroup -- per ELEMENT (~11 k of an element's 132 k
@@ -146,11 +137,11 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 //   (sum_c a1[c] ch_c), which meets the adjoint of G_0 at the end of the projection phase: d eps = sum_p Gbar_0[p] E[p]
 // NT2 = 1: a fourth channel, the mixed second tangent w0 u_xx + w1 u_yy (NetDesc::t2w) -- forward, tangent recompute and reverse
 // pass of kernels_tall.hip's algebra; its transposes of the weight-gradient products go through LDS in two passes of two channels.
-template <int L, bool SPLIT, bool QT, bool GS, int QX_, int QY_, int NTX_, int NTY_, bool MULTI = false, int NT2 = 0, bool GEN = false>
+template <int L, bool SPLIT, bool QT, int QX_, int QY_, int NTX_, int NTY_, bool MULTI = false, int NT2 = 0, bool GEN = false>
 __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     static_assert(!(SPLIT && QT), "the quarter-tile scheme is for whole elements");
-    static_assert(!(MULTI && (SPLIT || GS)), "the element loop is for whole elements on the register stash");
-    static_assert(!((NT2 > 0 || GEN) && (GS || MULTI)), "the general forms run on the register stash, one workgroup (or a split) per element");
+    static_assert(!(MULTI && SPLIT), "the element loop is for whole elements");
+    static_assert(!((NT2 > 0 || GEN) && MULTI), "the general forms run one workgroup (or a split) per element");
     static_assert(NT2 == 0 || GEN, "a second-tangent channel is always integrated through the general term weights");
     FZ_SHAPE_CONSTS
     static_assert(!(NT2 > 0 && QT && FZ_TPE % FZ_WAVES != 0), "four channels leave the packed quarter tile no slot for the data points: data-quarter plan only");
@@ -267,7 +258,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         bo = th[g.boff[L]];
     };
     [[maybe_unused]] int pre_failed = -1;      // the deferred-update prologue's verdict (identical in every workgroup); -1: no prologue
-    if constexpr (!GS && !MULTI) {
+    if constexpr (!MULTI) {
         if (g.pre_g) {
             // The multi-GPU iteration in two launches (round 5): the previous iteration's update has not been applied -- its
             // all-reduced gradient sits in g.pre_g.  Every workgroup forms the updated parameters for itself (the parking area is
@@ -382,22 +373,6 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         if (g.ntiles - g.data_tile0 <= g.proj_n_elem * n_free)
             dtile = mine ? g.data_tile0 + el * n_free + before : g.ntiles;
     }
-    if constexpr (GS) {
-        // the coordinates of the element's points and of the workgroup's boundary / data tile (+ its targets) to LDS: the tile loops
-        // then hold no global load besides the saved values' -- a wait for a coordinate would be a wait for every store / request
-        // issued before it (in-order vmcnt)
-        for (int i = tid; i < FZ_NQ; i += FZ_BLOCK) {
-            lds[M::XS + i] = g.X[e * FZ_NQ + i];
-            lds[M::XS + M::XLD + i] = g.X[g.N + e * FZ_NQ + i];
-        }
-        if (tid < 16) {
-            const long pd_ = dtile * 16 + tid;
-            const bool vd = dtile < g.ntiles && pd_ < g.N;
-            lds[M::XS + FZ_NQ + tid] = vd ? g.X[pd_] : 0.0;
-            lds[M::XS + M::XLD + FZ_NQ + tid] = vd ? g.X[g.N + pd_] : 0.0;
-            lds[M::XS + 2 * M::XLD + tid] = vd ? g.ud[pd_ - g.data_off] : 0.0;
-        }
-    }
     FZ_STAMP(0);
     __syncthreads();
     FZ_STAMP(1);
@@ -429,15 +404,10 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     constexpr int NREG = FZ_MAXT - 2 - (NT2 > 0 ? 1 : 0);  // tiles whose s live in AGPRs; the first one (waves 0, 1 -- NT2: every wave -- two) of a wave is parked in LDS
     constexpr int ABASE = 256 - NREG * 2 * NSV + 2 * NPART;    // (tight plan: the stash's FIRST place is NPART doubles short -- they are in LDS)
     constexpr int AFULL = ABASE - 2 * NPART;                   // place K of the stash begins at AFULL + K * 2 NSV (place 0: its doubles NPART.. only)
-    if constexpr (!GS) asm volatile("" ::: "a255");       // the kernel owns all 256 AGPRs
+    asm volatile("" ::: "a255");       // the kernel owns all 256 AGPRs
     // (waves 0, 1 may own FZ_MAXT tiles, waves 2, 3 one less -- QT: every wave FZ_MAXT - 1 whole ones; QT: slots 4, 5 -- NT2: 8, 9 -- of the
     //  parking area hold the quarter tiles' s)
-    const int n_lds = GS ? 0 : NT2 > 0 ? (QT ? 2 : (wv <= 1 ? 3 : 2)) : QT ? 1 : (wv <= 1 ? 2 : 1);
-    // GS: pairs per tile and lane -- {z_x, z_y}[layer >= 2][k-step], then s two by two; a tile's block of the activation store
-    constexpr int NZP = (L > 1 ? L - 1 : 0) * MF_KS, NSP = (NSV + 1) / 2, NP = NZP + NSP;
-    constexpr long GS_STRIDE = (long)L * 3 * MF_KS * 64;         // doubles per tile of the activation store (3 slots: kernels_mfma.hip)
-    static_assert(NP * 128 <= GS_STRIDE, "a tile's pairs fit its block of the activation store");
-    auto gs_ptr = [&](long tile) -> v2d* { return reinterpret_cast<v2d*>(g.ACTS + tile * GS_STRIDE) + lane; };
+    const int n_lds = NT2 > 0 ? (QT ? 2 : (wv <= 1 ? 3 : 2)) : QT ? 1 : (wv <= 1 ? 2 : 1);
     double* PKw = lds + M::PK + wv * (NSV * 64) + lane;
     double* PKw2 = lds + M::PK + (4 + (NT2 > 0 ? wv : (wv & 1))) * (NSV * 64) + lane;
     gdat = 0.0;
@@ -465,11 +435,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     [[maybe_unused]] const int q_cz = q * 8 + (qcs == 2 ? 4 : 0) + qj;
     gdat_q = 0.0;
     [[maybe_unused]] double qx0 = 0.0, qx1 = 0.0, qud = 0.0;
-    [[maybe_unused]] const int q_xs = qcs == 3 ? FZ_NQ + 4 * wv + qj : q_lp;      // GS: the slot's point in the staged coordinates
-    if constexpr (QT && GS) {
-        qx0 = lds[M::XS + q_xs]; qx1 = lds[M::XS + M::XLD + q_xs];
-        qud = q_vdat ? lds[M::XS + 2 * M::XLD + 4 * wv + qj] : 0.0;
-    } else if constexpr (QT) {              // (requested before the whole tiles: consumed after them)
+    if constexpr (QT) {              // (requested before the whole tiles: consumed after them)
         qx0 = g.X[q_p]; qx1 = g.X[g.N + q_p];
         qud = q_vdat ? g.ud[q_pdat - g.data_off] : 0.0;
     }
@@ -481,12 +447,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         x[0] = g.X[pc]; x[1] = g.X[g.N + pc];
     };
     auto stash = [&](int k, const double (&sv)[NSV]) {
-        if constexpr (GS) {
-            v2d* zs = gs_ptr(tile_of(k)) + NZP * 64;
-#pragma unroll
-            for (int j = 0; j < NSV / 2; ++j) zs[j * 64] = v2d{sv[2 * j], sv[2 * j + 1]};
-            if constexpr (NSV & 1) reinterpret_cast<double*>(zs + (NSV / 2) * 64 - lane)[lane] = sv[NSV - 1];   // (odd count: the last one alone, 8-byte lanes)
-        } else if (k < n_lds) {     // wave-uniform
+        if (k < n_lds) {     // wave-uniform
             double* pk = k == 0 ? PKw : PKw2;
             // (NT2: the slot is formed HERE -- a third parking pointer kept alive across the phases sent the register allocator to
             //  scratch memory, 420 - 540 scratch accesses per instantiation and 148 instead of 58 us per iteration: profiles/r06_notes.md)
@@ -523,24 +484,13 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         double xx[NT][2];
         bool valid[NT];
         long pp[NT];
-        if constexpr (GS) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int k = k0 + t;
-                const int lp = k < n_el ? (tbase + wv + k * FZ_WAVES) * 16 + pt : FZ_NQ + pt;
-                pp[t] = tile_of(k) * 16 + pt;
-                valid[t] = pp[t] < g.N;
-                xx[t][0] = lds[M::XS + lp]; xx[t][1] = lds[M::XS + M::XLD + lp];       // (points beyond the batch were staged as 0)
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                valid[t] = vn[t]; pp[t] = pn[t];
-                xx[t][0] = valid[t] ? xn[t][0] : 0.0; xx[t][1] = valid[t] ? xn[t][1] : 0.0;
-            }
-            load_x(k0 + NT, xn[0], vn[0], pn[0]);       // the next trip's coordinates travel while this one computes
-            load_x(k0 + NT + 1, xn[1], vn[1], pn[1]);
+        for (int t = 0; t < NT; ++t) {
+            valid[t] = vn[t]; pp[t] = pn[t];
+            xx[t][0] = valid[t] ? xn[t][0] : 0.0; xx[t][1] = valid[t] ? xn[t][1] : 0.0;
         }
+        load_x(k0 + NT, xn[0], vn[0], pn[0]);       // the next trip's coordinates travel while this one computes
+        load_x(k0 + NT + 1, xn[1], vn[1], pn[1]);
         int lofs = lane;
         asm volatile("" : "+v"(lofs));       // opaque: the LDS fragment reads stay inside the loop
         double h[NT][C][MF_KS], sv[NT][NSV];
@@ -577,14 +527,6 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][2], z[t][2]);
                 if constexpr (NT2 > 0)
                     fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][3], z[t][3]);
-            }
-            if constexpr (GS) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    v2d* zs = gs_ptr(tile_of(k0 + t)) + (i - 1) * MF_KS * 64;
-#pragma unroll
-                    for (int s = 0; s < MF_KS; ++s) zs[s * 64] = v2d{z[t][1][s], z[t][2][s]};
-                }
             }
             [[maybe_unused]] double QZ[MF_KS];
             if constexpr (WQ)
@@ -654,8 +596,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 }
             } else {
                 // lossb = w mean((u_d - u)^2) (P2:122,127): adjoint of u kept in a register, per-tile partial sum to memory
-                double udv;
-                if constexpr (GS) udv = lds[M::XS + 2 * M::XLD + pt]; else udv = valid[t] ? g.ud[pp[t] - g.data_off] : 0.0;
+                const double udv = valid[t] ? g.ud[pp[t] - g.data_off] : 0.0;
                 const double dd = valid[t] ? udv - o[0] : 0.0;
                 gdat = g.data_scale * dd;
                 const double sq = row_sum16(dd * dd);
@@ -688,10 +629,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             }
         }
     };
-    if constexpr (!GS) {
-        load_x(0, xn[0], vn[0], pn[0]);
-        load_x(1, xn[1], vn[1], pn[1]);
-    }
+    load_x(0, xn[0], vn[0], pn[0]);
+    load_x(1, xn[1], vn[1], pn[1]);
     int k0 = 0;
     if constexpr (QT) {      // six whole tiles: two trips of two, then the last two with the quarter tile beside them
         static_assert((FZ_TPE - (DQ ? 0 : 1)) / FZ_WAVES >= 2 && ((FZ_TPE - (DQ ? 0 : 1)) / FZ_WAVES) % 2 == 0, "trip plan of the QT instantiation: pairs of whole tiles");
@@ -719,23 +658,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             return;      // (the launch counter is advanced by the kernel that FOLLOWS this launch: k_finalize, hpv_fused_dev.h)
         }
     }
-    // (GS: an LDS-only barrier -- the stores of the saved values need no acknowledgement here: the wave that wrote them reads them back)
-    if constexpr (GS && !SPLIT) pj_lds_barrier(); else __syncthreads();
+    __syncthreads();
     FZ_STAMP(3);
-    // GS: the first reverse tile's pairs travel during the projection phase
-    [[maybe_unused]] v2d BA[GS ? NP : 1], BB[GS ? NP : 1];
-    [[maybe_unused]] auto request = [&](int k, v2d (&B)[GS ? NP : 1]) {
-        if constexpr (GS) {
-            const v2d* zs = gs_ptr(tile_of(k));
-            constexpr int NF = NZP + NSV / 2;      // full pairs
-#pragma unroll
-            for (int j = 0; j < NF; ++j) B[j] = zs[j * 64];
-            // (an odd s count: the last value alone -- a 16-byte load whose upper half nobody reads makes the compiler wait for the
-            //  whole request as soon as it reuses that register)
-            if constexpr (NSV & 1) B[NF] = v2d{reinterpret_cast<const double*>(zs + NF * 64 - lane)[lane], 0.0};
-        }
-    };
-    if constexpr (GS) { if (n_own > 0) request(0, BA); }
     if constexpr (QT) {      // lossb partial of the workgroup's boundary / data tile: the four waves' quarters (P2:122,127)
         if (tid == 0 && dtile < g.ntiles)
             g.data_part[dtile - g.data_off / 16] = (lds[M::RED + 8] + lds[M::RED + 9]) + (lds[M::RED + 10] + lds[M::RED + 11]);
@@ -1002,28 +926,19 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     fz_n_own = n_own;
     for (int i = 0; i < 2 + 2 * L; ++i) fz_seg[i] = 0;
 #endif
-    // one reverse tile; GS: `B` = the tile's pairs, requested a tile ahead
-    auto rev_tile = [&](int k, [[maybe_unused]] const v2d (&B)[GS ? NP : 1]) {
+    // one reverse tile
+    auto rev_tile = [&](int k) {
 #ifdef HPV_FZ_TIMING
         fz_last = clock64();
 #endif
-        double x0, x1;
-        if constexpr (GS) {
-            const int lp = k < n_el ? (tbase + wv + k * FZ_WAVES) * 16 + pt : FZ_NQ + pt;
-            x0 = lds[M::XS + lp]; x1 = lds[M::XS + M::XLD + lp];
-        } else {
-            const long tile = tile_of(k);
-            const long p = tile * 16 + pt;
-            const bool valid = p < g.N;
-            x0 = valid ? g.X[p] : 0.0; x1 = valid ? g.X[g.N + p] : 0.0;
-        }
+        const long tile = tile_of(k);
+        const long p = tile * 16 + pt;
+        const bool valid = p < g.N;
+        const double x0 = valid ? g.X[p] : 0.0, x1 = valid ? g.X[g.N + p] : 0.0;
         int lofs = lane;
         asm volatile("" : "+v"(lofs));
         double sv[NSV];
-        if constexpr (GS) {
-#pragma unroll
-            for (int j = 0; j < NSV; ++j) sv[j] = B[NZP + j / 2][j & 1];
-        } else if (k < n_lds) {
+        if (k < n_lds) {
             const double* pk = k == 0 ? PKw : PKw2;
             // (NT2: the slot is formed HERE -- a third parking pointer kept alive across the phases sent the register allocator to
             //  scratch memory, 420 - 540 scratch accesses per instantiation and 148 instead of 58 us per iteration: profiles/r06_notes.md)
@@ -1065,7 +980,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             if constexpr (NT2 > 0) gb[3] = 0.0;
         }
         // tangent pre-activations of every hidden layer: layer 0 has z_c = W1[c,:]; layer i: z_c = (sigma'(z_{i-1}) z_c,{i-1}) W_i
-        // (GS: read back; otherwise recomputed from s on the matrix pipe)
+        // (recomputed from s on the matrix pipe)
         double zc[L][2][MF_KS];
         [[maybe_unused]] double zq[L][MF_KS];       // NT2: second-order tangent pre-activations z_cc of the mixed channel (layer 0: zero)
         // s'' z_c^2 as the mixed second tangent sees it
@@ -1078,22 +993,17 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         }
 #pragma unroll
         for (int i = 1; i < L; ++i) {
-            if constexpr (GS) {
+            double hx[MF_KS], hy[MF_KS];
+            [[maybe_unused]] double hq[MF_KS];
 #pragma unroll
-                for (int s = 0; s < MF_KS; ++s) { zc[i][0][s] = B[(i - 1) * MF_KS + s][0]; zc[i][1][s] = B[(i - 1) * MF_KS + s][1]; }
-            } else {
-                double hx[MF_KS], hy[MF_KS];
-                [[maybe_unused]] double hq[MF_KS];
-#pragma unroll
-                for (int s = 0; s < MF_KS; ++s) {
-                    const double a = sv[(i - 1) * MF_KS + s], a1 = 1.0 - a * a;
-                    hx[s] = a1 * ZC(i - 1, 0, s); hy[s] = a1 * ZC(i - 1, 1, s);
-                    if constexpr (NT2 > 0) hq[s] = (-2.0 * a * a1) * sq2(i - 1, s) + (i > 1 ? a1 * zq[i > 1 ? i - 1 : 0][s] : 0.0);
-                }
-                fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hx, zc[i][0]);
-                fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hy, zc[i][1]);
-                if constexpr (NT2 > 0) fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hq, zq[i]);
+            for (int s = 0; s < MF_KS; ++s) {
+                const double a = sv[(i - 1) * MF_KS + s], a1 = 1.0 - a * a;
+                hx[s] = a1 * ZC(i - 1, 0, s); hy[s] = a1 * ZC(i - 1, 1, s);
+                if constexpr (NT2 > 0) hq[s] = (-2.0 * a * a1) * sq2(i - 1, s) + (i > 1 ? a1 * zq[i > 1 ? i - 1 : 0][s] : 0.0);
             }
+            fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hx, zc[i][0]);
+            fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hy, zc[i][1]);
+            if constexpr (NT2 > 0) fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hq, zq[i]);
         }
 
         FZ_SEG(0);
@@ -1276,43 +1186,26 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         FZ_SEG(1 + 2 * L);
     };
 #undef ZC
-    if constexpr (GS) {
-        // two tiles per trip of the loop (ping-pong buffers: no register copies), tile k + 1's pairs in flight during tile k
-#pragma unroll 1
-        for (int k = 0; k < n_own; k += 2) {
-            // (requests are unconditional -- past the wave's last tile they repeat it: a branch around a request would make the
-            //  compiler's wait for the OTHER buffer a wait for everything in flight)
-            request(k + 1 < n_own ? k + 1 : n_own - 1, BB);
-            rev_tile(k, BA);
-            __builtin_amdgcn_sched_barrier(0);       // (nothing of tile k + 1 -- it would wait for the request above -- moves up into tile k)
-            if (k + 1 < n_own) {
-                request(k + 2 < n_own ? k + 2 : n_own - 1, BA);
-                rev_tile(k + 1, BB);
-            }
-        }
-    } else {
 #ifdef HPV_FZ_REV2
-        constexpr bool REV2 = FZ_TPE <= 16;       // (where the stash leaves the compiler the registers for it: a125 against a95)
+    constexpr bool REV2 = FZ_TPE <= 16;       // (where the stash leaves the compiler the registers for it: a125 against a95)
 #else
-        constexpr bool REV2 = false;
+    constexpr bool REV2 = false;
 #endif
-        if constexpr (REV2) {   // experiment: two tiles per trip, the scheduler may overlap tile k + 1's recompute with tile k's tail
-            int k = 0;
+    if constexpr (REV2) {   // experiment: two tiles per trip, the scheduler may overlap tile k + 1's recompute with tile k's tail
+        int k = 0;
 #pragma unroll 1
-            for (; k + 1 < n_own; k += 2) { rev_tile(k, BA); rev_tile(k + 1, BA); }
-            if (k < n_own) rev_tile(k, BA);
-        } else {
+        for (; k + 1 < n_own; k += 2) { rev_tile(k); rev_tile(k + 1); }
+        if (k < n_own) rev_tile(k);
+    } else {
 #pragma unroll 1
-            for (int k = 0; k < n_own; ++k) rev_tile(k, BA);
-        }
+        for (int k = 0; k < n_own; ++k) rev_tile(k);
     }
 
     if constexpr (QT) {
         // ---- the packed quarter tile, reverse: the whole-tile steps above for ONE packed operand (every slot's adjoint at once) ----
         int lofs = lane;
         asm volatile("" : "+v"(lofs));
-        double X0, X1;                                         // (consumed at the very end: first-layer weight gradient)
-        if constexpr (GS) { X0 = lds[M::XS + q_xs]; X1 = lds[M::XS + M::XLD + q_xs]; } else { X0 = g.X[q_p]; X1 = g.X[g.N + q_p]; }
+        const double X0 = g.X[q_p], X1 = g.X[g.N + q_p];       // (consumed at the very end: first-layer weight gradient)
         double AAq[NSV];
 #pragma unroll
         for (int j = 0; j < NSV; ++j) AAq[j] = PKQ[j * 32 + q_ci];
@@ -1982,7 +1875,7 @@ __global__ void __launch_bounds__(SM_BLOCK, 1) k_iter_small(MfmaArgs g) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-template <int L, bool SPLIT, bool QT, bool GS, int QX_, int QY_, int NTX_, int NTY_, bool MULTI = false, int NT2 = 0, bool GEN = false>
+template <int L, bool SPLIT, bool QT, int QX_, int QY_, int NTX_, int NTY_, bool MULTI = false, int NT2 = 0, bool GEN = false>
 static void launch_iter_fused(const MfmaArgs& a, int blocks, hipStream_t s) {
     using LDS = FzLds<L, QX_, QY_, NTX_, NTY_, MULTI, FZ_C + NT2, FzPlan<L, QX_, QY_, NT2>::TRG, FzPlan<L, QX_, QY_, NT2>::NPART>;
     static_assert(LDS::EPI == LDS::TR || FZ_WAVES * (2 * MF_H + MF_H + (L - 1) * (MF_H * MF_H + MF_H) + MF_H + 1) <= LDS::PP - LDS::PK, "the epilogue's rows fit the parking area");
@@ -1990,13 +1883,13 @@ static void launch_iter_fused(const MfmaArgs& a, int blocks, hipStream_t s) {
     static_assert(LDS::total(2 * MF_H + MF_H + (L - 1) * (MF_H * MF_H + MF_H) + MF_H + 1) * sizeof(double) <= 160 * 1024, "LDS");
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_iter_fused<L, SPLIT, QT, GS, QX_, QY_, NTX_, NTY_, MULTI, NT2, GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        (void)hipFuncSetAttribute((const void*)k_iter_fused<L, SPLIT, QT, QX_, QY_, NTX_, NTY_, MULTI, NT2, GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_iter_fused<L, SPLIT, QT, GS, QX_, QY_, NTX_, NTY_, MULTI, NT2, GEN>), dim3(blocks), dim3(FZ_BLOCK), bytes, s, a);
+    hipLaunchKernelGGL((k_iter_fused<L, SPLIT, QT, QX_, QY_, NTX_, NTY_, MULTI, NT2, GEN>), dim3(blocks), dim3(FZ_BLOCK), bytes, s, a);
 }
 // Instantiation lookups: plan 0 = SPLIT, 1 = whole tiles, 2 = quarter tiles (shapes with 0 / 1 mod 4 tiles), 3 / 4 = 1 / 2 walking several
-// elements per workgroup (MULTI: grids larger than the chip).  nullptr: that (shape, depth, plan, channel set, GS) is not instantiated
+// elements per workgroup (MULTI: grids larger than the chip).  nullptr: that (shape, depth, plan, channel set) is not instantiated
 // -- or compiled out by the build guard (csrc/build.sh).  The plan (hpv_fused_plan) asks BEFORE anything is enqueued.
 // The general forms (GEN: term weights, trainable epsilon; NT2 = 1: the mixed second tangent) are instantiated in a translation unit
 // of their own (kernels_fused_gen.hip = this file with HPV_FZ_GEN_TU).
@@ -2017,9 +1910,9 @@ static FusedLauncher fused_launcher_gen_shape(int L, int plan, int nt2) {
 #endif
     [[maybe_unused]] const bool has_nt2 = QX_ != 20 || L == 2 || (HAS_TIGHT && plan <= 1);
     if (L != 2 && L != 3) return nullptr;
-#define FZ_GG(SPLIT_, QT_, NT2_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true> \
-                                         : &launch_iter_fused<3, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
-#define FZ_GG2(SPLIT_, QT_, NT2_) (&launch_iter_fused<2, SPLIT_, QT_, false, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
+#define FZ_GG(SPLIT_, QT_, NT2_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, QX_, QY_, NTX_, NTY_, false, NT2_, true> \
+                                         : &launch_iter_fused<3, SPLIT_, QT_, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
+#define FZ_GG2(SPLIT_, QT_, NT2_) (&launch_iter_fused<2, SPLIT_, QT_, QX_, QY_, NTX_, NTY_, false, NT2_, true>)
     if (nt2 == 0) {
         if (plan == 0) return FZ_GG(true, false, 0);
         if (plan == 1) return FZ_GG(false, false, 0);
@@ -2068,38 +1961,28 @@ const char* hpv_fused_gen_build_state() {
 #endif
 }
 #else    // ---- everything below: the main translation unit ----
-// One element shape of the one-hot form.  (GS: the saved values travel through the activation store instead of AGPRs / LDS + recompute;
-// HPV_FUSED_GSTASH=1 opts in; built for the 20x20 / 10x10 shape only)
+// One element shape of the one-hot form.
 template <int QX_, int QY_, int NTX_, int NTY_>
-static FusedLauncher fused_launcher_shape(int L, int plan, bool gs) {
-#ifdef HPV_EXPERIMENTS      // GS (measured slower: 67.8 against 60.6 us, profiles/r04_notes.md 6) is instantiated in libhpvpinn_testhooks.so only
-    constexpr bool HAS_GS = QX_ == 20;
-#else
-    constexpr bool HAS_GS = false;
-#endif
+static FusedLauncher fused_launcher_shape(int L, int plan) {
     constexpr bool HAS_QT = ((QX_ * QY_ / 16) % 4) <= 1 && QX_ * QY_ / 16 >= 8;     // (0 mod 4: the data-quarter plan)
-#define FZ_GO(SPLIT_, QT_, GS_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, GS_, QX_, QY_, NTX_, NTY_> : &launch_iter_fused<3, SPLIT_, QT_, GS_, QX_, QY_, NTX_, NTY_>)
+#define FZ_GO(SPLIT_, QT_) (L == 2 ? &launch_iter_fused<2, SPLIT_, QT_, QX_, QY_, NTX_, NTY_> : &launch_iter_fused<3, SPLIT_, QT_, QX_, QY_, NTX_, NTY_>)
     // (MULTI with three hidden layers on 20x20 points is not instantiated: inside the element loop the compiler parks the reverse
     //  loop's accumulators in a104..a117 -- inside the stash, base a106, while later tiles' values are still there)
-#define FZ_GOM(QT_) { if (L == 2) return &launch_iter_fused<2, false, QT_, false, QX_, QY_, NTX_, NTY_, true>; \
-                      if constexpr (QX_ != 20) return &launch_iter_fused<3, false, QT_, false, QX_, QY_, NTX_, NTY_, true>; \
+#define FZ_GOM(QT_) { if (L == 2) return &launch_iter_fused<2, false, QT_, QX_, QY_, NTX_, NTY_, true>; \
+                      if constexpr (QX_ != 20) return &launch_iter_fused<3, false, QT_, QX_, QY_, NTX_, NTY_, true>; \
                       return nullptr; }
     if (L != 2 && L != 3) return nullptr;
-    if (gs) {
-        if constexpr (HAS_GS) return plan == 0 ? FZ_GO(true, false, true) : plan == 1 ? FZ_GO(false, false, true) : FZ_GO(false, true, true);
-        return nullptr;
-    }
-    if (plan == 0) return FZ_GO(true, false, false);
-    if (plan == 1) return FZ_GO(false, false, false);
+    if (plan == 0) return FZ_GO(true, false);
+    if (plan == 1) return FZ_GO(false, false);
     if (plan == 3) FZ_GOM(false)
-    if constexpr (HAS_QT) { if (plan == 4) FZ_GOM(true) return FZ_GO(false, true, false); }
+    if constexpr (HAS_QT) { if (plan == 4) FZ_GOM(true) return FZ_GO(false, true); }
     return nullptr;
 #undef FZ_GOM
 #undef FZ_GO
 }
-static FusedLauncher fused_launcher(const ProjDesc& pd, int L, int plan, bool gs) {
+static FusedLauncher fused_launcher(const ProjDesc& pd, int L, int plan) {
 #define FZ_TRY(A_, B_, C_, D_) \
-    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return fused_launcher_shape<A_, B_, C_, D_>(L, plan, gs);
+    if (pd.qx == A_ && pd.qy == B_ && pd.ntx <= C_ && pd.nty <= D_) return fused_launcher_shape<A_, B_, C_, D_>(L, plan);
     FZ_SHAPES(FZ_TRY)
 #undef FZ_TRY
     return nullptr;
@@ -2205,12 +2088,12 @@ FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTer
     p.pre = pre;
     const int NQ = pd.qx * pd.qy, TPE = NQ / 16;              // points and 16-point tiles of an element
     const bool multi = p.gplan == 2;
-    const auto launcher = [&](int plan, bool gs) { return p.gen ? hpv_fused_launcher_gen(pd, m.L, plan, p.nT2) : fused_launcher(pd, m.L, plan, gs); };
+    const auto launcher = [&](int plan) { return p.gen ? hpv_fused_launcher_gen(pd, m.L, plan, p.nT2) : fused_launcher(pd, m.L, plan); };
     if (p.gplan == 3) {
         p.n_tail = n_elem % m.n_cus;
         p.tsplit = hpv_elem_split(p.n_tail, m.n_cus, 8);
         const long data_tiles = m.ntiles - n_elem * TPE;
-        p.launch_tail = launcher(0, false);
+        p.launch_tail = launcher(0);
         if (p.tsplit < 2 || p.n_tail > m.xsync_elems || (size_t)p.n_tail * 2 * NQ * 2 > m.xg_words || data_tiles > p.n_tail * p.tsplit || !p.launch_tail) {
             // (the tail cannot run in split mode: whole rounds as before)
             const long rounds = (n_elem + m.n_cus - 1) / m.n_cus;
@@ -2244,30 +2127,24 @@ FusedPlan hpv_fused_plan(const HpvMfma& m, const ProjArgs& pa, const MfmaDataTer
     p.rows_all = p.blocks + p.n_tail * p.tsplit;
     if (p.rows_all > hpv_mfma_grad_rows(&m) && p.rows_all > m.max_rows) FZ_NO(25);
     if (!has_data && rest > 0) FZ_NO(26);    // tiles behind the elements but no data term: not a layout this kernel knows
-    // GS is opt-in (HPV_FUSED_GSTASH=1): measured 67.8 against 60.6 us at config 4 -- the reverse phase does shrink (73.1 k -> 60.9 k
-    // cycles) but the forward phase pays for its stores (42.9 k -> 49.4 k: the four waves' bursts share one 64 B/clk path), and with
-    // 220 MB of extra traffic per iteration the chip clocks 10 % lower (1.94 against 2.16 GHz); profiles/r04_notes.md
-#ifdef HPV_EXPERIMENTS
-    const char* ge = getenv("HPV_FUSED_GSTASH");
-    p.gs = pd.qx == 20 && pd.qy == 20 && m.base.ACTS != nullptr && ge && ge[0] == '1';
-#endif
+    // (the saved values through device memory instead of the register stash: 67.8 against 60.6 us at config 4, profiles/r04_notes.md)
     // the prologue is paid per WORKGROUP: worth it only where every workgroup is resident at once (one round); on larger grids the caller's
     // k_adam launch in front of the pass is cheaper (4 096 elements: +12.3 us against +4.5)
-    if (pre && (p.gs || p.blocks > (long)m.n_cus)) FZ_NO(27);
+    if (pre && p.blocks > (long)m.n_cus) FZ_NO(27);
     // MULTI spills 45 doubles per lane into the activation store: [workgroup][wave][slot][64] -- it must hold that (it is sized for
     // the separate launches' slots of every tile: far larger on any grid that takes this branch)
     if (multi && (size_t)p.blocks * FZ_WAVES * 64 * 48 > hpv_mfma_activation_store_doubles(&m)) FZ_NO(28);
     p.plan = 2;
     if (p.split > 1) p.plan = 0;
 #ifdef HPV_AGPR_GUARD_TRIPPED_QT                    // csrc/build.sh: the compiler's registers reached the stash of the QT instantiation
-    else if (!p.gs) p.plan = 1;
+    else p.plan = 1;
 #endif
     else if (!(TPE % 4 <= 1 && TPE >= 8) || getenv("HPV_NO_QUARTER_TILE")) p.plan = 1;      // (A/B switch: whole tiles only, read per launch / capture)
     if (p.gen && p.plan == 2 && p.nT2 == 1 && TPE % 4 != 0) p.plan = 1;    // four channels: the packed quarter has room for the data points only
     if (multi) p.plan += 2;                                                // plans 3 / 4: several elements per workgroup
-    if (p.gen && (p.gs || multi)) FZ_NO(29);
-    p.launch = launcher(p.plan, p.gs);
-    if (!p.launch && p.gen && p.plan == 2) p.launch = launcher(p.plan = 1, false);      // (a quarter-tile instantiation the build guard compiled out: whole tiles)
+    if (p.gen && multi) FZ_NO(29);
+    p.launch = launcher(p.plan);
+    if (!p.launch && p.gen && p.plan == 2) p.launch = launcher(p.plan = 1);      // (a quarter-tile instantiation the build guard compiled out: whole tiles)
     if (!p.launch) FZ_NO(p.gen ? 30 : 31);
     return p;
 }
@@ -2284,7 +2161,7 @@ FusedPlan hpv_fused_plan_rule(const FusedShard& in, ProjDesc pd, int q, int ntx,
     if (!fit) FZ_NO(4);
     pd.qx = pd.qy = fit[0]; pd.ntx = ntx; pd.nty = nty;
     p = hpv_fused_plan_shard(in, pd);
-    if (!p.declined && !p.small && !(p.gen ? hpv_fused_launcher_gen(pd, in.L, 1, p.nT2) : fused_launcher(pd, in.L, 1, false))) FZ_NO(p.gen ? 30 : 31);
+    if (!p.declined && !p.small && !(p.gen ? hpv_fused_launcher_gen(pd, in.L, 1, p.nT2) : fused_launcher(pd, in.L, 1))) FZ_NO(p.gen ? 30 : 31);
     return p;
 }
 #undef FZ_NO
@@ -2298,7 +2175,7 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const MfmaPass& ps, const MfmaPendingAdam* 
     hipStream_t s = ps.s;
     const FusedPlan p = hpv_fused_plan(*m, pa, ps.dt, n_elem, pre != nullptr);
     if (p.declined) {
-#ifdef HPV_EXPERIMENTS
+#ifdef HPV_TEST_HOOKS
         if (getenv("HPV_TRACE_DISPATCH")) fprintf(stderr, "hpv_mfma_iter_fused: declined at check %d\n", p.declined);
 #endif
         return false;
@@ -2331,12 +2208,11 @@ bool hpv_mfma_iter_fused(HpvMfma* m, const MfmaPass& ps, const MfmaPendingAdam* 
     const bool base_shape = pd.qx == 20 && pd.qy == 20 && pd.ntx == 10 && pd.nty == 10;           // BASELINE config 4 itself
     if (!base_shape || p.gen) snprintf(shp, sizeof shp, ",%dx%d/%dx%d%s", pd.qx, pd.qy, pd.ntx, pd.nty, p.gen ? (p.nT2 ? ",NT2=1,GEN" : ",GEN") : "");
     if (p.counted) snprintf(shp + strlen(shp), sizeof shp - strlen(shp), ",NACT");
-    const char* gs = p.gs ? "true" : "false";
     if (p.small && pd.ntx == SM_NTX && pd.nty == SM_NTY) snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d>", m->L);
     else if (p.small) snprintf(m->variant, sizeof m->variant, "k_iter_small<L=%d,10x10/%dx%d>", m->L, pd.ntx, pd.nty);
-    else if (p.split > 1) snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=true,QT=false,GS=%s%s> split=%d", m->L, gs, shp, p.split);
-    else snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=false,QT=%s,GS=%s%s>%s", m->L, (p.plan == 2 || p.plan == 4) ? "true" : "false",
-                  gs, shp, p.plan >= 3 ? " elements-per-workgroup>1" : "");
+    else if (p.split > 1) snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=true,QT=false%s> split=%d", m->L, shp, p.split);
+    else snprintf(m->variant, sizeof m->variant, "k_iter_fused<L=%d,SPLIT=false,QT=%s%s>%s", m->L, (p.plan == 2 || p.plan == 4) ? "true" : "false",
+                  shp, p.plan >= 3 ? " elements-per-workgroup>1" : "");
     if (p.n_tail > 0) {
         const size_t l = strlen(m->variant);
         snprintf(m->variant + l, sizeof m->variant - l, " + SPLIT=true split=%d on the last %ld elements", p.tsplit, p.n_tail);

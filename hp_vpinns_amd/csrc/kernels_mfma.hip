@@ -835,7 +835,7 @@ int hpv_mfma_max_rows(HpvMfma* m, long n_elem, long n_data_tiles) {
 void hpv_mfma_forward(HpvMfma* m, const double* theta, const double* X, double* OUT, int save_act, hipStream_t s,
                       const MfmaDataTerm* dt) {
     MfmaArgs a = hpv_mfma_pass_args(*m, MfmaPass{theta, X, nullptr, nullptr, nullptr, s, dt, nullptr, 0}, 0, 0);
-    a.OUT = OUT; a.save_act = (save_act && m->store_s_only) ? 2 : save_act;
+    a.OUT = OUT; a.save_act = save_act;
     m->fwd(a, m->fwd_blocks, s);
 }
 

@@ -44,25 +44,8 @@ struct TlLds {
     static constexpr int total(int P) { return RA + (PROJ > WAVES * P ? PROJ : WAVES * P); }
 };
 
-// PERSIST (one-workgroup grids only -- the reference's own 1-element 1-D default, BASELINE config 1; verdict round 3, next 7): ONE
-// launch runs g.persist_iters whole iterations (forward, projection, reverse, TF1 Adam, loss history) back to back.  The iteration
-// is the SAME function as the one-iteration kernel's body (tile_body), called from the loop through a __noinline__ wrapper:
-// a loop around the inlined body lets the compiler keep the body's invariants (46 fp64 literals of sincos / tanh, ~100 uniform
-// addresses) in registers across the back edge -- 256 VGPRs (the cap of six waves on four SIMDs) + 0.5-1 KB of scratch per lane,
-// whose reloads serialise on vmcnt: 34.4 us per iteration against 22.9 for one launch per iteration (round 3, and round 4 again
-// with the thread id and every pointer argument laundered through empty asm per trip, and with -disable-machine-licm /
-// -disable-constant-hoisting).  Behind a call the body is compiled on its own.  Its arguments live in LDS (tl_args: the kernarg
-// segment is not addressable from a callee), the parameter pointer loses its __restrict__ (the Adam update of trip k writes what
-// trip k + 1 stages), and all hand-offs between trips go through global memory of ONE CU (stores, s_waitcnt vmcnt(0),
-// workgroup barrier, loads: coherent within a CU's L1).
-// MEASURED (round 4, config 1, same box, 4 000 iterations): 24.6 us per iteration persistent against 24.0 with one launch per
-// iteration -- the call removes the 34 us disaster but not the launch's worth: uniform arguments read from LDS occupy VGPRs
-// instead of SGPRs (256 VGPRs + 484 B of scratch in the callee), and the parameters still make the round trip through L2
-// between the Adam update and the next trip's staging.  The launch boundary it saves is ~1.5 us.  Hence OPT-IN (HPV_PERSIST=1).
-template <bool PERSIST> struct TlParamPtr { typedef const double* __restrict__ type; };
-template <> struct TlParamPtr<true> { typedef const double* type; };
-
-template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES, bool PERSIST>
+// (one launch looping over whole iterations on a one-workgroup grid: tried in rounds 3 and 4, measured no faster -- profiles/r04_notes.md)
+template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
 __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
     constexpr int C = 1 + NT1 + NT2, NQ = QX * QY, TPE = (NQ + 15) / 16, BT = WAVES * 64, LH = L - 1, FREE = WAVES - TPE;
     static_assert(L >= 2 && TPE <= WAVES, "one tile per wave");
@@ -70,7 +53,7 @@ __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, pt = lane & 15;
-    typename TlParamPtr<PERSIST>::type th = g.theta;
+    const double* __restrict__ th = g.theta;
     const ProjArgs& pa = g.pa;
     const long n_elem = g.proj_n_elem;
     const bool elem_wg = (long)blockIdx.x < n_elem;
@@ -582,104 +565,59 @@ __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
 template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64, 1) k_iter_tile(MfmaArgs g) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    tile_body<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES, false>(g, lds);
+    tile_body<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>(g, lds);
 }
-
-#ifdef HPV_EXPERIMENTS   // measured no faster (24.6 against 24.0 us, see tile_body): libhpvpinn_testhooks.so only, HPV_PERSIST=1 there
-// the persistent launch: arguments in (static) LDS, the body behind a call
-__shared__ MfmaArgs tl_args;
-template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
-__device__ __noinline__ void tile_body_call() {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    tile_body<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES, true>(tl_args, lds);
-}
-template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
-__global__ void __launch_bounds__(WAVES * 64, 1) k_iter_tile_persist(MfmaArgs g) {
-    static_assert(sizeof(MfmaArgs) % 4 == 0, "word-wise copy");
-    for (int i = threadIdx.x; i < (int)(sizeof(MfmaArgs) / 4); i += WAVES * 64) ((int*)&tl_args)[i] = ((const int*)&g)[i];
-    __syncthreads();
-    const int n_trips = g.persist_iters;
-    for (int trip = 0; trip < n_trips; ++trip) {
-        tile_body_call<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>();
-        __syncthreads();        // the next trip stages the updated parameters (s_waitcnt vmcnt(0) + barrier) and reuses the LDS
-    }
-}
-
-#endif  // HPV_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-#ifdef HPV_EXPERIMENTS
-static bool tile_debug() { static const bool dbg = getenv("HPV_TILE_DEBUG") != nullptr; return dbg; }
+// (libhpvpinn_testhooks.so: HPV_TRACE_DISPATCH=1 names the check at which hpv_mfma_iter_tile declines a pass, as hpv_mfma_iter_fused does)
+#ifdef HPV_TEST_HOOKS
+static bool tile_trace() { return getenv("HPV_TRACE_DISPATCH") != nullptr; }
 #else
-static constexpr bool tile_debug() { return false; }
+static constexpr bool tile_trace() { return false; }
 #endif
-// false: the runtime refused the kernel's LDS size; nothing has been enqueued.  (PERSIST: -DHPV_EXPERIMENTS builds, the 1-D rule only)
-template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES, bool PERSIST = false>
+// false: the runtime refused the kernel's LDS size; nothing has been enqueued.
+template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
 static bool launch_iter_tile(const MfmaArgs& a, int blocks, hipStream_t s) {
-#ifndef HPV_EXPERIMENTS
-    static_assert(!PERSIST, "the persistent launch exists in -DHPV_EXPERIMENTS builds only");
-#endif
-    static_assert(!PERSIST || QY == 1, "the persistent launch is instantiated for the 1-D rule only");
     using M = TlLds<L, WAVES, QX, QY, NTX, NTY, D>;
     const size_t bytes = (size_t)M::total(a.P) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
-        const void* kfn;
-#ifdef HPV_EXPERIMENTS
-        if constexpr (PERSIST) kfn = (const void*)k_iter_tile_persist<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>;
-        else
-#endif
-        kfn = (const void*)k_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>;
-        const hipError_t e = hipFuncSetAttribute(kfn,
+        const hipError_t e = hipFuncSetAttribute((const void*)k_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) {
-            if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: hipFuncSetAttribute(%zu bytes): %s\n", bytes, hipGetErrorString(e));
+            if (tile_trace()) fprintf(stderr, "hpv_mfma_iter_tile: declined, hipFuncSetAttribute(%zu bytes): %s\n", bytes, hipGetErrorString(e));
             (void)hipGetLastError();
             return false;
         }
         attr_set = true;
     }
-#ifdef HPV_EXPERIMENTS
-    if constexpr (PERSIST) hipLaunchKernelGGL((k_iter_tile_persist<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>), dim3(blocks), dim3(WAVES * 64), bytes, s, a);
-    else
-#endif
     hipLaunchKernelGGL((k_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>), dim3(blocks), dim3(WAVES * 64), bytes, s, a);
     return true;
 }
 
-// The lookups: the launcher of an instantiation (nullptr: there is none) and the LDS it needs for P parameters -- dynamic bytes, and
-// what the persistent launch keeps in static LDS on top.
+// The lookups: the launcher of an instantiation (nullptr: there is none) and the dynamic LDS it needs for P parameters.
 typedef bool (*TileLauncher)(const MfmaArgs&, int blocks, hipStream_t);
-struct TileKernel { TileLauncher launch = nullptr; size_t bytes = 0, fixed = 0; };
+struct TileKernel { TileLauncher launch = nullptr; size_t bytes = 0; };
 template <int D, int NT1, int NT2, int ACT, int L, int QX, int QY, int NTX, int NTY, int WAVES>
-static TileKernel tile_kernel(int P, bool persist) {
+static TileKernel tile_kernel(int P) {
     const size_t bytes = (size_t)TlLds<L, WAVES, QX, QY, NTX, NTY, D>::total(P) * sizeof(double);
-#ifdef HPV_EXPERIMENTS
-    if constexpr (QY == 1) {      // persistent loop: instantiated for the 1-D rule (config 1)
-        if (persist) return {&launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES, true>, bytes, sizeof(MfmaArgs) + 64};
-    }
-#endif
-    return {&launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>, bytes, 0};
+    return {&launch_iter_tile<D, NT1, NT2, ACT, L, QX, QY, NTX, NTY, WAVES>, bytes};
 }
 template <int D, int NT1, int NT2, int ACT, int QX, int QY, int NTX, int NTY, int WAVES, int MAXL>
-static TileKernel tile_kernel_L(int L, int P, bool persist) {
-    if (L == 2) return tile_kernel<D, NT1, NT2, ACT, 2, QX, QY, NTX, NTY, WAVES>(P, persist);
-    if (L == 3) return tile_kernel<D, NT1, NT2, ACT, 3, QX, QY, NTX, NTY, WAVES>(P, persist);
+static TileKernel tile_kernel_L(int L, int P) {
+    if (L == 2) return tile_kernel<D, NT1, NT2, ACT, 2, QX, QY, NTX, NTY, WAVES>(P);
+    if (L == 3) return tile_kernel<D, NT1, NT2, ACT, 3, QX, QY, NTX, NTY, WAVES>(P);
     if constexpr (MAXL >= 4) {
-        if (L == 4) return tile_kernel<D, NT1, NT2, ACT, 4, QX, QY, NTX, NTY, WAVES>(P, persist);
+        if (L == 4) return tile_kernel<D, NT1, NT2, ACT, 4, QX, QY, NTX, NTY, WAVES>(P);
     }
     return {};
 }
 
 // Whole training pass (forward, projection, reverse) of a shard of small elements in one launch.  Returns false when the
 // element shape / channel set / layout is not covered; the caller then runs the separate kernels.
-#ifdef HPV_EXPERIMENTS
-#define TL_WHY(K) do { if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: not applicable (check %d)\n", K); } while (0)
-#else
-#define TL_WHY(K) do { } while (0)
-#endif
+#define TL_WHY(K) do { if (tile_trace()) fprintf(stderr, "hpv_mfma_iter_tile: declined at check %d\n", K); } while (0)
 bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin, bool* fin_done) {
     const ProjArgs& pa = *p.pa;
     const ProjDesc& pd = pa.pd;
@@ -704,39 +642,30 @@ bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin, 
     const long left = n_dt - n_elem * (waves - tpe);
     const long blocks = n_elem + (left > 0 ? (left + waves - 1) / waves : 0);
     if (blocks > hpv_mfma_grad_rows(m) && blocks > m->max_rows) { TL_WHY(4); return false; }
-#ifdef HPV_EXPERIMENTS
+#ifdef HPV_TEST_HOOKS
     const bool fin_off = getenv("HPV_NO_INKERNEL_FINALIZE") != nullptr;            // (A/B switch of libhpvpinn_testhooks.so, read per launch / capture)
 #else
     constexpr bool fin_off = false;
 #endif
     const bool fin_here = fin && blocks == 1 && n_elem == 1 && !fin_off;
-    // persistent loop (k_iter_tile<.., PERSIST>): only where the kernel finishes the iteration itself AND applies the update
-    // (opt-in, HPV_PERSIST=1: measured 24.6 us per iteration against 24.0 for one launch per iteration -- see tile_body)
-#ifdef HPV_EXPERIMENTS
-    const bool persist_off = !(getenv("HPV_PERSIST") && getenv("HPV_PERSIST")[0] == '1');
-#else
-    constexpr bool persist_off = true;
-#endif
-    const bool persist = fin_here && fin->ad.theta && fin->n_iters > 1 && shape1d && !persist_off;
     TileKernel k;
     if (shape1d) {
-        if (key == 111) k = tile_kernel_L<1, 1, 1, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P, persist);
-        else k = tile_kernel_L<1, 1, 0, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P, persist);
+        if (key == 111) k = tile_kernel_L<1, 1, 1, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P);
+        else k = tile_kernel_L<1, 1, 0, HPV_ACT_SIN, 80, 1, 60, 1, 6, 4>(m->L, nd.P);
     } else {
-        if (key == 221) k = tile_kernel_L<2, 2, 1, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
-        else if (key == 222) k = tile_kernel_L<2, 2, 2, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
-        else if (key == 200) k = tile_kernel_L<2, 0, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
-        else k = tile_kernel_L<2, 2, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P, persist);
+        if (key == 221) k = tile_kernel_L<2, 2, 1, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P);
+        else if (key == 222) k = tile_kernel_L<2, 2, 2, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P);
+        else if (key == 200) k = tile_kernel_L<2, 0, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P);
+        else k = tile_kernel_L<2, 2, 0, HPV_ACT_TANH, 10, 10, 5, 5, 8, 3>(m->L, nd.P);
     }
     if (!k.launch) return false;
-    if (k.bytes + k.fixed > 160 * 1024) {
-        if (tile_debug()) fprintf(stderr, "hpv_mfma_iter_tile: %zu bytes of LDS needed\n", k.bytes);
+    if (k.bytes > 160 * 1024) {
+        if (tile_trace()) fprintf(stderr, "hpv_mfma_iter_tile: declined, %zu bytes of LDS needed\n", k.bytes);
         return false;
     }
     MfmaArgs a = hpv_mfma_pass_args(*m, p, n_elem, 1);
     a.OUT = const_cast<double*>(pa.OUT);
     a.fin_mode = 0;
-    a.persist_iters = persist ? fin->n_iters : 1;
     if (fin_here) {
         a.fin_mode = fin->ad.theta ? 2 : 1;
         a.fin_ad = fin->ad; a.fin_RB = fin->RB; a.fin_lossb_weight = fin->lossb_weight;
@@ -744,11 +673,9 @@ bool hpv_mfma_iter_tile(HpvMfma* m, const MfmaPass& p, const MfmaFinalize* fin, 
     }
     if (!k.launch(a, (int)blocks, p.s)) return false;
     m->last_split = false;
-    snprintf(m->variant, sizeof m->variant, "k_iter_tile<D=%d,NT1=%d,NT2=%d,%s,L=%d,%dx%d/%dx%d,waves=%d>%s%s", nd.d, nd.nT1, nd.nT2,
-             nd.act == HPV_ACT_SIN ? "sin" : "tanh", m->L, pd.qx, pd.qy, pd.ntx, pd.nty, waves, fin_here ? " +finalize" : "",
-             persist ? " persistent" : "");
+    snprintf(m->variant, sizeof m->variant, "k_iter_tile<D=%d,NT1=%d,NT2=%d,%s,L=%d,%dx%d/%dx%d,waves=%d>%s", nd.d, nd.nT1, nd.nT2,
+             nd.act == HPV_ACT_SIN ? "sin" : "tanh", m->L, pd.qx, pd.qy, pd.ntx, pd.nty, waves, fin_here ? " +finalize" : "");
     if (p.rows) *p.rows = (int)blocks;
     if (fin_done) *fin_done = fin_here;
-    if (fin && fin->iters_done) *fin->iters_done = a.persist_iters;
     return true;
 }

@@ -67,7 +67,7 @@ def report(key, hi, base, spills):
 # Per guarded file: the kernel, its template parameters, and rows (flag, when, alone, what the build says) evaluated in order
 # over the functions that tripped.  `when(a, flags)` sees one tripped function's template arguments and the flags set so far; a
 # row whose flag is already set is passed over; after an `alone` row nothing else is evaluated (the kernel is gone).
-FUSED = namedtuple("FUSED", "L SPLIT QT GS QX QY NTX NTY MULTI NT2 GEN")
+FUSED = namedtuple("FUSED", "L SPLIT QT QX QY NTX NTY MULTI NT2 GEN")
 TALL = namedtuple("TALL", "NT1 NT2 L QX QY NTX NTY QT")
 
 

@@ -86,17 +86,17 @@ def test_margins_of_the_built_kernels():
     objects; skipped when the library was built elsewhere."""
     S20, S16, S12, T = "ELi20ELi20ELi10ELi10E", "ELi16ELi16ELi8ELi8E", "ELi12ELi12ELi6ELi6E", "ELi80ELi80ELi5ELi5"
     # (name up to and including MULTI = false: the element-loop instantiations of the same shapes have ranges of their own)
-    expected = {"kernels_fused.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20 + "Lb0E", 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0E", 106),
-                                    ("k_iter_fusedILi3ELb1ELb0ELb0" + S20 + "Lb0E", 106), ("k_iter_fusedILi2ELb0ELb1ELb0" + S20 + "Lb0E", 156),
-                                    ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0E", 166), ("k_iter_fusedILi3ELb0ELb1ELb0" + S12 + "Lb0E", 226)],
+    expected = {"kernels_fused.s": [("k_iter_fusedILi3ELb0ELb1" + S20 + "Lb0E", 106), ("k_iter_fusedILi3ELb0ELb0" + S20 + "Lb0E", 106),
+                                    ("k_iter_fusedILi3ELb1ELb0" + S20 + "Lb0E", 106), ("k_iter_fusedILi2ELb0ELb1" + S20 + "Lb0E", 156),
+                                    ("k_iter_fusedILi3ELb0ELb1" + S16 + "Lb0E", 166), ("k_iter_fusedILi3ELb0ELb1" + S12 + "Lb0E", 226)],
                 # round 6, the general forms (template tail <.., MULTI = false, NT2, GEN = true>): three channels on the one-hot kernels' stash,
                 # four channels with one more tile per wave in LDS (the stash starts 2 L x 5 registers higher)
-                "kernels_fused_gen.s": [("k_iter_fusedILi3ELb0ELb1ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106),
-                                        ("k_iter_fusedILi3ELb1ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi0ELb1E", 166),
-                                        ("k_iter_fusedILi3ELb0ELb1ELb0" + S16 + "Lb0ELi1ELb1E", 196), ("k_iter_fusedILi3ELb1ELb0ELb0" + S16 + "Lb0ELi1ELb1E", 196),
-                                        ("k_iter_fusedILi2ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 176),
+                "kernels_fused_gen.s": [("k_iter_fusedILi3ELb0ELb1" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb0" + S20 + "Lb0ELi0ELb1E", 106),
+                                        ("k_iter_fusedILi3ELb1ELb0" + S20 + "Lb0ELi0ELb1E", 106), ("k_iter_fusedILi3ELb0ELb1" + S16 + "Lb0ELi0ELb1E", 166),
+                                        ("k_iter_fusedILi3ELb0ELb1" + S16 + "Lb0ELi1ELb1E", 196), ("k_iter_fusedILi3ELb1ELb0" + S16 + "Lb0ELi1ELb1E", 196),
+                                        ("k_iter_fusedILi2ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 176),
                                         # the tight plan (FzPlan): three of the first stash place's fifteen doubles in registers, twelve in LDS
-                                        ("k_iter_fusedILi3ELb0ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 160)],
+                                        ("k_iter_fusedILi3ELb0ELb0" + S20 + "Lb0ELi1ELb1E", 160)],
                 "kernels_tall.s": [("k_iter_tallILi2ELi1ELi3" + T + "ELb0", 136), ("k_iter_tallILi2ELi1ELi3" + T + "ELb1", 166),
                                    ("k_iter_tallILi2ELi0ELi3" + T + "ELb1", 166)]}
     for f, fns in _built(("k_iter_fused", "k_iter_tall")).items():
@@ -122,8 +122,8 @@ def test_no_whole_iteration_kernel_spills_to_scratch():
     assert spills == known, {k: v for k, v in spills.items() if k not in known}
 
 
-def _fused(L, SPLIT, QT, QX, MULTI=0, NT2=0, GEN=0, GS=0):
-    return "_Z12k_iter_fusedILi%dELb%dELb%dELb%dELi%dELi%dELi%dELi%dELb%dELi%dELb%dEEv9FusedArgs" % (L, SPLIT, QT, GS, QX, QX, QX // 2, QX // 2, MULTI, NT2, GEN)
+def _fused(L, SPLIT, QT, QX, MULTI=0, NT2=0, GEN=0):
+    return "_Z12k_iter_fusedILi%dELb%dELb%dELi%dELi%dELi%dELi%dELb%dELi%dELb%dEEv9FusedArgs" % (L, SPLIT, QT, QX, QX, QX // 2, QX // 2, MULTI, NT2, GEN)
 
 
 def _tall(L, QT):

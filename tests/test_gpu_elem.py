@@ -419,7 +419,7 @@ def test_hand_tuned_kernels_with_fewer_test_functions_than_instantiated(q, ntx, 
     assert rel(lm, lo) < TRAJ_TOL and rel(m.get_params(), o.get_params()) < TRAJ_TOL
 
 
-@pytest.mark.parametrize("q,nt,nex,want", [(14, 7, 16, "k_iter_fused<L=3,SPLIT=false,QT=true,GS=false,16x16/7x7>"),
+@pytest.mark.parametrize("q,nt,nex,want", [(14, 7, 16, "k_iter_fused<L=3,SPLIT=false,QT=true,16x16/7x7>"),
                                           (18, 9, 4, "20x20/9x9> split"), (11, 6, 16, "12x12/6x6>"), (7, 4, 8, "k_iter_small<L=3,10x10/4x4>")])
 def test_hand_tuned_kernels_with_smaller_quadrature_rules_than_instantiated(q, nt, nex, want):
     """N_quad is a free hyper-parameter (P2:282).  A rule with fewer points than an instantiated one goes to the device padded with

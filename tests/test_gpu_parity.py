@@ -668,7 +668,7 @@ def test_full_size_config4_properties():
         assert "k_project_wg<20x20/10x10>" in mw.h.kernel_variant()      # 256 elements: one workgroup per element
         os.environ["HPV_PJ_WG_SMALL"] = "0"                               # ... against "a lane owns a line" on the same grid
         from hp_vpinns_amd import _lib as _l
-        with _l.library(_l.TEST_HOOKS_LIB_PATH):                          # (an A/B switch of the -DHPV_EXPERIMENTS build)
+        with _l.library(_l.TEST_HOOKS_LIB_PATH):                          # (an A/B switch of the -DHPV_TEST_HOOKS build)
             mt = poisson2d.build_model(s, L, init_params=th)
             l3t, gt = mt.loss_and_grad()
             assert "k_project_tp<20x20/10x10>" in mt.h.kernel_variant()
@@ -1173,7 +1173,7 @@ def test_single_workgroup_grid_finishes_the_iteration_in_the_kernel():
     os.environ["HPV_NO_INKERNEL_FINALIZE"] = "1"
     try:
         from hp_vpinns_amd import _lib as _l
-        with _l.library(_l.TEST_HOOKS_LIB_PATH):       # (an A/B switch of the -DHPV_EXPERIMENTS build)
+        with _l.library(_l.TEST_HOOKS_LIB_PATH):       # (an A/B switch of the -DHPV_TEST_HOOKS build)
             m2 = VPINN1D(*a, init_params=th)
             l3b, gb = m2.loss_and_grad()
             assert m2.h.pass_structure() == "whole-iteration-tile"
@@ -1192,72 +1192,26 @@ def test_single_workgroup_grid_finishes_the_iteration_in_the_kernel():
     assert rel(hist[:, 0], lo) < TRAJ_TOL and rel(m.get_params(), o.get_params()) < TRAJ_TOL
 
 
-def test_persistent_single_workgroup_launch_is_the_same_iteration(monkeypatch):
-    """HPV_PERSIST=1 (measured no faster: kernels_tile.hip, tile_body; libhpvpinn_testhooks.so only): MANY iterations of the one-workgroup grid of config 1
-    in ONE launch -- the same body function behind a call.  Loss history, parameters, Adam moments and beta powers must equal the
-    one-launch-per-iteration run to round-off (two compilations of the same body), the recorded iterations must be all there, and
-    early-stop chunking on top of it must keep the reference's semantics."""
-    from hp_vpinns_amd.vpinn import VPINN1D
-    a = p1_args(gold("poisson1d_cfg1"), layers=[1, 20, 20, 20, 1])
-    th = theta0(a[8], 41)
-    th[20:40] = 0.03 * np.arange(20)
-    ref = VPINN1D(*a, init_params=th)
-    h_ref = ref._step_record(37)[0]
-    ref._step(100, False)
-    from hp_vpinns_amd import _lib
-    monkeypatch.setenv("HPV_PERSIST", "1")
-    mp = VPINN1D(*a, init_params=th)                   # the product library neither carries the persistent launch nor reads the switch
-    mp._step(3, False)
-    assert "persistent" not in mp.h.kernel_variant(), mp.h.kernel_variant()
-    with _lib.library(_lib.TEST_HOOKS_LIB_PATH):       # -DHPV_EXPERIMENTS
-        m = VPINN1D(*a, init_params=th)
-    h = m._step_record(37)[0]
-    assert "persistent" in m.h.kernel_variant(), m.h.kernel_variant()
-    m._step(100, False)
-    assert m.h.updates_applied() == 137
-    assert rel(h, h_ref) < 1e-12 and rel(m.h.get_state(), ref.h.get_state()) < 1e-11
-    rec = []
-    with _lib.library(_lib.TEST_HOOKS_LIB_PATH):
-        m2 = VPINN1D(*a, init_params=th, total_record=rec)
-    m2.train(41, 0.0)
-    assert [int(r[0]) for r in rec] == [0, 10, 20, 30, 40] and rel([r[1] for r in rec], h_ref[[0, 10, 20, 30], 0].tolist() + [rec[-1][1]]) < 1e-12
-
-
-def test_large_batch_projection_plans_agree(monkeypatch):
-    """The stand-alone projection on a LARGE synthetic batch (the HBM-roofline measurement of SURVEY.md 8d) has three plans:
-    the streaming residual kernel (LDS-staged batches of 6 elements, register double-buffered: residual only), the
-    column-in-registers kernel k_project_tp, and the general k_project.  On the same seeded data they must give the same R and
-    element losses (sums of the same terms in different orders) -- incl. a batch size that is not a multiple of 6 or 3."""
+def test_large_batch_projection_plans_agree():
+    """The stand-alone projection on a LARGE synthetic batch (the HBM-roofline measurement of SURVEY.md 8d) has two plans: the
+    column-in-registers kernel k_project_tp and the general k_project.  On the same seeded data they must give the same R and
+    element losses (sums of the same terms in different orders) -- incl. batch sizes that are no multiple of the 3 elements a
+    wavefront of k_project_tp serves."""
     from hp_vpinns_amd import _lib
     from hp_vpinns_amd.quadrature import GaussLobattoJacobiWeights
     from hp_vpinns_amd.testfcn import tables_1d
     x, w = GaussLobattoJacobiWeights(20, 0, 0)
 
-    def sums(adj, backend=_lib.BACKEND_AUTO, n=10007, experiments=False):
-        if experiments:                                # the measured-slower plans live in the -DHPV_EXPERIMENTS build only
-            with _lib.library(_lib.TEST_HOOKS_LIB_PATH):
-                return sums(adj, backend, n)
+    def sums(adj, backend=_lib.BACKEND_AUTO, n=10007):
         h = _lib.Handle(_lib.PDE_POISSON2D, 1, _lib.ACT_TANH, [2, 20, 20, 20, 1], lossb_weight=10, backend=backend)
         h.set_quadrature(x, w, x, w)
         h.set_tables(tables_1d(10, x), tables_1d(10, x))
         return h.bench_checksums(n, adj)
 
-    monkeypatch.setenv("HPV_PJ_STREAM", "1")        # (opt-in: equal speed to k_project_tp since that kernel's tables are SGPR operands)
-    s_stream = sums(False, experiments=True)
-    monkeypatch.delenv("HPV_PJ_STREAM")
-    monkeypatch.setenv("HPV_PJ_DMA", "1")           # the LDS-DMA stream (three batch buffers filled by global_load_lds)
-    s_dma, s_dma2 = sums(False, experiments=True), sums(False, n=6 * 4096 + 5, experiments=True)
-    monkeypatch.setenv("HPV_PJ_DMA", "2")           # every wave its own LDS-DMA loader and consumer
-    s_wd, s_wd2 = sums(False, experiments=True), sums(False, n=6 * 4096 + 5, experiments=True)
-    monkeypatch.delenv("HPV_PJ_DMA")
-    s_tp = sums(False)
-    assert rel(s_wd[[0, 1, 2, 5]], s_tp[[0, 1, 2, 5]]) < 1e-12, (s_wd, s_tp)
-    assert rel(s_wd2[[0, 1, 2, 5]], s_dma2[[0, 1, 2, 5]]) < 1e-12, (s_wd2, s_dma2)
-    assert rel(s_dma[[0, 1, 2, 5]], s_tp[[0, 1, 2, 5]]) < 1e-12, (s_dma, s_tp)
-    assert rel(s_dma2[[0, 1, 2, 5]], sums(False, n=6 * 4096 + 5)[[0, 1, 2, 5]]) < 1e-12
-    s_gen = sums(False, _lib.BACKEND_GENERIC)
-    assert np.all(np.isfinite(s_stream)) and s_stream[1] > 0
-    assert rel(s_stream[[0, 1, 2, 5]], s_tp[[0, 1, 2, 5]]) < 1e-12, (s_stream, s_tp)
+    s_tp, s_gen = sums(False), sums(False, _lib.BACKEND_GENERIC)
+    assert np.all(np.isfinite(s_tp)) and s_tp[1] > 0
     assert rel(s_tp[[0, 1, 2, 5]], s_gen[[0, 1, 2, 5]]) < 1e-12, (s_tp, s_gen)
+    s_tp2, s_gen2 = sums(False, n=6 * 4096 + 5), sums(False, _lib.BACKEND_GENERIC, n=6 * 4096 + 5)
+    assert rel(s_tp2[[0, 1, 2, 5]], s_gen2[[0, 1, 2, 5]]) < 1e-12, (s_tp2, s_gen2)
     a_tp, a_gen = sums(True), sums(True, _lib.BACKEND_GENERIC)
     assert rel(a_tp, a_gen) < 1e-12 and a_tp[4] > 0
