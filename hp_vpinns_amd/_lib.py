@@ -35,6 +35,8 @@ EXPORTS = [
     "hpv_rccl_available", "hpv_graphs_in_use", "hpv_updates_applied", "hpv_set_shared_element_kernels", "hpv_shared_element_kernels",
     "hpv_kernel_variant", "hpv_build_info", "hpv_rccl_abandon", "hpv_bench_residual_checksums", "hpv_rule_advice",
     "hpv_rccl_info", "hpv_rccl_time_allreduce", "hpv_grid_plan", "hpv_set_active_tests_2d",
+    "hpv_eval_points", "hpv_residual_points", "hpv_set_validation", "hpv_validate", "hpv_validation_reset", "hpv_validate_enqueue",
+    "hpv_validation_read", "hpv_step_validate",
 ]
 
 
@@ -183,6 +185,14 @@ def load():
     lib.hpv_build_info.argtypes = []
     lib.hpv_grid_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_long]
     lib.hpv_rule_advice.argtypes = [C.c_int] * 8 + [C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.hpv_eval_points.argtypes = [h, _dp, C.c_int, _dp, C.c_size_t]
+    lib.hpv_residual_points.argtypes = [h, _dp, _dp, C.c_int, _dp]
+    lib.hpv_set_validation.argtypes = [h, _dp, _dp, _dp, C.c_int]
+    lib.hpv_validate.argtypes = [h, _dp]
+    lib.hpv_validation_reset.argtypes = [h]
+    lib.hpv_validate_enqueue.argtypes = [h]
+    lib.hpv_validation_read.argtypes = [h, C.c_int, _dp]
+    lib.hpv_step_validate.argtypes = [h, C.c_int, C.c_int, _dp, C.c_size_t]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:
@@ -359,6 +369,63 @@ class Handle:
         X = _points(X, self.layers[0], "prediction points")
         out = np.empty(X.shape[0])
         self._chk(self.lib.hpv_predict(self._h, _p(X), X.shape[0], _p(out)))
+        return out
+
+    def eval_points(self, X):
+        """(C, n): the full channel list at arbitrary points -- u, u_x, u_xx in 1-D; u, u_x, u_y (u_t), u_xx, u_yy (u_tt) in 2-D
+        (hpv_eval_points; one forward launch)."""
+        X = _points(X, self.layers[0], "evaluation points")
+        out = np.empty((1 + 2 * self.layers[0], X.shape[0]))
+        self._chk(self.lib.hpv_eval_points(self._h, _p(X), X.shape[0], _p(out), out.size))
+        return out
+
+    def residual_points(self, X, f=None):
+        """(n,): the strong residual at arbitrary points (formulas: hpv_set_collocation); f None = zero right-hand side."""
+        X, f = _points(X, self.layers[0], "residual points"), (None if f is None else _c(f).reshape(-1))
+        if f is not None and f.size != X.shape[0]:
+            raise ValueError("one right-hand-side value per residual point")
+        out = np.empty(X.shape[0])
+        self._chk(self.lib.hpv_residual_points(self._h, _p(X), _p(f), X.shape[0], _p(out)))
+        return out
+
+    def set_validation(self, X, u, du=None):
+        """The validation set (uploaded once): points, exact values, optionally exact gradients (n, dim).  X None clears it."""
+        if X is None:
+            self._chk(self.lib.hpv_set_validation(self._h, None, None, None, 0))
+            return
+        X, u = _points(X, self.layers[0], "validation points"), _c(u).reshape(-1)
+        if u.size != X.shape[0]:
+            raise ValueError("one exact value per validation point")
+        if du is not None:
+            du = _points(du, self.layers[0], "exact gradients")
+            if du.shape[0] != X.shape[0]:
+                raise ValueError("one exact gradient per validation point")
+        self._chk(self.lib.hpv_set_validation(self._h, _p(X), _p(u), _p(du), X.shape[0]))
+
+    def validate(self):
+        """{sum (u^-u)^2, sum u^2, max |u^-u|, sum |grad u^ - grad u|^2, sum |grad u|^2, n} on the validation set (hpv_validate)."""
+        out = np.empty(6)
+        self._chk(self.lib.hpv_validate(self._h, _p(out)))
+        return out
+
+    def validation_reset(self):
+        self._chk(self.lib.hpv_validation_reset(self._h))
+
+    def validate_enqueue(self):
+        """Forward + reduction on the handle's stream, appended to the device-side history; no synchronisation."""
+        self._chk(self.lib.hpv_validate_enqueue(self._h))
+
+    def validation_read(self, n):
+        out = np.empty((int(n), 6))
+        self._chk(self.lib.hpv_validation_read(self._h, int(n), _p(out)))
+        return out
+
+    def step_validate(self, n_iters, every):
+        """n_iters Adam iterations, a validation enqueued after every `every`-th update, one read at the end:
+        (n_iters // every, 6)."""
+        every = int(every)
+        out = np.empty((max(int(n_iters), 0) // every if every >= 1 else 0, 6))
+        self._chk(self.lib.hpv_step_validate(self._h, int(n_iters), every, _p(out), out.size))
         return out
 
     def channels(self, n_points, n_channels):

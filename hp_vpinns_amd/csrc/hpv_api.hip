@@ -612,6 +612,8 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
         h->eval_differs = true;
     }
     h->nd_val = make_netdesc(*cfg, 0, t1, 0, t2);
+    h->nd_full = make_netdesc(*cfg, dim, t1, dim, t2);     // hpv_eval_points: u, u_x, (u_y | u_t), u_xx, (u_yy | u_tt)
+    h->nd_grad = make_netdesc(*cfg, dim, t1, 0, t2);       // hpv_validate against exact gradients
     if (cfg->scheme == HPV_SCHEME_PINN) {
         // channels of the strong-form residual (k_pinn_residual): 1-D [u, u_x, u_xx] (P1:150-155); AdvDiff [u, u_x, u_t, u_xx]
         // (P3:247-253; t2w = {1, 0}); 2-D u_xx + u_yy as ONE mixed second tangent, NetDesc::t2w: four channels instead of five
@@ -663,6 +665,11 @@ void hpv_destroy(hpv_handle h) {
     if (h->d_fcol) (void)hipFree(h->d_fcol);
     if (h->d_col_part) (void)hipFree(h->d_col_part);
     if (h->d_jac) (void)hipFree(h->d_jac);
+    if (h->mfma_evalp) hpv_mfma_destroy(h->mfma_evalp);
+    if (h->mfma_val) hpv_mfma_destroy(h->mfma_val);
+    free_batch(h->evalp); free_batch(h->valb);
+    { double* vp[] = {h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf}; for (double* q : vp) if (q) (void)hipFree(q); }
+    if (h->d_val_idx) (void)hipFree(h->d_val_idx);
     if (h->d_upart) (void)hipFree(h->d_upart);
     p2p_release(h);
     rccl_release(h);
@@ -1273,6 +1280,191 @@ int hpv_predict(hpv_handle h, const double* X, int n, double* u_out) {
     HIPCHK(h, hipMemcpyAsync(u_out, h->pred.OUT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---- device-side validation: derivative channels and the strong residual at the caller's points, error norms against an exact
+//      solution on a stored set, and a device-side history of those norms filled between training iterations (the reference takes
+//      u_pred on its test grid through the host: P1:197-199, P2:255-257; its pointwise residual is net_f, P2:187-194, P3:247-253) ----
+namespace {
+
+// a forward-only batch of n points under channel set nd, with the MFMA object where the shape has one (as hpv_predict does)
+int points_batch(hpv_ctx* h, Batch& b, HpvMfma** m, const NetDesc& nd, int n) {
+    if (*m) { hpv_mfma_destroy(*m); *m = nullptr; }
+    int rc = alloc_batch(h, b, nd, n, false);
+    if (rc) return rc;
+    if (n > 0 && h->cfg.backend != HPV_BACKEND_GENERIC) *m = hpv_mfma_create(nd, n, nullptr, false);
+    return 0;
+}
+
+int forward_only(hpv_ctx* h, Batch& b, HpvMfma* m) {
+    if (m) hpv_mfma_forward(m, h->d_theta, b.X, b.OUT, 0, h->stream);
+    else launch_mlp_fwd_generic(b.nd, h->d_theta, b.X, nullptr, b.OUT, b.N, 0, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the full channel list at the caller's points: upload + ONE forward launch on the handle's own batch (re-created when n changes)
+int eval_points_forward(hpv_ctx* h, const double* X, int n) {
+    int rc;
+    if (h->evalp.N != n) {
+        if ((rc = points_batch(h, h->evalp, &h->mfma_evalp, h->nd_full, n))) return rc;
+        if ((rc = dalloc(h, &h->d_res_f, (size_t)n))) return rc;
+        if ((rc = dalloc(h, &h->d_res_r, (size_t)n))) return rc;
+    }
+    if ((rc = upload_points(h, h->evalp, X, n, h->dim))) return rc;
+    return forward_only(h, h->evalp, h->mfma_evalp);
+}
+
+int validation_ready(hpv_ctx* h) {
+    if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
+    if (h->n_val <= 0) return fail(h, -3, "hpv_set_validation has not been called");
+    return 0;
+}
+
+// forward over the stored set + the reduction, on the handle's stream; no synchronisation, no host read
+int enqueue_validation(hpv_ctx* h, bool to_history) {
+    int rc = forward_only(h, h->valb, h->mfma_val);
+    if (rc) return rc;
+    const int cap = HPV_HIST_CAP;
+    double* buf = h->d_val_buf;
+    const ValArgs a{h->valb.OUT, h->valb.N, h->d_val_u, h->d_val_du, h->n_val, h->dim, buf + 6 + (size_t)6 * cap,
+                    reinterpret_cast<unsigned int*>(h->d_val_idx + 1), buf, to_history ? buf + 6 : nullptr, h->d_val_idx, cap};
+    launch_validate_reduce(a, validate_reduce_blocks(h->n_val), h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+int hpv_eval_points(hpv_handle h, const double* X, int n, double* out, size_t n_out) {
+    if (!h) return -1;
+    if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
+    if (n < 0 || (n > 0 && (!X || !out))) return fail(h, -1, "bad evaluation arguments");
+    const int C = h->nd_full.C;
+    if (n_out != (size_t)C * n) return fail(h, -1, "channel buffer has %zu entries, expected %zu", n_out, (size_t)C * n);
+    if (n == 0) return 0;
+    int rc = eval_points_forward(h, X, n);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, h->evalp.OUT, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int hpv_residual_points(hpv_handle h, const double* X, const double* f, int n, double* r_out) {
+    if (!h) return -1;
+    if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
+    if (n < 0 || (n > 0 && (!X || !r_out))) return fail(h, -1, "bad residual arguments");
+    if (n == 0) return 0;
+    int rc = eval_points_forward(h, X, n);
+    if (rc) return rc;
+    if (f && (rc = upload(h, h->d_res_f, f, (size_t)n))) return rc;
+    launch_residual_points(h->cfg.pde, h->evalp.OUT, h->evalp.N, f ? h->d_res_f : nullptr, h->has_eps ? h->d_theta + h->P : nullptr,
+                           h->cfg.V, n, h->d_res_r, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(r_out, h->d_res_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int hpv_set_validation(hpv_handle h, const double* X, const double* u, const double* du, int n) {
+    if (!h) return -1;
+    if (n < 0 || (n > 0 && (!X || !u))) return fail(h, -1, "bad validation arguments");
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued validation may still read the old set)
+    h->n_val = 0;
+    if ((rc = points_batch(h, h->valb, &h->mfma_val, du ? h->nd_grad : h->nd_val, n))) return rc;
+    if ((rc = dalloc(h, &h->d_val_u, (size_t)n))) return rc;
+    if ((rc = dalloc(h, &h->d_val_du, du ? (size_t)n * h->dim : 0))) return rc;
+    if (n == 0) return 0;
+    if (!h->d_val_buf) {
+        const size_t doubles = 6 + (size_t)6 * HPV_HIST_CAP + (size_t)5 * HPV_VAL_MAX_BLOCKS;
+        if ((rc = dalloc(h, &h->d_val_buf, doubles))) return rc;
+        if ((rc = dalloc(h, &h->d_val_idx, (size_t)2))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_val_buf, 0, doubles * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_val_idx, 0, 2 * sizeof(int), h->stream));
+    }
+    if ((rc = upload_points(h, h->valb, X, n, h->dim))) return rc;
+    if ((rc = upload(h, h->d_val_u, u, (size_t)n))) return rc;
+    if (du) {      // [n][dim] -> [dim][n]
+        std::vector<double> t((size_t)n * h->dim);
+        for (int p = 0; p < n; ++p)
+            for (int c = 0; c < h->dim; ++c) t[(size_t)c * n + p] = du[(size_t)p * h->dim + c];
+        if ((rc = upload(h, h->d_val_du, t.data(), t.size()))) return rc;
+    }
+    h->n_val = n;
+    return 0;
+}
+
+int hpv_validate(hpv_handle h, double* out6) {
+    if (!h) return -1;
+    if (!out6) return fail(h, -1, "bad validation arguments");
+    int rc = validation_ready(h);
+    if (rc || (rc = enqueue_validation(h, false))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out6, h->d_val_buf, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int hpv_validation_reset(hpv_handle h) {
+    if (!h) return -1;
+    int rc = validation_ready(h);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->d_val_idx, 0, sizeof(int), h->stream));
+    return 0;
+}
+
+int hpv_validate_enqueue(hpv_handle h) {
+    if (!h) return -1;
+    int rc = validation_ready(h);
+    return rc ? rc : enqueue_validation(h, true);
+}
+
+int hpv_validation_read(hpv_handle h, int n, double* out) {
+    if (!h) return -1;
+    if (n < 0 || (n > 0 && !out)) return fail(h, -1, "bad validation arguments");
+    const int cap = HPV_HIST_CAP;
+    if (n > cap) return fail(h, -1, "validation history holds %d entries, %d requested", cap, n);
+    int rc = validation_ready(h);
+    if (rc) return rc;
+    int have = 0;
+    HIPCHK(h, hipMemcpyAsync(&have, h->d_val_idx, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (n) HIPCHK(h, hipMemcpyAsync(out, h->d_val_buf + 6, (size_t)6 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (have < n) return fail(h, -3, "only %d validations since hpv_validation_reset, %d requested", have, n);
+    return 0;
+}
+
+// hpv_step with a validation enqueued behind every `every`-th update: chunks of `every` iterations (graph replays where hpv_step
+// replays them -- the validation launches sit BETWEEN the replays, the captured iterations are untouched), one synchronisation and
+// one read at the end.  An in-kernel exchange that timed out (-7) is handled as in hpv_step: the iterations that took place are
+// kept with the samples they completed, the rest runs on the barrier-free structures.
+int hpv_step_validate(hpv_handle h, int n_iters, int every, double* out, size_t n_out) {
+    if (!h) return -1;
+    if (n_iters < 0 || every < 1) return fail(h, -1, "bad arguments: %d iterations, a validation every %d", n_iters, every);
+    const int ns = n_iters / every, cap = HPV_HIST_CAP;
+    if (ns > cap) return fail(h, -1, "validation history holds %d entries, %d requested", cap, ns);
+    if (n_out < (size_t)6 * ns || (ns > 0 && !out)) return fail(h, -1, "validation buffer has %zu entries, expected %zu", n_out, (size_t)6 * ns);
+    int rc = validation_ready(h);
+    if (rc) return rc;
+    int it = 0;      // iterations that have taken place
+    for (int round = 0;; ++round) {
+        const int first = it / every;      // samples already complete
+        HIPCHK(h, hipMemcpyAsync(h->d_val_idx, &first, sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int k = it; k < n_iters;) {
+            const int c = std::min(every - k % every, n_iters - k);
+            if ((rc = enqueue_iterations(h, c))) return rc;
+            k += c;
+            if (k % every == 0 && (rc = enqueue_validation(h, true))) return rc;
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = sync_check(h)) != -7 || round) break;
+        const int done = after_exchange_timeout(h, n_iters - it);
+        if (done < 0) break;
+        it += done;
+    }
+    if (rc || (rc = p2p_check(h))) return rc;
+    return hpv_validation_read(h, ns, out);
 }
 
 // [theta | m | v | beta1^t | beta2^t]: everything a bit-exact resume needs.

@@ -110,6 +110,18 @@ struct hpv_ctx {
     int n_col = 0;
     long n_col_total = 0;      // collocation points of ALL shards (the mean of P2:124 runs over them)
     double* d_jac = nullptr;   // |J_e| of the owned elements (RHS assembly, hpv_assemble_rhs)
+    // device-side validation (hpv_eval_points .. hpv_step_validate): forward-only batches at the caller's points
+    NetDesc nd_full{};         // the full channel list: u, every first and every second input derivative (hpv_eval_points)
+    NetDesc nd_grad{};         // u and the first derivatives (validation against exact gradients)
+    Batch evalp;               // batch of hpv_eval_points / hpv_residual_points, re-created when n changes
+    HpvMfma* mfma_evalp = nullptr;
+    double *d_res_f = nullptr, *d_res_r = nullptr;      // [evalp.N] right-hand side and residual of hpv_residual_points
+    Batch valb;                // the stored validation set (nd_val, or nd_grad with exact gradients)
+    HpvMfma* mfma_val = nullptr;
+    int n_val = 0;
+    double *d_val_u = nullptr, *d_val_du = nullptr;     // exact values [n], exact gradients [dim][n] (nullptr: none given)
+    double* d_val_buf = nullptr;   // [6] result of hpv_validate | [HPV_HIST_CAP][6] history | [HPV_VAL_MAX_BLOCKS][5] partials
+    int* d_val_idx = nullptr;      // [0] history index, [1] the reduction's ticket counter
     // in-library exchange of the packed buffer between the ranks of a node (hpv_p2p_*)
     P2PArgs pp{};
     bool p2p_on = false;

@@ -182,3 +182,27 @@ struct PinnArgs {
 void launch_pinn_residual(int pde, const PinnArgs& a, hipStream_t s);
 bool launch_project_wg(const ProjArgs& pa, long n_elem, hipStream_t s, double* upart = nullptr);
 int project_row_split(const ProjDesc& pd, long n_elem, int backend_generic);   // workgroups per element of the row-split projection
+
+// ---- device-side validation (kernels_validate.hip) ----
+// All arguments of the error-norm reduction over a validation set: {sum (u^ - u)^2, sum u^2, max |u^ - u|, sum |grad u^ - grad u|^2,
+// sum |grad u|^2, n} -- six doubles written at `out`, or appended to the device-side history at hist[6 * (*hist_idx)++] (entries
+// beyond hist_cap are dropped, the index still counts them) when `hist` is given.
+struct ValArgs {
+    const double* OUT;       // [C][N] channels of the validation batch: u^, then d/dx, d/dy (d/dt) when du is given
+    long N;
+    const double* u;         // [n] exact values
+    const double* du;        // [dim][n] exact gradients, or nullptr (the two gradient sums are then 0)
+    int n, dim;
+    double* part;            // [HPV_VAL_MAX_BLOCKS][5] per-workgroup partial results (several workgroups only)
+    unsigned int* ticket;    // arrival counter of the workgroups, left at 0 by every launch
+    double* out;             // [6]
+    double* hist;            // [hist_cap][6], or nullptr
+    int* hist_idx;
+    int hist_cap;
+};
+#define HPV_VAL_MAX_BLOCKS 64
+int validate_reduce_blocks(int n);       // the workgroups the reduction runs with at n points (a function of n alone: fixed summation order)
+void launch_validate_reduce(const ValArgs& a, int blocks, hipStream_t s);
+// strong residual from the full channel list [u, u_x, (u_y | u_t), u_xx, (u_yy | u_tt)] at n foreign points (formulas: hpv_set_collocation)
+void launch_residual_points(int pde, const double* OUT, long N, const double* f_or_null, const double* eps_ptr, double V, int n,
+                            double* r, hipStream_t s);

@@ -114,22 +114,38 @@ def export_mat(path, s, u_record, u_records_iterhis, total_record, total_time_tr
 
 
 def run(LR=0.001, Opt_Niter=1500 + 1, Opt_tresh=2e-11, var_form=0, Net_layer=None, N_el_x=1, N_el_t=1, N_test_x=5,
-        N_test_t=5, N_quad=10, N_bound=80, init_params=None, backend="auto", verbose=True, mat_path=None, scheme="VPINNs"):
+        N_test_t=5, N_quad=10, N_bound=80, init_params=None, backend="auto", verbose=True, mat_path=None, scheme="VPINNs",
+        validate_every=None):
     """P3:31-54 hyper-parameters (reference defaults) -> identified epsilon, prediction, L2 error.  scheme 'PINNs' trains on the
     strong-form residual u_t + V u_x - epsilon u_xx at the NPf collocation points of P3:387-391 instead of the variational one."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P3:46
     s = setup(N_el_x, N_el_t, N_test_x, N_test_t, N_quad, N_bound)
     model = build_model(s, Net_layer, var_form, LR, init_params, backend, scheme=scheme)
-    error_record, total_record, u_record, u_his, t_train = model.train(Opt_Niter, Opt_tresh)   # P3:493-494
-    if mat_path is not None:                                                    # P3:500-508
-        export_mat(mat_path, s, u_record, u_his, total_record, t_train)
+    curve = None
+    if validate_every:
+        # the error on the test grid after every K-th update, reduced on the device (no records, no threshold, no .mat)
+        import time
+        model.set_validation()
+        t0 = time.time()
+        curve = model.train_validated(Opt_Niter, validate_every)
+        total_record, t_train = [], time.time() - t0
+        if verbose:
+            for it, l2, mx in zip(*curve):
+                print("It: %d, rel L2 error: %.3e, max error: %.3e" % (it, l2, mx))
+    else:
+        error_record, total_record, u_record, u_his, t_train = model.train(Opt_Niter, Opt_tresh)   # P3:493-494
+        if mat_path is not None:                                                # P3:500-508
+            export_mat(mat_path, s, u_record, u_his, total_record, t_train)
     u_pred = model.predict()
     err = np.linalg.norm(s["u_test"] - u_pred, 2) / np.linalg.norm(s["u_test"], 2)
     eps_id = float(model.epsilon[0])
     if verbose:
         print("identified epsilon: %.6f (exact %.6f)   relative L2 error of u: %.3e   train time %.2fs"
               % (eps_id, epsilon, err, t_train))
-    return dict(model=model, u_pred=u_pred, rel_l2=err, epsilon=eps_id, total_record=total_record, setup=s)
+    out = dict(model=model, u_pred=u_pred, rel_l2=err, epsilon=eps_id, total_record=total_record, setup=s)
+    if curve is not None:
+        out["error_curve"] = curve
+    return out
 
 
 if __name__ == "__main__":
@@ -141,6 +157,8 @@ if __name__ == "__main__":
     ap.add_argument("--var-form", type=int, default=0)
     ap.add_argument("--mat", default=None, help="write the reference's <case>_record.mat here (P3:500-508)")
     ap.add_argument("--scheme", default="VPINNs", choices=("VPINNs", "PINNs"))
+    ap.add_argument("--validate-every", type=int, default=None,
+                    help="print the error on the test grid after every K-th update (device-side validation history)")
     a = ap.parse_args()
     run(Opt_Niter=a.iters, N_el_x=a.elements_x, N_quad=a.quad, var_form=a.var_form, Net_layer=[2] + [a.width] * 3 + [1],
-        mat_path=a.mat, scheme=a.scheme)
+        mat_path=a.mat, scheme=a.scheme, validate_every=a.validate_every)

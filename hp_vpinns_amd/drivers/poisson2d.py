@@ -104,18 +104,32 @@ def build_model(s, Net_layer, var_form=1, init_params=None, backend="auto", loss
 
 
 def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10,
-        N_bound=80, N_residual=100, n_iter=10000 + 1, init_params=None, backend="auto", record_every=1, verbose=True):
-    """P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error."""
+        N_bound=80, N_residual=100, n_iter=10000 + 1, init_params=None, backend="auto", record_every=1, verbose=True,
+        validate_every=None):
+    """P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  validate_every=K trains
+    through `train_validated` instead of `train`: the error on the test grid after every K-th update, reduced on the device."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P2:280
     s = setup(N_el_x, N_el_y, N_test_x, N_test_y, N_quad, N_bound, N_residual)
     loss_his = []
     model = build_model(s, Net_layer, var_form, init_params, backend, loss_his, scheme=scheme)
-    model.train(n_iter, record_every=record_every)               # P2:434
+    curve = None
+    if validate_every:
+        model.set_validation()                                   # the test grid of P2:418-426, uploaded once
+        curve = model.train_validated(n_iter, validate_every)
+        loss_his.append(float(model.loss()[0]))
+        if verbose:
+            for it, l2, mx in zip(*curve):
+                print("It: %d, rel L2 error: %.3e, max error: %.3e" % (it, l2, mx))
+    else:
+        model.train(n_iter, record_every=record_every)           # P2:434
     u_pred = model.predict()                                     # P2:435
     err = np.linalg.norm(s["u_test"] - u_pred, 2) / np.linalg.norm(s["u_test"], 2)
     if verbose:
         print("relative L2 error of u: %.3e   final loss: %.3e" % (err, loss_his[-1]))
-    return dict(model=model, u_pred=u_pred, rel_l2=err, loss_his=loss_his, setup=s)
+    out = dict(model=model, u_pred=u_pred, rel_l2=err, loss_his=loss_his, setup=s)
+    if curve is not None:
+        out["error_curve"] = curve
+    return out
 
 
 if __name__ == "__main__":
@@ -125,6 +139,8 @@ if __name__ == "__main__":
     ap.add_argument("--var-form", type=int, default=1)
     ap.add_argument("--width", type=int, default=5)
     ap.add_argument("--record-every", type=int, default=1)
+    ap.add_argument("--validate-every", type=int, default=None,
+                    help="print the error on the test grid after every K-th update (device-side validation history)")
     a = ap.parse_args()
     run(n_iter=a.iters, N_el_x=a.elements, N_el_y=a.elements, var_form=a.var_form,
-        Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every)
+        Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every, validate_every=a.validate_every)

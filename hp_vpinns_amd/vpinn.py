@@ -593,6 +593,74 @@ class _VPINNBase:
         u_exact = np.asarray(u_exact, dtype=np.float64).reshape(-1, 1)
         return float(np.linalg.norm(u_exact - self._predict(X), 2) / np.linalg.norm(u_exact, 2))
 
+    # -- device-side validation: derivatives, residual and the error history (hpv_eval_points .. hpv_step_validate) -------------
+    _channel_names = ("u", "u_x", "u_y", "u_xx", "u_yy")      # 2-D; the 1-D and AdvDiff classes name their own
+    _val_default = ("X_test", "utest")                        # attributes holding the stored test grid
+
+    def evaluate(self, X):
+        """The network and its input derivatives at the points X (n, dim): a dict of (n, 1) arrays keyed `u, u_x, u_xx` in 1-D,
+        `u, u_x, u_y, u_xx, u_yy` in 2-D (`u_t`, `u_tt` for the second coordinate of AdvDiff) -- one forward launch."""
+        ch = self.h.eval_points(np.asarray(X, dtype=np.float64))
+        return {k: ch[i][:, None].copy() for i, k in enumerate(self._channel_names)}
+
+    def residual(self, X, f=None):
+        """The strong PDE residual at the points X (n, dim) as an (n, 1) array, in either scheme: -u_xx - f (Poisson-1D),
+        u_xx + u_yy - f (Poisson-2D), u_t + V u_x - epsilon u_xx - f (AdvDiff, epsilon as currently trained); f None = 0."""
+        return self.h.residual_points(np.asarray(X, dtype=np.float64), f)[:, None]
+
+    def set_validation(self, X=None, u=None, du=None):
+        """Upload the validation set once: points (n, dim), exact values, optionally exact gradients (n, dim).  Without arguments
+        the test grid handed to the constructor.  Multi-GPU: every rank holds and evaluates the whole set (no collective)."""
+        if X is None and u is None:
+            X, u = (getattr(self, a) for a in self._val_default)
+        if X is None or u is None:
+            raise ValueError("set_validation needs points and exact values (or no arguments: the stored test grid)")
+        self._val_has_du = du is not None
+        self.h.set_validation(X, u, du)
+
+    def clear_validation(self):
+        self._val_has_du = False
+        self.h.set_validation(None, None)
+
+    def _val_dict(self, raw):
+        raw = np.asarray(raw, dtype=np.float64)
+        h1 = float(np.sqrt(raw[3] / raw[4])) if getattr(self, "_val_has_du", False) else None
+        return dict(rel_l2=float(np.sqrt(raw[0] / raw[1])), max_abs=float(raw[2]), rel_h1=h1, raw=raw)
+
+    def validate(self):
+        """Error norms on the validation set, reduced on the device: dict(rel_l2, max_abs, rel_h1 (the relative error of the
+        gradient in L2; None without exact gradients), raw = the six sums of hpv_validate)."""
+        return self._val_dict(self.h.validate())
+
+    def train_validated(self, nIter, every):
+        """nIter Adam iterations with the validation error sampled after every `every`-th update, nothing read back in between:
+        (iterations, rel_l2, max_abs) arrays of nIter // every entries, iterations = number of updates applied at the sample.
+        A remainder nIter % every is trained, not validated."""
+        nIter, every = int(nIter), int(every)
+        if every < 1 or nIter < 0:
+            raise ValueError("train_validated needs nIter >= 0 and every >= 1")
+        ns = nIter // every
+        rows = np.empty((ns, 6))
+        done = 0
+        while done < ns or done == 0:
+            c = min(_lib.HIST_CAP, ns - done)
+            last = done + c == ns
+            n = c * every + (nIter - ns * every if last else 0)       # (the remainder rides in the last call)
+            if not self._coll:
+                rows[done:done + c] = self.h.step_validate(n, every)
+            else:
+                self.h.validation_reset()
+                for _ in range(c):
+                    self._step(every, False)
+                    self.h.validate_enqueue()
+                if n > c * every:
+                    self._step(n - c * every, False)
+                rows[done:done + c] = self.h.validation_read(c)
+            done += c
+            if last:
+                break
+        return every * np.arange(1, ns + 1), np.sqrt(rows[:, 0] / rows[:, 1]), rows[:, 2].copy()
+
     @staticmethod
     def _ckpt_path(path):
         path = os.fspath(path)
@@ -633,6 +701,8 @@ class VPINN1D(_VPINNBase):
     """Poisson 1-D hp-VPINN (reference P1:30-224; constructor P1:31-32, call site P1:333-334)."""
 
     _pde, _act = _lib.PDE_POISSON1D, _lib.ACT_SIN   # tf.sin, P1:134
+    _channel_names = ("u", "u_x", "u_xx")
+    _val_default = ("xtest", "utest")
 
     def __init__(self, X_u_train, u_train, X_quad, W_quad, F_exact_total, grid, X_test, u_test, layers,
                  X_f_train=None, f_train=None, *, var_form=None, lossb_weight=None, LR=None, init_params=None,
@@ -841,6 +911,8 @@ class VPINNAdvDiff(_VPINNBase):
 
     _pde, _act = _lib.PDE_ADVDIFF, _lib.ACT_TANH   # tf.tanh, P3:226
     _n_extra = 1                                   # epsilon, init 1.0 (P3:63)
+    _channel_names = ("u", "u_x", "u_t", "u_xx", "u_tt")
+    _val_default = ("XT_test", "utest")
 
     def __init__(self, XT_u_train, u_train, XT_f_train, XT_quad, W_quad, T_quad, WT_quad, grid_x, grid_t,
                  N_testfcn, XT_test, u_test, layers, lb=None, ub=None, *, var_form=None, LR=None, V=None,

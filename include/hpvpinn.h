@@ -199,6 +199,43 @@ int hpv_sync(hpv_handle h);
 /* u at arbitrary points: VPINN.predict (P1:197-199, P2:255-257).  X is [n][dim] row-major. */
 int hpv_predict(hpv_handle h, const double* X, int n, double* u_out);
 
+/* Device-side validation.  What the reference does with a trained network goes through the host and yields u only: VPINN.predict
+ * on the test grid (P1:197-199, P2:255-257), the norm taken in numpy; its pointwise PDE residual is net_f (P2:187-194, P3:247-253).
+ * The entry points below keep that on the device: derivative channels and the strong residual at the caller's own points, the error
+ * norms against an exact solution on a stored validation set, and a device-side history of those norms that is filled BETWEEN training
+ * iterations without a host round trip -- the error-versus-iteration curve of a convergence study at the cost of one forward launch
+ * and one reduction launch per sample.  Both schemes, both backends, every network shape the handle accepts.
+ *
+ * hpv_eval_points: the FULL channel list at n arbitrary points, out = [C][n]: u, u_x, u_xx (C = 3) in 1-D; u, u_x, u_y (u_t), u_xx,
+ *   u_yy (u_tt) (C = 5) in 2-D and for AdvDiff -- net_u / net_du / net_dxu / net_dyu / net_dtu of the classes (P1:140-148, P2:171-185,
+ *   P3:232-245).  One forward launch on a batch the handle owns (re-created only when n changes).  n_out = C * n.
+ * hpv_residual_points: the strong residual at n arbitrary points, in either scheme, with the formulas of hpv_set_collocation
+ *   (-u_xx - f | u_xx + u_yy - f | u_t + V u_x - epsilon u_xx - f); epsilon is read from the device parameters; f NULL = zero. */
+int hpv_eval_points(hpv_handle h, const double* X, int n, double* out, size_t n_out);
+int hpv_residual_points(hpv_handle h, const double* X, const double* f_or_null, int n, double* r_out);
+/* The validation set, uploaded once: points X [n][dim], exact values u [n] and, optionally, exact gradients du [n][dim]; n = 0
+ * clears it.  In a multi-GPU run every rank holds the whole set and evaluates it redundantly (the parameters are identical on all
+ * ranks: no collective).
+ * hpv_validate: one forward launch over the set (value only; value and first derivatives when du was given) and ONE reduction
+ *   launch; out6 = {sum (u^ - u)^2, sum u^2, max |u^ - u|, sum |grad u^ - grad u|^2, sum |grad u|^2, n}, the two gradient sums 0
+ *   without du.  fp64 throughout, a summation order that depends on n alone: the six numbers are bitwise reproducible from run to run
+ *   and from rank to rank.  -3 without parameters or without a validation set. */
+int hpv_set_validation(hpv_handle h, const double* X, const double* u, const double* du_or_null, int n);
+int hpv_validate(hpv_handle h, double* out6);
+/* Device-side history of those six numbers, modelled on hpv_history_*: hpv_validate_enqueue launches the forward and the reduction on
+ * the handle's stream and appends at a device-side index -- no synchronisation, no host read (callers that drive the iterations
+ * themselves put it between them); hpv_validation_read copies the first n entries since the reset, out = [n][6] (the history holds
+ * 4096 entries, later ones are dropped; -3 when fewer than n were enqueued). */
+int hpv_validation_reset(hpv_handle h);
+int hpv_validate_enqueue(hpv_handle h);
+int hpv_validation_read(hpv_handle h, int n, double* out);
+/* n_iters Adam iterations as hpv_step runs them, with a validation enqueued after every `every`-th update and nothing read back
+ * until the end: out = [n_iters / every][6] (n_out doubles available); a remainder n_iters % every is trained, not validated.  The
+ * iterations run in chunks of `every` (graph replays where hpv_step replays them; the validation launches sit between the replays),
+ * so the parameters are bit for bit those of `hpv_step(every)` repeated.  Collective after hpv_rccl_connect / hpv_p2p_connect like
+ * hpv_step, and with its handling of an exchange timeout.  -1: every < 1, n_out too small, more samples than the history holds. */
+int hpv_step_validate(hpv_handle h, int n_iters, int every, double* out, size_t n_out);
+
 /* Checkpoint / resume (the reference never saves weights): the packed state
  * [theta | Adam m | Adam v | beta1^t | beta2^t], 3*num_params+2 doubles; a resumed run continues bit-exactly. */
 int hpv_get_state(hpv_handle h, double* buf, size_t n);
