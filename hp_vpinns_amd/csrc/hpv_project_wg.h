@@ -2,45 +2,8 @@
 // forward+projection kernel in kernels_mfma.hip).
 #pragma once
 #include "hpv_internal.h"
+#include "hpv_lane.h"
 
-// Lane exchanges without an LDS round trip (__shfl_xor compiles to ds_bpermute_b32 pairs, ~100 cycles of latency each in the
-// dependent chain of a reduction): inside a row of 16 lanes DPP moves (one VALU instruction per half), across rows gfx950's
-// permlane swaps (v_permlane16_swap exchanges the odd rows of one register with the even rows of another, v_permlane32_swap
-// the upper half of one with the lower half of the other; with both registers = v the two results add up to v[l] + v[l ^ 16]
-// resp. v[l] + v[l ^ 32] in every lane).
-template <int CTRL>
-__device__ __forceinline__ double pj_dpp(double v) {
-    // (bound_ctrl: a lane whose source lies outside its row reads 0 -- the row shifts rely on it -- and no `old` operand has to
-    //  be zeroed first)
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double pj_xrow16(double v) {
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ double pj_xrow32(double v) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-// sum over every aligned group of SP adjacent lanes (SP a power of two), in every lane of the group; all 64 lanes must be active
-template <int SP>
-__device__ __forceinline__ double pj_group_sum(double v) {
-    static_assert(SP >= 1 && SP <= 64 && (SP & (SP - 1)) == 0, "power of two");
-    if constexpr (SP >= 2) v += pj_dpp<0xB1>(v);     // quad_perm [1,0,3,2]
-    if constexpr (SP >= 4) v += pj_dpp<0x4E>(v);     // quad_perm [2,3,0,1]
-    if constexpr (SP >= 8) v += pj_dpp<0x141>(v);    // row_half_mirror
-    if constexpr (SP >= 16) v += pj_dpp<0x140>(v);   // row_mirror
-    if constexpr (SP >= 32) v = pj_xrow16(v);
-    if constexpr (SP >= 64) v = pj_xrow32(v);
-    return v;
-}
-__device__ __forceinline__ double pj_wave_sum(double v) { return pj_group_sum<64>(v); }
-__device__ __forceinline__ double pj_quad_sum(double v) { return pj_group_sum<4>(v); }
-__device__ __forceinline__ double pj_wave_sum_dpp(double v) { return pj_group_sum<64>(v); }
 // Workgroup barrier for LDS hand-offs that leaves global loads IN FLIGHT: __syncthreads() waits for the whole vector-memory
 // queue (s_waitcnt vmcnt(0)), which puts the round trip of every load requested ahead of it -- the projection tables the
 // whole-iteration kernels request early and park late -- in front of the barrier (cdna_hip_programming.md section 5:
@@ -304,7 +267,7 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
 #pragma unroll 8
                     for (int i = part; i < QX; i += SPX) acc = fma(AXl[t * NTX * AXLD + r * AXLD + i], G[j * LDG + i], acc);
                 }
-                acc = pj_group_sum<SPX>(acc);
+                acc = group_sum<SPX>(acc);
                 if (ok && part == 0) T[o] = acc;
             }
         }
@@ -322,7 +285,7 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
                 double acc = 0.0;
 #pragma unroll 8
                 for (int j = part; j < QY; j += SPY) acc = fma(BYl[t * NTY * QY + k * QY + j], T[j * NTX + r], acc);
-                acc = pj_group_sum<SPY>(acc);
+                acc = group_sum<SPY>(acc);
                 if (ok && part == 0) U[o] = fma(c, acc, U[o]);
             }
         }
@@ -348,7 +311,7 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
         if (k_ < rny && r_ < rnx) R[e * rnr + k_ * rnx + r_] = u;
         sq = fma(u, u, sq);
     }
-    sq = pj_wave_sum(sq);
+    sq = group_sum<64>(sq);
     if ((tid & 63) == 0) red[tid >> 6] = sq;
     __syncthreads();
 #ifdef HPV_PJ_TIMING
@@ -381,7 +344,7 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
 #pragma unroll 4
                     for (int r = part; r < NTX; r += SPS) acc = fma(AXl[t * NTX * AXLD + r * AXLD + i], U[k * NTX + r], acc);
                 }
-                acc = pj_group_sum<SPS>(acc);
+                acc = group_sum<SPS>(acc);
                 if (ok && part == 0) S[t * NTY * QX + o] = acc * sc;
             }
         }
@@ -444,8 +407,8 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
             sl = fma(U[o], edge_dphi[2 * o], sl);
             sr = fma(U[o], edge_dphi[2 * o + 1], sr);
         }
-        sl = pj_wave_sum(sl);
-        sr = pj_wave_sum(sr);
+        sl = group_sum<64>(sl);
+        sr = group_sum<64>(sr);
         __syncthreads();
         if ((tid & 63) == 0) { red[tid >> 6] = sl; red[NWV + (tid >> 6)] = sr; }
         __syncthreads();
@@ -457,7 +420,7 @@ __device__ __forceinline__ void project_element_wg(const ProjArgs& pa, const lon
         }
     }
     if (pd.has_eps) {
-        deps = pj_wave_sum(deps);
+        deps = group_sum<64>(deps);
         __syncthreads();
         if ((tid & 63) == 0) red[2 * NWV + (tid >> 6)] = deps;
         __syncthreads();
@@ -564,7 +527,7 @@ __device__ __forceinline__ void project_element_1d(const ProjArgs& pa, const lon
             double acc = 0.0;
 #pragma unroll
             for (int it = 0; it < KIT; ++it) acc = fma(av[it], gq[it], acc);
-            acc = pj_quad_sum(acc);
+            acc = group_sum<4>(acc);
             const double c = cf[t] * mt[t];
             u = fma(c, fma(byv[t], acc, 0.0), u);
         }
@@ -575,7 +538,7 @@ __device__ __forceinline__ void project_element_1d(const ProjArgs& pa, const lon
             Rg[e * NTX + r] = u;
             sq = u * u;
         }
-        sq = pj_wave_sum_dpp(sq);
+        sq = group_sum<64>(sq);
         if ((tid & 63) == 0) red[tid >> 6] = sq;
     }
     pj_lds_barrier();
@@ -621,7 +584,7 @@ __device__ __forceinline__ void project_element_1d(const ProjArgs& pa, const lon
             double acc = 0.0;
 #pragma unroll
             for (int it = 0; it < KIT; ++it) acc = fma(av[it], uq[it], acc);
-            acc = pj_quad_sum(acc);
+            acc = group_sum<4>(acc);
             double gh = fma(byv[t], acc * sc, 0.0);
             gh *= cf[t];
             const double m = mt[t];
@@ -647,7 +610,7 @@ __device__ __forceinline__ void project_element_1d(const ProjArgs& pa, const lon
     if (threadIdx.x == 0) pa.GBAR[e * 16 + 4] = (double)clock64();
 #endif
     if (has_eps) {
-        deps = pj_wave_sum_dpp(deps);
+        deps = group_sum<64>(deps);
         pj_lds_barrier();
         if ((tid & 63) == 0) red[2 * NWV + (tid >> 6)] = deps;
         pj_lds_barrier();
@@ -736,7 +699,7 @@ __global__ void __launch_bounds__(PJ_RBLOCK) k_project_rows_fwd(ProjArgs pa, dou
                 double acc = 0.0;
 #pragma unroll 8
                 for (int i = part; i < QX; i += SPX) acc = fma(AXl[t * NTX * QX + r * QX + i], G[j * LDG + i], acc);
-                acc = pj_group_sum<SPX>(acc);
+                acc = group_sum<SPX>(acc);
                 if (ok && part == 0) T[o] = acc;
             }
         }
@@ -783,7 +746,7 @@ __global__ void __launch_bounds__(PJ_RBLOCK) k_project_rows_adj(ProjArgs pa, con
         U[o] = u;
         if (c == 0) { pa.R[e * NR + o] = u; sq = fma(u, u, sq); }
     }
-    sq = pj_wave_sum(sq);
+    sq = group_sum<64>(sq);
     if ((tid & 63) == 0) red[tid >> 6] = sq;
     __syncthreads();
     if (tid == 0) { double t = 0.0; for (int w = 0; w < NWV; ++w) t += red[w]; pa.loss_e[blockIdx.x] = c == 0 ? t / (double)NR : 0.0; }
@@ -837,7 +800,7 @@ __global__ void __launch_bounds__(PJ_RBLOCK) k_project_rows_adj(ProjArgs pa, con
         }
     }
     if (pd.has_eps) {
-        deps = pj_wave_sum(deps);
+        deps = group_sum<64>(deps);
         __syncthreads();
         if ((tid & 63) == 0) red[16 + (tid >> 6)] = deps;
         __syncthreads();

@@ -728,7 +728,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 sq = u * u;
             }
             if (wv < 2) {
-                sq = pj_wave_sum_dpp(sq);
+                sq = group_sum<64>(sq);
                 if (lane == 0) lds[M::RED + wv] = sq;
             }
             __syncthreads();
@@ -760,7 +760,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             if constexpr (GEN) {
                 if (pa.pd.has_eps) {      // (kernel-uniform)
                     // (into the head of the x-tables: their last reader was the S step, two barriers back; wave 0's own transpose tiles later)
-                    deps = pj_wave_sum_dpp(deps);
+                    deps = group_sum<64>(deps);
                     if (lane == 0) lds[M::AX + wv] = deps;
                 }
             }
@@ -834,7 +834,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 sq = u * u;
             }
             if (wv < 2) {
-                sq = pj_wave_sum_dpp(sq);
+                sq = group_sum<64>(sq);
                 if (lane == 0) lds[M::RED + wv] = sq;
             }
             pj_lds_barrier();
@@ -892,7 +892,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             if constexpr (GEN) {
                 if (pa.pd.has_eps) {      // (kernel-uniform)
                     // (into the UP array, which this phase no longer uses: the tables are still being read by waves in chain 2)
-                    deps = pj_wave_sum_dpp(deps);
+                    deps = group_sum<64>(deps);
                     if (lane == 0) lds[M::UP + wv] = deps;
                 }
             }
@@ -1681,7 +1681,7 @@ __global__ void __launch_bounds__(SM_BLOCK, 1) k_iter_small(MfmaArgs g) {
             sq = u * u;
         }
         if (wv == 0) {
-            sq = pj_wave_sum_dpp(sq);
+            sq = group_sum<64>(sq);
             if (lane == 0) lds[M::RED] = sq;
         }
         __syncthreads();

@@ -13,6 +13,7 @@
 
 #define WAVE 64
 
+// (not hpv_lane.h's group_sum<64>: a __shfl_down tree associates the 64 values differently and only lane 0 holds the result)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);

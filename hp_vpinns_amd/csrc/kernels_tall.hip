@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
                     const double av = lds[M::AX + (t * NTX + r) * QX + i] * (in ? 1.0 : 0.0);
                     acc = fma(av, lds[M::GB + t * MAXP + (in ? lp : 0)], acc);
                 }
-                acc = pj_group_sum<4>(acc);
+                acc = group_sum<4>(acc);
                 if (ok && part4 == 0) lds[M::UP + oc] = acc;
             }
             __syncthreads();
@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
             sq = u * u;
         }
         if (wv == 0) {
-            sq = pj_wave_sum(sq);
+            sq = group_sum<64>(sq);
             if (lane == 0) pa.loss_e[wg_slot] = part == 0 ? sq / (double)NR : 0.0;
         }
         __syncthreads();
@@ -588,7 +588,7 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
             for (int ch = 0; ch < C; ++ch) lds[M::GB + ch * MAXP + lp] = gb[ch];
         }
         if (pd.has_eps) {
-            deps = pj_wave_sum(deps);
+            deps = group_sum<64>(deps);
             if (lane == 0) lds[M::RED + wv] = deps;
         }
         if (EARLY0 && n_own > 0) {         // tile 0's tangents back from the parking place (before the barrier: the reverse pass reuses the region)

@@ -7,54 +7,21 @@
 //
 // Reproducibility of the reduction (bitwise, run to run and rank to rank): the summation order is a function of n alone.
 //   thread:     its points p = g, g + T, g + 2T, .. in that order (g the global thread index, T = blocks * 256);
-//   wave:       a fixed butterfly -- DPP quad_perm / row_half_mirror / row_mirror inside the 16-lane rows, v_permlane16_swap and
-//               v_permlane32_swap across them (VALU only, the same tree in every lane);
+//   wave:       the fixed butterfly of hpv_lane.h (group_reduce<64>: VALU only, the same tree in every lane, all 64 lanes active);
 //   workgroup:  its four wave results in wave order (thread 0);
 //   grid:       one workgroup below HPV_VAL_BLOCK_POINTS points.  Above, every workgroup stores its five partials, takes a ticket
 //               (integer atomic), and the workgroup that draws the LAST ticket combines the partials in WORKGROUP-INDEX order: lane b
 //               of its first wave loads workgroup b's partial, then the same fixed butterfly.  Which workgroup that is does not enter
 //               the result.  No floating-point atomics anywhere.
 #include "hpv_internal.h"
+#include "hpv_lane.h"
 
 #define VAL_THREADS 256
 #define HPV_VAL_BLOCK_POINTS 2048      // points per workgroup before another one is added (8 per thread)
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double val_dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-// the partner lane's value across the 16-lane rows (l ^ 16, l ^ 32): the swap of a register with itself yields {even rows, odd rows}
-// resp. {lower half, upper half} in both result registers' places, one of which is the lane's own value
-__device__ __forceinline__ void val_swap16(double v, double& a, double& b) {
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ void val_swap32(double v, double& a, double& b) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
-}
-
-struct OpSum { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
 struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
-
-// all 64 lanes active; the result is the same value in every lane
-template <class Op>
-__device__ __forceinline__ double val_wave(double v, Op op) {
-    v = op(v, val_dpp<0xB1>(v));     // quad_perm [1,0,3,2]
-    v = op(v, val_dpp<0x4E>(v));     // quad_perm [2,3,0,1]
-    v = op(v, val_dpp<0x141>(v));    // row_half_mirror
-    v = op(v, val_dpp<0x140>(v));    // row_mirror
-    double a, b;
-    val_swap16(v, a, b); v = op(a, b);
-    val_swap32(v, a, b); v = op(a, b);
-    return v;
-}
 
 __device__ __forceinline__ void val_store(double* p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
@@ -93,7 +60,7 @@ __global__ void __launch_bounds__(VAL_THREADS) k_validate_reduce(ValArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        v[k] = (k == 2) ? val_wave(v[k], OpMax()) : val_wave(v[k], OpSum());
+        v[k] = (k == 2) ? group_reduce<64>(v[k], OpMax()) : group_sum<64>(v[k]);
         if (lane == 0) red[k][w] = v[k];
     }
     __syncthreads();
@@ -119,7 +86,7 @@ __global__ void __launch_bounds__(VAL_THREADS) k_validate_reduce(ValArgs a) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const double pk = lane < nblk ? val_load(a.part + 5 * lane + k) : 0.0;
-            v[k] = (k == 2) ? val_wave(pk, OpMax()) : val_wave(pk, OpSum());
+            v[k] = (k == 2) ? group_reduce<64>(pk, OpMax()) : group_sum<64>(pk);
         }
         if (lane == 0) *a.ticket = 0u;
     }
