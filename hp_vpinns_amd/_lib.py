@@ -37,7 +37,9 @@ EXPORTS = [
     "hpv_rccl_info", "hpv_rccl_time_allreduce", "hpv_grid_plan", "hpv_set_active_tests_2d",
     "hpv_eval_points", "hpv_residual_points", "hpv_set_validation", "hpv_validate", "hpv_validation_reset", "hpv_validate_enqueue",
     "hpv_validation_read", "hpv_step_validate",
+    "hpv_set_element_boxes", "hpv_element_indicators",
 ]
+IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
 
 def rule_advice(device, pde, var_form, n_hidden, max_width, q, ntx, nty, n_elem_shard):
@@ -193,6 +195,8 @@ def load():
     lib.hpv_validate_enqueue.argtypes = [h]
     lib.hpv_validation_read.argtypes = [h, C.c_int, _dp]
     lib.hpv_step_validate.argtypes = [h, C.c_int, C.c_int, _dp, C.c_size_t]
+    lib.hpv_set_element_boxes.argtypes = [h, _dp, C.c_int, C.c_int, C.c_int]
+    lib.hpv_element_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:
@@ -250,6 +254,7 @@ class Handle:
             raise HpvError(f"hpv_create failed ({rc}): {msg.decode() if msg else ''}")
         self.cfg = cfg
         self.layers = layers
+        self.n_owned = None        # elements this handle owns (set_elements / set_element_boxes)
         self._keep = []
 
     def _chk(self, rc):
@@ -295,6 +300,26 @@ class Handle:
         if e_end is None:
             e_end = nex * ney
         self._chk(self.lib.hpv_set_elements(self._h, _p(gx), nex, _p(gy), ney, int(e_begin), int(e_end)))
+        self.n_owned = int(e_end) - int(e_begin)           # (what element_indicators returns rows for)
+
+    def set_element_boxes(self, boxes, e_begin=0, e_end=None):
+        """boxes: (n, 2*dim) rows (x0, x1[, y0, y1]) -- any list of axis-parallel elements (hpv_set_element_boxes); the handle owns
+        the rows [e_begin, e_end)."""
+        b = np.ascontiguousarray(boxes, dtype=np.float64)
+        if b.ndim != 2 or b.shape[1] != 2 * self.layers[0]:
+            raise ValueError(f"boxes must have shape (n, {2 * self.layers[0]}), got {b.shape}")
+        e_end = b.shape[0] if e_end is None else int(e_end)
+        self._chk(self.lib.hpv_set_element_boxes(self._h, _p(b), b.shape[0], int(e_begin), e_end))
+        self.n_owned = e_end - int(e_begin)
+
+    def element_indicators(self, f_quad=None):
+        """(n_owned, 5): loss_e, eta2_e, sumR2_e, topx_e, topy_e of the owned elements at the current parameters
+        (hpv_element_indicators); f_quad: f at the handle's own quadrature points, element-major, or None (zero).  n_owned is what
+        the last set_elements / set_element_boxes gave this handle."""
+        f = None if f_quad is None else _c(f_quad).reshape(-1)
+        out = np.empty((self.n_owned or 0, IND_N))         # (no elements yet: the library refuses the call)
+        self._chk(self.lib.hpv_element_indicators(self._h, _p(f), 0 if f is None else f.size, _p(out), out.size))
+        return out
 
     def set_rhs(self, F):
         F = _c(F)

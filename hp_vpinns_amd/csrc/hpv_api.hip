@@ -665,6 +665,8 @@ void hpv_destroy(hpv_handle h) {
     if (h->d_fcol) (void)hipFree(h->d_fcol);
     if (h->d_col_part) (void)hipFree(h->d_col_part);
     if (h->d_jac) (void)hipFree(h->d_jac);
+    if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
+    { double* ip[] = {h->d_wq, h->d_ind_out, h->d_ind_f, h->d_ind}; for (double* q : ip) if (q) (void)hipFree(q); }
     if (h->mfma_evalp) hpv_mfma_destroy(h->mfma_evalp);
     if (h->mfma_val) hpv_mfma_destroy(h->mfma_val);
     free_batch(h->evalp); free_batch(h->valb);
@@ -706,6 +708,12 @@ int hpv_set_quadrature(hpv_handle h, const double* xi, const double* wx, int qx,
     else { h->yi.assign(1, 0.0); h->wy.assign(1, 1.0); }
     h->qx = qx; h->qy = qy;
     h->pd.qx = qx; h->pd.qy = qy;
+    {   // the raw weights [qx | qy] for hpv_element_indicators (the tables on the device are w * phi)
+        int rc;
+        if ((rc = dalloc(h, &h->d_wq, (size_t)qx + qy))) return rc;
+        if ((rc = upload(h, h->d_wq, h->wx.data(), (size_t)qx))) return rc;
+        if ((rc = upload(h, h->d_wq + qx, h->wy.data(), (size_t)qy))) return rc;
+    }
     h->have_quad = true;
     drop_graph(h);
     h->have_tables = false;  // weighted tables depend on the weights
@@ -755,19 +763,18 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
     return 0;
 }
 
-int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* gridy, int ney, int e_begin, int e_end) {
-    if (!h) return -1;
-    if (!h->have_quad || !h->have_tables) return fail(h, -3, "call hpv_set_quadrature and hpv_set_tables first");
-    if (!gridx || nex < 1) return fail(h, -1, "bad x grid");
-    if (h->dim == 1) { if (ney != 1) return fail(h, -1, "ney must be 1 for the 1-D problem"); }
-    else if (!gridy || ney < 1) return fail(h, -1, "bad y grid");
-    const int ne_tot = nex * ney;
+// The elements of the whole mesh as boxes [ne_tot][2 * dim] = (x0, x1[, y0, y1]) and the owned slice [e_begin, e_end): the affine map of
+// the reference nodes, |J_e| and the per-term coefficients of every pde / var_form.  Both hpv_set_elements (the boxes of a tensor grid,
+// e = ex * ney + ey) and hpv_set_element_boxes (any list) end here; nothing below this function knows a grid.
+static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, int nex, int ney, int e_begin, int e_end) {
     if (e_begin < 0 || e_end > ne_tot || e_begin > e_end) return fail(h, -1, "bad element range [%d,%d) of %d", e_begin, e_end, ne_tot);
     // per-grid inputs given earlier must fit the new grid: checked BEFORE anything of the old grid is replaced
     if (!h->nact_all.empty() && (int)h->nact_all.size() != ne_tot)
         return fail(h, -1, "n_active has %zu entries but the new grid has %d elements (hpv_set_active_tests(NULL) drops them)", h->nact_all.size(), ne_tot);
     if (h->have_F && h->F_all.size() != (size_t)ne_tot * h->ntx * h->nty)
         return fail(h, -1, "F has %zu entries but the new grid needs %zu (hpv_set_rhs(NULL) drops it)", h->F_all.size(), (size_t)ne_tot * h->ntx * h->nty);
+    const int bs = 2 * h->dim;
+    h->ne_tot = ne_tot;
     h->nex = nex; h->ney = ney; h->e_begin = e_begin; h->e_end = e_end;
     const long ne = e_end - e_begin;
     h->n_elem = ne;
@@ -778,11 +785,10 @@ int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* g
     const int nterms = h->pd.nterms;
     std::vector<double> X((size_t)h->dim * N), coef((size_t)nterms * ne), ecoef((size_t)ne), EX((size_t)2 * ne), jac((size_t)ne);
     for (long le = 0; le < ne; ++le) {
-        const int e = e_begin + (int)le;
-        const int ex = e / ney, ey = e % ney;
-        const double gx0 = gridx[ex], gx1 = gridx[ex + 1];
+        const double* box = boxes + (size_t)(e_begin + le) * bs;
+        const double gx0 = box[0], gx1 = box[1];
         double gy0 = 0, gy1 = 0;
-        if (h->dim == 2) { gy0 = gridy[ey]; gy1 = gridy[ey + 1]; }
+        if (h->dim == 2) { gy0 = box[2]; gy1 = box[3]; }
         // affine map of the reference nodes, same expression as P1:69 / P2:75-76 / P3:120-121
         for (int j = 0; j < qy; ++j)
             for (int i = 0; i < qx; ++i) {
@@ -852,6 +858,36 @@ int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* g
     return 0;
 }
 
+int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* gridy, int ney, int e_begin, int e_end) {
+    if (!h) return -1;
+    if (!h->have_quad || !h->have_tables) return fail(h, -3, "call hpv_set_quadrature and hpv_set_tables first");
+    if (!gridx || nex < 1) return fail(h, -1, "bad x grid");
+    if (h->dim == 1) { if (ney != 1) return fail(h, -1, "ney must be 1 for the 1-D problem"); }
+    else if (!gridy || ney < 1) return fail(h, -1, "bad y grid");
+    const int ne_tot = nex * ney, bs = 2 * h->dim;
+    std::vector<double> boxes((size_t)ne_tot * bs);
+    for (int e = 0; e < ne_tot; ++e) {
+        const int ex = e / ney, ey = e % ney;
+        boxes[(size_t)e * bs] = gridx[ex]; boxes[(size_t)e * bs + 1] = gridx[ex + 1];
+        if (h->dim == 2) { boxes[(size_t)e * bs + 2] = gridy[ey]; boxes[(size_t)e * bs + 3] = gridy[ey + 1]; }
+    }
+    return set_elements_from_boxes(h, boxes.data(), ne_tot, nex, ney, e_begin, e_end);
+}
+
+int hpv_set_element_boxes(hpv_handle h, const double* boxes, int n_total, int e_begin, int e_end) {
+    if (!h) return -1;
+    if (!h->have_quad || !h->have_tables) return fail(h, -3, "call hpv_set_quadrature and hpv_set_tables first");
+    if (!boxes || n_total < 1) return fail(h, -1, "bad element boxes");
+    const int bs = 2 * h->dim;
+    for (int e = 0; e < n_total; ++e)
+        for (int c = 0; c < h->dim; ++c) {
+            const double a = boxes[(size_t)e * bs + 2 * c], b = boxes[(size_t)e * bs + 2 * c + 1];
+            if (!std::isfinite(a) || !std::isfinite(b) || !(a < b))
+                return fail(h, -1, "element box %d: [%g, %g] in direction %d is not a finite interval with lower < upper", e, a, b, c);
+        }
+    return set_elements_from_boxes(h, boxes, n_total, n_total, 1, e_begin, e_end);
+}
+
 // the device copies of the per-element counts go; the row-split projection (which ignores counts) is on again where it applies
 static void drop_device_counts(hpv_ctx* h) {
     h->nacty_all.clear();
@@ -877,7 +913,7 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n) {
     for (int i = 0; i < n; ++i)
         if (n_active[i] < 1 || n_active[i] > h->ntx) return fail(h, -1, "n_active[%d] = %d is outside 1..%d", i, n_active[i], h->ntx);
     if (h->have_elems) {
-        if (n != h->nex * h->ney) return fail(h, -1, "n_active has %d entries, expected %d", n, h->nex * h->ney);
+        if (n != h->ne_tot) return fail(h, -1, "n_active has %d entries, expected %d", n, h->ne_tot);
         if (h->d_nact) { (void)hipFree(h->d_nact); h->d_nact = nullptr; }
         h->pd.nact = nullptr;
         if (h->n_elem > 0) {
@@ -912,7 +948,7 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
         if (nay[i] < 1 || nay[i] > h->nty) return fail(h, -1, "nay[%d] = %d is outside 1..%d", i, nay[i], h->nty);
     }
     if (h->have_elems) {
-        if (n != h->nex * h->ney) return fail(h, -1, "nax / nay have %d entries, expected %d", n, h->nex * h->ney);
+        if (n != h->ne_tot) return fail(h, -1, "nax / nay have %d entries, expected %d", n, h->ne_tot);
         if (h->d_nact) { (void)hipFree(h->d_nact); h->d_nact = nullptr; }
         if (h->d_nacty) { (void)hipFree(h->d_nacty); h->d_nacty = nullptr; }
         h->pd.nact = nullptr;
@@ -940,7 +976,7 @@ int hpv_set_rhs(hpv_handle h, const double* F, size_t n) {
     if (!F) { h->have_F = false; h->F_all.clear(); if (h->d_F) { (void)hipFree(h->d_F); h->d_F = nullptr; } return 0; }
     if (h->have_elems) {
         const size_t NR = (size_t)h->ntx * h->nty;
-        if (n != (size_t)h->nex * h->ney * NR) return fail(h, -1, "F has %zu entries, expected %zu", n, (size_t)h->nex * h->ney * NR);
+        if (n != (size_t)h->ne_tot * NR) return fail(h, -1, "F has %zu entries, expected %zu", n, (size_t)h->ne_tot * NR);
         int rc;
         if ((rc = dalloc(h, &h->d_F, (size_t)h->n_elem * NR))) return rc;
         if (h->n_elem > 0 && (rc = upload(h, h->d_F, F + (size_t)h->e_begin * NR, (size_t)h->n_elem * NR))) return rc;
@@ -1597,6 +1633,47 @@ int hpv_eval_channels(hpv_handle h, double* out, size_t n) {
     for (int ch = 0; ch < C; ++ch)     // the device batch may carry padding / data points behind the quadrature points
         HIPCHK(h, hipMemcpyAsync(out + (size_t)ch * h->Nq, src + (size_t)ch * h->var.N, (size_t)h->Nq * sizeof(double),
                                  hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// Per-element refinement indicators at the current parameters (include/hpvpinn.h), all on the handle's stream, one synchronisation:
+//   (1) the forward-only pass of hpv_eval_loss makes d_R current.  enqueue_pass(backward = false) never takes a whole-iteration
+//       kernel (pass_whole_iteration is entered for reverse-mode passes only -- so neither SPLIT mode nor k_iter_tall can run here):
+//       it is always forward -> projection, and every projection kernel (k_project, k_project_tp, k_project_wg, the row-split pair)
+//       stores R of all owned elements before its forward-only return;
+//   (2) one forward-only launch of the full channel set nd_full on the quadrature batch's own X;
+//   (3) one k_elem_indicators launch, one workgroup per owned element;
+//   (4) one copy of n_owned * HPV_IND_N doubles.
+int hpv_element_indicators(hpv_handle h, const double* f_quad, size_t n, double* out, size_t n_out) {
+    if (!h) return -1;
+    if (h->cfg.scheme != HPV_SCHEME_VPINN) return fail(h, -1, "element indicators belong to the variational scheme");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    const long ne = h->n_elem, NQ = (long)h->qx * h->qy;
+    if (f_quad && n != (size_t)(ne * NQ)) return fail(h, -1, "f has %zu entries, expected %ld", n, ne * NQ);
+    if (n_out != (size_t)ne * HPV_IND_N || (ne > 0 && !out)) return fail(h, -1, "indicator buffer has %zu entries, expected %zu", n_out, (size_t)ne * HPV_IND_N);
+    if (ne == 0) return 0;
+    // the cached buffers are sized by three numbers, and all three are the key: d_ind_f by Nq = ne * NQ (NOT by var.N, which pads Nq
+    // to 16 and adds the data points: two rules can share a var.N and differ in Nq), d_ind_out and the MFMA object by var.N, d_ind by ne
+    if (h->ind_Nq != h->Nq || h->ind_N != h->var.N || h->ind_ne != ne) {
+        if (h->mfma_ind) { hpv_mfma_destroy(h->mfma_ind); h->mfma_ind = nullptr; }
+        h->ind_Nq = h->ind_N = h->ind_ne = -1;
+        if ((rc = dalloc(h, &h->d_ind_out, (size_t)h->nd_full.C * h->var.N))) return rc;
+        if ((rc = dalloc(h, &h->d_ind_f, (size_t)(ne * NQ)))) return rc;
+        if ((rc = dalloc(h, &h->d_ind, (size_t)ne * HPV_IND_N))) return rc;
+        if (h->backend == HPV_BACKEND_MFMA) h->mfma_ind = hpv_mfma_create(h->nd_full, h->var.N, nullptr, false);
+        h->ind_Nq = h->Nq; h->ind_N = h->var.N; h->ind_ne = ne;
+    }
+    if (f_quad) HIPCHK(h, hipMemcpyAsync(h->d_ind_f, f_quad, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = enqueue_pass(h, false))) return rc;
+    if (h->mfma_ind) hpv_mfma_forward(h->mfma_ind, h->d_theta, h->var.X, h->d_ind_out, 0, h->stream);
+    else launch_mlp_fwd_generic(h->nd_full, h->d_theta, h->var.X, nullptr, h->d_ind_out, h->var.N, 0, h->stream);
+    const IndArgs a{h->d_ind_out, h->var.N, f_quad ? h->d_ind_f : nullptr, h->has_eps ? h->d_theta + h->P : nullptr, h->cfg.V,
+                    h->d_wq, h->d_wq + h->qx, h->qx, h->qy, h->d_jac, h->d_R, h->ntx, h->nty, h->pd.nact, h->pd.nacty, h->d_ind};
+    launch_elem_indicators(h->cfg.pde, a, ne, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -60,6 +60,7 @@ struct hpv_ctx {
     bool have_quad = false, have_tables = false, have_elems = false, have_params = false;
     // elements
     int nex = 0, ney = 1, e_begin = 0, e_end = 0;
+    int ne_tot = 0;                // elements of the whole mesh: nex * ney of a grid, the rows of a box list (hpv_set_element_boxes)
     long n_elem = 0;
     double *d_coef = nullptr, *d_edge_coef = nullptr, *d_F = nullptr, *d_R = nullptr, *d_loss_e = nullptr,
            *d_deps_e = nullptr;
@@ -110,6 +111,13 @@ struct hpv_ctx {
     int n_col = 0;
     long n_col_total = 0;      // collocation points of ALL shards (the mean of P2:124 runs over them)
     double* d_jac = nullptr;   // |J_e| of the owned elements (RHS assembly, hpv_assemble_rhs)
+    // per-element refinement indicators (hpv_element_indicators): the raw 1-D weights [qx | qy] (uploaded with the quadrature), a
+    // forward-only object of the full channel set on the quadrature batch's own X and its buffers; re-created when Nq (sizes d_ind_f),
+    // the batch size var.N (sizes d_ind_out and the object) or the owned element count (sizes d_ind) changes
+    double* d_wq = nullptr;
+    HpvMfma* mfma_ind = nullptr;
+    double *d_ind_out = nullptr, *d_ind_f = nullptr, *d_ind = nullptr;
+    long ind_Nq = -1, ind_N = -1, ind_ne = -1;
     // device-side validation (hpv_eval_points .. hpv_step_validate): forward-only batches at the caller's points
     NetDesc nd_full{};         // the full channel list: u, every first and every second input derivative (hpv_eval_points)
     NetDesc nd_grad{};         // u and the first derivatives (validation against exact gradients)

@@ -206,3 +206,22 @@ void launch_validate_reduce(const ValArgs& a, int blocks, hipStream_t s);
 // strong residual from the full channel list [u, u_x, (u_y | u_t), u_xx, (u_yy | u_tt)] at n foreign points (formulas: hpv_set_collocation)
 void launch_residual_points(int pde, const double* OUT, long N, const double* f_or_null, const double* eps_ptr, double V, int n,
                             double* r, hipStream_t s);
+
+// ---- per-element refinement indicators (kernels_adapt.hip; hpv_element_indicators) ----
+struct IndArgs {
+    const double* OUT;       // [5 | 3][N] the full channel list at the quadrature batch's points (element-major, q = j * qx + i)
+    long N;
+    const double* f;         // [n_elem * qx * qy] right-hand side at those points, or nullptr (zero)
+    const double* eps_ptr;   // theta + P on the device (AdvDiff only)
+    double V;
+    const double* wx;        // [qx] raw 1-D weights
+    const double* wy;        // [qy] (1-D problems: one entry, 1.0)
+    int qx, qy;
+    const double* jac;       // [n_elem] |J_e|
+    const double* R;         // [n_elem][nty][ntx] residuals of the most recent pass
+    int ntx, nty;
+    const int* nact;         // [n_elem] active counts per direction, or nullptr (all)
+    const int* nacty;
+    double* out;             // [n_elem][HPV_IND_N]
+};
+void launch_elem_indicators(int pde, const IndArgs& a, long n_elem, hipStream_t s);

@@ -15,6 +15,7 @@
 //               the result.  No floating-point atomics anywhere.
 #include "hpv_internal.h"
 #include "hpv_lane.h"
+#include "hpv_residual.h"
 
 #define VAL_THREADS 256
 #define HPV_VAL_BLOCK_POINTS 2048      // points per workgroup before another one is added (8 per thread)
@@ -123,9 +124,7 @@ __global__ void __launch_bounds__(256) k_residual_points(const double* __restric
     const double eps = PDE == HPV_PDE_ADVDIFF ? *eps_ptr : 0.0;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
         const double fp = f ? f[p] : 0.0;
-        if constexpr (PDE == HPV_PDE_POISSON1D) r[p] = -OUT[2 * N + p] - fp;
-        else if constexpr (PDE == HPV_PDE_POISSON2D) r[p] = OUT[3 * N + p] + OUT[4 * N + p] - fp;
-        else r[p] = OUT[2 * N + p] + V * OUT[N + p] - eps * OUT[3 * N + p] - fp;
+        r[p] = strong_residual<PDE>(OUT, N, p, fp, V, eps);      // (hpv_residual.h: shared with k_elem_indicators)
     }
 }
 

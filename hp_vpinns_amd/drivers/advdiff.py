@@ -115,8 +115,9 @@ def export_mat(path, s, u_record, u_records_iterhis, total_record, total_time_tr
 
 def run(LR=0.001, Opt_Niter=1500 + 1, Opt_tresh=2e-11, var_form=0, Net_layer=None, N_el_x=1, N_el_t=1, N_test_x=5,
         N_test_t=5, N_quad=10, N_bound=80, init_params=None, backend="auto", verbose=True, mat_path=None, scheme="VPINNs",
-        validate_every=None):
-    """P3:31-54 hyper-parameters (reference defaults) -> identified epsilon, prediction, L2 error.  scheme 'PINNs' trains on the
+        validate_every=None, adapt_every=None, max_elements=None):
+    """adapt_every=K: local hp-refinement (`train_adaptive`) after every K-th update, at most max_elements elements.
+    P3:31-54 hyper-parameters (reference defaults) -> identified epsilon, prediction, L2 error.  scheme 'PINNs' trains on the
     strong-form residual u_t + V u_x - epsilon u_xx at the NPf collocation points of P3:387-391 instead of the variational one."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P3:46
     s = setup(N_el_x, N_el_t, N_test_x, N_test_t, N_quad, N_bound)
@@ -132,6 +133,14 @@ def run(LR=0.001, Opt_Niter=1500 + 1, Opt_tresh=2e-11, var_form=0, Net_layer=Non
         if verbose:
             for it, l2, mx in zip(*curve):
                 print("It: %d, rel L2 error: %.3e, max error: %.3e" % (it, l2, mx))
+    elif adapt_every:
+        import time
+        t0 = time.time()
+        rounds = model.train_adaptive(Opt_Niter, adapt_every, None, max_elements)      # zero right-hand side (P3:180)
+        total_record, t_train = [], time.time() - t0
+        if verbose:
+            for it, ne, loss in rounds:
+                print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
     else:
         error_record, total_record, u_record, u_his, t_train = model.train(Opt_Niter, Opt_tresh)   # P3:493-494
         if mat_path is not None:                                                # P3:500-508
@@ -159,6 +168,8 @@ if __name__ == "__main__":
     ap.add_argument("--scheme", default="VPINNs", choices=("VPINNs", "PINNs"))
     ap.add_argument("--validate-every", type=int, default=None,
                     help="print the error on the test grid after every K-th update (device-side validation history)")
+    ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
+    ap.add_argument("--max-elements", type=int, default=None, help="never refine beyond this many elements")
     a = ap.parse_args()
     run(Opt_Niter=a.iters, N_el_x=a.elements_x, N_quad=a.quad, var_form=a.var_form, Net_layer=[2] + [a.width] * 3 + [1],
-        mat_path=a.mat, scheme=a.scheme, validate_every=a.validate_every)
+        mat_path=a.mat, scheme=a.scheme, validate_every=a.validate_every, adapt_every=a.adapt_every, max_elements=a.max_elements)

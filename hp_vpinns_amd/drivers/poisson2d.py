@@ -105,8 +105,9 @@ def build_model(s, Net_layer, var_form=1, init_params=None, backend="auto", loss
 
 def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10,
         N_bound=80, N_residual=100, n_iter=10000 + 1, init_params=None, backend="auto", record_every=1, verbose=True,
-        validate_every=None):
-    """P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  validate_every=K trains
+        validate_every=None, adapt_every=None, max_elements=None):
+    """adapt_every=K: local hp-refinement (`train_adaptive`, right-hand side f_ext) after every K-th update, at most max_elements
+    elements.  P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  validate_every=K trains
     through `train_validated` instead of `train`: the error on the test grid after every K-th update, reduced on the device."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P2:280
     s = setup(N_el_x, N_el_y, N_test_x, N_test_y, N_quad, N_bound, N_residual)
@@ -120,6 +121,11 @@ def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_
         if verbose:
             for it, l2, mx in zip(*curve):
                 print("It: %d, rel L2 error: %.3e, max error: %.3e" % (it, l2, mx))
+    elif adapt_every:
+        rounds = model.train_adaptive(n_iter, adapt_every, f_ext, max_elements)
+        if verbose:
+            for it, ne, loss in rounds:
+                print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
     else:
         model.train(n_iter, record_every=record_every)           # P2:434
     u_pred = model.predict()                                     # P2:435
@@ -141,6 +147,9 @@ if __name__ == "__main__":
     ap.add_argument("--record-every", type=int, default=1)
     ap.add_argument("--validate-every", type=int, default=None,
                     help="print the error on the test grid after every K-th update (device-side validation history)")
+    ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
+    ap.add_argument("--max-elements", type=int, default=None, help="never refine beyond this many elements")
     a = ap.parse_args()
     run(n_iter=a.iters, N_el_x=a.elements, N_el_y=a.elements, var_form=a.var_form,
-        Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every, validate_every=a.validate_every)
+        Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every, validate_every=a.validate_every,
+        adapt_every=a.adapt_every, max_elements=a.max_elements)

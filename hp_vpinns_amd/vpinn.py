@@ -30,6 +30,7 @@ import time
 import numpy as np
 
 from . import _lib
+from .adapt import ElementMesh, mark, refine
 from .dist import Reducer, dist_info, shard_range
 from .init import n_params, pad_plan, xavier_init
 from .testfcn import dTest_fcn, tables_1d
@@ -89,6 +90,28 @@ def _device_rule_2d(xi, wx, yi, wy, ntx, nty, n_elem_shard, pde, var_form, hidde
         return xi, wx, yi, wy
     q_dev, _ = _lib.rule_advice(device, pde, var_form, len(hidden), max(hidden), xi.size, ntx, nty, n_elem_shard)
     return _pad_rule(xi, wx, q_dev) + _pad_rule(yi, wy, q_dev)
+
+
+def _device_rule_1d(xi, wq, ntx, n_elem_shard, pde, var_form, hidden, device=0, backend="auto"):
+    """(xi, wq, nt_dev) for the device, 1-D problem: the element-resident 1-D kernel (csrc/kernels_tile.hip) is instantiated for the
+    reference's own rule, 80 points and 60 test functions (P1:237-238), for var_forms 1 / 2 on 20-wide networks of 2-4 hidden layers.
+    Where THAT kernel can run:
+      * fewer test functions (N_testfcn is a free hyper-parameter) ride as a p-refinement with equal counts -- the device gets the
+        first 60 test functions (phi_k does not depend on how many follow), F padded with zeros, the count per element;
+      * a smaller rule is padded with zero-weight points to 80 -- only while the library says the shard is small enough for one
+        workgroup per element to beat the separate launches on the rule as it is (hpv_rule_advice; advisor, round 4: an h-refined
+        grid of 10 k elements x 10 points must NOT run 8x the points and 12x the test functions).
+    Everywhere else (generic backend, var_form 3, wider / deeper networks) the device sees the problem as it is: nt_dev == ntx.
+    One definition for the constructor and for set_mesh."""
+    if backend == "generic":
+        return xi, wq, ntx
+    force = bool(os.environ.get("HPV_FORCE_RULE_PADDING"))     # (measurement knob, scripts/rule1d_sweep.py: the advice for ONE element)
+    q_dev, nt_dev = _lib.rule_advice(device, pde, var_form, len(hidden), max(hidden), xi.size, ntx, 1, 1 if force else n_elem_shard)
+    pad_rule = q_dev > xi.size and (force or not os.environ.get("HPV_NO_RULE_PADDING"))
+    nt = nt_dev if (pad_rule or xi.size == 80) else ntx
+    if pad_rule:
+        xi, wq = _pad_rule(xi, wq, 80)
+    return xi, wq, nt
 
 
 def _caller_globals(depth=2):
@@ -661,6 +684,114 @@ class _VPINNBase:
                 break
         return every * np.arange(1, ns + 1), np.sqrt(rows[:, 0] / rows[:, 1]), rows[:, 2].copy()
 
+    # -- local hp-refinement: element boxes, device-side indicators, refine-and-continue (adapt.py; hpv_set_element_boxes,
+    #    hpv_element_indicators) ---------------------------------------------------------------------------------------------
+    _mesh = None               # the box list handed to set_mesh (None: the constructor's grid)
+    _dev_rule = None           # (xi, yi) of the rule the device holds (yi None in 1-D); set by the populate step
+
+    def _need_vpinns(self, what):
+        if getattr(self, "scheme", "VPINNs") != "VPINNs":
+            raise ValueError(f"{what} belongs to the variational scheme")
+
+    @property
+    def mesh(self):
+        """The elements as an `adapt.ElementMesh` (a copy): what `set_mesh` was given last, else the constructor's grid."""
+        return (self._mesh if self._mesh is not None else self._grid_mesh()).copy()
+
+    def _f_at_quad(self, mesh, f, eb, ee):
+        """f at the DEVICE rule's points of the elements [eb, ee), element-major (q = j * qx + i)."""
+        xi, yi = self._dev_rule
+        P = mesh.quad_points(xi, yi, eb, ee)
+        fq = np.asarray(f(*[P[:, c] for c in range(P.shape[1])]), dtype=np.float64)
+        return np.broadcast_to(fq.reshape(-1) if fq.size > 1 else fq, (P.shape[0],)).copy()
+
+    def _populate_mesh(self, mesh, f):
+        """The populate step on a box list: rule advice for the new shard, tables for the maximal counts, the boxes, F assembled on
+        the device from f at the device rule's points, the active counts.  Data / boundary points are left as they are."""
+        h, n = self.h, len(mesh)
+        eb, ee = shard_range(n, self.rank, self.world)
+        ntx, nty = int(mesh.nax.max()), int(mesh.nay.max())
+        xi, wx, yi, wy, ntx_dev = self._mesh_rule(ee - eb, ntx, nty)
+        if mesh.dim == 1:
+            h.set_active_tests(None)
+        else:
+            h.set_active_tests_2d(None, None)
+        h.set_rhs(None)                                    # (counts and F of the old mesh would be checked against the new one)
+        h.set_quadrature(xi, wx, yi, wy)
+        edge = None
+        if mesh.dim == 1 and self.var_form == 3:
+            edge = np.ascontiguousarray(dTest_fcn(ntx_dev, np.array([-1.0, 1.0]))[0])
+        h.set_tables(tables_1d(ntx_dev, xi), None if mesh.dim == 1 else tables_1d(nty, yi), edge)
+        h.set_element_boxes(mesh.boxes, eb, ee)
+        self._dev_rule = (xi, yi)
+        if f is not None:
+            NR = ntx_dev * nty
+            F = np.zeros((n, NR))                          # (only the owned rows are read: hpv_set_rhs slices [eb, ee))
+            if ee > eb:
+                F[eb:ee] = h.assemble_rhs(self._f_at_quad(mesh, f, eb, ee), (ee - eb) * NR).reshape(ee - eb, NR)
+            h.set_rhs(F.reshape(-1))
+        if mesh.dim == 1:
+            if np.any(mesh.nax != ntx_dev):
+                h.set_active_tests(mesh.nax)
+        elif np.any(mesh.nax != ntx) or np.any(mesh.nay != nty):
+            h.set_active_tests_2d(mesh.nax, mesh.nay)
+
+    def set_mesh(self, mesh, f=None):
+        """Continue on another set of elements: `mesh` an `adapt.ElementMesh` (any list of boxes with per-element counts), `f` a
+        callable f(x) / f(x, y) on flat arrays giving the right-hand side, or None where it is zero (AdvDiff).  Parameters, Adam
+        moments and step counters are untouched -- `h.get_state()` is the same before and after, bit for bit -- and the histories
+        are kept; only the variational term's elements change.  Multi-GPU: every rank calls it with the same mesh and takes
+        its `shard_range(len(mesh), rank, world)`."""
+        self._need_vpinns("set_mesh")
+        if not isinstance(mesh, ElementMesh) or mesh.dim != self.layers[0]:
+            raise ValueError("set_mesh needs an adapt.ElementMesh of the problem's dimension")
+        mesh = mesh.copy()
+        self._populate_mesh(mesh, f)
+        self._mesh = mesh
+
+        def populate():                                    # what a fresh handle would be given: the mesh AND the data points
+            self._populate_mesh(mesh, f)
+            self._hand_data()
+        self._populate = populate
+        self.h.backend_in_use()                            # assembles the device batches; raises if a requested backend is unavailable
+
+    def element_indicators(self, f=None):
+        """(n_owned, 5) refinement indicators of this rank's elements at the current parameters, computed on the device:
+        columns loss_e, eta2_e, sumR2_e, topx_e, topy_e (include/hpvpinn.h, hpv_element_indicators).  `f` as in `set_mesh`."""
+        self._need_vpinns("element_indicators")
+        mesh = self._mesh if self._mesh is not None else self._grid_mesh()
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        fq = None if f is None or ee == eb else self._f_at_quad(mesh, f, eb, ee)
+        return self.h.element_indicators(fq)
+
+    def adapt(self, f=None, **mark_kw):
+        """One round of indicators -> `adapt.mark` -> `adapt.refine` -> `set_mesh`; returns the new mesh.  Keyword arguments go to
+        `mark` (theta, smooth, p_max, max_elements).  Single GPU only: gathering the indicators across ranks is not implemented."""
+        if self.world > 1:
+            raise NotImplementedError("adapt() on several GPUs needs the indicators of all ranks; not implemented")
+        mesh = self.mesh
+        new = refine(mesh, mark(self.element_indicators(f), mesh, **mark_kw), p_max=mark_kw.get("p_max"))
+        self.set_mesh(new, f)
+        return new
+
+    def train_adaptive(self, nIter, adapt_every, f=None, max_elements=None, **mark_kw):
+        """nIter iterations of `train`, with one `adapt` round after every `adapt_every` of them (none after the last chunk).
+        Returns [(iterations done, elements after the round, loss on the new mesh)], one entry per adaptation."""
+        if self.world > 1:
+            raise NotImplementedError("train_adaptive() on several GPUs needs the indicators of all ranks; not implemented")
+        nIter, adapt_every = int(nIter), int(adapt_every)
+        if adapt_every < 1:
+            raise ValueError("adapt_every >= 1")
+        out, it = [], 0
+        while it < nIter:
+            n = min(adapt_every, nIter - it)
+            self._train_n(n)
+            it += n
+            if it < nIter:
+                new = self.adapt(f, max_elements=max_elements, **mark_kw)
+                out.append((it, len(new), float(self.loss()[0])))
+        return out
+
     @staticmethod
     def _ckpt_path(path):
         path = os.fspath(path)
@@ -738,24 +869,13 @@ class VPINN1D(_VPINNBase):
         self._create(layers, var_form, LR, lossb_weight, 1.0, init_params, seed, backend, device,
                      scheme=_lib.SCHEME_PINN if scheme == "PINNs" else _lib.SCHEME_VPINN)
 
-        # The element-resident 1-D kernel (csrc/kernels_tile.hip) is instantiated for the reference's own rule, 80 points and 60 test
-        # functions (P1:237-238), for var_forms 1 / 2 on 20-wide networks of 2-4 hidden layers.  Where THAT kernel can run:
-        #   * fewer test functions (N_testfcn is a free hyper-parameter) ride as a p-refinement with equal counts -- the device gets
-        #     the first 60 test functions (phi_k does not depend on how many follow), F padded with zeros, the count per element;
-        #   * a smaller rule is padded with zero-weight points -- only while the library says the shard is small enough for one
-        #     workgroup per element to beat the separate launches on the rule as it is (hpv_rule_advice; advisor, round 4: an
-        #     h-refined grid of 10 k elements x 10 points must NOT run 8x the points and 12x the test functions).
-        # Everywhere else (generic backend, var_form 3, wider / deeper networks) the device sees the problem as it is.
-        hidden = self.layers[1:-1]
-        pad_rule = False
-        if backend != "generic" and scheme == "VPINNs":
+        # the rule and the table size the device gets: one decision, shared with set_mesh (_device_rule_1d)
+        dev_rule = None
+        if scheme == "VPINNs":
             eb, ee = shard_range(self.Nelement, self.rank, self.world)
-            force = bool(os.environ.get("HPV_FORCE_RULE_PADDING"))     # (measurement knob, scripts/rule1d_sweep.py: the advice for ONE element)
-            q_dev, nt_dev = _lib.rule_advice(self.device, self._pde, var_form, len(hidden), max(hidden), self.xquad.size, self.N_test, 1,
-                                             1 if force else ee - eb)
-            pad_rule = q_dev > self.xquad.size and (force or not os.environ.get("HPV_NO_RULE_PADDING"))
-            if pad_rule or self.xquad.size == 80:
-                self._N_test_dev = nt_dev
+            dev_rule = _device_rule_1d(self.xquad.reshape(-1), self.wquad.reshape(-1), self.N_test, ee - eb, self._pde, var_form,
+                                       self.layers[1:-1], self.device, backend)
+            self._N_test_dev = dev_rule[2]
 
         def populate():
             if scheme == "PINNs":
@@ -763,10 +883,9 @@ class VPINN1D(_VPINNBase):
                 if self.rank == 0:
                     self.h.set_data(self.x, self.u.reshape(-1))
                 return
-            xi, wq = self.xquad.reshape(-1), self.wquad.reshape(-1)
-            if pad_rule:
-                xi, wq = _pad_rule(xi, wq, 80)
+            xi, wq = dev_rule[0], dev_rule[1]
             self.h.set_quadrature(xi, wq)
+            self._dev_rule = (xi, None)
             edge = None
             nt = self._N_test_dev
             if var_form == 3:
@@ -785,8 +904,24 @@ class VPINN1D(_VPINNBase):
             if self.rank == 0:
                 self.h.set_data(self.x, self.u.reshape(-1))
         self._populate = populate
+        self._backend_arg = backend
         populate()
         self._finish()
+
+    def _grid_mesh(self):
+        return ElementMesh.from_grid(self.grid, None, self._n_active)
+
+    def _mesh_rule(self, n_shard, ntx, nty):
+        xi, wq, nt = _device_rule_1d(self.xquad.reshape(-1), self.wquad.reshape(-1), ntx, n_shard, self._pde, self.var_form,
+                                     self.layers[1:-1], self.device, self._backend_arg)
+        return xi, wq, None, None, nt
+
+    def _hand_data(self):
+        if self.rank == 0:
+            self.h.set_data(self.x, self.u.reshape(-1))
+
+    def _train_n(self, n):
+        self.train(n, 0.0)
 
     def predict(self, x):                                   # P1:197-199
         return self._predict(x)
@@ -864,6 +999,7 @@ class VPINN2D(_VPINNBase):
                 xi, wx, yi, wy = _device_rule_2d(xi, wx, yi, wy, self.Ntestx, self.Ntesty, ee - eb, self._pde, var_form, self.layers[1:-1],
                                                  self.device, backend)
                 self.h.set_quadrature(xi, wx, yi, wy)
+                self._dev_rule = (xi, yi)
                 self.h.set_tables(tables_1d(self.Ntestx, xi), tables_1d(self.Ntesty, yi))
                 eb, ee = shard_range(self.Nelementx * self.Nelementy, self.rank, self.world)
                 self.h.set_elements(self.gridx, self.gridy, eb, ee)
@@ -873,8 +1009,24 @@ class VPINN2D(_VPINNBase):
             if self.rank == 0:
                 self.h.set_data(self.X_u_train, self.utrain.reshape(-1))
         self._populate = populate
+        self._backend_arg, self._rule_args = backend, (X_quad, W_quad)
         populate()
         self._finish()
+
+    def _grid_mesh(self):
+        return ElementMesh(ElementMesh.from_grid(self.gridx, self.gridy).boxes, self._nax_e, self._nay_e)
+
+    def _mesh_rule(self, n_shard, ntx, nty):
+        xi, wx, yi, wy = _tensor_rule(*self._rule_args)
+        return _device_rule_2d(xi, wx, yi, wy, ntx, nty, n_shard, self._pde, self.var_form, self.layers[1:-1], self.device,
+                               self._backend_arg) + (ntx,)
+
+    def _hand_data(self):
+        if self.rank == 0:
+            self.h.set_data(self.X_u_train, self.utrain.reshape(-1))
+
+    def _train_n(self, n):
+        self.train(n)
 
     def predict(self, X=None):                              # P2:255-257 (stored test grid)
         return self._predict(self.X_test if X is None else X)
@@ -954,6 +1106,7 @@ class VPINNAdvDiff(_VPINNBase):
             xi, wx, ti, wt = _device_rule_2d(xi, wx, ti, wt, self.Ntestx, self.Ntestt, ee - eb, self._pde, var_form, self.layers[1:-1],
                                              self.device, backend)
             self.h.set_quadrature(xi, wx, ti, wt)
+            self._dev_rule = (xi, ti)
             self.h.set_tables(tables_1d(self.Ntestx, xi), tables_1d(self.Ntestt, ti))
             eb, ee = shard_range(self.Nelementx * self.Nelementt, self.rank, self.world)
             self.h.set_elements(self.grid_x, self.grid_t, eb, ee)
@@ -963,8 +1116,21 @@ class VPINNAdvDiff(_VPINNBase):
             if self.rank == 0:
                 self.h.set_data(self.XT_u_train, self.u.reshape(-1))
         self._populate = populate
+        self._backend_arg, self._rule_args = backend, (XT_quad, W_quad)
         populate()
         self._finish()
+
+    def _grid_mesh(self):
+        return ElementMesh(ElementMesh.from_grid(self.grid_x, self.grid_t).boxes, self._nax_e, self._nat_e)
+
+    _mesh_rule = VPINN2D._mesh_rule
+
+    def _hand_data(self):
+        if self.rank == 0:
+            self.h.set_data(self.XT_u_train, self.u.reshape(-1))
+
+    def _train_n(self, n):
+        self.train(n, 0.0)
 
     @property
     def epsilon(self):

@@ -77,13 +77,24 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
 int hpv_set_elements(hpv_handle h, const double* gridx, int nex, const double* gridy, int ney,
                      int e_begin, int e_end);
 
-/* Right-hand sides F_ext_total for ALL nex*ney elements, C-order [nex][ney][nty][ntx]
- * (P1:294, P2:414); pass NULL for a zero right-hand side (P3:180). */
+/* Elements as an arbitrary list of axis-parallel boxes instead of a tensor grid (local h-refinement): boxes is [n_total][2*dim]
+ * row-major = (x0, x1) in 1-D, (x0, x1, y0, y1) in 2-D / (x0, x1, t0, t1) for AdvDiff; the element index e is the row of `boxes`
+ * and [e_begin, e_end) slices the list as it slices a grid (multi-GPU sharding needs nothing else).  Same preconditions, return
+ * codes and side effects as hpv_set_elements, which is this call on the boxes of e = ex*ney + ey: a box list made from a grid is
+ * bit-identical to the grid.  Every per-element input (hpv_set_rhs, hpv_set_active_tests[_2d]) then counts n_total elements.
+ * Each box is checked for finite bounds and x0 < x1 (y0 < y1).  The list is NOT checked for overlap or for covering the domain:
+ * the test functions vanish on every element's boundary, elements are independent and hanging nodes are harmless, so any list
+ * is a valid set of test spaces -- whether it is the intended one is the caller's business. */
+int hpv_set_element_boxes(hpv_handle h, const double* boxes, int n_total, int e_begin, int e_end);
+
+/* Right-hand sides F_ext_total for ALL elements of the mesh, C-order [n_total][nty][ntx] with n_total = nex*ney of a grid
+ * (e = ex*ney + ey, i.e. [nex][ney][nty][ntx]: P1:294, P2:414) or the rows of a box list; pass NULL for a zero right-hand
+ * side (P3:180). */
 int hpv_set_rhs(hpv_handle h, const double* F, size_t n);
 
 /* p-refinement of the 1-D driver: element e projects onto its first n_active[e] <= ntest test functions only and its loss
  * is the mean over those (P1:66-67: Ntest_element = len(F_ext_total[e]); the driver builds F_ext_total from the per-element
- * list N_testfcn_total, P1:268-281).  n = nex (all elements of the grid); rows of F beyond n_active[e] are ignored and the
+ * list N_testfcn_total, P1:268-281).  n = all elements of the mesh (nex of a grid, n_total of a box list); rows of F beyond n_active[e] are ignored and the
  * residuals returned for them are zero.  NULL restores "all ntest in every element".  1-D only: 2-D handles are refused
  * here and take their counts through hpv_set_active_tests_2d below. */
 int hpv_set_active_tests(hpv_handle h, const int* n_active, int n);
@@ -93,7 +104,8 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n);
  * (P2:72-73, P3:112-113) -- build that element's tables from them (P2:85-88, P3:127-130) and take its reduce_mean over exactly
  * those residuals (P2:118-120).  Only the Poisson-2D DRIVER's np.reshape of F_ext_total (P2:414) asks for equal counts; the
  * AdvDiff right-hand side is zero (P3:180).
- * n = nex*ney: the counts of ALL elements of the grid, indexed by the flattened element e = ex*ney + ey, 1 <= nax[e] <= ntx and
+ * n = nex*ney of a grid, n_total of a box list: the counts of ALL elements of the mesh, indexed by the flattened element
+ * e = ex*ney + ey (the row of the box list), 1 <= nax[e] <= ntx and
  * 1 <= nay[e] <= nty -- one PAIR per element, a superset of the reference's column x row product.  Element e projects onto its
  * first nax[e] x nay[e] test functions (the family is nested: the first rows of a larger table are the smaller table) and its
  * loss is the mean over those nax[e]*nay[e] residuals; rows and columns of F beyond the counts are ignored, the residuals
@@ -256,6 +268,27 @@ int hpv_test_tables(hpv_handle h, int ntest, const double* xi, int q, double* ta
 
 /* Introspection for tests / benchmarks. */
 int hpv_get_residuals(hpv_handle h, double* R, size_t n);   /* R of the owned elements [ne][nty][ntx] */
+
+/* Per-element refinement indicators of the owned elements at the CURRENT parameters; variational scheme only.
+ * out = [n_owned][HPV_IND_N]:
+ *  0 loss_e  = mean over the element's ACTIVE test functions of R^2  (the term the training pass sums into lossv)
+ *  1 eta2_e  = J_e * sum_q w_q r_q^2, r the strong residual of hpv_set_collocation
+ *              (-u_xx - f | u_xx + u_yy - f | u_t + V u_x - eps u_xx - f), eps read from the device parameters
+ *  2 sumR2_e = sum of R^2 over the active block
+ *  3 topx_e  = sum of R^2 over the highest active x index (r == nax_e - 1)
+ *  4 topy_e  = the same for the highest active y / t index (k == nay_e - 1); 0 in 1-D
+ * f_quad: f at the handle's own quadrature points, element-major, q = j*qx + i, n = n_owned*qx*qy (the layout of
+ * hpv_assemble_rhs); NULL = zero right-hand side (n is then ignored).
+ * Launches, all on the handle's stream with one synchronisation at the end: the forward-only pass of hpv_eval_loss (which makes R
+ * current), one forward-only launch of the full channel list on the quadrature batch's own points, one k_elem_indicators launch
+ * (one workgroup per element; fixed summation order, no atomics: the result is bitwise reproducible from call to call), one copy.
+ * The first step needs no special structure: a forward-only pass never runs a whole-iteration kernel (SPLIT mode and k_iter_tall
+ * exist for reverse-mode passes only), it is always forward + projection, and every projection kernel stores R of all owned
+ * elements.  Like hpv_eval_loss it overwrites the loss slots of the packed buffer.  Zero-weight padding points of a padded rule
+ * contribute exactly 0.  Refused (negative status, hpv_last_error; the handle stays usable): the strong-form scheme, a handle
+ * without parameters / elements, wrong n or n_out. */
+#define HPV_IND_N 5
+int hpv_element_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, double* out, size_t n_out);
 int hpv_backend_in_use(hpv_handle h);                       /* HPV_BACKEND_GENERIC or HPV_BACKEND_MFMA */
 /* Launch structure of the most recent reverse-mode pass over the quadrature batch (tests assert that the kernel they mean to
  * exercise is the one that ran): 0 separate forward / projection / reverse launches, 1 forward + projection-fused reverse,
