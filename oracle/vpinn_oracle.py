@@ -12,15 +12,15 @@ the product propagates closed-form Taylor channels forward and a hand-derived ad
 backward in HIP; this file uses autograd (double backward) for every derivative and
 scipy.special for the polynomial tables (as the reference does, Q:16-26,46-61).
 
-Pinning status -- **parity partly UNPINNED**: the reference has no tests, golden vectors or
-known-answer fixtures, and its TF1 graph cannot be executed here (no
-tensorflow wheel, no network).  Pinned: everything numpy in the reference (quadrature,
-test-function tables, grids, F_ext_total, boundary sets) via tests/golden/*.npz generated by
-*running* the reference's own code (tests/golden/make_golden.py).  Unpinned: the TF1 graph
-arithmetic (loss, tf.gradients, AdamOptimizer), restated from the cited lines and the
-documented TF1 Adam rule; anchored by known answers (zero-network loss
+Pinning status: the reference has no tests, golden vectors or known-answer fixtures and TensorFlow cannot
+be installed here.  Pinned by *running* the reference's own code (tests/golden/make_golden.py): everything numpy in it (quadrature,
+test-function tables, grids, F_ext_total, boundary sets -> tests/golden/*.npz), and the bodies of its three VPINN classes, executed
+verbatim on a torch-fp64 stand-in for the `tf` symbols they use (tests/golden/tf1_shim.py -> tests/golden/*_graph.npz: loss triple,
+gradient, six Adam updates with the loss read after each, parameters, prediction).  This file reproduces those numbers within 1e-11
+(tests/test_oracle.py).  Still by documentation: what the TensorFlow ops themselves compute (the stand-in is not TensorFlow; its
+semantics are checked on closed forms).  Further anchors: known answers (zero-network loss
 = sum_e mean(F_e^2) + w*lossb, which reproduces the ~4e2 plateau of the reference's
-`Results/loss.pdf`), by the reference's own exact solutions (substituted for the network they make
+`Results/loss.pdf`), the reference's own exact solutions (substituted for the network they make
 the restated variational residual vanish against the reference-produced F_ext_total: round-off for
 the strong form, quadrature error decreasing under refinement for the weak forms incl. the 1-D
 element-edge terms -- tests/test_oracle.py), finite differences, full-length training runs landing

@@ -1,5 +1,7 @@
 """The CPU oracle itself: known answers, finite differences, TF1 Adam rule, recording semantics.
-(The TF1 graph cannot run here, so these are the anchors of the unpinned part -- see oracle header.)"""
+Its last part holds the oracle against what the reference's own class code computed (tests/golden/*_graph.npz, executed on
+tests/golden/tf1_shim.py -- whose op semantics the shim tests here check on closed forms); the known answers above it are the
+older anchors -- see oracle header."""
 import numpy as np
 import pytest
 import torch
@@ -388,3 +390,190 @@ def test_exact_solution_annihilates_the_advdiff_variational_residual(vf):
         assert coarse < 1e-4 * default and fine < 1e-1 * coarse and fine < 1e-10
     assert fine < 1e-10 * wrong, (fine, wrong)
     assert off5 > 1e4 * fine                                     # the variational loss identifies the coefficient
+
+
+# ---- the reference's own classes, executed: tests/golden/tf1_shim.py and the *_graph.npz fixtures -----------------------------------
+def _shim():
+    import importlib.util
+    import os
+    from cases import GOLD
+    spec = importlib.util.spec_from_file_location("tf1_shim_under_test", os.path.join(GOLD, "tf1_shim.py"))
+    tf = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tf)
+    tf.reset_default_graph()
+    return tf
+
+
+def test_shim_imports_nothing_of_the_repository():
+    import os
+    import re
+    from cases import GOLD
+    src = open(os.path.join(GOLD, "tf1_shim.py")).read()
+    mods = set(re.findall(r"^\s*(?:import|from)\s+([A-Za-z_][\w]*)", src, flags=re.M))
+    assert mods == {"sys", "types", "numpy", "torch"}, mods
+
+
+def test_shim_gradients_to_second_order_on_a_closed_form():
+    """f = sum_i sin(x_i) y_i^2 + x_i^3 y_i with x a placeholder and y a constant: first and second derivatives and the mixed one,
+    each a `gradients` of a `gradients`."""
+    tf = _shim()
+    xv, yv = np.array([[0.3], [-1.1], [0.7]]), np.array([[1.5], [0.4], [-0.8]])
+    x, y = tf.placeholder(tf.float64, shape=[None, 1]), tf.constant(yv)
+    f = tf.sin(x) * tf.square(y) + x * x * x * y
+    fx, fy = tf.gradients(f, x)[0], tf.gradients(f, y)[0]
+    fxx, fxy, fyy = tf.gradients(fx, x)[0], tf.gradients(fx, y)[0], tf.gradients(fy, y)[0]
+    fxxx = tf.gradients(fxx, x)[0]
+    s = tf.Session()
+    got = s.run([fx, fy, fxx, fxy, fyy, fxxx], {x: xv})
+    want = [np.cos(xv) * yv ** 2 + 3 * xv ** 2 * yv, 2 * np.sin(xv) * yv + xv ** 3, -np.sin(xv) * yv ** 2 + 6 * xv * yv,
+            2 * np.cos(xv) * yv + 3 * xv ** 2, 2 * np.sin(xv), -np.cos(xv) * yv ** 2 + 6 * yv]
+    for a, b in zip(got, want):
+        assert a.shape == b.shape and np.abs(a - b).max() < 1e-14
+    # d(sum y)/dx: a broadcast input collects the sum over what it was broadcast to
+    w = tf.constant(np.array([[2.0]]))
+    assert s.run(tf.gradients(w * x, w)[0], {x: xv}).shape == (1, 1)
+    assert abs(s.run(tf.gradients(w * x, w)[0], {x: xv})[0, 0] - xv.sum()) < 1e-15
+    assert tf.gradients(f, tf.constant(1.0)) == [None]
+
+
+def test_shim_shapes_operators_and_reductions():
+    tf = _shim()
+    s = tf.Session()
+    a = tf.constant(np.arange(6.0).reshape(3, 2))
+    assert s.run(tf.reduce_mean(a)) == 2.5 and s.run(tf.reduce_sum(a)) == 15.0 and np.ndim(s.run(tf.reduce_mean(a))) == 0
+    assert s.run(tf.reshape(a, (-1, 1))).shape == (6, 1) and s.run(tf.reshape(a, [1, -1])).shape == (1, 6)
+    assert np.array_equal(s.run(tf.reshape(a, [1, -1]))[0], np.arange(6.0))                # row-major
+    assert s.run(tf.concat([a[:, 0:1], a[:, 1:2], a[:, 0:1]], 1)).shape == (3, 3)
+    assert np.array_equal(s.run(tf.concat([a[:, 0:1]], 1)), np.arange(6.0).reshape(3, 2)[:, 0:1])
+    rows = [[tf.reduce_sum(a) * r + k for r in range(4)] for k in range(3)]            # [k][r], as the classes nest them
+    t = s.run(tf.convert_to_tensor(rows, dtype=tf.float64))
+    assert t.shape == (3, 4) and t[2, 1] == 17.0
+    assert s.run(tf.reshape(tf.stack([tf.reduce_sum(a) * i for i in range(5)]), (-1, 1))).shape == (5, 1)
+    assert tf.constant(0.5, dtype=tf.float64, shape=a.shape).shape == (3, 2) and np.all(s.run(tf.constant(0.5, shape=(3, 2))) == 0.5)
+    # numpy on the left (arrays and scalars), unary minus, tensor minus array
+    n = np.array([[1.0], [2.0], [3.0]])
+    for got, want in [(n * a, n * np.arange(6.0).reshape(3, 2)), (np.float64(2.0) * a, 2 * np.arange(6.0).reshape(3, 2)),
+                      (-a, -np.arange(6.0).reshape(3, 2)), (a - n, np.arange(6.0).reshape(3, 2) - n), (n - a, n - np.arange(6.0).reshape(3, 2)),
+                      (n[:, 0:1] * n * a[:, 0:1] * a, n * n * np.arange(6.0).reshape(3, 2)[:, 0:1] * np.arange(6.0).reshape(3, 2)),
+                      (0 + a / np.float64(4.0), np.arange(6.0).reshape(3, 2) / 4), (1 / (a + 1), 1 / (np.arange(6.0).reshape(3, 2) + 1))]:
+        assert isinstance(got, tf.Tensor) and np.array_equal(s.run(got), want)
+    v = tf.Variable(1 * tf.ones([1], dtype=tf.float64), dtype=tf.float64)
+    assert s.run(v).shape == (1,) and s.run(tf.matmul(a, tf.constant(np.ones((2, 4))))).shape == (3, 4)
+    assert np.all(s.run(tf.Variable(tf.truncated_normal([2, 3], stddev=0.1, dtype=tf.float64), dtype=tf.float64)) == 0.0)
+
+
+def test_shim_adam_is_the_tf1_rule_and_skips_an_unconnected_variable():
+    """Three updates of loss = 3 p^2 + 0.5 q (p, q scalars in two variables) against numbers worked out here from the TF1 rule with
+    epsilon = 1e-1: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), update lr_t m / (sqrt(v) + epsilon) -- epsilon is NOT divided by
+    sqrt(1 - b2^t), which at t = 1 is a factor of 31 on a term of the size of sqrt(v)."""
+    tf = _shim()
+    p, q = tf.Variable(np.array([[2.0]]), dtype=tf.float64), tf.Variable(np.array([-1.0]), dtype=tf.float64)
+    unused = tf.Variable(0.01, dtype=tf.float64)
+    loss = tf.reduce_sum(3.0 * tf.square(p)) + tf.reduce_sum(0.5 * q)
+    opt = tf.train.AdamOptimizer(0.01, epsilon=1e-1)
+    op = opt.minimize(loss)
+    later = tf.Variable(5.0, dtype=tf.float64)          # created after minimize: not the optimizer's
+    s = tf.Session()
+    s.run(tf.global_variables_initializer())
+    p.load(np.array([[1.5]]))                           # set from outside AFTER the initializer
+    assert [id(v) for v in opt.vars] == [id(p), id(q)]
+    lr, b1, b2, eps = 0.01, 0.9, 0.999, 1e-1
+    pv, qv, m, v = 1.5, -1.0, np.zeros(2), np.zeros(2)
+    for t in range(1, 4):
+        g = np.array([6.0 * pv, 0.5])
+        lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        pv, qv = pv - lr_t * m[0] / (np.sqrt(v[0]) + eps), qv - lr_t * m[1] / (np.sqrt(v[1]) + eps)
+        s.run(op)
+        assert abs(s.run(p)[0, 0] - pv) < 1e-15 and abs(s.run(q)[0] - qv) < 1e-15, t
+    # the placement is visible: the other rule (epsilon inside the bias correction) moves q by 0.01 * 0.5 / (0.5 + 0.1) at t = 1
+    assert abs((-1.0 - 0.01 * 0.5 / 0.6) - (-1.0 - 0.01 * np.sqrt(1 - b2) / (1 - b1) * 0.05 / (np.sqrt(0.001 * 0.25) + 0.1))) > 5e-3
+    assert s.run(unused) == 0.01 and s.run(later) == 5.0
+    s.run(tf.global_variables_initializer())            # back to the initial values, the optimizer back to t = 0
+    assert s.run(p)[0, 0] == 2.0
+    s.run(op)
+    assert abs(s.run(p)[0, 0] - (2.0 - lr * np.sqrt(1 - b2) / (1 - b1) * 1.2 / (np.sqrt(0.001 * 144.0) + eps))) < 1e-15
+
+
+def test_graph_fixtures_hold_numbers_only():
+    import os
+    import reference_graph as rg
+    from cases import GOLD
+    biggest = max(os.path.getsize(os.path.join(GOLD, f)) for f in os.listdir(GOLD) if f.endswith(".npz") and not f.endswith("_graph.npz"))
+    for name in rg.FILES:
+        path = os.path.join(GOLD, name + ".npz")
+        assert os.path.getsize(path) <= biggest
+        f = np.load(path, allow_pickle=False)
+        for k in f.files:
+            assert f[k].dtype.kind in "fiu", (name, k, f[k].dtype)
+    for c in rg.CASES:
+        d, _ = rg.load(c)
+        assert set(d) >= {"theta0", "loss3", "grad"} and (not c[3] or d["loss_his"].shape == (rg.K,)), rg.case_id(c)
+        rg.step_mask(d)
+        if c[0] == "advdiff":
+            assert d["theta0"][-1] == 0.9
+
+
+@pytest.mark.parametrize("c", __import__("reference_graph").CASES, ids=__import__("reference_graph").case_id)
+def test_oracle_reproduces_what_the_reference_classes_computed(c):
+    """The oracle's element loop on the fixture's inputs and theta0 against the numbers the reference's own class code produced:
+    loss triple, gradient per parameter block, the K losses read after each update, the parameters after them (through the Adam
+    mask, epsilon on its own) and the prediction -- all within shape_matrix.BLOCK_AGREE, the project's figure for two CPU
+    restatements of one graph."""
+    import reference_graph as rg
+    import shape_matrix as sm
+    d, _ = rg.load(c)
+    _, _, layers, n_extra = rg.setup(c)
+    o = rg.oracle(c)
+    l3, g = o.loss_and_grad()
+    his = theta = pred = None
+    if c[3]:
+        his = []
+        for _ in range(rg.K):                       # the recording order of train(): update, then read the loss
+            o.adam_step()
+            with torch.enable_grad():
+                his.append(float(o.loss_parts()[0].detach()))
+        theta, pred = o.get_params(), o._predict(d["X_pred"])
+    e = rg.gaps(d, layers, n_extra, l3, g, his, theta, pred)
+    print("%s | %s" % (rg.case_id(c), " ".join("%s %s" % (k, v if isinstance(v, str) else "%.2e" % v) for k, v in e.items())))
+    for k, v in e.items():
+        assert isinstance(v, str) or v < sm.BLOCK_AGREE, (rg.case_id(c), k, v, e)
+
+
+def test_oracle_train_methods_record_as_the_reference_did():
+    """the oracle's own train() methods (not only adam_step + loss_parts) against the recorded lists: Poisson-2D appends every
+    iteration; Poisson-1D at it % 10 == 0, so train(1) K times is what the fixture holds"""
+    import reference_graph as rg
+    import shape_matrix as sm
+    c = ("poisson2d", "small", "vf1", True)
+    assert rg.scalar_rel(rg.oracle(c).train(rg.K), rg.load(c)[0]["loss_his"]) < sm.BLOCK_AGREE
+    c = ("poisson1d", "small", "vf3", True)
+    o, rec = rg.oracle(c), []
+    for _ in range(rg.K):
+        o.train(1, 2e-32, rec)
+    assert [r[0] for r in rec] == [0] * rg.K and rg.scalar_rel([r[1] for r in rec], rg.load(c)[0]["loss_his"]) < sm.BLOCK_AGREE
+
+
+def test_graph_fixtures_regenerate_bit_for_bit(tmp_path):
+    """Where the reference is present: make_golden.regenerate_small into a scratch directory, every array of every small fixture and
+    graph fixture equal to the committed one bit for bit."""
+    import importlib.util
+    import os
+    import subprocess
+    import sys
+    from cases import GOLD
+    if not os.path.isdir("/root/reference/main"):
+        pytest.skip("the reference's scripts are not on this machine")
+    # (a child process: make_golden installs stand-in `tensorflow` / `pyDOE` modules and imports the reference's scripts)
+    code = ("import importlib.util, sys; s = importlib.util.spec_from_file_location('mg', %r); m = importlib.util.module_from_spec(s); "
+            "s.loader.exec_module(m); m.regenerate_small(%r)" % (os.path.join(GOLD, "make_golden.py"), str(tmp_path)))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    made = sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz"))
+    assert len([f for f in made if f.endswith("_graph.npz")]) == 4 and len(made) == 8, made
+    for f in made:
+        a, b = np.load(os.path.join(tmp_path, f), allow_pickle=False), np.load(os.path.join(GOLD, f), allow_pickle=False)
+        assert a.files == b.files, f
+        for k in a.files:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (f, k)
