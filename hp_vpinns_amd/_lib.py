@@ -38,6 +38,7 @@ EXPORTS = [
     "hpv_eval_points", "hpv_residual_points", "hpv_set_validation", "hpv_validate", "hpv_validation_reset", "hpv_validate_enqueue",
     "hpv_validation_read", "hpv_step_validate",
     "hpv_set_element_boxes", "hpv_element_indicators",
+    "hpv_set_flux_data", "hpv_read_flux_loss",
 ]
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
@@ -130,6 +131,8 @@ def load():
     lib.hpv_set_elements.argtypes = [h, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int]
     lib.hpv_set_rhs.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_data.argtypes = [h, _dp, _dp, C.c_int]
+    lib.hpv_set_flux_data.argtypes = [h, _dp, _dp, _dp, C.c_int, C.c_double]
+    lib.hpv_read_flux_loss.argtypes = [h, _dp]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
     lib.hpv_num_params.restype = C.c_size_t
@@ -342,6 +345,24 @@ class Handle:
         if u.size != X.shape[0]:
             raise ValueError("one target value per data point")
         self._chk(self.lib.hpv_set_data(self._h, _p(X), _p(u), X.shape[0]))
+
+    def set_flux_data(self, X, coef, g, weight=1.0):
+        """The flux term (hpv_set_flux_data): points (n, dim), coefficients (n, 1 + dim) = (a, b_0 .. b_{dim-1}), targets (n,) and
+        the weight w_f.  X None removes the term."""
+        if X is None:
+            self._chk(self.lib.hpv_set_flux_data(self._h, None, None, None, 0, 0.0))
+            return
+        d = self.layers[0]
+        X, coef, g = _points(X, d, "flux points"), np.ascontiguousarray(coef, dtype=np.float64), _c(g).reshape(-1)
+        if coef.shape != (X.shape[0], 1 + d) or g.size != X.shape[0]:
+            raise ValueError(f"flux data needs coefficients of shape (n, {1 + d}) and one target per point")
+        self._chk(self.lib.hpv_set_flux_data(self._h, _p(X), _p(coef), _p(g), X.shape[0], float(weight)))
+
+    def read_flux_loss(self):
+        """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""
+        out = np.empty(2)
+        self._chk(self.lib.hpv_read_flux_loss(self._h, _p(out)))
+        return float(out[0]), float(out[1])
 
     # ---- parameters ---------------------------------------------------------------------
     def num_params(self):

@@ -224,6 +224,21 @@ int ensure_small_mfma(hpv_ctx* h, Batch& b, HpvMfma** m) {
     return 0;
 }
 
+// ---- the flux term of a pass: forward over its batch, k_flux_loss, reverse (same sequence in both schemes) ----
+int ensure_flux_mfma(hpv_ctx* h) { return h->n_flux > 0 ? ensure_small_mfma(h, h->flux, &h->mfma_flux) : 0; }
+void pass_flux(hpv_ctx* h, bool backward) {
+    if (h->n_flux <= 0) return;
+    run_fwd(h, h->flux, h->mfma_flux, backward ? 1 : 0);
+    launch_flux_loss(h->flux.OUT, h->flux.N, h->dim, h->d_flux_coef, h->d_flux_g, backward ? h->flux.GBAR : nullptr,
+                     2.0 * h->w_flux / (double)h->n_flux, h->d_flux_part, h->n_flux, h->stream);
+    if (backward) run_bwd(h, h->flux, h->mfma_flux);
+}
+FluxFin flux_fin(hpv_ctx* h, bool backward) {
+    if (h->n_flux <= 0) return FluxFin{};
+    return FluxFin{backward ? h->flux.GPART : nullptr, h->flux.rows, h->d_flux_part, flux_loss_parts(h->n_flux), h->w_flux, h->n_flux,
+                   h->d_flux_part + 64};
+}
+
 AdamArgs adam_args(hpv_ctx* h) {
     return AdamArgs{h->d_theta, h->d_m, h->d_v, h->d_state, h->cfg.lr, h->cfg.beta1, h->cfg.beta2, h->cfg.eps,
                     h->d_hist, h->d_hist_idx, HPV_HIST_CAP, h->d_xerr, h->d_nupd};
@@ -278,7 +293,8 @@ static bool pass_whole_iteration(hpv_ctx* h, const MfmaPass& p, bool fuse_adam, 
     if (structure < 0) {
         MfmaFinalize fin{adam_args(h), h->d_RB, h->cfg.lossb_weight, h->n_data, (h->n_data + 15) / 16, h->has_eps, adam_state_doubles(h->P) / 2};
         if (!fuse_adam) fin.ad.theta = nullptr;
-        if (hpv_mfma_iter_tile(m, p, h->merged ? &fin : nullptr, &pl.fin_done)) structure = 4;
+        // (flux data: its launches follow this one, and their rows must reach the finalize step -- no in-kernel finalize)
+        if (hpv_mfma_iter_tile(m, p, h->merged && h->n_flux == 0 ? &fin : nullptr, &pl.fin_done)) structure = 4;
     }
     if (structure < 0 && hpv_mfma_iter_elem(m, p)) structure = 6;
     if (structure < 0) {
@@ -353,11 +369,12 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
     if (rc) { apply_pend(); return rc; }
     const bool use_mfma = h->mfma && h->backend == HPV_BACKEND_MFMA;
     // the deferred update can only ride in a whole-iteration kernel that is the ONLY reader of the parameters in this pass (boundary
-    // points merged into it, no edge batch); otherwise it is applied here, before anything of this pass is launched or forked
-    if (!(use_mfma && h->var.N > 0 && (h->merged || h->n_data == 0) && !h->pd.edge && !hpv_mfma_prefers_elem(h->mfma))) apply_pend();
+    // points merged into it, no edge batch, no flux batch); otherwise it is applied here, before anything of this pass is launched or forked
+    if (!(use_mfma && h->var.N > 0 && (h->merged || h->n_data == 0) && !h->pd.edge && h->n_flux == 0 && !hpv_mfma_prefers_elem(h->mfma))) apply_pend();
     if (!h->side_active) {  // allocations are not allowed inside a stream capture
         if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) { apply_pend(); return rc; }
         if (h->pd.edge && (rc = ensure_small_mfma(h, h->edge, &h->mfma_edge))) { apply_pend(); return rc; }
+        if ((rc = ensure_flux_mfma(h))) { apply_pend(); return rc; }
     }
     hipStream_t smain = h->stream;
     const bool fork = h->side_active && !h->merged && h->n_data > 0;
@@ -386,6 +403,7 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
         if (backward) run_bwd(h, h->data, h->mfma_data);
         h->stream = smain;
     }
+    pass_flux(h, backward);      // on the main stream, behind the variational term
     if (fork) {
         (void)hipEventRecord(h->ev_join, h->stream2);
         (void)hipStreamWaitEvent(smain, h->ev_join, 0);
@@ -397,7 +415,7 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = 
                         backward && h->pd.edge && h->edge.N > 0 ? h->edge.GPART : nullptr, h->edge.rows, h->d_loss_e,
                         pl.n_loss, h->d_deps_e, h->d_data_part, ndp, h->cfg.lossb_weight, h->n_data, h->P, h->has_eps, h->d_RB,
                         backward ? 1 : 0, (backward && (fuse_adam || pl.pend_taken)) ? &ad : nullptr, h->stream, h->d_xerr,
-                        pl.xch_used ? hpv_mfma_xiter(h->mfma) : nullptr, pl.pend_taken ? 1 : 0);
+                        pl.xch_used ? hpv_mfma_xiter(h->mfma) : nullptr, pl.pend_taken ? 1 : 0, flux_fin(h, backward));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, -2, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
@@ -430,6 +448,7 @@ int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
             } else if (h->cfg.backend == HPV_BACKEND_MFMA) return fail(h, -4, "MFMA backend not available: %s", why.c_str());
         }
         if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) return rc;
+        if ((rc = ensure_flux_mfma(h))) return rc;
     }
     run_fwd(h, h->colloc, h->mfma_colloc, backward ? 1 : 0);
     const int nparts = pinn_residual_parts(h->n_col);
@@ -451,11 +470,12 @@ int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
                          -2.0 * h->cfg.lossb_weight / (double)h->n_data, h->d_data_part, h->n_data, h->stream);
         if (backward) run_bwd(h, h->data, h->mfma_data);
     }
+    pass_flux(h, backward);
     const AdamArgs ad = adam_args(h);
     launch_finalize(backward ? h->colloc.GPART : nullptr, h->colloc.rows, backward && h->n_data > 0 ? h->data.GPART : nullptr,
                     h->data.rows, nullptr, 0, h->d_col_part, nparts, h->has_eps ? h->d_col_part + 64 : nullptr, h->d_data_part, ndp,
                     h->cfg.lossb_weight, h->n_data, h->P, h->has_eps, h->d_RB, backward ? 1 : 0, (backward && fuse_adam) ? &ad : nullptr,
-                    h->stream);
+                    h->stream, nullptr, nullptr, 0, flux_fin(h, backward));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, -2, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
@@ -509,6 +529,7 @@ int build_step_graph(hpv_ctx* h, int iters, hipGraphExec_t* out) {
     // one direct pass first: lazily created objects (small-batch MFMA stores) must exist before capture
     if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) return rc;
     if (h->pd.edge && (rc = ensure_small_mfma(h, h->edge, &h->mfma_edge))) return rc;
+    if ((rc = ensure_flux_mfma(h))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -656,6 +677,9 @@ void hpv_destroy(hpv_handle h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->mfma) hpv_mfma_destroy(h->mfma);
     if (h->mfma_data) hpv_mfma_destroy(h->mfma_data);
+    if (h->mfma_flux) hpv_mfma_destroy(h->mfma_flux);
+    free_batch(h->flux);
+    { double* fp[] = {h->d_flux_coef, h->d_flux_g, h->d_flux_part}; for (double* q : fp) if (q) (void)hipFree(q); }
     if (h->mfma_edge) hpv_mfma_destroy(h->mfma_edge);
     if (h->mfma_pred) hpv_mfma_destroy(h->mfma_pred);
     if (h->mfma_eval) hpv_mfma_destroy(h->mfma_eval);
@@ -996,6 +1020,47 @@ int hpv_set_data(hpv_handle h, const double* X, const double* u, int n) {
     h->batch_dirty = true;
     if ((rc = dalloc(h, &h->d_udata, (size_t)n))) return rc;
     if (n > 0 && (rc = upload(h, h->d_udata, u, (size_t)n))) return rc;
+    return 0;
+}
+
+int hpv_set_flux_data(hpv_handle h, const double* X, const double* coef, const double* g, int n, double weight) {
+    if (!h) return -1;
+    if (n < 0 || (n > 0 && (!X || !coef || !g)) || !std::isfinite(weight)) return fail(h, -1, "bad flux data arguments");
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old set)
+    drop_graph(h);
+    h->n_flux = 0;
+    if (h->mfma_flux) { hpv_mfma_destroy(h->mfma_flux); h->mfma_flux = nullptr; }
+    const int d = h->dim;
+    const long N = ((long)n + 15) / 16 * 16;      // whole 16-point tiles; the padding sits at the origin and carries zero adjoints
+    if ((rc = alloc_batch(h, h->flux, h->nd_grad, N, true))) return rc;
+    if ((rc = dalloc(h, &h->d_flux_coef, (size_t)(1 + d) * n))) return rc;
+    if ((rc = dalloc(h, &h->d_flux_g, (size_t)n))) return rc;
+    if (n == 0) return 0;
+    if (!h->d_flux_part) {
+        if ((rc = dalloc(h, &h->d_flux_part, (size_t)65))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_flux_part, 0, 65 * sizeof(double), h->stream));
+    }
+    std::vector<double> t((size_t)d * N, 0.0), c((size_t)(1 + d) * n);      // [n][d] -> [d][N], [n][1 + d] -> [1 + d][n]
+    for (int p = 0; p < n; ++p) {
+        for (int k = 0; k < d; ++k) t[(size_t)k * N + p] = X[(size_t)p * d + k];
+        for (int k = 0; k <= d; ++k) c[(size_t)k * n + p] = coef[(size_t)p * (1 + d) + k];
+    }
+    if ((rc = upload(h, h->flux.X, t.data(), t.size()))) return rc;
+    if ((rc = upload(h, h->d_flux_coef, c.data(), c.size()))) return rc;
+    if ((rc = upload(h, h->d_flux_g, g, (size_t)n))) return rc;
+    h->w_flux = weight;
+    h->n_flux = n;
+    return 0;
+}
+
+int hpv_read_flux_loss(hpv_handle h, double* out2) {
+    if (!h || !out2) return -1;
+    double msf = 0.0;
+    if (h->n_flux > 0) HIPCHK(h, hipMemcpyAsync(&msf, h->d_flux_part + 64, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out2[0] = h->w_flux * msf;
+    out2[1] = msf;
     return 0;
 }
 

@@ -81,6 +81,14 @@ struct hpv_ctx {
     double* d_udata = nullptr;
     double* d_data_part = nullptr;
     int n_data = 0;
+    // flux term (hpv_set_flux_data): lossf = w_f * mean((a u + b . grad u - g)^2) at points of its own -- a batch under nd_grad
+    // (N = n_flux rounded up to a 16-point tile), k_flux_loss between its forward and its reverse launch
+    Batch flux;
+    HpvMfma* mfma_flux = nullptr;
+    int n_flux = 0;
+    double w_flux = 0.0;
+    double *d_flux_coef = nullptr, *d_flux_g = nullptr;   // [1 + dim][n_flux] rows a, b_0 ..; [n_flux]
+    double* d_flux_part = nullptr;                        // [64] partial sums of r^2, then [1] the plain mean of the most recent pass
     // parameters / optimizer
     double *d_theta = nullptr, *d_m = nullptr, *d_v = nullptr, *d_state = nullptr, *d_RB = nullptr;
     double* d_hist = nullptr;   // [HPV_HIST_CAP][4] loss / epsilon history (AdamArgs)

@@ -152,11 +152,24 @@ int mlp_bwd_generic_rows(long N);
 void launch_project(const ProjArgs& pa, long n_elem, hipStream_t s);
 void launch_data_loss(const double* U, const double* Ud, double* GBAR, double scale_grad, double* part, int n,
                       hipStream_t s);
+// the flux term of a pass (k_flux_loss) as the finalize step sees it; all-zero: the handle has no flux data
+struct FluxFin {
+    const double* GPART;     // [rows][P] gradient rows of the flux batch's reverse pass (nullptr: forward-only pass)
+    int rows;
+    const double* part;      // [n_part] partial sums of r^2 (nullptr: no flux term)
+    int n_part;
+    double w;                // w_f
+    int n;                   // n_f
+    double* ms;              // the plain mean of r^2 (hpv_read_flux_loss)
+};
+int flux_loss_parts(int n);
+void launch_flux_loss(const double* OUT, long N, int dim, const double* coef, const double* g, double* GBAR,
+                      double scale_grad, double* part, int n, hipStream_t s);
 void launch_finalize(const double* GPART_v, int rows_v, const double* GPART_b, int rows_b, const double* GPART_e,
                      int rows_e, const double* loss_e, long n_elem, const double* deps_e, const double* data_part,
                      int n_data_part, double lossb_weight, int n_data, int P, int has_eps, double* RB, int write_grad,
                      const AdamArgs* fused_adam, hipStream_t s, const int* xerr = nullptr, unsigned int* xiter_bump = nullptr,
-                     int pending_adam = 0);
+                     int pending_adam = 0, const FluxFin& fx = FluxFin{});
 void launch_adam(const AdamArgs& ad, const double* RB, int P, int Ptot, hipStream_t s);
 void launch_p2p_exchange(const P2PArgs& pp, double* RB, const AdamArgs* adam_or_null, int P, int Ptot, hipStream_t s);
 int adam_state_doubles(int P);

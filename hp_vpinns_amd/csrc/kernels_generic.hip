@@ -469,6 +469,50 @@ void launch_data_loss(const double* U, const double* Ud, double* GBAR, double sc
 }
 
 // ------------------------------------------------------------------------------------------------
+// Flux term (Neumann / Robin conditions, derivative observations): lossf = w_f * mean(r^2),
+//   r_p = a_p u(X_p) + b_p . grad u(X_p) - g_p,   OUT = [1 + dim][N] channels u, u_x, (u_y | u_t) of the flux batch (nd_grad),
+//   coef = [1 + dim][n] rows a, b_0 .. b_{dim-1}.
+// GBAR[c][p] = d lossf / d OUT[c][p] = scale_grad * r_p * (a_p | b_p[c]), scale_grad = 2 w_f / n (the sign k_data_loss passes:
+// -2w/n (u_d - u)); the padded points n <= p < N of the batch get 0 in every channel.  The order of the sums depends on n alone:
+// thread-strided in index order, block_sum, the partials summed by k_finalize in index order -- no atomics.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_flux_loss(const double* __restrict__ OUT, long N, int dim,
+                                                  const double* __restrict__ coef, const double* __restrict__ g,
+                                                  double* __restrict__ GBAR, double scale_grad,
+                                                  double* __restrict__ part, int n) {
+    __shared__ double red[16];
+    double sq = 0.0;
+    const int stride = gridDim.x * blockDim.x;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        const double a = coef[p];
+        double r = a * OUT[p] - g[p];
+        for (int c = 0; c < dim; ++c) r += coef[(long)(1 + c) * n + p] * OUT[(long)(1 + c) * N + p];
+        sq += r * r;
+        if (GBAR) {
+            const double sr = scale_grad * r;
+            GBAR[p] = sr * a;
+            for (int c = 0; c < dim; ++c) GBAR[(long)(1 + c) * N + p] = sr * coef[(long)(1 + c) * n + p];
+        }
+    }
+    if (GBAR)      // the tail of the last 16-point tile (at most 15 points: the first threads of block 0)
+        for (long p = (long)n + blockIdx.x * blockDim.x + threadIdx.x; p < N; p += stride)
+            for (int c = 0; c <= dim; ++c) GBAR[(long)c * N + p] = 0.0;
+    sq = block_sum(sq, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = sq;
+}
+
+int flux_loss_parts(int n) {
+    int blocks = (n + 255) / 256;
+    return blocks > 64 ? 64 : blocks;
+}
+
+void launch_flux_loss(const double* OUT, long N, int dim, const double* coef, const double* g, double* GBAR,
+                      double scale_grad, double* part, int n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_flux_loss, dim3(flux_loss_parts(n)), dim3(256), 0, s, OUT, N, dim, coef, g, GBAR, scale_grad, part, n);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Finalize: fixed-order sums of all partials into the packed reduce buffer
 //   RB = [grad (P) | (d eps) | lossv | w*lossb | mean-square of the data term | pad]
 // ------------------------------------------------------------------------------------------------
@@ -499,7 +543,10 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
                                                          const double* __restrict__ data_part, int n_data_part,
                                                          double lossb_weight, int n_data, int P, int has_eps,
                                                          double* RB, int write_grad, AdamArgs ad,
-                                                         const int* __restrict__ xerr, unsigned int* __restrict__ xiter_bump, int pend) {
+                                                         const int* __restrict__ xerr, unsigned int* __restrict__ xiter_bump, int pend,
+                                                         FluxFin fx) {
+    // fx (the flux term, k_flux_loss): a fourth gradient source and a fourth partial array; both pointers are nullptr on a handle
+    // without flux data, and every branch on them is uniform and not taken
     // pend (the multi-GPU iteration in two launches, round 5): `ad` is the update of the PREVIOUS iteration -- its all-reduced
     // gradient is still in RB, the iteration kernel in front of this launch has already computed with the updated parameters
     // (k_iter_fused prologue, same arithmetic: hpv_adam_one) -- applied here, before RB takes this iteration's partial sums.  The
@@ -546,6 +593,7 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
             }
             if (GPART_b) for (int r = part; r < rows_b; r += FIN_PARTS) acc += GPART_b[(long)r * P + idx];
             if (GPART_e) for (int r = part; r < rows_e; r += FIN_PARTS) acc += GPART_e[(long)r * P + idx];
+            if (fx.GPART) for (int r = part; r < fx.rows; r += FIN_PARTS) acc += fx.GPART[(long)r * P + idx];
         }
         red[part * FIN_COLS + c] = acc;
         __syncthreads();
@@ -600,8 +648,19 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
     lv = block_sum(lv, red);
     de = block_sum(de, red);
     sq = block_sum(sq, red);
+    double sf = 0.0;
+    if (fx.part) {
+        for (int i = threadIdx.x; i < fx.n_part; i += blockDim.x) sf += fx.part[i];
+        sf = block_sum(sf, red);
+    }
     if (threadIdx.x == 0) {
         const double msq = n_data > 0 ? sq / (double)n_data : 0.0;
+        double lb = lossb_weight * msq;      // the history's second column and RB[Ptot + 1]: w * lossb (+ lossf)
+        if (fx.part) {
+            const double msf = sf / (double)fx.n;
+            lb += fx.w * msf;
+            *fx.ms = msf;
+        }
         const double eps_now = (has_eps && ad.theta) ? eps_th : 0.0;   // the coefficient this forward pass used
         if (has_eps && write_grad) {
             RB[P] = de;
@@ -622,13 +681,13 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
                 if (i >= 0 && i < ad.hist_cap) {   // the index saturates at hist_cap (it never wraps)
                     if (pend) { ad.hist[4 * i] = old4[1]; ad.hist[4 * i + 1] = old4[2]; ad.hist[4 * i + 2] = old4[3]; ad.hist[4 * i + 3] = eps_now; }
                     else
-                    ad.hist[4 * i] = lv, ad.hist[4 * i + 1] = lossb_weight * msq, ad.hist[4 * i + 2] = msq, ad.hist[4 * i + 3] = eps_now;
+                    ad.hist[4 * i] = lv, ad.hist[4 * i + 1] = lb, ad.hist[4 * i + 2] = msq, ad.hist[4 * i + 3] = eps_now;
                     *ad.hist_idx = i + 1;
                 }
             }
         }
         RB[Ptot + 0] = lv;
-        RB[Ptot + 1] = lossb_weight * msq;
+        RB[Ptot + 1] = lb;
         RB[Ptot + 2] = msq;
         RB[Ptot + 3] = failed_now ? 1.0 : 0.0;   // pad slot: the all-reduce carries a failure on any rank to every rank (k_adam)
         // launch counter of the shared-element kernels' tagged exchange (hpv_fused_dev.h): advanced HERE, behind the launch that used
@@ -640,19 +699,20 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
 void launch_finalize(const double* GPART_v, int rows_v, const double* GPART_b, int rows_b, const double* GPART_e,
                      int rows_e, const double* loss_e, long n_elem, const double* deps_e, const double* data_part,
                      int n_data_part, double lossb_weight, int n_data, int P, int has_eps, double* RB, int write_grad,
-                     const AdamArgs* fused_adam, hipStream_t s, const int* xerr, unsigned int* xiter_bump, int pending_adam) {
+                     const AdamArgs* fused_adam, hipStream_t s, const int* xerr, unsigned int* xiter_bump, int pending_adam,
+                     const FluxFin& fx) {
     int gblocks = (P + FIN_COLS - 1) / FIN_COLS;
     AdamArgs ad{};
     if (fused_adam && write_grad) ad = *fused_adam;
-    const int rows = (GPART_v ? rows_v : 0) + (GPART_b ? rows_b : 0) + (GPART_e ? rows_e : 0);
+    const int rows = (GPART_v ? rows_v : 0) + (GPART_b ? rows_b : 0) + (GPART_e ? rows_e : 0) + (fx.GPART ? fx.rows : 0);
     if (rows <= 1024 && n_elem <= 4096)
         hipLaunchKernelGGL(k_finalize<256>, dim3(gblocks + 1), dim3(256), 0, s, GPART_v, rows_v, GPART_b, rows_b, GPART_e,
                            rows_e, loss_e, n_elem, deps_e, data_part, n_data_part, lossb_weight, n_data, P, has_eps, RB,
-                           write_grad, ad, xerr, xiter_bump, pending_adam);
+                           write_grad, ad, xerr, xiter_bump, pending_adam, fx);
     else
         hipLaunchKernelGGL(k_finalize<1024>, dim3(gblocks + 1), dim3(1024), 0, s, GPART_v, rows_v, GPART_b, rows_b, GPART_e,
                            rows_e, loss_e, n_elem, deps_e, data_part, n_data_part, lossb_weight, n_data, P, has_eps, RB,
-                           write_grad, ad, xerr, xiter_bump, pending_adam);
+                           write_grad, ad, xerr, xiter_bump, pending_adam, fx);
 }
 int adam_state_doubles(int P) { return 2 * ((P + FIN_COLS - 1) / FIN_COLS + 1); }
 

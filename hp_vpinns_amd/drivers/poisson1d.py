@@ -25,6 +25,11 @@ def f_ext(x):                                                    # P1:252-254
     return -amp * gtemp
 
 
+def du_ext(x):
+    """u_ext': what a Neumann end prescribes"""
+    return amp * (0.1 * omega * np.cos(omega * x) + r1 / np.cosh(r1 * x) ** 2)
+
+
 def setup(N_Element=1, N_testfcn=60, N_Quad=80, N_F=500, seed=1234, N_testfcn_total=None):
     """N_testfcn_total: per-element number of test functions (the list the reference builds at P1:268 / 273 and a user
     edits for p-refinement); F_ext_total / U_ext_total are then lists of columns of different lengths."""
@@ -64,17 +69,22 @@ def setup(N_Element=1, N_testfcn=60, N_Quad=80, N_F=500, seed=1234, N_testfcn_to
 
 
 def run(LR=0.001, Opt_Niter=1000 + 1, Opt_tresh=2e-32, var_form=1, N_Element=1, Net_layer=None, N_testfcn=60,
-        N_Quad=80, N_F=500, lossb_weight=1, init_params=None, backend="auto", verbose=True, scheme="VPINNs"):
-    """P1:231-240 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  scheme 'PINNs' trains on the
+        N_Quad=80, N_F=500, lossb_weight=1, init_params=None, backend="auto", verbose=True, scheme="VPINNs",
+        neumann_right=False, flux_weight=1.0):
+    """neumann_right: the right end x = 1 prescribes u' (`set_flux_data`, weight flux_weight) instead of u.  P1:231-240 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  scheme 'PINNs' trains on the
     strong-form residual -u'' - f at the N_F collocation points of P1:303 instead of the variational one."""
     from ..vpinn import VPINN1D
     Net_layer = [1] + [20] * 4 + [1] if Net_layer is None else Net_layer      # P1:236
     s = setup(N_Element, N_testfcn, N_Quad, N_F)
+    if neumann_right:
+        s = dict(s, X_u_train=s["X_u_train"][:1], u_train=s["u_train"][:1])
     total_record = []
     model = VPINN1D(s["X_u_train"], s["u_train"], s["X_quad_train"], s["W_quad_train"], s["F_ext_total"], s["grid"],
                     s["X_test"], s["u_test"], Net_layer, s["X_f_train"], s["f_train"], var_form=var_form,
                     lossb_weight=lossb_weight, LR=LR, init_params=init_params, backend=backend,
                     total_record=total_record, scheme=scheme)    # P1:333-334
+    if neumann_right:
+        model.set_flux_data(np.array([[1.0]]), du_ext(np.array([1.0])), a=0.0, b=[1.0], weight=flux_weight)
     model.train(Opt_Niter, Opt_tresh)                            # P1:336
     u_pred = model.predict(s["X_test"])                          # P1:337
     err = np.linalg.norm(s["u_test"] - u_pred, 2) / np.linalg.norm(s["u_test"], 2)
@@ -89,5 +99,6 @@ if __name__ == "__main__":
     ap.add_argument("--elements", type=int, default=1)
     ap.add_argument("--var-form", type=int, default=1)
     ap.add_argument("--scheme", default="VPINNs", choices=("VPINNs", "PINNs"))
+    ap.add_argument("--neumann-right", action="store_true", help="x = 1 prescribes u' instead of u")
     a = ap.parse_args()
-    run(Opt_Niter=a.iters, N_Element=a.elements, var_form=a.var_form, scheme=a.scheme)
+    run(Opt_Niter=a.iters, N_Element=a.elements, var_form=a.var_form, scheme=a.scheme, neumann_right=a.neumann_right)

@@ -26,6 +26,37 @@ def f_ext(x, y):                                                 # P2:304-307
         * np.sin(omegay * (y)) + (0.1 * np.sin(omegax * x) + np.tanh(r1 * x)) * (-omegay ** 2 * np.sin(omegay * (y)))
 
 
+def grad_u_ext(x, y):
+    """(u_x, u_y) of u_ext: what a Neumann side prescribes"""
+    return ((0.1 * omegax * np.cos(omegax * x) + r1 / np.cosh(r1 * x) ** 2) * np.sin(omegay * y),
+            (0.1 * np.sin(omegax * x) + np.tanh(r1 * x)) * omegay * np.cos(omegay * y))
+
+
+# the boundary points of `setup` come side by side in this order (P2:314-347), N_bound rows each, with these outward normals
+SIDES = {"top": (0, (0.0, 1.0)), "bottom": (1, (0.0, -1.0)), "right": (2, (1.0, 0.0)), "left": (3, (-1.0, 0.0))}
+
+
+def split_neumann(s, sides):
+    """(setup dict without the boundary points of `sides`, flux data dict(X, g, b) for `set_flux_data`): the points of those sides
+    leave X_u_train / u_train and carry the exact normal derivative g = n . grad u_ext instead of the value."""
+    sides = [v.strip() for v in sides.split(",")] if isinstance(sides, str) else list(sides)
+    bad = [v for v in sides if v not in SIDES]
+    if bad or len(set(sides)) != len(sides) or not 0 < len(sides) < 4:
+        raise ValueError("neumann sides: one to three of left,right,bottom,top (a Dirichlet side must remain); got %r" % (sides,))
+    nb = s["X_u_train"].shape[0] // 4
+    keep = np.ones(4 * nb, dtype=bool)
+    X, g, b = [], [], []
+    for side in sides:
+        k, n = SIDES[side]
+        rows = slice(k * nb, (k + 1) * nb)
+        keep[rows] = False
+        Xs = s["X_u_train"][rows]
+        ux, uy = grad_u_ext(Xs[:, 0], Xs[:, 1])
+        X.append(Xs); g.append(n[0] * ux + n[1] * uy); b.append(np.tile(n, (nb, 1)))
+    s = dict(s, X_u_train=s["X_u_train"][keep], u_train=s["u_train"][keep])
+    return s, dict(X=np.concatenate(X), g=np.concatenate(g), b=np.concatenate(b))
+
+
 def setup(N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10, N_bound=80, N_residual=100, seed=1234,
           with_test_grid=True, assemble="host", device=0):
     np.random.seed(seed)                                         # P2:23
@@ -105,14 +136,20 @@ def build_model(s, Net_layer, var_form=1, init_params=None, backend="auto", loss
 
 def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10,
         N_bound=80, N_residual=100, n_iter=10000 + 1, init_params=None, backend="auto", record_every=1, verbose=True,
-        validate_every=None, adapt_every=None, max_elements=None):
-    """adapt_every=K: local hp-refinement (`train_adaptive`, right-hand side f_ext) after every K-th update, at most max_elements
+        validate_every=None, adapt_every=None, max_elements=None, neumann_sides=None, flux_weight=1.0):
+    """neumann_sides: a comma list out of left,right,bottom,top -- those sides carry the flux n . grad u of the exact solution
+    (`set_flux_data`, weight flux_weight) instead of its value.  adapt_every=K: local hp-refinement (`train_adaptive`, right-hand side f_ext) after every K-th update, at most max_elements
     elements.  P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  validate_every=K trains
     through `train_validated` instead of `train`: the error on the test grid after every K-th update, reduced on the device."""
     Net_layer = [2] + [5] * 3 + [1] if Net_layer is None else Net_layer        # P2:280
     s = setup(N_el_x, N_el_y, N_test_x, N_test_y, N_quad, N_bound, N_residual)
+    flux = None
+    if neumann_sides:
+        s, flux = split_neumann(s, neumann_sides)
     loss_his = []
     model = build_model(s, Net_layer, var_form, init_params, backend, loss_his, scheme=scheme)
+    if flux is not None:
+        model.set_flux_data(flux["X"], flux["g"], a=0.0, b=flux["b"], weight=flux_weight)
     curve = None
     if validate_every:
         model.set_validation()                                   # the test grid of P2:418-426, uploaded once
@@ -149,7 +186,9 @@ if __name__ == "__main__":
                     help="print the error on the test grid after every K-th update (device-side validation history)")
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None, help="never refine beyond this many elements")
+    ap.add_argument("--neumann-sides", default=None,
+                    help="comma list out of left,right,bottom,top: sides that prescribe the flux n . grad u instead of u")
     a = ap.parse_args()
     run(n_iter=a.iters, N_el_x=a.elements, N_el_y=a.elements, var_form=a.var_form,
         Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every, validate_every=a.validate_every,
-        adapt_every=a.adapt_every, max_elements=a.max_elements)
+        adapt_every=a.adapt_every, max_elements=a.max_elements, neumann_sides=a.neumann_sides)

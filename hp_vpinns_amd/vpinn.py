@@ -302,6 +302,7 @@ class _VPINNBase:
         try:
             self.h = _lib.Handle(*self._handle_args[0], **self._handle_args[1])
             self._populate()
+            self._hand_flux()
             self.h.set_params(self._to_dev(self._init_params))
             self.h.backend_in_use()
             return self.h
@@ -598,6 +599,42 @@ class _VPINNBase:
         self.h.eval_loss()
         self._reducer.allreduce()
         return self.h.read_loss()
+
+    # -- flux term: Neumann / Robin conditions and derivative observations (hpv_set_flux_data) ------
+    _flux = None      # (X, coef, g, weight) as handed to the library, kept for a handle that is rebuilt
+
+    def set_flux_data(self, X, g=None, a=0.0, b=None, weight=1.0):
+        """Add  lossf = weight * mean((a u + b . grad u - g)^2)  at the points X (n, dim) to the loss; grad u = (u_x) in 1-D,
+        (u_x, u_y) in 2-D, (u_x, u_t) for AdvDiff.  `a` a scalar or (n,); `b` an (n, dim) array or one vector for all points
+        (None: zero); `g` (n,) targets.  Neumann: a = 0, b = the outward normal, g = the flux; Robin: both; a derivative sensor:
+        b = e_c.  X None clears the term.  Multi-GPU: every rank calls it, rank 0 holds the points (as the boundary points)."""
+        if X is None:
+            self._flux = None
+            self.h.set_flux_data(None, None, None)
+            return
+        d = self.layers[0]
+        X = np.asarray(X, dtype=np.float64).reshape(-1, d)
+        n = X.shape[0]
+        if g is None:
+            raise ValueError("set_flux_data needs one target value g per point")
+        coef = np.zeros((n, 1 + d))
+        coef[:, 0] = np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1), (n,))
+        if b is not None:
+            b = np.asarray(b, dtype=np.float64)
+            coef[:, 1:] = np.broadcast_to(b.reshape(1, d) if b.size == d else b.reshape(n, d), (n, d))
+        g = np.asarray(g, dtype=np.float64).reshape(-1)
+        if g.size != n:
+            raise ValueError("set_flux_data needs one target value g per point")
+        self._flux = (X.copy(), coef, g.copy(), float(weight))
+        self._hand_flux()
+
+    def _hand_flux(self):
+        if self._flux is not None and self.rank == 0:
+            self.h.set_flux_data(*self._flux)
+
+    def flux_loss(self):
+        """(weight * msf, msf) of the flux term in the most recent pass on this rank's handle; zeros without the term."""
+        return self.h.read_flux_loss()
 
     def get_params(self):
         return self._from_dev(self.h.get_params())

@@ -118,6 +118,26 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
 int hpv_set_data(hpv_handle h, const double* X, const double* u, int n);
 
+/* Flux term: Neumann / Robin conditions and derivative observations as a penalty at points (an extension; the test functions
+ * vanish on every element boundary, so the weak forms carry no natural boundary condition).  With
+ *   r_p = a_p u(X_p) + b_p . grad u(X_p) - g_p,   grad = (u_x) in 1-D, (u_x, u_y) in 2-D, (u_x, u_t) for AdvDiff,
+ *   lossf = weight * mean_p(r_p^2),   loss = lossb_weight * lossb + lossf + lossv   (lossp for lossv under scheme PINNs).
+ * Neumann: a = 0, b = the outward normal; Robin: both non-zero; a derivative sensor: b = e_c; a = 1, b = 0 is the value term.
+ * X is [n][dim], coef is [n][1 + dim] = (a, b_0 .. b_{dim-1}), both row-major; g is [n].  Everything is copied.  n = 0 removes the
+ * term (ranks other than 0 of a multi-GPU run: the term lives on rank 0 like the data term); the handle then computes bit for bit
+ * what a handle that never had the term computes.  Epsilon of AdvDiff does not enter: its gradient slot gets nothing from the term.
+ * Side effects: waits for the handle's stream, drops the captured iteration graphs (like hpv_set_data), re-creates the term's
+ * point batch.  The data sets are not state: hpv_get_state / hpv_set_state do not carry them.
+ * Where the sums go: the packed buffer's slot [Ptot + 1] and the history's second column hold lossb_weight * msq + weight * msf
+ * (so `loss` = loss3[0] includes the term and the multi-GPU reduce layout keeps its size); slot [Ptot + 2] stays the plain msq.
+ * loss3[1] therefore is lossb_weight * lossb + lossf for AdvDiff (which reports the weighted slot, P3:184) and stays the plain
+ * mean of the Dirichlet term for the Poisson problems (P1:98, P2:122); hpv_read_flux_loss returns the term on its own.
+ * Returns 0; -1 for a NULL handle, negative n, a NULL array with n > 0, a non-finite weight; -2 on a HIP error. */
+int hpv_set_flux_data(hpv_handle h, const double* X, const double* coef, const double* g, int n, double weight);
+/* sync + copy: out2 = {weight * msf, msf}, msf = mean_p(r_p^2) of the most recent pass (forward-only or reverse-mode) on this
+ * handle; {0, 0} without the term or before the first pass.  Returns 0; -1 for NULL arguments; -2 on a HIP error. */
+int hpv_read_flux_loss(hpv_handle h, double* out2);
+
 /* Collocation points of the strong-form PINN branch (`scheme == 'PINNs'`, P2:124-129): lossp = mean(r^2)
  * over the points X [n][dim] replaces the variational term, loss = lossb_weight * lossb + lossp (P2:129).  Residual per problem:
  *   Poisson-1D  r = -u_xx - f                        (net_f, P1:150-155, against f_train as P2:124)
