@@ -42,11 +42,10 @@ int hpv_test_hook_split_skip() {
 #endif
 }
 
-
-
 namespace {
 
 void free_batch(Batch& b) {
+    if (b.m) hpv_mfma_destroy(b.m);
     if (b.X) (void)hipFree(b.X);
     if (b.ACT) (void)hipFree(b.ACT);
     if (b.OUT) (void)hipFree(b.OUT);
@@ -98,36 +97,41 @@ int alloc_batch(hpv_ctx* h, Batch& b, const NetDesc& nd, long N, bool need_bwd) 
     return 0;
 }
 
-// [n][d] row-major host points -> [d][n] device
-int upload_points(hpv_ctx* h, Batch& b, const double* X, long n, int d) {
-    std::vector<double> t((size_t)n * d);
+// [n][d] row-major host values -> [d][N], zeros behind the n values of each row (N >= n)
+std::vector<double> transposed(const double* X, long n, int d, long N) {
+    std::vector<double> t((size_t)N * d, 0.0);
     for (long p = 0; p < n; ++p)
-        for (int c = 0; c < d; ++c) t[(size_t)c * n + p] = X[(size_t)p * d + c];
-    return upload(h, b.X, t.data(), t.size());
+        for (int c = 0; c < d; ++c) t[(size_t)c * N + p] = X[(size_t)p * d + c];
+    return t;
+}
+int upload_points(hpv_ctx* h, Batch& b, const double* X, long n, int d) {
+    return upload(h, b.X, transposed(X, n, d, n).data(), (size_t)n * d);
 }
 
-void tstart(hpv_ctx* h, int which) {
-    if (!h->timing) return;
-    TimerClass& t = h->timers[which];
-    if (t.used + 2 > t.ev.size()) {
-        size_t old = t.ev.size();
-        t.ev.resize(old + 512);
-        for (size_t i = old; i < t.ev.size(); ++i) (void)hipEventCreate(&t.ev[i]);
-    }
-    (void)hipEventRecord(t.ev[t.used], h->stream);
+// A forward-only batch of n points under channel set nd (prediction, evaluation and validation points), with the MFMA object where the
+// shape has one; and the forward launch over it.
+int points_batch(hpv_ctx* h, Batch& b, const NetDesc& nd, int n) {
+    int rc = alloc_batch(h, b, nd, n, false);
+    if (rc) return rc;
+    if (n > 0 && h->cfg.backend != HPV_BACKEND_GENERIC) b.m = hpv_mfma_create(nd, n, nullptr, false);
+    return 0;
 }
-void tstop(hpv_ctx* h, int which) {
-    if (!h->timing) return;
-    TimerClass& t = h->timers[which];
-    (void)hipEventRecord(t.ev[t.used + 1], h->stream);
-    t.used += 2;
-    t.launches += 1;
-    if (t.used >= 4096) {  // flush
-        (void)hipStreamSynchronize(h->stream);
-        for (size_t i = 0; i < t.used; i += 2) { float ms = 0; (void)hipEventElapsedTime(&ms, t.ev[i], t.ev[i + 1]); t.total_ms += ms; }
-        t.used = 0;
-    }
+int forward_only(hpv_ctx* h, Batch& b) {
+    run_fwd(h, b, 0);
+    HIPCHK(h, hipGetLastError());
+    return 0;
 }
+
+}  // namespace
+
+// The boundary/data points as a batch of their own: every structure but the merged batch of the MFMA path below.
+int hpvd::assemble_data_batch(hpv_ctx* h) {
+    int rc = alloc_batch(h, h->data, h->nd_val, h->n_data, true);
+    if (!rc && h->n_data > 0) rc = upload_points(h, h->data, h->Xd_host.data(), h->n_data, h->dim);
+    return rc;
+}
+
+namespace {
 
 // Build the device point batches from the host copies.  MFMA path: ONE batch = quadrature points (padded
 // to a 16-point tile) followed by the boundary/data points, so a single forward and a single reverse
@@ -137,25 +141,26 @@ int assemble_batches(hpv_ctx* h) {
     int rc;
     const long N = h->Nq;
     const int d = h->dim, nd = h->n_data;
-    if (h->mfma) { hpv_mfma_destroy(h->mfma); h->mfma = nullptr; }
-    if (h->mfma_data) { hpv_mfma_destroy(h->mfma_data); h->mfma_data = nullptr; }
+    free_batch(h->var);      // (with their objects: none outlives the batch it was sized for)
+    free_batch(h->data);
     h->backend = HPV_BACKEND_GENERIC;
     h->merged = false;
     if (h->cfg.backend != HPV_BACKEND_GENERIC && N > 0) {
         const long Npad = (N + 15) / 16 * 16, Ntot = Npad + nd;
         std::string why;
-        h->mfma = hpv_mfma_create(h->nd_var, Ntot, &why);
-        if (h->mfma) {
+        HpvMfma* m = hpv_mfma_create(h->nd_var, Ntot, &why);
+        if (m) {
             h->backend = HPV_BACKEND_MFMA;
             h->merged = true;
             h->data_off = Npad;
-            hpv_mfma_set_err_flag(h->mfma, h->d_xerr);
-            hpv_mfma_set_split_ok(h->mfma, h->shared_elem_ok);
-            if ((rc = alloc_batch(h, h->var, h->nd_var, Ntot, true))) return rc;
+            hpv_mfma_set_err_flag(m, h->d_xerr);
+            hpv_mfma_set_split_ok(m, h->shared_elem_ok);
+            if ((rc = alloc_batch(h, h->var, h->nd_var, Ntot, true))) { hpv_mfma_destroy(m); return rc; }
+            h->var.m = m;
             if (h->var.ACT) { (void)hipFree(h->var.ACT); h->var.ACT = nullptr; }   // the MFMA path has its own store
-            const int rows = hpv_mfma_max_rows(h->mfma, h->n_elem, (nd + 15) / 16);
+            const int rows = hpv_mfma_max_rows(m, h->n_elem, data_tiles(nd));
             if ((rc = dalloc(h, &h->var.GPART, (size_t)rows * h->P))) return rc;
-            h->var.rows = hpv_mfma_grad_rows(h->mfma);
+            h->var.rows = hpv_mfma_grad_rows(m);
             std::vector<double> X((size_t)d * Ntot, 0.0);
             for (int c = 0; c < d; ++c) {
                 for (long p = 0; p < N; ++p) X[(size_t)c * Ntot + p] = h->Xq_host[(size_t)c * N + p];
@@ -164,8 +169,7 @@ int assemble_batches(hpv_ctx* h) {
             if ((rc = upload(h, h->var.X, X.data(), X.size()))) return rc;
             HIPCHK(h, hipMemsetAsync(h->var.GBAR, 0, (size_t)h->nd_var.C * Ntot * sizeof(double), h->stream));
             HIPCHK(h, hipMemsetAsync(h->var.OUT, 0, (size_t)h->nd_var.C * Ntot * sizeof(double), h->stream));
-            free_batch(h->data);
-            const size_t nparts = (size_t)std::max(64, (nd + 15) / 16);
+            const size_t nparts = (size_t)std::max(64, data_tiles(nd));
             if ((rc = dalloc(h, &h->d_data_part, nparts))) return rc;
             HIPCHK(h, hipMemsetAsync(h->d_data_part, 0, nparts * sizeof(double), h->stream));
         } else if (h->cfg.backend == HPV_BACKEND_MFMA) {
@@ -181,15 +185,16 @@ int assemble_batches(hpv_ctx* h) {
     if (!h->merged) {
         if ((rc = alloc_batch(h, h->var, h->nd_var, N, true))) return rc;
         if (N > 0 && (rc = upload(h, h->var.X, h->Xq_host.data(), h->Xq_host.size()))) return rc;
-        if ((rc = alloc_batch(h, h->data, h->nd_val, nd, true))) return rc;
-        if (nd > 0 && (rc = upload_points(h, h->data, h->Xd_host.data(), nd, d))) return rc;
+        if ((rc = assemble_data_batch(h))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->batch_dirty = false;
     return 0;
 }
 
-int check_ready(hpv_ctx* h) {
+}  // namespace
+
+int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_quad) return fail(h, -3, "hpv_set_quadrature has not been called");
     if (!h->have_tables) return fail(h, -3, "hpv_set_tables has not been called");
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
@@ -198,356 +203,6 @@ int check_ready(hpv_ctx* h) {
     if (h->batch_dirty) return assemble_batches(h);
     return 0;
 }
-
-void run_fwd(hpv_ctx* h, Batch& b, HpvMfma* m, int save_act) {
-    if (b.N == 0) return;
-    if (m) hpv_mfma_forward(m, h->d_theta, b.X, b.OUT, save_act, h->stream);
-    else launch_mlp_fwd_generic(b.nd, h->d_theta, b.X, b.ACT, b.OUT, b.N, save_act, h->stream);
-}
-void run_bwd(hpv_ctx* h, Batch& b, HpvMfma* m) {
-    if (b.N == 0) return;
-    if (m) hpv_mfma_backward(m, h->d_theta, b.X, b.GBAR, b.GPART, &b.rows, h->stream);
-    else launch_mlp_bwd_generic(b.nd, h->d_theta, b.X, b.ACT, b.GBAR, b.GPART, b.rows, b.N, h->stream);
-}
-
-// The small value-only batches (boundary/data points, element edges) ride the MFMA path too once the
-// quadrature batch does; their generic activation stores are dropped.
-int ensure_small_mfma(hpv_ctx* h, Batch& b, HpvMfma** m) {
-    if (*m || h->backend != HPV_BACKEND_MFMA || b.N == 0) return 0;
-    std::string why;
-    *m = hpv_mfma_create(b.nd, b.N, &why);
-    if (!*m) return 0;  // stays on the generic kernels
-    if (b.ACT) { (void)hipFree(b.ACT); b.ACT = nullptr; }
-    int rows = hpv_mfma_grad_rows(*m);
-    if (rows > b.rows) { int rc = dalloc(h, &b.GPART, (size_t)rows * h->P); if (rc) return rc; }
-    b.rows = rows;
-    return 0;
-}
-
-// ---- the flux term of a pass: forward over its batch, k_flux_loss, reverse (same sequence in both schemes) ----
-int ensure_flux_mfma(hpv_ctx* h) { return h->n_flux > 0 ? ensure_small_mfma(h, h->flux, &h->mfma_flux) : 0; }
-void pass_flux(hpv_ctx* h, bool backward) {
-    if (h->n_flux <= 0) return;
-    run_fwd(h, h->flux, h->mfma_flux, backward ? 1 : 0);
-    launch_flux_loss(h->flux.OUT, h->flux.N, h->dim, h->d_flux_coef, h->d_flux_g, backward ? h->flux.GBAR : nullptr,
-                     2.0 * h->w_flux / (double)h->n_flux, h->d_flux_part, h->n_flux, h->stream);
-    if (backward) run_bwd(h, h->flux, h->mfma_flux);
-}
-FluxFin flux_fin(hpv_ctx* h, bool backward) {
-    if (h->n_flux <= 0) return FluxFin{};
-    return FluxFin{backward ? h->flux.GPART : nullptr, h->flux.rows, h->d_flux_part, flux_loss_parts(h->n_flux), h->w_flux, h->n_flux,
-                   h->d_flux_part + 64};
-}
-
-AdamArgs adam_args(hpv_ctx* h) {
-    return AdamArgs{h->d_theta, h->d_m, h->d_v, h->d_state, h->cfg.lr, h->cfg.beta1, h->cfg.beta2, h->cfg.eps,
-                    h->d_hist, h->d_hist_idx, HPV_HIST_CAP, h->d_xerr, h->d_nupd};
-}
-
-int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam);
-
-// the boundary / data term as the merged kernels see it, the projection arguments of the quadrature batch (edge: with the element-edge
-// batch's pointers, for the stand-alone projection kernels that integrate that term) and the pass over that batch as the MFMA launch
-// functions take it (one definition for enqueue_pass and the stand-alone timing of the iteration kernel)
-static MfmaDataTerm pass_data_term(hpv_ctx* h, bool backward) {
-    return MfmaDataTerm{h->data_off, h->merged ? h->n_data : 0, h->d_udata, h->var.GBAR, h->d_data_part,
-                        h->n_data > 0 ? -2.0 * h->cfg.lossb_weight / (double)h->n_data : 0.0, backward ? 1 : 0};
-}
-static ProjArgs pass_proj_args(hpv_ctx* h, bool backward, bool edge = false) {
-    const double* eps_ptr = h->has_eps ? h->d_theta + h->P : nullptr;
-    ProjArgs pa{h->pd, h->var.OUT, h->var.GBAR, h->d_R, h->d_F, h->d_coef, h->n_elem, h->d_wtx, h->d_wty, eps_ptr,
-                h->d_loss_e, h->d_deps_e, h->var.N, backward ? 1 : 0, nullptr, nullptr, nullptr, nullptr};
-    if (edge) { pa.edge_u = h->edge.OUT; pa.edge_dphi = h->d_edge_dphi; pa.edge_coef = h->d_edge_coef; pa.edge_gbar = h->edge.GBAR; }
-    return pa;
-}
-static MfmaPass pass_mfma(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa) {
-    return MfmaPass{h->d_theta, h->var.X, h->var.GBAR, h->var.GPART, &h->var.rows, h->stream, &dt, &pa, h->n_elem};
-}
-
-// ---- one pass over both loss terms ------------------------------------------------------------------------------------------
-// What a pass did (hpv_pass_structure / hpv_kernel_variant report structure and names): filled while the pass walks its plan.
-struct PassPlan {
-    long n_loss;             // loss_e / deps_e entries the pass wrote
-    bool fin_done = false;   // the whole-iteration tile kernel ran the finalize step itself
-    bool xch_used = false;   // a shared-element kernel (SPLIT mode, k_iter_tall) ran: k_finalize advances the exchange's launch counter
-    bool pend_taken = false; // the deferred TF1-Adam update rode in k_iter_fused's prologue: k_finalize stores it
-};
-
-// (1) The variational term as ONE launch -- the element-resident whole-iteration kernels, tried in the order of their speed on the
-// shapes they take (each declines what it does not cover): k_iter_fused (two-term / general forms on 12x12, 16x16, 20x20 points;
-// takes a deferred update `pend` into its prologue), k_iter_tile (one tile per wave: 1-D rules, 10x10 points; a one-workgroup grid
-// finishes the iteration itself), k_iter_elem (any instantiated shape / channel set; first with HPV_FUSE=e), k_iter_tall (80x80
-// points).  Timed as the reverse-pass class.  false: nothing was launched.
-static bool pass_whole_iteration(hpv_ctx* h, const MfmaPass& p, bool fuse_adam, bool& pend, PassPlan& pl) {
-    HpvMfma* m = h->mfma;
-    int structure = -1;
-    tstart(h, 2);
-    if (pend) {      // the deferred update rides in k_iter_fused's prologue -- or is applied here, before anything else is launched
-        const MfmaPendingAdam pre{adam_args(h), h->d_RB, h->Ptot};
-        if (hpv_mfma_iter_fused(m, p, &pre)) { pl.pend_taken = true; structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2; }
-        else launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream);
-        pend = false;
-    }
-    if (structure < 0 && hpv_mfma_prefers_elem(m) && hpv_mfma_iter_elem(m, p)) structure = 6;      // HPV_FUSE=e (A/B runs): the generic element-resident kernel first
-    if (structure < 0 && hpv_mfma_iter_fused(m, p)) structure = hpv_mfma_sync_failed_possible(m) ? 3 : 2;
-    if (structure < 0) {
-        MfmaFinalize fin{adam_args(h), h->d_RB, h->cfg.lossb_weight, h->n_data, (h->n_data + 15) / 16, h->has_eps, adam_state_doubles(h->P) / 2};
-        if (!fuse_adam) fin.ad.theta = nullptr;
-        // (flux data: its launches follow this one, and their rows must reach the finalize step -- no in-kernel finalize)
-        if (hpv_mfma_iter_tile(m, p, h->merged && h->n_flux == 0 ? &fin : nullptr, &pl.fin_done)) structure = 4;
-    }
-    if (structure < 0 && hpv_mfma_iter_elem(m, p)) structure = 6;
-    if (structure < 0) {
-        const int ts = hpv_mfma_tall_split(m, h->pd, h->n_elem);
-        if (ts > 1 && h->n_elem * ts <= h->n_red_alloc && hpv_mfma_iter_tall(m, p)) { structure = 5; pl.n_loss = h->n_elem * ts; }
-    }
-    if (structure < 0) return false;     // (nothing was launched; the caller re-records the start event)
-    tstop(h, 2);
-    h->pass_structure = structure;
-    snprintf(h->variant, sizeof h->variant, "%s", hpv_mfma_variant(m, 0));
-    pl.xch_used = hpv_mfma_sync_failed_possible(m);
-    return true;
-}
-
-// (2) / (3) The variational term as separate launches: forward (+ edge batch) -> projection -> reverse; on the MFMA path the
-// projection rides inside the reverse kernel where that applies (element-block mode), otherwise it is the fastest projection
-// kernel that takes the shape.
-static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_mfma) {
-    Batch& v = h->var;
-    tstart(h, 0);
-    if (use_mfma) hpv_mfma_forward(h->mfma, h->d_theta, v.X, v.OUT, backward ? 1 : 0, h->stream, p.dt);
-    else run_fwd(h, v, nullptr, backward ? 1 : 0);
-    tstop(h, 0);
-    if (h->pd.edge) run_fwd(h, h->edge, h->mfma_edge, backward ? 1 : 0);
-    bool bfused = false;
-    if (backward && use_mfma) {
-        tstart(h, 2);   // timed as the reverse-pass class (the projection is ~1 % of its flops)
-        bfused = hpv_mfma_backward_fused(h->mfma, p);
-        if (bfused) tstop(h, 2);
-    }
-    if (backward) h->pass_structure = bfused ? 1 : 0;
-    if (bfused) { snprintf(h->variant, sizeof h->variant, "%s + %s", hpv_mfma_variant(h->mfma, 1), hpv_mfma_variant(h->mfma, 3)); }
-    else {
-        tstart(h, 1);
-        // (the specialised kernels need GBAR's unused channels pre-zeroed: true for every batch, see alloc_batch)
-        const bool special = h->cfg.backend != HPV_BACKEND_GENERIC;
-        const ProjArgs pj = pass_proj_args(h, backward, true);
-        // few elements (at most two per CU) of a 2-D shape: one workgroup per element before "a lane owns a line"
-        bool small_grid = h->dim == 2 && h->n_elem <= 512 && h->proj_split == 1 && !h->pd.nact;
-#ifdef HPV_TEST_HOOKS
-        if (getenv("HPV_PJ_WG_SMALL")) small_grid = false;      // (A/B: "a lane owns a line" on small grids too)
-#endif
-        const char* pname = "k_project";
-        if (special && small_grid && launch_project_wg(pj, h->n_elem, h->stream)) pname = "k_project_wg";
-        else if (special && launch_project_tp(pj, h->n_elem, h->stream)) pname = "k_project_tp";
-        else if (special && launch_project_wg(pj, h->n_elem, h->stream, h->d_upart)) pname = h->proj_split > 1 ? "k_project_rows" : "k_project_wg";
-        else launch_project(pj, h->n_elem, h->stream);
-        tstop(h, 1);
-        if (backward) {
-            snprintf(h->variant, sizeof h->variant, "%s + %s<%dx%d/%dx%d> + %s", use_mfma ? hpv_mfma_variant(h->mfma, 1) : "k_mlp_fwd_generic", pname,
-                     h->pd.qx, h->pd.qy, h->pd.ntx, h->pd.nty, use_mfma ? hpv_mfma_variant(h->mfma, 2) : "k_mlp_bwd_generic");
-            tstart(h, 2);
-            if (use_mfma) hpv_mfma_backward(h->mfma, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);
-            else run_bwd(h, v, nullptr);
-            tstop(h, 2);
-        }
-    }
-    if (backward && h->pd.edge) run_bwd(h, h->edge, h->mfma_edge);
-}
-
-// backward: also the reverse pass and the gradient reduction; fuse_adam: the finalize kernel applies the TF1 Adam update itself
-// (single-GPU training step); pend: RB holds the previous iteration's reduced gradient, its update not applied yet (multi-GPU
-// sequence, see hpv_ctx::defer_adam): k_iter_fused takes it into its prologue and k_finalize stores it; any other structure gets a
-// k_adam launch in front.
-int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = false) {
-    // (an error exit BEFORE the pending update has been taken over by a launch applies it first, best effort: it was counted when
-    //  its iteration was enqueued, and dropping it would leave the device one update behind the host's count -- advisor, round 5)
-    auto apply_pend = [&] { if (pend) { launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream); pend = false; } };
-    if (h->cfg.scheme == HPV_SCHEME_PINN || !backward) apply_pend();
-    if (h->cfg.scheme == HPV_SCHEME_PINN) return enqueue_pinn_pass(h, backward, fuse_adam);
-    int rc = check_ready(h);
-    if (rc) { apply_pend(); return rc; }
-    const bool use_mfma = h->mfma && h->backend == HPV_BACKEND_MFMA;
-    // the deferred update can only ride in a whole-iteration kernel that is the ONLY reader of the parameters in this pass (boundary
-    // points merged into it, no edge batch, no flux batch); otherwise it is applied here, before anything of this pass is launched or forked
-    if (!(use_mfma && h->var.N > 0 && (h->merged || h->n_data == 0) && !h->pd.edge && h->n_flux == 0 && !hpv_mfma_prefers_elem(h->mfma))) apply_pend();
-    if (!h->side_active) {  // allocations are not allowed inside a stream capture
-        if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) { apply_pend(); return rc; }
-        if (h->pd.edge && (rc = ensure_small_mfma(h, h->edge, &h->mfma_edge))) { apply_pend(); return rc; }
-        if ((rc = ensure_flux_mfma(h))) { apply_pend(); return rc; }
-    }
-    hipStream_t smain = h->stream;
-    const bool fork = h->side_active && !h->merged && h->n_data > 0;
-    if (fork) {
-        (void)hipEventRecord(h->ev_fork, smain);
-        (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
-    }
-    PassPlan pl{(long)h->n_elem * h->proj_split};
-    // --- variational term on this shard's quadrature batch ---
-    if (h->var.N > 0) {
-        const MfmaDataTerm dt = pass_data_term(h, backward);
-        const ProjArgs pa = pass_proj_args(h, backward);
-        const MfmaPass p = pass_mfma(h, dt, pa);
-        if (!(backward && use_mfma && pass_whole_iteration(h, p, fuse_adam, pend, pl))) pass_separate(h, p, backward, use_mfma);
-    }
-    // --- boundary / data term: inside the quadrature batch (one partial per 16-point data tile), or its own small batch ---
-    int ndp = 0;
-    if (h->n_data > 0 && h->merged) {
-        ndp = (h->n_data + 15) / 16;
-    } else if (h->n_data > 0) {
-        if (fork) h->stream = h->stream2;   // the launch helpers read h->stream
-        run_fwd(h, h->data, h->mfma_data, backward ? 1 : 0);
-        ndp = (h->n_data + 255) / 256; if (ndp > 64) ndp = 64;
-        launch_data_loss(h->data.OUT, h->d_udata, backward ? h->data.GBAR : nullptr,
-                         -2.0 * h->cfg.lossb_weight / (double)h->n_data, h->d_data_part, h->n_data, h->stream);
-        if (backward) run_bwd(h, h->data, h->mfma_data);
-        h->stream = smain;
-    }
-    pass_flux(h, backward);      // on the main stream, behind the variational term
-    if (fork) {
-        (void)hipEventRecord(h->ev_join, h->stream2);
-        (void)hipStreamWaitEvent(smain, h->ev_join, 0);
-    }
-    const AdamArgs ad = adam_args(h);
-    if (!pl.fin_done)
-        launch_finalize(backward && h->var.N > 0 ? h->var.GPART : nullptr, h->var.rows,
-                        backward && h->n_data > 0 && !h->merged ? h->data.GPART : nullptr, h->data.rows,
-                        backward && h->pd.edge && h->edge.N > 0 ? h->edge.GPART : nullptr, h->edge.rows, h->d_loss_e,
-                        pl.n_loss, h->d_deps_e, h->d_data_part, ndp, h->cfg.lossb_weight, h->n_data, h->P, h->has_eps, h->d_RB,
-                        backward ? 1 : 0, (backward && (fuse_adam || pl.pend_taken)) ? &ad : nullptr, h->stream, h->d_xerr,
-                        pl.xch_used ? hpv_mfma_xiter(h->mfma) : nullptr, pl.pend_taken ? 1 : 0, flux_fin(h, backward));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, -2, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-// scheme == 'PINNs' (P2:128-129; the same switch for the other two problems): loss = w*lossb + lossp, lossp = mean(r^2) at the
-// collocation points with the problem's strong-form residual r (k_pinn_residual); AdvDiff: the partials of d lossp / d epsilon ride
-// where the variational path puts its own (deps_e of k_finalize -> the packed buffer's slot [P])
-int enqueue_pinn_pass(hpv_ctx* h, bool backward, bool fuse_adam) {
-    if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
-    if (h->n_col <= 0) return fail(h, -3, "hpv_set_collocation has not been called");
-    int rc;
-    if (h->batch_dirty) {   // only the data batch matters here
-        if ((rc = alloc_batch(h, h->data, h->nd_val, h->n_data, true))) return rc;
-        if (h->n_data > 0 && (rc = upload_points(h, h->data, h->Xd_host.data(), h->n_data, h->dim))) return rc;
-        if (h->mfma_data) { hpv_mfma_destroy(h->mfma_data); h->mfma_data = nullptr; }
-        h->merged = false;
-        h->batch_dirty = false;
-    }
-    if (!h->side_active) {
-        if (h->cfg.backend != HPV_BACKEND_GENERIC && !h->mfma_colloc) {
-            std::string why;
-            h->mfma_colloc = hpv_mfma_create(h->colloc.nd, h->colloc.N, &why);
-            if (h->mfma_colloc) {
-                h->backend = HPV_BACKEND_MFMA;
-                if (h->colloc.ACT) { (void)hipFree(h->colloc.ACT); h->colloc.ACT = nullptr; }
-                int rows = hpv_mfma_grad_rows(h->mfma_colloc);
-                if (rows > h->colloc.rows && (rc = dalloc(h, &h->colloc.GPART, (size_t)rows * h->P))) return rc;
-                h->colloc.rows = rows;
-            } else if (h->cfg.backend == HPV_BACKEND_MFMA) return fail(h, -4, "MFMA backend not available: %s", why.c_str());
-        }
-        if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) return rc;
-        if ((rc = ensure_flux_mfma(h))) return rc;
-    }
-    run_fwd(h, h->colloc, h->mfma_colloc, backward ? 1 : 0);
-    const int nparts = pinn_residual_parts(h->n_col);
-    launch_pinn_residual(h->cfg.pde, PinnArgs{h->colloc.OUT, h->d_fcol, h->colloc.GBAR, h->d_col_part, h->d_col_part + 64,
-                                              h->has_eps ? h->d_theta + h->P : nullptr, h->cfg.V, h->colloc.N, h->n_col,
-                                              h->n_col_total, backward ? 1 : 0}, h->stream);
-    if (backward) {
-        run_bwd(h, h->colloc, h->mfma_colloc);
-        // (hpv_kernel_variant: the layer kernels of the collocation batch -- recorded after their launches, as pass_separate does)
-        HpvMfma* mc = h->mfma_colloc;
-        snprintf(h->variant, sizeof h->variant, "%s + k_pinn_residual + %s", mc ? hpv_mfma_variant(mc, 1) : "k_mlp_fwd_generic",
-                 mc ? hpv_mfma_variant(mc, 2) : "k_mlp_bwd_generic");
-    }
-    int ndp = 0;
-    if (h->n_data > 0) {
-        run_fwd(h, h->data, h->mfma_data, backward ? 1 : 0);
-        ndp = (h->n_data + 255) / 256; if (ndp > 64) ndp = 64;
-        launch_data_loss(h->data.OUT, h->d_udata, backward ? h->data.GBAR : nullptr,
-                         -2.0 * h->cfg.lossb_weight / (double)h->n_data, h->d_data_part, h->n_data, h->stream);
-        if (backward) run_bwd(h, h->data, h->mfma_data);
-    }
-    pass_flux(h, backward);
-    const AdamArgs ad = adam_args(h);
-    launch_finalize(backward ? h->colloc.GPART : nullptr, h->colloc.rows, backward && h->n_data > 0 ? h->data.GPART : nullptr,
-                    h->data.rows, nullptr, 0, h->d_col_part, nparts, h->has_eps ? h->d_col_part + 64 : nullptr, h->d_data_part, ndp,
-                    h->cfg.lossb_weight, h->n_data, h->P, h->has_eps, h->d_RB, backward ? 1 : 0, (backward && fuse_adam) ? &ad : nullptr,
-                    h->stream, nullptr, nullptr, 0, flux_fin(h, backward));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, -2, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-// A pass whose packed buffer is made global: with the in-library exchange connected the reduced buffer (and, for a
-// training iteration, the Adam update) follows the finalize kernel on the same stream; otherwise the plain pass.
-int enqueue_pass_x(hpv_ctx* h, bool backward, bool fuse_adam) {
-    if (h->rccl_on) {
-        // ONE collective per iteration: ncclAllReduce(sum) of [grad | d eps | lossv | w*lossb | msq | pad] over
-        // xGMI, on the handle's stream (captured into the iteration graphs like the kernels), then the identical TF1 Adam
-        // update on every rank
-        const bool pend = h->adam_pending;
-        h->adam_pending = false;                  // (taken into this pass's kernels, or applied in front of them)
-        int rc = enqueue_pass(h, backward, false, pend);
-        if (rc) return rc;
-        ncclResult_t r = rccl_allreduce(h, h->d_RB, (size_t)h->Ptot + 4, h->stream);
-        if (r != ncclSuccess) return fail(h, -6, "ncclAllReduce failed: %s", rccl_error_string(r));
-        if (backward && fuse_adam) {
-            // inside a sequence of iterations the update is deferred into the NEXT iteration's kernels (two launches + one collective
-            // per iteration); the sequence's last one -- and every stand-alone iteration -- is applied here
-            if (h->defer_adam && h->defer_ok) h->adam_pending = true;
-            else launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(h, -2, "adam launch failed: %s", hipGetErrorString(e));
-        return 0;
-    }
-    if (!h->p2p_on) return enqueue_pass(h, backward, fuse_adam);
-    int rc = enqueue_pass(h, backward, false);
-    if (rc) return rc;
-    const AdamArgs ad = adam_args(h);
-    launch_p2p_exchange(h->pp, h->d_RB, (backward && fuse_adam) ? &ad : nullptr, h->P, h->Ptot, h->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, -2, "exchange launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-// end of a sequence of training iterations: the deferred update, if any, is applied (k_adam)
-void flush_adam(hpv_ctx* h) {
-    if (h->adam_pending) launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream);
-    h->adam_pending = false;
-    h->defer_adam = false;
-}
-
-#define HPV_GRAPH_ITERS 8
-
-// Capture `iters` whole training iterations (incl. the Adam updates) into an executable graph.
-int build_step_graph(hpv_ctx* h, int iters, hipGraphExec_t* out) {
-    int rc;
-    // one direct pass first: lazily created objects (small-batch MFMA stores) must exist before capture
-    if ((rc = ensure_small_mfma(h, h->data, &h->mfma_data))) return rc;
-    if (h->pd.edge && (rc = ensure_small_mfma(h, h->edge, &h->mfma_edge))) return rc;
-    if ((rc = ensure_flux_mfma(h))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipGraph_t graph = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    h->side_active = true;
-    h->defer_adam = true;
-    for (int k = 0; k < iters && !rc; ++k) rc = enqueue_pass_x(h, true, true);   // forward .. finalize (+ fused Adam / exchange)
-    if (!rc) flush_adam(h); else { h->adam_pending = false; h->defer_adam = false; }
-    h->side_active = false;
-    hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) return fail(h, -2, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { *out = nullptr; return fail(h, -2, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-    return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -675,39 +330,17 @@ void hpv_destroy(hpv_handle h) {
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->mfma) hpv_mfma_destroy(h->mfma);
-    if (h->mfma_data) hpv_mfma_destroy(h->mfma_data);
-    if (h->mfma_flux) hpv_mfma_destroy(h->mfma_flux);
-    free_batch(h->flux);
-    { double* fp[] = {h->d_flux_coef, h->d_flux_g, h->d_flux_part}; for (double* q : fp) if (q) (void)hipFree(q); }
-    if (h->mfma_edge) hpv_mfma_destroy(h->mfma_edge);
-    if (h->mfma_pred) hpv_mfma_destroy(h->mfma_pred);
+    for (Batch* b : {&h->var, &h->data, &h->edge, &h->pred, &h->flux, &h->colloc, &h->evalp, &h->valb}) free_batch(*b);
     if (h->mfma_eval) hpv_mfma_destroy(h->mfma_eval);
-    if (h->d_eval_out) (void)hipFree(h->d_eval_out);
-    if (h->mfma_colloc) hpv_mfma_destroy(h->mfma_colloc);
-    free_batch(h->colloc);
-    if (h->d_fcol) (void)hipFree(h->d_fcol);
-    if (h->d_col_part) (void)hipFree(h->d_col_part);
-    if (h->d_jac) (void)hipFree(h->d_jac);
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
-    { double* ip[] = {h->d_wq, h->d_ind_out, h->d_ind_f, h->d_ind}; for (double* q : ip) if (q) (void)hipFree(q); }
-    if (h->mfma_evalp) hpv_mfma_destroy(h->mfma_evalp);
-    if (h->mfma_val) hpv_mfma_destroy(h->mfma_val);
-    free_batch(h->evalp); free_batch(h->valb);
-    { double* vp[] = {h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf}; for (double* q : vp) if (q) (void)hipFree(q); }
-    if (h->d_val_idx) (void)hipFree(h->d_val_idx);
-    if (h->d_upart) (void)hipFree(h->d_upart);
     p2p_release(h);
     rccl_release(h);
-    free_batch(h->var); free_batch(h->data); free_batch(h->edge); free_batch(h->pred);
-    double* ptrs[] = {h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e,
-                      h->d_deps_e, h->d_udata, h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist};
-    for (double* p : ptrs) if (p) (void)hipFree(p);
-    if (h->d_hist_idx) (void)hipFree(h->d_hist_idx);
-    if (h->d_xerr) (void)hipFree(h->d_xerr);
-    if (h->d_nupd) (void)hipFree(h->d_nupd);
-    if (h->d_nact) (void)hipFree(h->d_nact);
-    if (h->d_nacty) (void)hipFree(h->d_nacty);
+    void* ptrs[] = {h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
+                    h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
+                    h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
+                    h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
+                    h->d_nact, h->d_nacty};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& t : h->timers) for (auto e : t.ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -878,7 +511,6 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         if (!nay.empty()) { if ((rc = hpv_set_active_tests_2d(h, na.data(), nay.data(), (int)na.size()))) return rc; }
         else if ((rc = hpv_set_active_tests(h, na.data(), (int)na.size()))) return rc;
     }
-    if (h->mfma_edge) { hpv_mfma_destroy(h->mfma_edge); h->mfma_edge = nullptr; }
     return 0;
 }
 
@@ -1030,7 +662,6 @@ int hpv_set_flux_data(hpv_handle h, const double* X, const double* coef, const d
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old set)
     drop_graph(h);
     h->n_flux = 0;
-    if (h->mfma_flux) { hpv_mfma_destroy(h->mfma_flux); h->mfma_flux = nullptr; }
     const int d = h->dim;
     const long N = ((long)n + 15) / 16 * 16;      // whole 16-point tiles; the padding sits at the origin and carries zero adjoints
     if ((rc = alloc_batch(h, h->flux, h->nd_grad, N, true))) return rc;
@@ -1041,11 +672,7 @@ int hpv_set_flux_data(hpv_handle h, const double* X, const double* coef, const d
         if ((rc = dalloc(h, &h->d_flux_part, (size_t)65))) return rc;
         HIPCHK(h, hipMemsetAsync(h->d_flux_part, 0, 65 * sizeof(double), h->stream));
     }
-    std::vector<double> t((size_t)d * N, 0.0), c((size_t)(1 + d) * n);      // [n][d] -> [d][N], [n][1 + d] -> [1 + d][n]
-    for (int p = 0; p < n; ++p) {
-        for (int k = 0; k < d; ++k) t[(size_t)k * N + p] = X[(size_t)p * d + k];
-        for (int k = 0; k <= d; ++k) c[(size_t)k * n + p] = coef[(size_t)p * (1 + d) + k];
-    }
+    const std::vector<double> t = transposed(X, n, d, N), c = transposed(coef, n, 1 + d, n);      // -> [d][N], [1 + d][n]
     if ((rc = upload(h, h->flux.X, t.data(), t.size()))) return rc;
     if ((rc = upload(h, h->d_flux_coef, c.data(), c.size()))) return rc;
     if ((rc = upload(h, h->d_flux_g, g, (size_t)n))) return rc;
@@ -1075,7 +702,6 @@ int hpv_set_collocation_shard(hpv_handle h, const double* X, const double* f, in
     if (n < 1 || !X || (!f && h->cfg.pde != HPV_PDE_ADVDIFF) || n_total < n) return fail(h, -1, "bad collocation arguments");
     drop_graph(h);
     int rc;
-    if (h->mfma_colloc) { hpv_mfma_destroy(h->mfma_colloc); h->mfma_colloc = nullptr; }
     if ((rc = alloc_batch(h, h->colloc, h->nd_pinn, n, true))) return rc;
     if ((rc = upload_points(h, h->colloc, X, n, h->dim))) return rc;
     if ((rc = dalloc(h, &h->d_fcol, (size_t)n))) return rc;
@@ -1123,9 +749,8 @@ int hpv_reduce_buffer(hpv_handle h, void** dev_ptr, size_t* n_doubles) {
 
 int hpv_apply_adam(hpv_handle h) {
     if (!h) return -1;
-    launch_adam(adam_args(h), h->d_RB, h->P, h->Ptot, h->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, -2, "adam launch failed: %s", hipGetErrorString(e));
+    enqueue_adam(h);
+    if (int rc = launch_check(h, "adam launch")) return rc;
     h->nupd_host += 1;
     return 0;
 }
@@ -1136,14 +761,18 @@ int hpv_sync(hpv_handle h) {
     return sync_check(h);     // (the caller-driven multi-GPU pieces -- forward_backward / apply_adam -- end their runs here)
 }
 
+static void loss_triple(hpv_ctx* h, const double* raw, double* loss3) {
+    loss3[0] = raw[0] + raw[1];
+    loss3[1] = (h->cfg.pde == HPV_PDE_ADVDIFF) ? raw[1] : raw[2];  // P3:184 folds the weight into lossb
+    loss3[2] = raw[0];
+}
+
 int hpv_read_loss(hpv_handle h, double* loss3) {
     if (!h || !loss3) return -1;
     double t[4];
     HIPCHK(h, hipMemcpyAsync(t, h->d_RB + h->Ptot, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    loss3[0] = t[0] + t[1];
-    loss3[1] = (h->cfg.pde == HPV_PDE_ADVDIFF) ? t[1] : t[2];  // P3:184 folds the weight into lossb
-    loss3[2] = t[0];
+    loss_triple(h, t, loss3);
     return 0;
 }
 
@@ -1160,56 +789,13 @@ int hpv_loss_and_grad(hpv_handle h, double* loss3, double* grad) {
     return p2p_check(h);
 }
 
-// n_iters training iterations enqueued on the handle's stream (graph replays where possible), no synchronisation
-static int enqueue_iterations(hpv_ctx* h, int n_iters) {
-    int rc;
-    if (h->use_graph && h->own_stream && !h->timing && n_iters > 0 && h->cfg.scheme == HPV_SCHEME_VPINN) {
-        if ((rc = check_ready(h))) return rc;
-        // n = a * HPV_GRAPH_ITERS + r: a replays of the K-iteration graph and ONE replay of an r-iteration graph (captured
-        // the first time a call leaves that remainder -- callers that time a call run it once untimed before)
-        static_assert(HPV_GRAPH_ITERS <= 8, "g_rem size");
-        if (n_iters >= HPV_GRAPH_ITERS && !h->g_stepK && (rc = build_step_graph(h, HPV_GRAPH_ITERS, &h->g_stepK))) {
-            if (!h->rccl_on) return rc;
-            // a collective that refuses stream capture must not stop the run: eager launches from here on
-            h->use_graph = false;
-            h->err.clear();
-            return enqueue_iterations(h, n_iters);
-        }
-        int it = 0;
-        for (; it + HPV_GRAPH_ITERS <= n_iters; it += HPV_GRAPH_ITERS) HIPCHK(h, hipGraphLaunch(h->g_stepK, h->stream));
-        const int rem = n_iters - it;
-        if (rem > 0) {
-            if (!h->g_rem[rem] && (rc = build_step_graph(h, rem, &h->g_rem[rem]))) {
-                if (!h->rccl_on) { h->nupd_host += it; return rc; }
-                h->use_graph = false;
-                h->err.clear();
-                h->nupd_host += it;           // (the iterations already launched through g_stepK: advisor, round 3)
-                return enqueue_iterations(h, rem);
-            }
-            HIPCHK(h, hipGraphLaunch(h->g_rem[rem], h->stream));
-        }
-    } else {
-        h->defer_adam = true;
-        for (int it = 0; it < n_iters; ++it) {
-            if ((rc = enqueue_pass_x(h, true, true))) { h->adam_pending = false; h->defer_adam = false; return rc; }
-            h->nupd_host += 1;            // (counted per enqueued iteration: an error exit leaves the count right -- a pending update is
-                                          //  either stored by the failing pass's k_finalize or applied by enqueue_pass's error exit; the
-                                          //  handle is in a failed state afterwards: hpv_last_error says why)
-        }
-        flush_adam(h);
-        return 0;
-    }
-    h->nupd_host += n_iters;
-    return 0;
-}
-
 // after a synchronisation point: did a SPLIT-mode element barrier time out (on this rank, or -- carried by the pad slot of the
 // all-reduced buffer -- on any rank)?  The kernels have left theta, m, v, the beta powers and the loss history as they were
 // before the failing iteration and have ignored every iteration since (sticky flag); here the failure is reported (-7), the
 // flag cleared (the exchange is stateless: tagged granules), so that the caller may go on (e.g. with HPV_FUSE=s on a shared GPU).
 static int sync_check(hpv_ctx* h) {
-    if (!h->d_xerr || !h->mfma) return 0;
-    if (!hpv_mfma_split_used(h->mfma) && !h->rccl_on && !h->p2p_on) return 0;   // nothing can have set it
+    if (!h->d_xerr || !h->var.m) return 0;
+    if (!hpv_mfma_split_used(h->var.m) && !h->rccl_on && !h->p2p_on) return 0;   // nothing can have set it
     int err = 0;
     HIPCHK(h, hipMemcpyAsync(&err, h->d_xerr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1245,7 +831,6 @@ static int after_exchange_timeout(hpv_ctx* h, int n) {
     return (int)done;
 }
 
-
 int hpv_step(hpv_handle h, int n_iters, double* loss3_after) {
     if (!h) return -1;
     int rc;
@@ -1268,11 +853,6 @@ int hpv_step(hpv_handle h, int n_iters, double* loss3_after) {
 
 // ---- loss history (the reference records the loss after every update with a second forward pass, P2:243-244; the
 //      forward pass of the NEXT iteration computes exactly that value, so the device keeps it) ----
-static void loss_triple(hpv_ctx* h, const double* raw, double* loss3) {
-    loss3[0] = raw[0] + raw[1];
-    loss3[1] = (h->cfg.pde == HPV_PDE_ADVDIFF) ? raw[1] : raw[2];  // P3:184 folds the weight into lossb
-    loss3[2] = raw[0];
-}
 
 int hpv_history_reset(hpv_handle h) {
     if (!h) return -1;
@@ -1300,7 +880,7 @@ int hpv_time_iteration_kernel(hpv_handle h, int reps, double* avg_ms) {
     if (!h || reps < 1 || !avg_ms) return -1;
     int rc = check_ready(h);
     if (rc) return rc;
-    if (h->cfg.scheme == HPV_SCHEME_PINN || !(h->mfma && h->backend == HPV_BACKEND_MFMA) || h->var.N <= 0)
+    if (h->cfg.scheme == HPV_SCHEME_PINN || !(h->var.m && h->backend == HPV_BACKEND_MFMA) || h->var.N <= 0)
         return fail(h, -4, "no whole-iteration kernel on this handle");
     if ((rc = enqueue_pass(h, true))) return rc;        // everything a first pass allocates / selects
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1315,7 +895,7 @@ int hpv_time_iteration_kernel(hpv_handle h, int reps, double* avg_ms) {
     bool ok = true;
     (void)hipEventRecord(e0, h->stream);
     for (int i = 0; i < reps && ok; ++i)
-        ok = hpv_mfma_iter_fused(h->mfma, p);
+        ok = hpv_mfma_iter_fused(h->var.m, p);
     (void)hipEventRecord(e1, h->stream);
     hipError_t e = hipStreamSynchronize(h->stream);
     float ms = 0.0f;
@@ -1369,15 +949,9 @@ int hpv_predict(hpv_handle h, const double* X, int n, double* u_out) {
     if (n < 0 || (n > 0 && (!X || !u_out))) return fail(h, -1, "bad predict arguments");
     if (n == 0) return 0;
     int rc;
-    if (h->pred.N != n) {
-        if ((rc = alloc_batch(h, h->pred, h->nd_val, n, false))) return rc;
-        if (h->mfma_pred) { hpv_mfma_destroy(h->mfma_pred); h->mfma_pred = nullptr; }
-        if (h->cfg.backend != HPV_BACKEND_GENERIC) h->mfma_pred = hpv_mfma_create(h->nd_val, n, nullptr, false);
-    }
+    if (h->pred.N != n && (rc = points_batch(h, h->pred, h->nd_val, n))) return rc;
     if ((rc = upload_points(h, h->pred, X, n, h->dim))) return rc;
-    if (h->mfma_pred) hpv_mfma_forward(h->mfma_pred, h->d_theta, h->pred.X, h->pred.OUT, 0, h->stream);
-    else launch_mlp_fwd_generic(h->pred.nd, h->d_theta, h->pred.X, nullptr, h->pred.OUT, n, 0, h->stream);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = forward_only(h, h->pred))) return rc;
     HIPCHK(h, hipMemcpyAsync(u_out, h->pred.OUT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
@@ -1388,32 +962,16 @@ int hpv_predict(hpv_handle h, const double* X, int n, double* u_out) {
 //      u_pred on its test grid through the host: P1:197-199, P2:255-257; its pointwise residual is net_f, P2:187-194, P3:247-253) ----
 namespace {
 
-// a forward-only batch of n points under channel set nd, with the MFMA object where the shape has one (as hpv_predict does)
-int points_batch(hpv_ctx* h, Batch& b, HpvMfma** m, const NetDesc& nd, int n) {
-    if (*m) { hpv_mfma_destroy(*m); *m = nullptr; }
-    int rc = alloc_batch(h, b, nd, n, false);
-    if (rc) return rc;
-    if (n > 0 && h->cfg.backend != HPV_BACKEND_GENERIC) *m = hpv_mfma_create(nd, n, nullptr, false);
-    return 0;
-}
-
-int forward_only(hpv_ctx* h, Batch& b, HpvMfma* m) {
-    if (m) hpv_mfma_forward(m, h->d_theta, b.X, b.OUT, 0, h->stream);
-    else launch_mlp_fwd_generic(b.nd, h->d_theta, b.X, nullptr, b.OUT, b.N, 0, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
 // the full channel list at the caller's points: upload + ONE forward launch on the handle's own batch (re-created when n changes)
 int eval_points_forward(hpv_ctx* h, const double* X, int n) {
     int rc;
     if (h->evalp.N != n) {
-        if ((rc = points_batch(h, h->evalp, &h->mfma_evalp, h->nd_full, n))) return rc;
+        if ((rc = points_batch(h, h->evalp, h->nd_full, n))) return rc;
         if ((rc = dalloc(h, &h->d_res_f, (size_t)n))) return rc;
         if ((rc = dalloc(h, &h->d_res_r, (size_t)n))) return rc;
     }
     if ((rc = upload_points(h, h->evalp, X, n, h->dim))) return rc;
-    return forward_only(h, h->evalp, h->mfma_evalp);
+    return forward_only(h, h->evalp);
 }
 
 int validation_ready(hpv_ctx* h) {
@@ -1424,7 +982,7 @@ int validation_ready(hpv_ctx* h) {
 
 // forward over the stored set + the reduction, on the handle's stream; no synchronisation, no host read
 int enqueue_validation(hpv_ctx* h, bool to_history) {
-    int rc = forward_only(h, h->valb, h->mfma_val);
+    int rc = forward_only(h, h->valb);
     if (rc) return rc;
     const int cap = HPV_HIST_CAP;
     double* buf = h->d_val_buf;
@@ -1473,7 +1031,7 @@ int hpv_set_validation(hpv_handle h, const double* X, const double* u, const dou
     int rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued validation may still read the old set)
     h->n_val = 0;
-    if ((rc = points_batch(h, h->valb, &h->mfma_val, du ? h->nd_grad : h->nd_val, n))) return rc;
+    if ((rc = points_batch(h, h->valb, du ? h->nd_grad : h->nd_val, n))) return rc;
     if ((rc = dalloc(h, &h->d_val_u, (size_t)n))) return rc;
     if ((rc = dalloc(h, &h->d_val_du, du ? (size_t)n * h->dim : 0))) return rc;
     if (n == 0) return 0;
@@ -1486,12 +1044,7 @@ int hpv_set_validation(hpv_handle h, const double* X, const double* u, const dou
     }
     if ((rc = upload_points(h, h->valb, X, n, h->dim))) return rc;
     if ((rc = upload(h, h->d_val_u, u, (size_t)n))) return rc;
-    if (du) {      // [n][dim] -> [dim][n]
-        std::vector<double> t((size_t)n * h->dim);
-        for (int p = 0; p < n; ++p)
-            for (int c = 0; c < h->dim; ++c) t[(size_t)c * n + p] = du[(size_t)p * h->dim + c];
-        if ((rc = upload(h, h->d_val_du, t.data(), t.size()))) return rc;
-    }
+    if (du && (rc = upload(h, h->d_val_du, transposed(du, n, h->dim, n).data(), (size_t)n * h->dim))) return rc;      // -> [dim][n]
     h->n_val = n;
     return 0;
 }
@@ -1659,7 +1212,6 @@ int hpv_test_tables(hpv_handle h, int ntest, const double* xi, int q, double* ta
     return rc;
 }
 
-
 int hpv_get_residuals(hpv_handle h, double* R, size_t n) {
     if (!h || !R) return -1;
     const size_t want = (size_t)h->n_elem * h->ntx * h->nty;
@@ -1689,10 +1241,8 @@ int hpv_eval_channels(hpv_handle h, double* out, size_t n) {
         if (h->mfma_eval) hpv_mfma_forward(h->mfma_eval, h->d_theta, h->var.X, h->d_eval_out, 0, h->stream);
         else launch_mlp_fwd_generic(h->nd_eval, h->d_theta, h->var.X, nullptr, h->d_eval_out, h->var.N, 0, h->stream);
         src = h->d_eval_out;
-    } else if (h->mfma && h->backend == HPV_BACKEND_MFMA) {
-        hpv_mfma_forward(h->mfma, h->d_theta, h->var.X, h->var.OUT, 0, h->stream);
     } else {
-        run_fwd(h, h->var, nullptr, 0);
+        run_fwd(h, h->var, 0);
     }
     HIPCHK(h, hipGetLastError());
     for (int ch = 0; ch < C; ++ch)     // the device batch may carry padding / data points behind the quadrature points
@@ -1750,9 +1300,9 @@ int hpv_debug_read_out(hpv_handle h, double* out, size_t n) {
     if (!h || !out || !h->var.GBAR) return -1;
     const double* src = h->var.GBAR;
     size_t have = (size_t)h->nd_var.C * (size_t)h->var.N;
-    if (getenv("HPV_DEBUG_READ_STORE") && h->mfma && hpv_mfma_activation_store(h->mfma)) {
-        src = hpv_mfma_activation_store(h->mfma);
-        have = hpv_mfma_activation_store_doubles(h->mfma);
+    if (getenv("HPV_DEBUG_READ_STORE") && h->var.m && hpv_mfma_activation_store(h->var.m)) {
+        src = hpv_mfma_activation_store(h->var.m);
+        have = hpv_mfma_activation_store_doubles(h->var.m);
     }
     if (getenv("HPV_DEBUG_READ_CHANNELS") && h->var.OUT) { src = h->var.OUT; have = (size_t)h->nd_var.C * (size_t)h->var.N; }
     if (n > have) return fail(h, -1, "debug read of %zu doubles from a buffer of %zu", n, have);
@@ -1841,7 +1391,7 @@ int hpv_set_shared_element_kernels(hpv_handle h, int on) {
     if (!h) return -1;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->shared_elem_ok = on != 0;
-    if (h->mfma) hpv_mfma_set_split_ok(h->mfma, h->shared_elem_ok);
+    if (h->var.m) hpv_mfma_set_split_ok(h->var.m, h->shared_elem_ok);
     drop_graph(h);      // captured iterations hold the launch structure chosen before
     return 0;
 }

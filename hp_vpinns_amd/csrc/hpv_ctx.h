@@ -1,6 +1,6 @@
-// Shared by the host-side translation units of libhpvpinn.so (hpv_api.hip: handle, set-up, passes, training loop;
-// hpv_exchange.hip: the multi-GPU exchanges; hpv_bench.hip: timing / benchmark / debug hooks): the handle itself and the
-// few helpers all of them use.
+// Shared by the host-side translation units of libhpvpinn.so (hpv_api.hip: handle, set-up, batches, the C-ABI's entry points;
+// hpv_pass.hip: the pass engine -- passes, exchange, sequences of iterations; hpv_exchange.hip: the multi-GPU exchanges;
+// hpv_bench.hip: timing / benchmark / debug hooks): the handle itself and the few helpers and entry points they share.
 #pragma once
 #include <dlfcn.h>
 #include <unistd.h>
@@ -21,8 +21,6 @@
 #include "hpv_mfma.h"
 #include "hpv_project_wg.h"
 
-
-
 struct Batch {
     long N = 0;
     NetDesc nd{};
@@ -33,6 +31,7 @@ struct Batch {
     double* GPART = nullptr; // [rows][P] partial parameter gradients
     int rows = 0;
     size_t act_doubles = 0;
+    HpvMfma* m = nullptr;    // the MFMA layer kernels' object for exactly this batch (nullptr: generic kernels); goes with it (free_batch)
 };
 
 struct TimerClass {
@@ -41,7 +40,6 @@ struct TimerClass {
     double total_ms = 0.0;
     long launches = 0;
 };
-
 
 struct hpv_ctx {
     hpv_config cfg{};
@@ -84,7 +82,6 @@ struct hpv_ctx {
     // flux term (hpv_set_flux_data): lossf = w_f * mean((a u + b . grad u - g)^2) at points of its own -- a batch under nd_grad
     // (N = n_flux rounded up to a 16-point tile), k_flux_loss between its forward and its reverse launch
     Batch flux;
-    HpvMfma* mfma_flux = nullptr;
     int n_flux = 0;
     double w_flux = 0.0;
     double *d_flux_coef = nullptr, *d_flux_g = nullptr;   // [1 + dim][n_flux] rows a, b_0 ..; [n_flux]
@@ -98,11 +95,6 @@ struct hpv_ctx {
     long long nupd_host = 0;    // updates ENQUEUED so far (equals *d_nupd once the stream is idle unless a run failed)
     int n_fallbacks = 0;        // runs finished on the barrier-free structures after an exchange timeout (after_exchange_timeout)
     int* d_xerr = nullptr;      // sticky failure flag: a SPLIT-mode element barrier timed out (kernels_fused.hip); see sync_check
-    // mfma path (one object per batch: quadrature points, boundary/data points, element edges)
-    HpvMfma* mfma = nullptr;
-    HpvMfma* mfma_data = nullptr;
-    HpvMfma* mfma_edge = nullptr;
-    HpvMfma* mfma_pred = nullptr;
     // hpv_eval_channels reports the REFERENCE's channel list (nd_eval); where the training pass runs on fewer channels (Poisson-2D
     // var_form 0: u_xx + u_yy as one mixed second tangent, NetDesc::t2w) a forward-only object + output buffer are created on demand
     NetDesc nd_eval{};
@@ -114,7 +106,6 @@ struct hpv_ctx {
     // u, u_x, u_xx; 2-D u, u_x, u_y and the Laplacian as one mixed second tangent; AdvDiff u, u_x, u_t, u_xx
     NetDesc nd_pinn{};
     Batch colloc;
-    HpvMfma* mfma_colloc = nullptr;
     double *d_fcol = nullptr, *d_col_part = nullptr;      // d_col_part: [64] r^2 partials, then [64] d epsilon partials
     int n_col = 0;
     long n_col_total = 0;      // collocation points of ALL shards (the mean of P2:124 runs over them)
@@ -130,10 +121,8 @@ struct hpv_ctx {
     NetDesc nd_full{};         // the full channel list: u, every first and every second input derivative (hpv_eval_points)
     NetDesc nd_grad{};         // u and the first derivatives (validation against exact gradients)
     Batch evalp;               // batch of hpv_eval_points / hpv_residual_points, re-created when n changes
-    HpvMfma* mfma_evalp = nullptr;
     double *d_res_f = nullptr, *d_res_r = nullptr;      // [evalp.N] right-hand side and residual of hpv_residual_points
     Batch valb;                // the stored validation set (nd_val, or nd_grad with exact gradients)
-    HpvMfma* mfma_val = nullptr;
     int n_val = 0;
     double *d_val_u = nullptr, *d_val_du = nullptr;     // exact values [n], exact gradients [dim][n] (nullptr: none given)
     double* d_val_buf = nullptr;   // [6] result of hpv_validate | [HPV_HIST_CAP][6] history | [HPV_VAL_MAX_BLOCKS][5] partials
@@ -183,6 +172,19 @@ extern std::string g_create_error;          // last hpv_create() error (hpv_last
 int fail(hpv_ctx* h, int code, const char* fmt, ...);
 int upload(hpv_ctx* h, double* dst, const double* src, size_t n);
 void drop_graph(hpv_ctx* h);                 // captured iteration graphs (hpv_api.hip)
+int check_ready(hpv_ctx* h);                 // everything of the variational scheme is set; (re)assembles the device batches (hpv_api.hip)
+int assemble_data_batch(hpv_ctx* h);
+// the pass engine (hpv_pass.hip)
+void run_fwd(hpv_ctx* h, Batch& b, int save_act);       // forward launch over a batch
+void enqueue_adam(hpv_ctx* h);
+int launch_check(hpv_ctx* h, const char* what);
+int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam = false, bool pend = false);
+int enqueue_pass_x(hpv_ctx* h, bool backward, bool fuse_adam);      // ... with the multi-GPU exchange behind it
+int enqueue_iterations(hpv_ctx* h, int n_iters);
+// the pass over the quadrature batch as the MFMA launch functions take it (hpv_time_iteration_kernel launches one stand-alone)
+MfmaDataTerm pass_data_term(hpv_ctx* h, bool backward);
+ProjArgs pass_proj_args(hpv_ctx* h, bool backward, bool edge = false);
+MfmaPass pass_mfma(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa);
 void p2p_release(hpv_ctx* h);                // hpv_exchange.hip
 void rccl_release(hpv_ctx* h);
 int p2p_check(hpv_ctx* h);
@@ -198,6 +200,9 @@ const char* rccl_error_string(ncclResult_t r);
     } while (0)
 
 namespace hpvd {
+// 16-point tiles of n boundary/data points riding inside the quadrature batch (hpv_ctx::merged): one loss partial per tile
+inline int data_tiles(int n) { return (n + 15) / 16; }
+
 template <typename T>
 int dalloc(hpv_ctx* h, T** p, size_t n) {
     if (*p) { (void)hipFree(*p); *p = nullptr; }

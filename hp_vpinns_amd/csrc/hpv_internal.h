@@ -1,4 +1,4 @@
-// Internal descriptors shared by the host orchestration (hpv_api.hip, hpv_exchange.hip, hpv_bench.hip) and the kernels.
+// Internal descriptors shared by the host orchestration (hpv_api.hip, hpv_pass.hip, hpv_exchange.hip, hpv_bench.hip) and the kernels.
 // Everything here is plain-old-data passed to kernels by value (kernarg segment).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -150,6 +150,7 @@ void launch_mlp_bwd_generic(const NetDesc& nd, const double* theta, const double
                             const double* GBAR, double* GPART, int rows, long N, hipStream_t s);
 int mlp_bwd_generic_rows(long N);
 void launch_project(const ProjArgs& pa, long n_elem, hipStream_t s);
+int data_loss_parts(int n);
 void launch_data_loss(const double* U, const double* Ud, double* GBAR, double scale_grad, double* part, int n,
                       hipStream_t s);
 // the flux term of a pass (k_flux_loss) as the finalize step sees it; all-zero: the handle has no flux data
@@ -165,11 +166,27 @@ struct FluxFin {
 int flux_loss_parts(int n);
 void launch_flux_loss(const double* OUT, long N, int dim, const double* coef, const double* g, double* GBAR,
                       double scale_grad, double* part, int n, hipStream_t s);
-void launch_finalize(const double* GPART_v, int rows_v, const double* GPART_b, int rows_b, const double* GPART_e,
-                     int rows_e, const double* loss_e, long n_elem, const double* deps_e, const double* data_part,
-                     int n_data_part, double lossb_weight, int n_data, int P, int has_eps, double* RB, int write_grad,
-                     const AdamArgs* fused_adam, hipStream_t s, const int* xerr = nullptr, unsigned int* xiter_bump = nullptr,
-                     int pending_adam = 0, const FluxFin& fx = FluxFin{});
+// All arguments of the finalize launch (k_finalize); a field left at its zero value is an argument that is not there.
+struct GradRows { const double* GPART; int rows; };   // [rows][P] partial gradients of one batch's reverse pass (nullptr: not a source)
+struct FinalizeArgs {
+    GradRows g[3];           // quadrature (PINN scheme: collocation) batch, the data batch of its own, the element-edge batch
+    const double* loss_e;    // [n_loss] loss partials: per element (and row split) / per block of k_pinn_residual
+    long n_loss;
+    const double* deps_e;    // [n_loss] partials of d loss / d epsilon (nullptr: none)
+    const double* data_part; // [n_data_part] partial sums of the data term
+    int n_data_part;
+    double lossb_weight;
+    int n_data;
+    int P, has_eps;
+    double* RB;              // the packed buffer [grad (P) | (d eps) | lossv | w*lossb | mean square | pad]
+    int write_grad;          // reverse-mode pass: the gradient rows are summed
+    AdamArgs adam;           // the TF1-Adam update applied behind the sums (theta == nullptr: none; ignored without write_grad)
+    const int* xerr;         // the handle's sticky failure flag (nullptr: no kernel of the pass can set it)
+    unsigned int* xiter_bump;// launch counter of the shared-element kernels' exchange, advanced here (nullptr: none ran)
+    int pending_adam;        // `adam` is the PREVIOUS iteration's deferred update: stored before RB takes this pass's sums
+    FluxFin fx;              // the flux term
+};
+void launch_finalize(const FinalizeArgs& a, hipStream_t s);
 void launch_adam(const AdamArgs& ad, const double* RB, int P, int Ptot, hipStream_t s);
 void launch_p2p_exchange(const P2PArgs& pp, double* RB, const AdamArgs* adam_or_null, int P, int Ptot, hipStream_t s);
 int adam_state_doubles(int P);

@@ -460,12 +460,15 @@ __global__ void __launch_bounds__(256) k_data_loss(const double* __restrict__ U,
     if (threadIdx.x == 0) part[blockIdx.x] = sq;
 }
 
+int data_loss_parts(int n) {
+    int blocks = (n + 255) / 256;
+    return blocks > 64 ? 64 : blocks;
+}
+
 void launch_data_loss(const double* U, const double* Ud, double* GBAR, double scale_grad, double* part, int n,
                       hipStream_t s) {
     if (n <= 0) return;
-    int blocks = (n + 255) / 256;
-    if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(k_data_loss, dim3(blocks), dim3(256), 0, s, U, Ud, GBAR, scale_grad, part, n);
+    hipLaunchKernelGGL(k_data_loss, dim3(data_loss_parts(n)), dim3(256), 0, s, U, Ud, GBAR, scale_grad, part, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -696,23 +699,19 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
     }
 }
 
-void launch_finalize(const double* GPART_v, int rows_v, const double* GPART_b, int rows_b, const double* GPART_e,
-                     int rows_e, const double* loss_e, long n_elem, const double* deps_e, const double* data_part,
-                     int n_data_part, double lossb_weight, int n_data, int P, int has_eps, double* RB, int write_grad,
-                     const AdamArgs* fused_adam, hipStream_t s, const int* xerr, unsigned int* xiter_bump, int pending_adam,
-                     const FluxFin& fx) {
-    int gblocks = (P + FIN_COLS - 1) / FIN_COLS;
-    AdamArgs ad{};
-    if (fused_adam && write_grad) ad = *fused_adam;
-    const int rows = (GPART_v ? rows_v : 0) + (GPART_b ? rows_b : 0) + (GPART_e ? rows_e : 0) + (fx.GPART ? fx.rows : 0);
-    if (rows <= 1024 && n_elem <= 4096)
-        hipLaunchKernelGGL(k_finalize<256>, dim3(gblocks + 1), dim3(256), 0, s, GPART_v, rows_v, GPART_b, rows_b, GPART_e,
-                           rows_e, loss_e, n_elem, deps_e, data_part, n_data_part, lossb_weight, n_data, P, has_eps, RB,
-                           write_grad, ad, xerr, xiter_bump, pending_adam, fx);
-    else
-        hipLaunchKernelGGL(k_finalize<1024>, dim3(gblocks + 1), dim3(1024), 0, s, GPART_v, rows_v, GPART_b, rows_b, GPART_e,
-                           rows_e, loss_e, n_elem, deps_e, data_part, n_data_part, lossb_weight, n_data, P, has_eps, RB,
-                           write_grad, ad, xerr, xiter_bump, pending_adam, fx);
+template <int FIN_THREADS>
+static void launch_finalize_as(const FinalizeArgs& a, hipStream_t s) {
+    const int gblocks = (a.P + FIN_COLS - 1) / FIN_COLS;
+    hipLaunchKernelGGL(k_finalize<FIN_THREADS>, dim3(gblocks + 1), dim3(FIN_THREADS), 0, s, a.g[0].GPART, a.g[0].rows, a.g[1].GPART,
+                       a.g[1].rows, a.g[2].GPART, a.g[2].rows, a.loss_e, a.n_loss, a.deps_e, a.data_part, a.n_data_part, a.lossb_weight,
+                       a.n_data, a.P, a.has_eps, a.RB, a.write_grad, a.write_grad ? a.adam : AdamArgs{}, a.xerr, a.xiter_bump,
+                       a.pending_adam, a.fx);
+}
+void launch_finalize(const FinalizeArgs& a, hipStream_t s) {
+    int rows = a.fx.GPART ? a.fx.rows : 0;
+    for (const GradRows& g : a.g) rows += g.GPART ? g.rows : 0;
+    if (rows <= 1024 && a.n_loss <= 4096) launch_finalize_as<256>(a, s);
+    else launch_finalize_as<1024>(a, s);
 }
 int adam_state_doubles(int P) { return 2 * ((P + FIN_COLS - 1) / FIN_COLS + 1); }
 

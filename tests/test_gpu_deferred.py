@@ -1,7 +1,7 @@
 """The multi-GPU iteration in two launches + one collective (round 5, verdict item 1c): inside a sequence of training iterations on
 the in-library RCCL exchange the TF1-Adam update of iteration i is DEFERRED -- k_iter_fused of iteration i + 1 forms the updated
 parameters in its prologue and computes with them, k_finalize behind it stores parameters, moments and beta powers, and only the
-sequence's last update is a k_adam launch (hpv_api.hip: enqueue_pass_x / flush_adam).  Checked on ONE GPU with the exchange connected
+sequence's last update is a k_adam launch (hpv_pass.hip: enqueue_pass_x / flush_adam).  Checked on ONE GPU with the exchange connected
 to a 1-rank world (the launches an 8-GPU run makes, minus the xGMI hops): the deferred sequence against the same sequence with
 HPV_NO_DEFERRED_ADAM=1 (finalize, collective, k_adam per iteration) and against the single-GPU iteration (Adam inside k_finalize) --
 loss history, parameters, Adam moments, beta powers and the count of applied updates, through graph replays, remainder graphs, eager

@@ -2,7 +2,7 @@
 rank with a 1-rank nccl group -- the path the 8-GPU SCALE run takes, with the failures a first real multi-GPU run may meet:
 
   * a collective that REFUSES STREAM CAPTURE (HPV_TEST_RCCL_FAIL=capture): hpv_step must drop to eager launches
-    (hpv_api.hip, enqueue_iterations) and really train -- same parameters as an undisturbed run -- and the communicator must
+    (hpv_pass.hip, enqueue_iterations) and really train -- same parameters as an undisturbed run -- and the communicator must
     still be usable afterwards;
   * a collective that FAILS EAGERLY in the middle of a run (HPV_TEST_RCCL_FAIL=eager:k): -6 from hpv_step, the failing
     iteration NOT applied (parameters, Adam moments, beta powers = the state after the last good iteration), the count of

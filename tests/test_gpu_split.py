@@ -147,7 +147,7 @@ def _rccl_timeout_worker(rank, port, out_path):
         ref._step(20, False)
         res["fallback"] = []
         # (launch 9 = the first iteration of an iteration graph; 11 and 16 = in the middle / at the end of one: the update of the iteration
-        #  before -- deferred into the failing launch's kernels, hpv_api.hip flush_adam -- must have been applied, the failing one not)
+        #  before -- deferred into the failing launch's kernels, hpv_pass.hip flush_adam -- must have been applied, the failing one not)
         for launch in (9, 11, 16):
             m2 = _with_knob(launch, _build_small_shard)
             m2._step(20, False)
