@@ -44,6 +44,31 @@ __device__ __forceinline__ void acc_get_from(double (&sv)[N]) {
     if constexpr (J < N) { sv[J] = acc_get<BASE + 2 * (J - J0)>(); acc_get_from<BASE, N, J0, J + 1>(sv); }
 }
 
+// Place k (wave-uniform) of a stash of NSLOT places of NSV doubles each, the first at a[BASE]: the place must be a compile-time
+// register index, hence the switch.  The caller keeps k < NSLOT: a place in [NSLOT, 4) is neither stored nor written by a fetch; a
+// fetch of k >= 4 yields zeros.
+template <int BASE, int NSLOT, int NSV>
+__device__ __forceinline__ void acc_stash(int k, const double (&sv)[NSV]) {
+    switch (k) {
+        case 0: if constexpr (0 < NSLOT) acc_put_all<BASE, NSV>(sv); break;
+        case 1: if constexpr (1 < NSLOT) acc_put_all<BASE + 1 * 2 * NSV, NSV>(sv); break;
+        case 2: if constexpr (2 < NSLOT) acc_put_all<BASE + 2 * 2 * NSV, NSV>(sv); break;
+        case 3: if constexpr (3 < NSLOT) acc_put_all<BASE + 3 * 2 * NSV, NSV>(sv); break;
+    }
+}
+template <int BASE, int NSLOT, int NSV>
+__device__ __forceinline__ void acc_fetch(int k, double (&sv)[NSV]) {
+    switch (k) {
+        case 0: if constexpr (0 < NSLOT) acc_get_all<BASE, NSV>(sv); break;
+        case 1: if constexpr (1 < NSLOT) acc_get_all<BASE + 1 * 2 * NSV, NSV>(sv); break;
+        case 2: if constexpr (2 < NSLOT) acc_get_all<BASE + 2 * 2 * NSV, NSV>(sv); break;
+        case 3: if constexpr (3 < NSLOT) acc_get_all<BASE + 3 * 2 * NSV, NSV>(sv); break;
+        default:
+#pragma unroll
+            for (int j = 0; j < NSV; ++j) sv[j] = 0.0;
+    }
+}
+
 // N doubles p[0], p[64], p[128], .. (one 512-byte wave row each) straight INTO the hand-managed AGPRs a[BASE + 2j : BASE + 2j + 1]:
 // all loads in flight at once without a single compiler-allocated register (k_iter_fused<.., MULTI>: the spilled gradient sums of
 // the workgroup's earlier elements come back in ONE memory round trip; through compiler registers it was either six serialized
@@ -75,6 +100,23 @@ __device__ __forceinline__ void fz_layer(const double* WTl, const double* WRl, c
 #pragma unroll
     for (int s = 0; s < 4; ++s) z[s] = acc[s];
     z[4] = z16;
+}
+
+// "activation, then channels" behind the products of a hidden layer (tanh only): s = tanh(z[0]) goes to sv and h[0], the first
+// tangents are h[1 + u] = s' z_c[u], the second ones h[1 + NT1 + b] = s'' z_c[b]^2 + s' z_cc[b] (channel b rides on first tangent b)
+template <int NT1, int NT2, int C>
+__device__ __forceinline__ void fz_act(const double (&z)[C][MF_KS], double (&h)[C][MF_KS], double* sv) {
+#pragma unroll
+    for (int s = 0; s < MF_KS; ++s) {
+        double a, a1, a2;
+        act_fwd<HPV_ACT_TANH>(z[0][s], a, a1, a2);
+        sv[s] = a;
+        h[0][s] = a;
+#pragma unroll
+        for (int u = 0; u < NT1; ++u) h[1 + u][s] = a1 * z[1 + u][s];
+#pragma unroll
+        for (int b = 0; b < NT2; ++b) h[1 + NT1 + b][s] = a2 * z[1 + b][s] * z[1 + b][s] + a1 * z[1 + NT1 + b][s];
+    }
 }
 
 // An opaque use of a computed value: keeps the compiler from sinking its computation into one arm of a later per-lane select --

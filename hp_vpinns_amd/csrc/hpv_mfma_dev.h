@@ -182,6 +182,29 @@ struct SlotCount {
     static constexpr int value = 1 + (ACT == HPV_ACT_SIN ? 1 : 0) + NT1 + NT2;
 };
 
+// Linear head of one channel: the lane's KS neurons against their head weights wo[s * stride], then the sum over the four neuron groups
+// -- every lane ends up with the full sum of its point; the bias is the caller's.  Two spellings, because the device code depends on
+// it: `+= *` (the tanh-only whole-iteration kernels) and fma (k_iter_tile, k_iter_elem).  k_fwd_mfma keeps its own
+// third one (head weights in registers, __shfl_xor).
+template <int KS>
+__device__ __forceinline__ double mf_head(const double (&h)[KS], const double* wo, int stride) {
+    double v = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) v += h[s] * wo[s * stride];
+    v = xrow_sum16(v);
+    v = xrow_sum32(v);
+    return v;
+}
+template <int KS>
+__device__ __forceinline__ double mf_head_fma(const double (&h)[KS], const double* wo, int stride) {
+    double v = 0.0;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) v = fma(h[s], wo[s * stride], v);
+    v = xrow_sum16(v);
+    v = xrow_sum32(v);
+    return v;
+}
+
 // kernels_elem.hip: the generic element-resident whole-iteration kernel, one translation unit per element shape
 // (= ELEM_SHAPES of csrc/build.sh); the lookup yields nullptr where that (H, channel set, depth, waves) is not instantiated or its
 // LDS does not fit; the launcher returns false (nothing enqueued) when the runtime refuses the kernel's LDS size

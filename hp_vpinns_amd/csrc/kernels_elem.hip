@@ -154,11 +154,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) k_iter_elem(MfmaArgs g) {
         const int lt = wv + k * WAVES;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
-            double v = 0.0;
-#pragma unroll
-            for (int s = 0; s < KS; ++s) v = fma(h[ch][s], W1[(D + 1) * H + 4 * s + ql], v);
-            v = xrow_sum16(v);
-            v = xrow_sum32(v);
+            double v = mf_head_fma(h[ch], W1 + (D + 1) * H + ql, 4);
             if (ch == 0) v += bo;
             if (is_el) {
                 if (q == 0 && valid) lds[M::CHN + ch * NQ + 16 * lt + pt] = v;

@@ -186,6 +186,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
     auto stage_all = [&](auto th) {
         // layer index as a compile-time constant (kernarg offsets become scalar loads instead of a dependent vector load per
         // lane), every global read issued before the first LDS store (one memory round trip)
+        // (a shared MfFragRegs load / store was tried for this staging: all 60 instantiations, e.g. <3, false, false, 20, 20, 10, 10, false, 0, false> moved:
+        //  profiles/mfma_building_blocks.md, mfma_fragregs_attempt.patch)
         constexpr int N1 = 4 * MF_KS * 64, IT1 = (N1 + FZ_BLOCK - 1) / FZ_BLOCK;
         constexpr int ITW = (MF_KS * 64 + FZ_BLOCK - 1) / FZ_BLOCK;
         double vwt[L > 1 ? L - 1 : 1][ITW], vbh[L > 1 ? L - 1 : 1][ITW], vwn[L > 1 ? L - 1 : 1][ITW];
@@ -455,6 +457,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
 #pragma unroll
             for (int j = 0; j < NSV; ++j) pk[j * 64] = sv[j];
         } else {
+            // (acc_stash behind `default:` was tried here and in the fetch below: 27 instantiations moved, e.g.
+            //  k_iter_fused<2, false, false, 16, 16, 8, 8, true, 0, false> from 4667 to 4704 instructions)
             switch (k - n_lds) {
 #define FZ_STASH(K) case K: if constexpr (K < NREG) acc_put_all<AFULL + K * 2 * NSV, NSV>(sv); break;
                 case 0:
@@ -532,6 +536,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             if constexpr (WQ)
                 fz_layer_m(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, lds + M::BH + (i - 1) * MF_KS * 64, lofs,
                            q_tan ? 0.0 : 1.0, QH, QZ);
+            // (fz_act of hpv_fused_dev.h, which k_iter_tall uses, was tried here for NT2 == 0: 29 instantiations moved, e.g.
+            //  k_iter_fused<2, false, false, 12, 12, 6, 6, true, 0, false> from 4539 to 4532 instructions)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -564,6 +570,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             const int k = k0 + t;
             // linear head
             double o[C];
+            // (mf_head was tried here: k_iter_fused<2, true, false, 12, 12, 6, 6, false, 0, false> and six of the general
+            //  instantiations moved)
 #pragma unroll
             for (int ch = 0; ch < C; ++ch) {
                 double v = 0.0;
@@ -605,11 +613,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             stash(k, sv[t]);
         }
         if constexpr (WQ) {
-            double v = 0.0;
-#pragma unroll
-            for (int s = 0; s < MF_KS; ++s) v += QH[s] * lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
-            v = xrow_sum16(v);
-            v = xrow_sum32(v);
+            const double v = mf_head(QH, lds + M::W1O + 2 * MF_KS * 64 + lofs, 64);
             if constexpr (GEN && !DQ) {
                 // slot 1 (d/dx) writes array 0, slot 2 (d/dy) array 1 -- each needs the OTHER tangent slot of its point as well
                 const double vo = dpp_move<0x104>(v), vm = dpp_move<0x114>(v);       // row_shl:4 = lane + 4, row_shr:4 = lane - 4
@@ -1186,20 +1190,9 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         FZ_SEG(1 + 2 * L);
     };
 #undef ZC
-#ifdef HPV_FZ_REV2
-    constexpr bool REV2 = FZ_TPE <= 16;       // (where the stash leaves the compiler the registers for it: a125 against a95)
-#else
-    constexpr bool REV2 = false;
-#endif
-    if constexpr (REV2) {   // experiment: two tiles per trip, the scheduler may overlap tile k + 1's recompute with tile k's tail
-        int k = 0;
+    // (two tiles per trip, for the compiler's own cross-tile overlap, lost: profiles/r04_notes.md section 9)
 #pragma unroll 1
-        for (; k + 1 < n_own; k += 2) { rev_tile(k); rev_tile(k + 1); }
-        if (k < n_own) rev_tile(k);
-    } else {
-#pragma unroll 1
-        for (int k = 0; k < n_own; ++k) rev_tile(k);
-    }
+    for (int k = 0; k < n_own; ++k) rev_tile(k);
 
     if constexpr (QT) {
         // ---- the packed quarter tile, reverse: the whole-tile steps above for ONE packed operand (every slot's adjoint at once) ----
@@ -1503,6 +1496,8 @@ __global__ void __launch_bounds__(SM_BLOCK, 1) k_iter_small(MfmaArgs g) {
     {
         // layer index as a compile-time constant (kernarg offsets become scalar loads instead of a dependent vector load per
         // lane), every global read issued before the first LDS store (one memory round trip)
+        // (a shared MfFragRegs load / store was tried for this staging: both instantiations, k_iter_small<2> from 168 to 164 VGPRs moved:
+        //  profiles/mfma_building_blocks.md, mfma_fragregs_attempt.patch)
         constexpr int N1 = 4 * MF_KS * 64, IT1 = (N1 + SM_BLOCK - 1) / SM_BLOCK;
         constexpr int ITW = (MF_KS * 64 + SM_BLOCK - 1) / SM_BLOCK;
         double vwt[L > 1 ? L - 1 : 1][ITW], vbh[L > 1 ? L - 1 : 1][ITW], vwn[L > 1 ? L - 1 : 1][ITW];
@@ -1622,6 +1617,7 @@ __global__ void __launch_bounds__(SM_BLOCK, 1) k_iter_small(MfmaArgs g) {
             }
         }
         double o[FZ_C];
+        // (mf_head was tried here: both instantiations moved, k_iter_small<2> from 168 to 164 VGPRs)
 #pragma unroll
         for (int ch = 0; ch < FZ_C; ++ch) {
             double v = 0.0;

@@ -80,6 +80,8 @@ __global__ void __launch_bounds__(MF_BLOCK, 2) k_fwd_mfma(MfmaArgs g) {
     double* WR = BH + (L > 1 ? L - 1 : 0) * MF_KS * 64;       // [(L-1)][MF_KS][4 (q)][4 (a)]
     {   // all global reads of the staging are issued before the first LDS store (one round trip instead of three); the layer
         // index is a compile-time constant, so that the kernarg offsets are scalar loads and not a dependent vector load
+        // (a shared MfFragRegs load / store was tried for this staging: all 82 instantiations, <1, 0, 0, 1, 1, false> with its empty loops among them moved:
+        //  profiles/mfma_building_blocks.md, mfma_fragregs_attempt.patch)
         constexpr int LH_ = L > 1 ? L - 1 : 1, ITW = (MF_KS * 64 + BLK - 1) / BLK;
         static_assert(MF_KS * 16 <= BLK, "one remainder fragment per thread");
         double vw[LH_][ITW], vb[LH_][ITW], vr[LH_];
@@ -129,6 +131,8 @@ __global__ void __launch_bounds__(MF_BLOCK, 2) k_fwd_mfma(MfmaArgs g) {
         // ---- layer 1 (VALU): z = b + x W, z_c = W[c,:], z_cc = 0 ----
         // (sin: the activation loops exist in a branch-free and a guarded copy, chosen by ONE wave-uniform test per layer -- a
         //  fallback branch per value would cut the five independent chains of a lane into separate basic blocks)
+        // (a shared mf_layer1 / mf_layer for this step and the next was tried here and in k_iter_tile: with both, instantiations of
+        //  every shape moved; with mf_layer alone 41 of 82, e.g. <1, 0, 0, 1, 2, false> from 2879 to 2874 instructions)
         {
             double z1[MF_KS];
 #pragma unroll

@@ -31,24 +31,12 @@
 //              Gh[j][i] = c sum_k BY[k][j] V[k][i]     (lane = i)     -> coalesced stores
 // The one-hot streaming instantiation: 8 waves per workgroup, 4 waves per SIMD (126 VGPRs), a term's channel column loaded when the
 // term starts.  (Requesting the NEXT column while this one's contractions run measured slower: profiles/r04_notes.md)
-// HPV_PJ_NT (compile time, scripts/build_variant.sh <name> -DHPV_PJ_NT=1): the one-hot instantiation writes R with a
-// non-temporal hint (each byte is touched once).  Measured (round 4): no gain (46-47 % vs 47.5-48.7 % of 8 TB/s
-// without) and +5 % written bytes by PMC (8-byte nt stores with an 80-byte lane stride are not merged into whole lines): off.
-// HPV_PJ_SGPR (compile time, default 1): k_project_tp reads its test-function tables from
-// global memory at wave-uniform addresses -- scalar loads, an SGPR operand per FMA -- instead of LDS broadcast reads (800 ds_read
-// per element group with an s_waitcnt in front of the FMAs that use them).
-#ifndef HPV_PJ_SGPR
-#define HPV_PJ_SGPR 1
-#endif
-#ifndef HPV_PJ_NT
-#define HPV_PJ_NT 0
-#endif
+// (Writing R of the one-hot instantiation with a non-temporal hint measured no gain and +5 % written bytes: profiles/r04_notes.md.)
+// k_project_tp reads its test-function tables from global memory at wave-uniform addresses -- scalar loads, an SGPR operand per
+// FMA -- instead of LDS broadcast reads (800 ds_read per element group with an s_waitcnt in front of the FMAs that use them; the
+// LDS-table form lost: profiles/r04_notes.md section 1).
 __device__ __forceinline__ void pj_stream_store(double* p, double v) {
-#if HPV_PJ_NT
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
 struct ActiveCh {
@@ -77,47 +65,11 @@ __global__ void __launch_bounds__(PJ_WAVES * 64, (OH && PJ_WAVES == 8) ? 4 : 1) 
     constexpr int LDT = QX + 1;
     constexpr int TB_D = EPW * NTY * LDT;
     constexpr int WAVE_DOUBLES = TB_D + 64;
-    constexpr int PJ_BLOCK = PJ_WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // tables in both orientations, so that every contraction walks its table contiguously in the OUTPUT
-    // index (independent accumulators, wide broadcast reads, many LDS reads in flight).  The transposed copies
-    // are derived here; ALL global loads of the staging are issued before the first LDS store (one L2 round
-    // trip instead of one per loop iteration -- the staging was most of the kernel's latency at 256 elements).
-    constexpr bool SGT = HPV_PJ_SGPR != 0;   // tables as SGPR operands (scalar loads at uniform addresses), not LDS reads
-    double* AXs = sm;                      // [3][NTX][QX]  w_x phi^(d)[r][i]
-    double* BYs = AXs + 3 * NTX * QX;      // [3][NTY][QY]  w_y phi^(d)[k][j]
-    double* AXT = BYs + 3 * NTY * QY;      // [3][QX][NTX]
-    double* BYT = AXT + 3 * NTX * QX;      // [3][QY][NTY]
-    if constexpr (!SGT) {      // (with SGPR tables nothing is staged: the kernel starts with its first element group's loads)
-        constexpr int NAX = 3 * NTX * QX, NBY = 3 * NTY * QY;
-        constexpr int ITA = (NAX + PJ_BLOCK - 1) / PJ_BLOCK, ITB = (NBY + PJ_BLOCK - 1) / PJ_BLOCK;
-        double va[ITA], vb[ITB];
-#pragma unroll
-        for (int it = 0; it < ITA; ++it) { const int i = it * PJ_BLOCK + threadIdx.x; va[it] = i < NAX ? wtx[i] : 0.0; }
-#pragma unroll
-        for (int it = 0; it < ITB; ++it) { const int i = it * PJ_BLOCK + threadIdx.x; vb[it] = i < NBY ? wty[i] : 0.0; }
-#pragma unroll
-        for (int it = 0; it < ITA; ++it) {
-            const int i = it * PJ_BLOCK + threadIdx.x;
-            if (i < NAX) {
-                AXs[i] = va[it];
-                const int d = i / (NTX * QX), r = (i / QX) % NTX, c = i % QX;
-                AXT[d * (NTX * QX) + c * NTX + r] = va[it];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < ITB; ++it) {
-            const int i = it * PJ_BLOCK + threadIdx.x;
-            if (i < NBY) {
-                BYs[i] = vb[it];
-                const int d = i / (NTY * QY), k = (i / QY) % NTY, c = i % QY;
-                BYT[d * (NTY * QY) + c * NTY + k] = vb[it];
-            }
-        }
-    }
-    if constexpr (!SGT) __syncthreads();
-    double* Tb = BYT + 3 * NTY * QY + wv * WAVE_DOUBLES;   // [EPW][NTY][LDT]  transpose tile (T, then V)
+    // (the tables are SGPR operands: nothing is staged, the kernel starts with its first element group's loads.  The launch still
+    //  reserves the room of the LDS-table form in front of the wave tiles: both tables in both orientations.)
+    double* Tb = sm + 2 * (3 * NTX * QX + 3 * NTY * QY) + wv * WAVE_DOUBLES;   // [EPW][NTY][LDT]  transpose tile (T, then V)
     double* Rd = Tb + TB_D;                                // [64] slot-wise reductions
     const int slot = lane / LPE, li = lane % LPE;
     const bool lane_ok = slot < EPW;
@@ -190,29 +142,20 @@ __global__ void __launch_bounds__(PJ_WAVES * 64, (OH && PJ_WAVES == 8) ? 4 : 1) 
             pj_wave_sync();   // previous readers of Tb are done
             // (b) y-contraction, lane = column i
             if (col) {
-                const double* byt = BYT + td.dy * (NTY * QY);
                 const double* __restrict__ byg = wty + (long)td.dy * (NTY * QY);      // [k][j], wave-uniform
                 double acc[NTY];
 #pragma unroll
                 for (int k = 0; k < NTY; ++k) acc[k] = 0.0;
-                if constexpr (SGT) {
 #pragma unroll
-                    for (int k = 0; k < NTY; ++k)
+                for (int k = 0; k < NTY; ++k)
 #pragma unroll
-                        for (int j = 0; j < QY; ++j) acc[k] = fma(byg[k * QY + j], gcol[j], acc[k]);
-                } else {
-#pragma unroll
-                for (int j = 0; j < QY; ++j)
-#pragma unroll
-                    for (int k = 0; k < NTY; ++k) acc[k] = fma(byt[j * NTY + k], gcol[j], acc[k]);
-                }
+                    for (int j = 0; j < QY; ++j) acc[k] = fma(byg[k * QY + j], gcol[j], acc[k]);
 #pragma unroll
                 for (int k = 0; k < NTY; ++k) Tb[slot * (NTY * LDT) + k * LDT + li] = acc[k];
             }
             pj_wave_sync();
             // (c) x-contraction, lane = residual row k
             if (row) {
-                const double* axt = AXT + td.dx * (NTX * QX);
                 const double* __restrict__ axg = wtx + (long)td.dx * (NTX * QX);      // [r][i], wave-uniform
                 const double c = cf[t] * (td.eps_mult ? eps : 1.0) * alpha_t;
                 double trow[QX], acc[NTX];
@@ -220,17 +163,10 @@ __global__ void __launch_bounds__(PJ_WAVES * 64, (OH && PJ_WAVES == 8) ? 4 : 1) 
                 for (int i = 0; i < QX; ++i) trow[i] = Tb[slot * (NTY * LDT) + li * LDT + i];
 #pragma unroll
                 for (int r = 0; r < NTX; ++r) acc[r] = 0.0;
-                if constexpr (SGT) {
 #pragma unroll
-                    for (int r = 0; r < NTX; ++r)
+                for (int r = 0; r < NTX; ++r)
 #pragma unroll
-                        for (int i = 0; i < QX; ++i) acc[r] = fma(axg[r * QX + i], trow[i], acc[r]);
-                } else {
-#pragma unroll
-                for (int i = 0; i < QX; ++i)
-#pragma unroll
-                    for (int r = 0; r < NTX; ++r) acc[r] = fma(axt[i * NTX + r], trow[i], acc[r]);
-                }
+                    for (int i = 0; i < QX; ++i) acc[r] = fma(axg[r * QX + i], trow[i], acc[r]);
 #pragma unroll
                 for (int r = 0; r < NTX; ++r) u[r] = fma(c, acc[r], u[r]);
             }
@@ -263,7 +199,7 @@ __global__ void __launch_bounds__(PJ_WAVES * 64, (OH && PJ_WAVES == 8) ? 4 : 1) 
             pj_wave_sync();
             // (d) V[k][i] = sum_r AX[r][i] Rs[k][r], lane = row k
             if (row) {
-                const double* ax = SGT ? wtx + (long)td.dx * (NTX * QX) : AXs + td.dx * (NTX * QX);
+                const double* ax = wtx + (long)td.dx * (NTX * QX);
                 double acc[QX];
 #pragma unroll
                 for (int i = 0; i < QX; ++i) acc[i] = 0.0;
@@ -277,7 +213,7 @@ __global__ void __launch_bounds__(PJ_WAVES * 64, (OH && PJ_WAVES == 8) ? 4 : 1) 
             pj_wave_sync();
             // (e) Gh[j][i] = c sum_k BY[k][j] V[k][i], lane = column i; scattered onto the integrated channels
             if (col) {
-                const double* by = SGT ? wty + (long)td.dy * (NTY * QY) : BYs + td.dy * (NTY * QY);
+                const double* by = wty + (long)td.dy * (NTY * QY);
                 const double c = cf[t];
                 const double m = td.eps_mult ? eps : 1.0;
                 double vcol[NTY], gh[QY];

@@ -94,6 +94,8 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
     constexpr int NTABX = HPV_MAXT * NTX * QX, NTABY = HPV_MAXT * NTY * QY;
     constexpr int ITX = (NTABX + TA_BLOCK - 1) / TA_BLOCK, ITY = (NTABY + TA_BLOCK - 1) / TA_BLOCK;
     double vax[ITX], vby[ITY];
+    // (a shared MfFragRegs load / store was tried for this staging: all 8 instantiations, e.g. <2, 1, 3, 80, 80, 5, 5, true> moved:
+    //  profiles/mfma_building_blocks.md, mfma_fragregs_attempt.patch)
     {
         constexpr int N1 = 4 * MF_KS * 64, IT1 = (N1 + TA_BLOCK - 1) / TA_BLOCK;
         constexpr int ITW = (MF_KS * 64 + TA_BLOCK - 1) / TA_BLOCK;
@@ -244,29 +246,12 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
 #pragma unroll
             for (int ch = 1; ch < C; ++ch)
                 fz_layer<false>(WTl + (i - 1) * MF_KS * 64, WRl + (i - 1) * MF_KS * 16, nullptr, lofs, h[ch], z[ch]);
-#pragma unroll
-            for (int s = 0; s < MF_KS; ++s) {
-                double a, a1, a2;
-                act_fwd<HPV_ACT_TANH>(z[0][s], a, a1, a2);
-                sv[i * MF_KS + s] = a;
-                h[0][s] = a;
-#pragma unroll
-                for (int u = 0; u < NT1; ++u) h[1 + u][s] = a1 * z[1 + u][s];
-#pragma unroll
-                for (int b = 0; b < NT2; ++b) h[1 + NT1 + b][s] = a2 * z[1 + b][s] * z[1 + b][s] + a1 * z[1 + NT1 + b][s];
-            }
+            fz_act<NT1, NT2>(z, h, sv + i * MF_KS);
         }
         // linear head
         double o[C];
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) {
-            double v = 0.0;
-#pragma unroll
-            for (int s = 0; s < MF_KS; ++s) v += h[ch][s] * lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
-            v = xrow_sum16(v);
-            v = xrow_sum32(v);
-            o[ch] = v;
-        }
+        for (int ch = 0; ch < C; ++ch) o[ch] = mf_head(h[ch], lds + M::W1O + 2 * MF_KS * 64 + lofs, 64);
         o[0] += bo;
         if (k < n_el) {
             if (q == 0) {
@@ -281,11 +266,7 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
             const double sq = row_sum16(dd * dd);
             if (lane == 0) g.data_part[p / 16 - g.data_off / 16] = sq;
         }
-        switch (k) {     // wave-uniform; the stash slot must be a compile-time register index
-#define TA_STASH(K) case K: if constexpr (K < NSLOT) acc_put_all<ABASE + K * 2 * NSV, NSV>(sv); break;
-            TA_STASH(0) TA_STASH(1) TA_STASH(2) TA_STASH(3)
-#undef TA_STASH
-        }
+        acc_stash<ABASE, NSLOT, NSV>(k, sv);     // (k: wave-uniform)
     }
     // ---- QT: this wave's packed quarter of the workgroup's extra tile (slot c = pt >> 2 = channel, j = pt & 3 = point) ----
     const int qcs = pt >> 2, qj = pt & 3;
@@ -332,11 +313,7 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
                 H[s] = mv * ab + ((mf + ms) * b1) * Z[s] + (ms * b2) * (zx * zx);
             }
         }
-        double v = 0.0;
-#pragma unroll
-        for (int s = 0; s < MF_KS; ++s) v += H[s] * lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
-        v = xrow_sum16(v);
-        v = xrow_sum32(v);
+        double v = mf_head(H, lds + M::W1O + 2 * MF_KS * 64 + lofs, 64);
         if (q_val) v += bo;
         if (q_kind == 1) {
             if (q == 0 && qcs < C) lds[M::CH + qcs * MAXP + q_lp] = v;
@@ -369,28 +346,15 @@ __global__ void __launch_bounds__(TA_BLOCK, 1) k_iter_tall(MfmaArgs g) {
     // gathered partial sums; the four waves' blocks straddle the per-wave transpose tiles, so everybody reads its block back BEFORE
     // the barrier that ends phase P
     // (the quarter-tile instantiations only: the other ones sit too close to the hand-managed AGPR range for a second copy of the
-    //  tile body; -DHPV_TALL_NO_EARLY: A/B)
-#ifdef HPV_TALL_NO_EARLY
-    constexpr bool EARLY0 = false;
-#else
+    //  tile body; A/B against none at all: profiles/r04_notes.md)
     constexpr bool EARLY0 = QT;
-#endif
     constexpr int NPARK = (L - 1) * (NT1 + NT2) * MF_KS;
     static_assert(64 * NR + TA_WAVES * NPARK * 64 <= TA_WAVES * M::TR_WAVE, "gathered sums + parked tangents fit the transpose region");
     double* PARK = lds + M::TR + 64 * NR + wv * (NPARK * 64) + lane;     // (behind the gathered sums: at most 64 partners x NR)
     // s of tile k back from the stash and its tangent pre-activations recomputed on the matrix pipe.  Tile 0's are produced BEFORE
     // the gather of the exchange (they need nothing of the projection): the wait for the partners' partial sums (10 k cycles per
     // launch) covers them
-    auto fetch_sv = [&](int k, double (&sv)[NSV]) {
-        switch (k) {
-#define TA_FETCH(K) case K: if constexpr (K < NSLOT) acc_get_all<ABASE + K * 2 * NSV, NSV>(sv); break;
-            TA_FETCH(0) TA_FETCH(1) TA_FETCH(2) TA_FETCH(3)
-#undef TA_FETCH
-            default:
-#pragma unroll
-                for (int j = 0; j < NSV; ++j) sv[j] = 0.0;
-        }
-    };
+    auto fetch_sv = [&](int k, double (&sv)[NSV]) { acc_fetch<ABASE, NSLOT, NSV>(k, sv); };
     auto tangents = [&](int lofs, bool recompute, const double (&sv)[NSV], double (&zc)[L][NT1 > 0 ? NT1 : 1][MF_KS], double (&zcc)[L][NT2 > 0 ? NT2 : 1][MF_KS]) {
         // tangent pre-activations of every hidden layer, recomputed: layer 0 has z_c = W1[c,:], z_cc = 0;
         // layer i: z_c = (s' z_c)_{i-1} W_i, z_cc = (s'' z_c^2 + s' z_cc)_{i-1} W_i

@@ -93,6 +93,8 @@ __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
     const double udv = (di >= 0 && valid) ? g.ud[pc - g.data_off] : 0.0;
 
     // ---- stage the weight fragments of both passes and the projection's tables: every global read before the first LDS store ----
+    // (a shared MfFragRegs load / store was tried for this staging: all 14 instantiations, e.g. <2, 2, 0, 0, 2, 10, 10, 5, 5, 8> moved:
+    //  profiles/mfma_building_blocks.md, mfma_fragregs_attempt.patch)
     ProjTableRegs<QX, QY, NTX, NTY, BT> ptab;
     {
         constexpr int ITW = (MF_KS * 64 + BT - 1) / BT;
@@ -168,6 +170,8 @@ __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
     // =============================================================================================
     if (active) {
         double h[C][MF_KS];
+        // (a shared mf_layer1 / mf_layer for this step and the next was tried here and in k_fwd_mfma: 8 of the 14 instantiations moved,
+        //  e.g. <1, 1, 0, 1, 2, 80, 1, 60, 1, 6> from 188 to 196 VGPRs)
         // the activation loops exist twice: branch-free sincos (FAST) when the whole wave's pre-activations are in its range --
         // the five chains of a lane then interleave -- and the guarded one otherwise (tanh: FAST is the only version)
         {
@@ -258,11 +262,7 @@ __device__ __forceinline__ void tile_body(const MfmaArgs& g, double* lds) {
         // linear head: every lane ends up with the full sum of its point
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
-            double v = 0.0;
-#pragma unroll
-            for (int s = 0; s < MF_KS; ++s) v = fma(h[ch][s], W1O[(D * MF_KS + s) * 64 + lane], v);
-            v = xrow_sum16(v);
-            v = xrow_sum32(v);
+            double v = mf_head_fma(h[ch], W1O + D * MF_KS * 64 + lane, 64);
             if (ch == 0) v += bo;
             if (is_el) {
                 if (q == 0 && valid) lds[M::CHN + ch * NQ + 16 * wv + pt] = v;

@@ -179,6 +179,7 @@ __global__ void __launch_bounds__(WF_BLOCK, (H <= 32 ? 2 : 1)) k_fwd_wide(MfmaAr
         // ---- linear head (VALU + the cross-row sums over the 4 neuron groups) ----
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
+            // (mf_head_fma was tried here: 127 instantiations of k_fwd_wide moved, e.g. <1, 1, 0, 1, 2, 64> from 342 to 352 VGPRs)
             double v = 0.0;
 #pragma unroll
             for (int s = 0; s < KS; ++s) v = fma(h[ch][s], W1[(D + 1) * H + 4 * s + (lofs >> 4)], v);

@@ -23,7 +23,8 @@ MAGIC = 6755399441055744.0
 
 def device_coeffs():
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hp_vpinns_amd", "csrc", "hpv_math.h")).read()
-    body = src[src.index("#ifndef HPV_TANH_R4"):src.index("#else")]
+    start = src.index("double hpv_tanh(double x)")
+    body = src[start:src.index("\n}\n", start)]
     first = re.search(r"double p = (-?[0-9.e+-]+);", body).group(1)
     rest = re.findall(r"p = fma\(p, w, (-?[0-9.e+-]+)\);", body)
     return [float(c) for c in reversed([first] + rest)]       # ascending powers of w
