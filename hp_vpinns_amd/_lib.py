@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("HPV_LIBRARY") or os.path.join(_HERE, "libhpvpinn.so")
 HPV_MAX_LAYERS = 16
 HIST_CAP = 4096          # HPV_HIST_CAP of csrc/hpv_internal.h: loss-history entries the device keeps
 PDE_POISSON1D, PDE_POISSON2D, PDE_ADVDIFF = 0, 1, 2
+PDE_LINEAR1D, PDE_LINEAR2D = 3, 4      # variable-coefficient linear problems (hpv_set_operator)
 ACT_TANH, ACT_SIN = 0, 1
 BACKEND_AUTO, BACKEND_GENERIC, BACKEND_MFMA = 0, 1, 2
 SCHEME_VPINN, SCHEME_PINN = 0, 1
@@ -39,6 +40,7 @@ EXPORTS = [
     "hpv_validation_read", "hpv_step_validate",
     "hpv_set_element_boxes", "hpv_element_indicators",
     "hpv_set_flux_data", "hpv_read_flux_loss",
+    "hpv_set_operator",
 ]
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
@@ -133,6 +135,7 @@ def load():
     lib.hpv_set_data.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_set_flux_data.argtypes = [h, _dp, _dp, _dp, C.c_int, C.c_double]
     lib.hpv_read_flux_loss.argtypes = [h, _dp]
+    lib.hpv_set_operator.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
     lib.hpv_num_params.restype = C.c_size_t
@@ -357,6 +360,12 @@ class Handle:
         if coef.shape != (X.shape[0], 1 + d) or g.size != X.shape[0]:
             raise ValueError(f"flux data needs coefficients of shape (n, {1 + d}) and one target per point")
         self._chk(self.lib.hpv_set_flux_data(self._h, _p(X), _p(coef), _p(g), X.shape[0], float(weight)))
+
+    def set_operator(self, coef):
+        """The coefficient planes of a linear problem (hpv_set_operator): (K, n_owned * qx * qy), K = 3 rows (k, b, s) in 1-D, 5 rows
+        (kx, ky, bx, by, s) in 2-D, each element-major over the owned elements, q = j * qx + i."""
+        coef = None if coef is None else _c(coef).reshape(-1)
+        self._chk(self.lib.hpv_set_operator(self._h, _p(coef), 0 if coef is None else coef.size))
 
     def read_flux_loss(self):
         """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""

@@ -198,6 +198,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_quad) return fail(h, -3, "hpv_set_quadrature has not been called");
     if (!h->have_tables) return fail(h, -3, "hpv_set_tables has not been called");
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
+    if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->have_F && !h->d_F && h->n_elem > 0) return fail(h, -3, "internal: F not sliced");
     if (h->batch_dirty) return assemble_batches(h);
@@ -241,6 +242,11 @@ static const char* form_terms(int pde, int vf, double V, ProjDesc& pd, int& nT1,
             TermDesc& t = term(0, 0, 0); t.a0[1] = V; t.a0[2] = 1.0;
             term(1, 0, 1).a0[1] = 1.0;
         } else return "AdvDiff var_form must be 0 or 1";
+    } else if (pde == HPV_PDE_LINEAR1D || pde == HPV_PDE_LINEAR2D) {
+        // channels u, u_x, (u_y); the three integrand terms carry per-point coefficients and live in k_project_lin (kernels_linop.hip),
+        // not in this descriptor: nterms stays 0
+        if (vf != 1) return "the linear problem takes var_form 1 (the once-integrated-by-parts form)";
+        nT1 = pde == HPV_PDE_LINEAR1D ? 1 : 2;
     } else return "unknown pde";
     return nullptr;
 }
@@ -249,8 +255,11 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     if (!out || !cfg) return fail(nullptr, -1, "null argument");
     *out = nullptr;
     if (cfg->n_layers < 2 || cfg->n_layers > HPV_MAX_LAYERS) return fail(nullptr, -1, "n_layers out of range");
-    const int dim = (cfg->pde == HPV_PDE_POISSON1D) ? 1 : 2;
-    if (cfg->pde < 0 || cfg->pde > 2) return fail(nullptr, -1, "unknown pde %d", cfg->pde);
+    const int dim = (cfg->pde == HPV_PDE_POISSON1D || cfg->pde == HPV_PDE_LINEAR1D) ? 1 : 2;
+    if (cfg->pde < 0 || cfg->pde > HPV_PDE_LINEAR2D) return fail(nullptr, -1, "unknown pde %d", cfg->pde);
+    const bool linear = cfg->pde == HPV_PDE_LINEAR1D || cfg->pde == HPV_PDE_LINEAR2D;
+    if (linear && cfg->scheme != HPV_SCHEME_VPINN)
+        return fail(nullptr, -1, "the linear problem runs under the variational scheme only (the strong form needs derivatives of its coefficients)");
     if (cfg->layers[0] != dim) return fail(nullptr, -1, "layers[0]=%d but the problem is %d-D", cfg->layers[0], dim);
     if (cfg->layers[cfg->n_layers - 1] != 1) return fail(nullptr, -1, "the network must have one output");
     for (int l = 1; l < cfg->n_layers - 1; ++l)
@@ -264,6 +273,7 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     hpv_ctx* h = new hpv_ctx();
     h->cfg = *cfg;
     h->dim = dim;
+    h->linear = linear;
     if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return fail(nullptr, -2, "hipStreamCreate failed"); }
     h->own_stream = true;
     if (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
@@ -335,7 +345,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
+    void* ptrs[] = {h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -414,7 +424,8 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
     }
     h->ntx = ntx; h->nty = nty;
     h->pd.ntx = ntx; h->pd.nty = nty;
-    if (hpv_proj_lds_bytes(h->pd) > 64 * 1024) return fail(h, -1, "element too large for the projection kernel's LDS (%zu B)", hpv_proj_lds_bytes(h->pd));
+    const size_t lds = h->linear ? hpv_linop_lds_bytes(qx, qy, ntx, nty) : hpv_proj_lds_bytes(h->pd);
+    if (lds > 64 * 1024) return fail(h, -1, "element too large for the projection kernel's LDS (%zu B)", lds);
     h->have_tables = true;
     drop_graph(h);
     return 0;
@@ -441,6 +452,12 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
     h->Nq = N;
     const int nterms = h->pd.nterms;
     std::vector<double> X((size_t)h->dim * N), coef((size_t)nterms * ne), ecoef((size_t)ne), EX((size_t)2 * ne), jac((size_t)ne);
+    std::vector<double> jxy(h->linear ? (size_t)2 * ne : 0, 1.0);
+    if (h->linear) {      // the coefficient planes belong to the old elements' points
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->have_lin = false;
+        if (h->d_lin) { (void)hipFree(h->d_lin); h->d_lin = nullptr; }
+    }
     for (long le = 0; le < ne; ++le) {
         const double* box = boxes + (size_t)(e_begin + le) * bs;
         const double gx0 = box[0], gx1 = box[1];
@@ -455,7 +472,10 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
             }
         const double Jx = (gx1 - gx0) / 2;
         jac[le] = (h->dim == 1) ? Jx : ((gx1 - gx0) / 2) * ((gy1 - gy0) / 2);   // P1:276 / P2:393
-        if (h->cfg.pde == HPV_PDE_POISSON1D) {
+        if (h->linear) {                                             // k_project_lin forms its coefficients from J, Jx, Jy itself
+            jxy[le] = Jx;
+            if (h->dim == 2) jxy[ne + le] = (gy1 - gy0) / 2;
+        } else if (h->cfg.pde == HPV_PDE_POISSON1D) {
             const double J = Jx;                                     // P1:71
             if (h->cfg.var_form == 1) coef[le] = -J;
             else if (h->cfg.var_form == 2) coef[le] = 1.0;
@@ -475,6 +495,10 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
     if ((rc = dalloc(h, &h->d_coef, coef.size()))) return rc;
     if ((rc = dalloc(h, &h->d_jac, jac.size()))) return rc;
     if (ne > 0 && (rc = upload(h, h->d_jac, jac.data(), jac.size()))) return rc;
+    if (h->linear) {
+        if ((rc = dalloc(h, &h->d_jxy, jxy.size()))) return rc;
+        if (ne > 0 && (rc = upload(h, h->d_jxy, jxy.data(), jxy.size()))) return rc;
+    }
     if ((rc = dalloc(h, &h->d_R, (size_t)ne * h->ntx * h->nty))) return rc;
     // (per-element counts switch the row-split projection off -- set_proj_split below -- but its buffers are sized without them)
     h->proj_split = project_row_split(h->pd, ne, h->cfg.backend == HPV_BACKEND_GENERIC);
@@ -652,6 +676,25 @@ int hpv_set_data(hpv_handle h, const double* X, const double* u, int n) {
     h->batch_dirty = true;
     if ((rc = dalloc(h, &h->d_udata, (size_t)n))) return rc;
     if (n > 0 && (rc = upload(h, h->d_udata, u, (size_t)n))) return rc;
+    return 0;
+}
+
+// The coefficient planes of a linear problem at the owned quadrature points (include/hpvpinn.h); k_project_lin reads them in place.
+int hpv_set_operator(hpv_handle h, const double* coef, size_t n) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_operator belongs to the linear problems");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    const size_t K = h->dim == 1 ? 3 : 5;
+    if (!coef || n != K * (size_t)h->Nq) return fail(h, -1, "the operator has %zu entries, expected %zu planes of %ld", n, K, h->Nq);
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(coef[i])) return fail(h, -1, "coefficient plane %zu holds a non-finite value at point %zu", i / (size_t)std::max(h->Nq, 1L), i % (size_t)std::max(h->Nq, 1L));
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old planes)
+    drop_graph(h);
+    h->have_lin = false;
+    if ((rc = dalloc(h, &h->d_lin, n))) return rc;
+    if ((rc = upload(h, h->d_lin, coef, n))) return rc;
+    h->have_lin = true;
     return 0;
 }
 
@@ -1011,6 +1054,7 @@ int hpv_eval_points(hpv_handle h, const double* X, int n, double* out, size_t n_
 
 int hpv_residual_points(hpv_handle h, const double* X, const double* f, int n, double* r_out) {
     if (!h) return -1;
+    if (h->linear) return fail(h, -1, "the strong residual of a linear problem needs derivatives of its coefficients: not available");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (n < 0 || (n > 0 && (!X || !r_out))) return fail(h, -1, "bad residual arguments");
     if (n == 0) return 0;
@@ -1263,6 +1307,7 @@ int hpv_eval_channels(hpv_handle h, double* out, size_t n) {
 int hpv_element_indicators(hpv_handle h, const double* f_quad, size_t n, double* out, size_t n_out) {
     if (!h) return -1;
     if (h->cfg.scheme != HPV_SCHEME_VPINN) return fail(h, -1, "element indicators belong to the variational scheme");
+    if (h->linear) return fail(h, -1, "the element indicators of a linear problem need its strong residual: not available");
     int rc = check_ready(h);
     if (rc) return rc;
     const long ne = h->n_elem, NQ = (long)h->qx * h->qy;
@@ -1341,6 +1386,7 @@ int hpv_rule_advice(int device, int pde, int var_form, int n_hidden, int max_wid
     bool mixed;
     if (!q_dev || !nt_dev || q < 1 || ntx < 1 || n_elem_shard < 0 || form_terms(pde, var_form, 1.0, pd, nd.nT1, nd.nT2, mixed)) return -1;
     *q_dev = q; *nt_dev = ntx;
+    if (pde == HPV_PDE_LINEAR1D || pde == HPV_PDE_LINEAR2D) return 0;      // forward -> k_project_lin -> reverse takes any rule as it is
     const int n_cus = device_cus(device);
     const bool net20 = max_width <= 20 && n_hidden >= 2;       // the element-resident kernels are written for 20-wide layers
     if (pde == HPV_PDE_POISSON1D) {                   // kernels_tile.hip: 80 points / 60 test functions (P1:237-238), var_form 1 / 2, 2-4 hidden layers

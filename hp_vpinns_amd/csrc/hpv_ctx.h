@@ -110,6 +110,11 @@ struct hpv_ctx {
     int n_col = 0;
     long n_col_total = 0;      // collocation points of ALL shards (the mean of P2:124 runs over them)
     double* d_jac = nullptr;   // |J_e| of the owned elements (RHS assembly, hpv_assemble_rhs)
+    // linear problems (HPV_PDE_LINEAR1D / _LINEAR2D; hpv_set_operator): the coefficient planes [3 | 5][Nq] at the owned quadrature
+    // points and the half widths [2][n_elem] = (Jx | Jy) of the owned elements; k_project_lin (kernels_linop.hip) reads both
+    bool linear = false;
+    bool have_lin = false;     // the planes belong to the current elements
+    double *d_lin = nullptr, *d_jxy = nullptr;
     // per-element refinement indicators (hpv_element_indicators): the raw 1-D weights [qx | qy] (uploaded with the quadrature), a
     // forward-only object of the full channel set on the quadrature batch's own X and its buffers; re-created when Nq (sizes d_ind_f),
     // the batch size var.N (sizes d_ind_out and the object) or the owned element count (sizes d_ind) changes

@@ -87,6 +87,28 @@ static inline size_t hpv_proj_lds_bytes(const ProjDesc& pd) {
            sizeof(double);
 }
 
+// All arguments of the linear-problem projection launch (k_project_lin, kernels_linop.hip): the variable-coefficient class
+//   d/dx(kx u_x) + d/dy(ky u_y) + bx u_x + by u_y + s u = f   with per-quadrature-point coefficients.
+struct LinProjArgs {
+    const double* OUT;       // [1 + dim][N] channels u, u_x, (u_y) of the quadrature batch
+    double* GBAR;            // [1 + dim][N] their adjoints (written when do_adjoint)
+    const double* coef;      // planes (k, b, s) in 1-D, (kx, ky, bx, by, s) in 2-D; element-major over the owned elements, q = j * qx + i
+    long coef_stride;        // doubles between two planes (= n_owned * qx * qy)
+    const double* F;         // [n_elem][nty][ntx], or nullptr (zero)
+    double* R;               // [n_elem][nty][ntx]
+    double* loss_e;          // [n_elem]
+    const double* wtx;       // [3][ntx][qx] weighted tables (w phi, w phi', w phi''); the first two are read
+    const double* wty;       // [3][nty][qy]
+    const double *J, *Jx, *Jy;   // [n_elem] |J_e| and the half widths per direction (Jy: 2-D only)
+    const int* nact;         // [n_elem] active counts per direction, or nullptr (all)
+    const int* nacty;
+    long N;
+    int qx, qy, ntx, nty, dim;
+    int do_adjoint;
+};
+size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty);
+void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s);
+
 struct AdamArgs {
     double *theta, *m, *v, *state;   // theta == nullptr: no update
     double lr, b1, b2, eps;

@@ -229,6 +229,30 @@ static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use
     if (backward && h->pd.edge) run_bwd(h, h->edge);
 }
 
+// The linear problems (hpv_set_operator): always forward -> k_project_lin -> reverse.  Their integrand carries per-point coefficients
+// and a third term, which neither ProjDesc nor a whole-iteration kernel knows; the layer kernels are the ones every handle of the
+// channel set u, u_x, (u_y) runs, the merged boundary points ride in the forward launch as ever.
+static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_mfma) {
+    Batch& v = h->var;
+    tstart(h, 0);
+    if (use_mfma) hpv_mfma_forward(v.m, h->d_theta, v.X, v.OUT, backward ? 1 : 0, h->stream, p.dt);
+    else run_fwd(h, v, backward ? 1 : 0);
+    tstop(h, 0);
+    tstart(h, 1);
+    const LinProjArgs a{v.OUT, v.GBAR, h->d_lin, h->Nq, h->d_F, h->d_R, h->d_loss_e, h->d_wtx, h->d_wty, h->d_jac, h->d_jxy,
+                        h->d_jxy + h->n_elem, h->pd.nact, h->pd.nacty, v.N, h->qx, h->qy, h->ntx, h->nty, h->dim, backward ? 1 : 0};
+    launch_project_lin(a, h->n_elem, h->stream);
+    tstop(h, 1);
+    if (!backward) return;
+    h->pass_structure = 0;
+    snprintf(h->variant, sizeof h->variant, "%s + k_project_lin<%dx%d/%dx%d> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
+             h->qx, h->qy, h->ntx, h->nty, use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
+    tstart(h, 2);
+    if (use_mfma) hpv_mfma_backward(v.m, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);
+    else run_bwd(h, v);
+    tstop(h, 2);
+}
+
 // backward: also the reverse pass and the gradient reduction; fuse_adam: the finalize kernel applies the TF1 Adam update itself
 // (single-GPU training step); pend: RB holds the previous iteration's reduced gradient, its update not applied yet (multi-GPU
 // sequence, see hpv_ctx::defer_adam): k_iter_fused takes it into its prologue and k_finalize stores it; any other structure gets a
@@ -244,7 +268,7 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam, bool pend) {
     const bool use_mfma = h->var.m && h->backend == HPV_BACKEND_MFMA;
     // the deferred update can only ride in a whole-iteration kernel that is the ONLY reader of the parameters in this pass (boundary
     // points merged into it, no edge batch, no flux batch); otherwise it is applied here, before anything of this pass is launched or forked
-    if (!(use_mfma && h->var.N > 0 && (h->merged || h->n_data == 0) && !h->pd.edge && h->n_flux == 0 && !hpv_mfma_prefers_elem(h->var.m))) apply_pend();
+    if (!(use_mfma && h->var.N > 0 && (h->merged || h->n_data == 0) && !h->pd.edge && h->n_flux == 0 && !hpv_mfma_prefers_elem(h->var.m)) || h->linear) apply_pend();
     if (!h->side_active && (rc = ensure_small_batches(h))) { apply_pend(); return rc; }   // (allocations are not allowed inside a stream capture)
     hipStream_t smain = h->stream;
     const bool fork = h->side_active && !h->merged && h->n_data > 0;
@@ -252,13 +276,14 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam, bool pend) {
         (void)hipEventRecord(h->ev_fork, smain);
         (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
     }
-    PassPlan pl{(long)h->n_elem * h->proj_split};
+    PassPlan pl{h->linear ? (long)h->n_elem : (long)h->n_elem * h->proj_split};      // (k_project_lin: one workgroup, one partial per element)
     // --- variational term on this shard's quadrature batch ---
     if (h->var.N > 0) {
         const MfmaDataTerm dt = pass_data_term(h, backward);
         const ProjArgs pa = pass_proj_args(h, backward);
         const MfmaPass p = pass_mfma(h, dt, pa);
-        if (!(backward && use_mfma && pass_whole_iteration(h, p, fuse_adam, pend, pl))) pass_separate(h, p, backward, use_mfma);
+        if (h->linear) pass_linear(h, p, backward, use_mfma);
+        else if (!(backward && use_mfma && pass_whole_iteration(h, p, fuse_adam, pend, pl))) pass_separate(h, p, backward, use_mfma);
     }
     // --- boundary / data term: inside the quadrature batch (one partial per 16-point data tile), or its own small batch ---
     int ndp = 0;

@@ -1,0 +1,105 @@
+"""Two textbook problems of the variable-coefficient linear class (VPINNLinear), each with a manufactured solution; prints the
+relative L2 error.
+
+  boundary layer   -eps u'' + u' = 1 on [0, 1], u(0) = u(1) = 0:  u = x - (exp((x - 1) / eps) - exp(-1 / eps)) / (1 - exp(-1 / eps)),
+                   a layer of width eps at x = 1; the elements are graded towards it.  In the class's convention
+                   (k u')' + b u' + s u = f this is k = -eps, b = 1, s = 0, f = 1.
+  L-shape          div(kappa grad u) + beta . grad u + sigma u = f on [-1, 1]^2 without its lower right quadrant, as three boxes;
+                   kappa = 1 + x y, beta = (1, -1), sigma = 2, u = sin(pi x) sin(pi y) (zero on the whole boundary), f manufactured.
+
+    python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05
+    python -m hp_vpinns_amd.drivers.linear l-shape
+"""
+import argparse
+
+import numpy as np
+
+from ..adapt import ElementMesh
+from ..vpinn import VPINNLinear
+
+# the smallest setting of the boundary-layer run (tests/test_gpu_linear.py trains it once)
+SMALLEST = dict(eps=0.2, n_elements=3, n_quad=8, n_test=4, n_iter=600, layers=[1, 8, 8, 1], LR=5e-3)
+
+
+def boundary_layer_exact(x, eps):
+    x = np.asarray(x, dtype=np.float64)
+    return x - (np.exp((x - 1.0) / eps) - np.exp(-1.0 / eps)) / (1.0 - np.exp(-1.0 / eps))
+
+
+def graded_grid(n, grade=2.0):
+    """n elements on [0, 1] with widths shrinking towards x = 1: x_i = 1 - (1 - i / n)^grade"""
+    return 1.0 - (1.0 - np.arange(n + 1) / n) ** grade
+
+
+def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000, layers=(1, 20, 20, 20, 1), grade=2.0, LR=1e-3,
+                       lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True):
+    grid = graded_grid(int(n_elements), grade)
+    m = VPINNLinear(list(layers), grid_x=grid, n_quad=int(n_quad), n_test=int(n_test), kappa=-float(eps), beta=1.0, sigma=0.0, f=1.0,
+                    X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2), lossb_weight=lossb_weight, activation="sin", LR=LR,
+                    seed=seed, backend=backend, device=device)
+    m.train(int(n_iter), verbose=verbose)
+    X = np.linspace(0.0, 1.0, 401)[:, None]
+    u = boundary_layer_exact(X, eps)
+    err = m.rel_l2_error(X, u)
+    if verbose:
+        print("boundary layer eps = %g, %d graded elements: relative L2 error %.4e (%s)" % (eps, n_elements, err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+
+
+L_BOXES = np.array([[-1.0, 0.0, -1.0, 0.0], [-1.0, 0.0, 0.0, 1.0], [0.0, 1.0, 0.0, 1.0]])
+
+
+def _l_exact(P):
+    return np.sin(np.pi * P[:, 0]) * np.sin(np.pi * P[:, 1])
+
+
+def _l_f(P):
+    x, y = P[:, 0], P[:, 1]
+    u = _l_exact(P)
+    ux, uy = np.pi * np.cos(np.pi * x) * np.sin(np.pi * y), np.pi * np.sin(np.pi * x) * np.cos(np.pi * y)
+    kappa = 1.0 + x * y
+    return kappa * (-2.0 * np.pi ** 2 * u) + y * ux + x * uy + ux - uy + 2.0 * u
+
+
+def _l_boundary(n):
+    """n points per edge on the six edges of the L"""
+    t = np.linspace(0.0, 1.0, n)
+    c = [(-1, -1), (0, -1), (0, 0), (1, 0), (1, 1), (-1, 1), (-1, -1)]
+    return np.concatenate([np.stack([a[0] + (b[0] - a[0]) * t, a[1] + (b[1] - a[1]) * t], 1) for a, b in zip(c[:-1], c[1:])])
+
+
+def run_l_shape(n_iter=2000, n_quad=20, n_test=10, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0, seed=1234,
+                backend="auto", device=None, verbose=True):
+    Xb = _l_boundary(int(n_bound))
+    m = VPINNLinear(list(layers), mesh=ElementMesh(L_BOXES, int(n_test), int(n_test)), n_quad=int(n_quad),
+                    kappa=lambda P: 1.0 + P[:, 0] * P[:, 1], beta=np.array([1.0, -1.0]), sigma=2.0, f=_l_f, X_u_train=Xb, u_train=_l_exact(Xb),
+                    lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device)
+    m.train(int(n_iter), verbose=verbose)
+    g = np.linspace(-1.0, 1.0, 81)
+    X = np.stack([v.reshape(-1) for v in np.meshgrid(g, g)], 1)
+    X = X[~((X[:, 0] > 0) & (X[:, 1] < 0))]
+    u = _l_exact(X)[:, None]
+    err = m.rel_l2_error(X, u)
+    if verbose:
+        print("L-shape, kappa = 1 + x y, beta = (1, -1), sigma = 2: relative L2 error %.4e (%s)" % (err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("problem", choices=["boundary-layer", "l-shape"])
+    ap.add_argument("--eps", type=float, default=0.05)
+    ap.add_argument("--elements", type=int, default=8)
+    ap.add_argument("--grade", type=float, default=2.0)
+    ap.add_argument("--n-quad", type=int, default=20)
+    ap.add_argument("--n-test", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=2000)
+    a = ap.parse_args(argv)
+    if a.problem == "boundary-layer":
+        run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade)
+    else:
+        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test)
+
+
+if __name__ == "__main__":
+    main()

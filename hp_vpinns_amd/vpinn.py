@@ -1230,3 +1230,171 @@ class VPINNAdvDiff(_VPINNBase):
         self.h.sync()
         error_records = [loss_value, 1]
         return error_records, total_records, u_records, u_records_iterhis, total_time_train
+
+
+def _coef_field(c, P, dim, what, vector):
+    """A coefficient at the points P (n, dim): `c` a constant (a scalar; for a vector-valued coefficient also one (dim,) vector) or a
+    callable of P returning (n, dim) -- or (n,) for a scalar field, which an isotropic kappa may also be.  Returns (n, dim) for
+    vector-valued coefficients, (n,) otherwise."""
+    n = P.shape[0]
+    if callable(c):
+        v = np.asarray(c(P), dtype=np.float64)
+        if v.shape == (n, 1) and (not vector or dim == 1):
+            v = v.reshape(n)
+        if v.shape == (n,):
+            return np.repeat(v[:, None], dim, axis=1) if vector else v.copy()
+        if vector and v.shape == (n, dim):
+            return v.copy()
+        raise ValueError(f"{what}(points) returned shape {v.shape}; expected {(n, dim) if vector else (n,)}")
+    v = np.asarray(c, dtype=np.float64)
+    if v.size == 1:
+        return np.full((n, dim) if vector else (n,), float(v.reshape(-1)[0]))
+    if vector and v.shape == (dim,):
+        return np.broadcast_to(v, (n, dim)).copy()
+    raise ValueError(f"a constant {what} is a scalar" + (f" or a vector of {dim} entries" if vector else ""))
+
+
+class VPINNLinear(_VPINNBase):
+    """Variable-coefficient linear convection-diffusion-reaction problems in 1-D and 2-D (no reference counterpart; the library's
+    linear problems, include/hpvpinn.h: hpv_set_operator):
+
+        div(kappa grad u) + beta . grad u + sigma u = f        kappa = diag(kx, ky), or one scalar field for both directions
+
+    with the sign convention that makes Poisson kappa = 1.  Everything is a keyword argument and nothing is looked up in the
+    caller's module.  `layers[0]` (1 or 2) is the dimension.  The elements are a grid per direction (`grid_x`[, `grid_y`]) or an
+    `adapt.ElementMesh` (`mesh`: any list of boxes, with its per-element test-function counts).  `n_quad` is the number of
+    Gauss-Lobatto points per direction (one number or a pair) unless `rule` = ((xi, wx)[, (yi, wy)]) hands the 1-D rules over;
+    `n_test` the test-function counts of a grid: one number, a pair (x, y), or per-element arrays (one, or a pair in 2-D).
+    `kappa`, `beta`, `sigma`, `f`: a constant, or a callable of the points (n, dim); `kappa` and `beta` return (n, dim) -- kappa
+    also (n,) when isotropic -- and a constant `beta` may be one vector.  They are evaluated at the handle's own quadrature points;
+    F is assembled on the device (hpv_assemble_rhs).  `X_u_train`, `u_train`: Dirichlet data, weighted by `lossb_weight`."""
+
+    _n_extra = 0
+    _val_default = ("X_test", "utest")
+    X_test = utest = None
+    var_form = 1
+    scheme = "VPINNs"
+
+    def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
+                 sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
+                 init_params=None, seed=1234, backend="auto", device=None):
+        dim = int(layers[0])
+        if dim not in (1, 2):
+            raise ValueError("layers[0] is the dimension of the problem: 1 or 2")
+        self._pde = _lib.PDE_LINEAR1D if dim == 1 else _lib.PDE_LINEAR2D
+        self._act = {"tanh": _lib.ACT_TANH, "sin": _lib.ACT_SIN}[activation]
+        self._channel_names = ("u", "u_x", "u_xx") if dim == 1 else ("u", "u_x", "u_y", "u_xx", "u_yy")
+        self._module_globals = None
+        if mesh is None:
+            if grid_x is None or (dim == 2 and grid_y is None):
+                raise ValueError("give the elements as grid_x[, grid_y] or as mesh=ElementMesh(...)")
+            nt = n_test if isinstance(n_test, (tuple, list)) and dim == 2 else (n_test, n_test)
+            g = ElementMesh.from_grid(grid_x, grid_y if dim == 2 else None)
+            mesh = ElementMesh(g.boxes, nt[0], nt[1] if dim == 2 else None)
+        if not isinstance(mesh, ElementMesh) or mesh.dim != dim:
+            raise ValueError("mesh must be an adapt.ElementMesh of the problem's dimension")
+        if rule is None:
+            from .quadrature import GaussLobattoJacobiWeights
+            nq = tuple(n_quad) if isinstance(n_quad, (tuple, list)) else (n_quad,) * dim
+            rule = tuple(GaussLobattoJacobiWeights(int(q), 0, 0) for q in nq)
+        elif dim == 1 and len(rule) == 2 and np.ndim(rule[0]) == 1:
+            rule = (rule,)
+        if len(rule) != dim:
+            raise ValueError("rule holds one (nodes, weights) pair per direction")
+        self._rule = tuple((np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(w, dtype=np.float64).reshape(-1)) for x, w in rule)
+        self._op = dict(kappa=kappa, beta=beta, sigma=sigma)
+        self._f = f
+        self.X_u_train = None if X_u_train is None else np.asarray(X_u_train, dtype=np.float64).reshape(-1, dim)
+        self.utrain = None if u_train is None else np.asarray(u_train, dtype=np.float64).reshape(-1)
+        self.LR, self.lossb_weight = LR, lossb_weight
+        self.loss_his = []
+        self._backend_arg = backend
+        self._create(layers, 1, LR, lossb_weight, 1.0, init_params, seed, backend, device)
+        mesh = mesh.copy()
+        self._mesh = mesh
+
+        def populate():
+            self._populate_mesh(self._mesh, self._f)
+            self._hand_data()
+        self._populate = populate
+        populate()
+        self._finish()
+
+    # -- the populate step: _VPINNBase._populate_mesh with this class's rule and point convention, then the operator ----------
+    def _grid_mesh(self):
+        return self._mesh
+
+    def _mesh_rule(self, n_shard, ntx, nty):
+        (xi, wx), (yi, wy) = self._rule[0], (self._rule[1] if len(self._rule) == 2 else (None, None))
+        return xi, wx, yi, wy, ntx
+
+    def _quad_points(self, mesh, eb, ee):
+        xi, yi = self._dev_rule
+        return mesh.quad_points(xi, yi, eb, ee)
+
+    def _f_at_quad(self, mesh, f, eb, ee):
+        return _coef_field(f, self._quad_points(mesh, eb, ee), mesh.dim, "f", False)
+
+    def _hand_operator(self, mesh):
+        """kappa, beta, sigma at this rank's quadrature points as the planes hpv_set_operator takes"""
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        P, d = self._quad_points(mesh, eb, ee), mesh.dim
+        k, b = _coef_field(self._op["kappa"], P, d, "kappa", True), _coef_field(self._op["beta"], P, d, "beta", True)
+        s = _coef_field(self._op["sigma"], P, d, "sigma", False)
+        self.h.set_operator(np.concatenate([k.T, b.T, s[None, :]], axis=0))
+
+    def _populate_mesh(self, mesh, f):
+        super()._populate_mesh(mesh, f)
+        self._hand_operator(mesh)
+
+    def _hand_data(self):
+        if self.rank == 0 and self.X_u_train is not None:
+            self.h.set_data(self.X_u_train, self.utrain)
+
+    def set_operator(self, kappa=None, beta=None, sigma=None):
+        """Re-evaluate the operator on the live model: the coefficients given replace the stored ones (the others stay), all three
+        are evaluated at the current mesh's quadrature points and handed to the library.  Parameters and optimizer state stay."""
+        for k, v in (("kappa", kappa), ("beta", beta), ("sigma", sigma)):
+            if v is not None:
+                self._op[k] = v
+        self._hand_operator(self._mesh)
+
+    def set_mesh(self, mesh, f=None):
+        """As `_VPINNBase.set_mesh`; the coefficients are re-evaluated on the new elements.  f None keeps the model's own f."""
+        if f is None:
+            f = self._f
+        self._f = f
+        super().set_mesh(mesh, f)
+
+    def _no_strong_form(self, what):
+        raise NotImplementedError(f"{what} needs the strong residual of the problem, which takes derivatives of kappa: "
+                                  "not available for VPINNLinear")
+
+    def element_indicators(self, f=None):
+        self._no_strong_form("element_indicators")
+
+    def residual(self, X, f=None):
+        self._no_strong_form("residual")
+
+    def adapt(self, f=None, **mark_kw):
+        self._no_strong_form("adapt")
+
+    def train_adaptive(self, nIter, adapt_every, f=None, max_elements=None, **mark_kw):
+        self._no_strong_form("train_adaptive")
+
+    def _train_n(self, n):
+        self.train(n)
+
+    def predict(self, X):
+        return self._predict(np.asarray(X, dtype=np.float64).reshape(-1, self.layers[0]))
+
+    def train(self, nIter, verbose=False):
+        """nIter Adam iterations; the loss after every update is appended to `loss_his` (device-side history)."""
+        it = 0
+        while it < nIter:
+            n = min(self._RECORD_CHUNK, nIter - it)
+            self.loss_his.extend(float(v) for v in self._step_record(n)[0][:, 0])
+            it += n
+            if verbose and self.rank == 0:
+                print('It: %d, Loss: %.3e' % (it, self.loss_his[-1]))
+        self.h.sync()

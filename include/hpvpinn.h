@@ -29,7 +29,8 @@ extern "C" {
 
 #define HPV_MAX_LAYERS 16
 
-enum { HPV_PDE_POISSON1D = 0, HPV_PDE_POISSON2D = 1, HPV_PDE_ADVDIFF = 2 };
+enum { HPV_PDE_POISSON1D = 0, HPV_PDE_POISSON2D = 1, HPV_PDE_ADVDIFF = 2,
+       HPV_PDE_LINEAR1D = 3, HPV_PDE_LINEAR2D = 4 };   /* variable-coefficient linear problems: hpv_set_operator */
 enum { HPV_ACT_TANH = 0, HPV_ACT_SIN = 1 };
 enum { HPV_BACKEND_AUTO = 0, HPV_BACKEND_GENERIC = 1, HPV_BACKEND_MFMA = 2 };
 enum { HPV_SCHEME_VPINN = 0, HPV_SCHEME_PINN = 1 };
@@ -113,6 +114,30 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n);
  * inside and the counts are re-applied after hpv_set_elements / hpv_set_tables.  NULL, NULL restores "all ntx x nty everywhere"
  * bit for bit.  Refused for 1-D handles, the strong-form PINN scheme, a wrong n and counts out of range. */
 int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n);
+
+/* Variable-coefficient convection-diffusion-reaction problems (an extension: HPV_PDE_LINEAR1D, HPV_PDE_LINEAR2D; no reference
+ * counterpart).  With the sign convention that makes Poisson kx = ky = 1,
+ *     L u = d/dx(kx u_x) + d/dy(ky u_y) + bx u_x + by u_y + s u = f            1-D:  (k u')' + b u' + s u = f
+ * and kx, ky, bx, by, s given at the handle's quadrature points.  Every test function v_kr = phi_r(x) phi_k(y) vanishes on its
+ * element's boundary, so the once-integrated-by-parts residual of element e is
+ *     R[e][k][r] = -(J/Jx) sum_q w_q kx u_x phi_r' phi_k - (J/Jy) sum_q w_q ky u_y phi_r phi_k'
+ *                  + J sum_q w_q (bx u_x + by u_y + s u) phi_r phi_k - F[e][k][r]
+ * (J = Jx Jy; 1-D: no ky / by pieces, J = Jx; table derivatives with respect to the reference coordinate; F as hpv_assemble_rhs
+ * builds it), lossv = sum_e mean over the ACTIVE test functions of R^2, loss = lossb_weight * lossb + lossf + lossv.
+ * Special cases: k = 1, b = s = 0 is Poisson-2D var_form 1; kx = -eps, ky = 0, bx = V, by = 1 is AdvDiff var_form 1 at a fixed
+ * epsilon; 1-D k = -1 is Poisson-1D var_form 2.
+ * Such a handle is created with var_form = 1 and HPV_SCHEME_VPINN (anything else is refused), has no trainable coefficient
+ * (hpv_num_params counts the network alone) and runs forward -> k_project_lin -> reverse (hpv_pass_structure 0).  Everything
+ * else of the variational scheme works on it unchanged; the strong form needs derivatives of k and is refused:
+ * hpv_set_collocation*, hpv_residual_points, hpv_element_indicators (negative status, the handle stays usable).
+ *
+ * coef is [K][n_owned*qx*qy] in planes, K = 3 in 1-D in the order (k, b, s), K = 5 in 2-D in the order (kx, ky, bx, by, s); each
+ * plane element-major over the OWNED elements, q = j*qx + i (the layout of f_quad in hpv_assemble_rhs); n = K*n_owned*qx*qy.
+ * Everything is copied.  Waits for the handle's stream and drops the captured iteration graphs (like hpv_set_data).
+ * hpv_set_elements / hpv_set_element_boxes invalidate the planes: a pass then answers -3 until they are set again.  The planes are
+ * not state: hpv_get_state / hpv_set_state do not carry them.
+ * Returns 0; -1 for a handle of another problem, a wrong n, NULL, a non-finite value; -3 before hpv_set_elements; -2 on a HIP error. */
+int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
 
 /* Boundary / data points of lossb (P1:98, P2:122, P3:184): X is [n][dim] row-major, u is [n].
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
