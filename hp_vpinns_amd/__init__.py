@@ -14,7 +14,7 @@ __all__ = ["Jacobi", "DJacobi", "GaussJacobiWeights", "GaussLobattoJacobiWeights
 
 def __getattr__(name):
     """`from hp_vpinns_amd import VPINN2D` without importing torch / the HIP library at package import."""
-    if name in ("VPINN1D", "VPINN2D", "VPINNAdvDiff", "VPINNLinear"):
+    if name in ("VPINN1D", "VPINN2D", "VPINNAdvDiff", "VPINNLinear", "VPINNNonlinear"):
         from . import vpinn
         return getattr(vpinn, name)
     raise AttributeError(f"module 'hp_vpinns_amd' has no attribute {name!r}")

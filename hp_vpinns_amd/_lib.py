@@ -40,7 +40,7 @@ EXPORTS = [
     "hpv_validation_read", "hpv_step_validate",
     "hpv_set_element_boxes", "hpv_element_indicators",
     "hpv_set_flux_data", "hpv_read_flux_loss",
-    "hpv_set_operator",
+    "hpv_set_operator", "hpv_set_nonlinear",
 ]
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
@@ -136,6 +136,7 @@ def load():
     lib.hpv_set_flux_data.argtypes = [h, _dp, _dp, _dp, C.c_int, C.c_double]
     lib.hpv_read_flux_loss.argtypes = [h, _dp]
     lib.hpv_set_operator.argtypes = [h, _dp, C.c_size_t]
+    lib.hpv_set_nonlinear.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
     lib.hpv_num_params.restype = C.c_size_t
@@ -366,6 +367,12 @@ class Handle:
         (kx, ky, bx, by, s) in 2-D, each element-major over the owned elements, q = j * qx + i."""
         coef = None if coef is None else _c(coef).reshape(-1)
         self._chk(self.lib.hpv_set_operator(self._h, _p(coef), 0 if coef is None else coef.size))
+
+    def set_nonlinear(self, coef):
+        """The planes of the nonlinear term of a linear problem (hpv_set_nonlinear): (M, n_owned * qx * qy), M = 4 rows (a2, a3, ae, g)
+        in 1-D, 5 rows (a2, a3, ae, gx, gy) in 2-D, laid out like set_operator's.  None, or all zeros, removes the term."""
+        coef = None if coef is None else _c(coef).reshape(-1)
+        self._chk(self.lib.hpv_set_nonlinear(self._h, _p(coef), 0 if coef is None else coef.size))
 
     def read_flux_loss(self):
         """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""

@@ -199,6 +199,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_tables) return fail(h, -3, "hpv_set_tables has not been called");
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
+    if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->have_F && !h->d_F && h->n_elem > 0) return fail(h, -3, "internal: F not sliced");
     if (h->batch_dirty) return assemble_batches(h);
@@ -345,7 +346,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
+    void* ptrs[] = {h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -457,6 +458,9 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->have_lin = false;
         if (h->d_lin) { (void)hipFree(h->d_lin); h->d_lin = nullptr; }
+        if (h->nl_mask) h->nl_stale = true;      // a pass must not silently train the linear problem
+        h->nl_mask = 0;
+        if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
     }
     for (long le = 0; le < ne; ++le) {
         const double* box = boxes + (size_t)(e_begin + le) * bs;
@@ -695,6 +699,36 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n) {
     if ((rc = dalloc(h, &h->d_lin, n))) return rc;
     if ((rc = upload(h, h->d_lin, coef, n))) return rc;
     h->have_lin = true;
+    return 0;
+}
+
+// The planes of the nonlinear term (include/hpvpinn.h); k_project_nl reads them in place.  The mask is decided here, once.
+int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_nonlinear belongs to the linear problems");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    const size_t M = h->dim == 1 ? 4 : 5, Nq = (size_t)h->Nq;
+    if ((!coef && n != 0) || (coef && n != M * Nq)) return fail(h, -1, "the nonlinear term has %zu entries, expected %zu planes of %ld", n, M, h->Nq);
+    if (!coef) n = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(coef[i])) return fail(h, -1, "nonlinear plane %zu holds a non-finite value at point %zu", i / std::max(Nq, (size_t)1), i % std::max(Nq, (size_t)1));
+    int mask = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (coef[i] != 0.0) mask |= 1 << std::min(i / Nq, (size_t)3);      // (gx and gy are one term)
+    if (mask && hpv_nonlin_lds_bytes(h->qx, h->qy, h->ntx, h->nty) > 64 * 1024)
+        return fail(h, -1, "element too large for the nonlinear projection kernel's LDS (%zu B)", hpv_nonlin_lds_bytes(h->qx, h->qy, h->ntx, h->nty));
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old planes)
+    drop_graph(h);
+    h->nl_mask = 0;
+    h->nl_stale = false;
+    if (!mask) {                                     // no term: the handle runs k_project_lin again
+        if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
+        return 0;
+    }
+    if ((rc = dalloc(h, &h->d_nl, n))) return rc;
+    if ((rc = upload(h, h->d_nl, coef, n))) return rc;
+    h->nl_mask = mask;
     return 0;
 }
 

@@ -115,6 +115,11 @@ struct hpv_ctx {
     bool linear = false;
     bool have_lin = false;     // the planes belong to the current elements
     double *d_lin = nullptr, *d_jxy = nullptr;
+    // the nonlinear term of such a handle (hpv_set_nonlinear): planes [4 | 5][Nq], the HPV_NL_* mask of the planes that are not zero
+    // everywhere (0: no term, k_project_lin runs), and whether new elements have orphaned a term that has not been set again or removed
+    double* d_nl = nullptr;
+    int nl_mask = 0;
+    bool nl_stale = false;
     // per-element refinement indicators (hpv_element_indicators): the raw 1-D weights [qx | qy] (uploaded with the quadrature), a
     // forward-only object of the full channel set on the quadrature batch's own X and its buffers; re-created when Nq (sizes d_ind_f),
     // the batch size var.N (sizes d_ind_out and the object) or the owned element count (sizes d_ind) changes

@@ -109,6 +109,17 @@ struct LinProjArgs {
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty);
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s);
 
+// The same launch with a pointwise nonlinear term (k_project_nl, kernels_nonlin.hip; hpv_set_nonlinear):
+//   L u + a2 u^2 + a3 u^3 + ae exp(u) + u (gx u_x + gy u_y) = f.   A term outside `mask` is not evaluated and its plane not read.
+enum { HPV_NL_QUADRATIC = 1, HPV_NL_CUBIC = 2, HPV_NL_EXP = 4, HPV_NL_ADVECTION = 8 };
+struct NlProjArgs {
+    LinProjArgs lin;
+    const double* nl;        // planes (a2, a3, ae, g) in 1-D, (a2, a3, ae, gx, gy) in 2-D; layout and stride of lin.coef
+    int mask;                // HPV_NL_* of the planes that are not zero everywhere (never 0: such a handle launches k_project_lin)
+};
+size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty);
+void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s);
+
 struct AdamArgs {
     double *theta, *m, *v, *state;   // theta == nullptr: no update
     double lr, b1, b2, eps;

@@ -231,7 +231,8 @@ static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use
 
 // The linear problems (hpv_set_operator): always forward -> k_project_lin -> reverse.  Their integrand carries per-point coefficients
 // and a third term, which neither ProjDesc nor a whole-iteration kernel knows; the layer kernels are the ones every handle of the
-// channel set u, u_x, (u_y) runs, the merged boundary points ride in the forward launch as ever.
+// channel set u, u_x, (u_y) runs, the merged boundary points ride in the forward launch as ever.  With a nonlinear term
+// (hpv_set_nonlinear) k_project_nl takes k_project_lin's place in the same launch slot; nothing else differs.
 static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_mfma) {
     Batch& v = h->var;
     tstart(h, 0);
@@ -241,12 +242,17 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     tstart(h, 1);
     const LinProjArgs a{v.OUT, v.GBAR, h->d_lin, h->Nq, h->d_F, h->d_R, h->d_loss_e, h->d_wtx, h->d_wty, h->d_jac, h->d_jxy,
                         h->d_jxy + h->n_elem, h->pd.nact, h->pd.nacty, v.N, h->qx, h->qy, h->ntx, h->nty, h->dim, backward ? 1 : 0};
-    launch_project_lin(a, h->n_elem, h->stream);
+    if (h->nl_mask) launch_project_nl(NlProjArgs{a, h->d_nl, h->nl_mask}, h->n_elem, h->stream);      // (hpv_set_nonlinear)
+    else launch_project_lin(a, h->n_elem, h->stream);
     tstop(h, 1);
     if (!backward) return;
     h->pass_structure = 0;
-    snprintf(h->variant, sizeof h->variant, "%s + k_project_lin<%dx%d/%dx%d> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
-             h->qx, h->qy, h->ntx, h->nty, use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
+    std::string terms;                               // the active terms of k_project_nl, e.g. ";u2,u3,exp,adv"
+    static const char* const term_names[] = {"u2", "u3", "exp", "adv"};
+    for (int t = 0; t < 4; ++t)
+        if (h->nl_mask >> t & 1) terms += std::string(terms.empty() ? ";" : ",") + term_names[t];
+    snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
+             h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
     tstart(h, 2);
     if (use_mfma) hpv_mfma_backward(v.m, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);
     else run_bwd(h, v);

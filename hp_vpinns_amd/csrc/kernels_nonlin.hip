@@ -1,0 +1,229 @@
+// k_project_nl: k_project_lin (kernels_linop.hip) with a pointwise nonlinear term on the same handles (HPV_PDE_LINEAR1D / _LINEAR2D)
+//
+//     L u + N(x; u, grad u) = f          N = a2 u^2 + a3 u^3 + ae exp(u) + u (gx u_x + gy u_y)        (1-D: ... + g u u_x)
+//
+// with L the operator of hpv_set_operator, its sign convention unchanged, and a2, a3, ae, gx, gy given per quadrature point
+// (hpv_set_nonlinear).  N is projected against phi_r phi_k without integration by parts, so it joins the first integrand:
+//     t = 0: G0 = (bx u_x + by u_y + s u) + N   tables (0, 0)   c0 = J
+//     t = 1: G1 = kx u_x                        tables (1, 0)   c1 = -(J/Jx)
+//     t = 2: G2 = ky u_y                        tables (0, 1)   c2 = -(J/Jy)                (2-D only)
+// The projection stays linear in its integrands: tables, c_t, masking, F, R and loss_e are those of k_project_lin, and so are the two
+// forward and the two adjoint contractions.  The nonlinearity is undone by the chain rule at the point, after the adjoint ones:
+//     dN/du     = 2 a2 u + 3 a3 u^2 + ae exp(u) + gx u_x + gy u_y
+//     GBAR[u]   = (s + dN/du) Gbar_0
+//     GBAR[u_x] = kx Gbar_1 + (bx + gx u) Gbar_0
+//     GBAR[u_y] = ky Gbar_2 + (by + gy u) Gbar_0.
+// Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
+// y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
+// eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
+// Out of scope: a solution-dependent diffusion coefficient kappa(u); trainable coefficients; the strong form (hpv_set_collocation*,
+// hpv_residual_points and hpv_element_indicators stay refused as for the linear class).
+//
+// Term mask (HPV_NL_*): a plane that is zero at every owned point is left out of the mask on the host, and its term is not evaluated
+// at all -- the branch is uniform over the grid, an exp nobody asked for is never computed and 0 * inf cannot arise.  exp(u) is
+// evaluated once per point and phase and serves N and dN/du; there is no guard against its overflow.
+// The channels and exp(u) are NOT kept in LDS across the two contraction phases: the adjoint phase reads u, u_x, u_y from OUT again
+// (L2-resident, 3 coalesced loads per point) and recomputes the one exp, so the kernel's LDS footprint is k_project_lin's to the byte
+// and as many workgroups share a CU (profiles/nonlinear_terms.md).
+// One 256-thread workgroup per element, run-time shapes, odd-padded LDS rows, every sum in index order in one thread, the block sum
+// a fixed tree: no atomics, the same bits from call to call.  A zero-weight padding point has all-zero table columns: whatever finite
+// value N takes there is multiplied by 0 in T, and its Gbar_0 = 0 makes every GBAR entry above 0.
+#include "hpv_internal.h"
+
+namespace {
+
+__device__ __forceinline__ int odd(int n) { return n | 1; }
+
+// sum over the 256 threads, fixed order: butterfly inside each wave, the four wave sums added in wave order; every thread gets it
+__device__ __forceinline__ double nl_block_sum(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[w] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// N and dN/du at one point; ga = gx u_x + gy u_y (0 without the advection term).  Terms outside the mask are not touched.
+__device__ __forceinline__ void nl_point(int mask, const double* nl, long cs, double u, double ga, double& Nv, double& dNu) {
+    double n = 0.0, d = 0.0;
+    if (mask & HPV_NL_QUADRATIC) {
+        const double a2 = nl[0];
+        n = a2 * (u * u);
+        d = 2.0 * (a2 * u);
+    }
+    if (mask & HPV_NL_CUBIC) {
+        const double a3 = nl[cs], uu = u * u;
+        n += a3 * (uu * u);
+        d += 3.0 * (a3 * uu);
+    }
+    if (mask & HPV_NL_EXP) {
+        const double t = nl[2 * cs] * exp(u);
+        n += t;
+        d += t;
+    }
+    if (mask & HPV_NL_ADVECTION) {
+        n += u * ga;
+        d += ga;
+    }
+    Nv = n;
+    dNu = d;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const LinProjArgs& a = b.lin;
+    const long e = blockIdx.x;
+    const int qx = a.qx, qy = a.qy, ntx = a.ntx, nty = a.nty, nt = a.dim + 1;
+    const int NQ = qx * qy, NR = ntx * nty;
+    const int gs = odd(qx), ts = odd(ntx), xs = odd(qx), ys = odd(qy);
+    double* G = sm;                            // [nt][qy][gs]
+    double* T = G + 3 * qy * gs;               // [nt][qy][ts]   T_t, later S_t
+    double* U = T + 3 * qy * ts;               // [nty][ntx]
+    double* X = U + NR;                        // [2][ntx][xs]   w phi, w phi' of the x direction
+    double* Y = X + 2 * ntx * xs;              // [2][nty][ys]
+    double* red = Y + 2 * nty * ys;            // [4]
+    const int tid = threadIdx.x;
+    const long base = e * NQ, N = a.N;
+    const long cs = a.coef_stride;
+    const double* cf = a.coef + base;
+    const double* nl = b.nl + base;            // planes a2, a3, ae, gx, (gy), the stride of the operator's
+    const int mask = b.mask;
+    const bool adv = mask & HPV_NL_ADVECTION;
+
+    // ---- stage the tables and the three integrands ----
+    for (int idx = tid; idx < 2 * ntx * qx; idx += 256) {
+        const int row = idx / qx, i = idx - row * qx;       // row = d * ntx + r: the first two planes of wtx are contiguous
+        X[row * xs + i] = a.wtx[idx];
+    }
+    for (int idx = tid; idx < 2 * nty * qy; idx += 256) {
+        const int row = idx / qy, j = idx - row * qy;
+        Y[row * ys + j] = a.wty[idx];
+    }
+    for (int q = tid; q < NQ; q += 256) {
+        const int j = q / qx, i = q - j * qx;
+        const double u = a.OUT[base + q], ux = a.OUT[N + base + q];
+        double Nv, dNu;
+        if (a.dim == 2) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double kx = cf[q], ky = cf[cs + q], bx = cf[2 * cs + q], by = cf[3 * cs + q], s = cf[4 * cs + q];
+            const double ga = adv ? nl[3 * cs + q] * ux + nl[4 * cs + q] * uy : 0.0;
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            G[j * gs + i] = ((bx * ux + by * uy) + s * u) + Nv;
+            G[(qy + j) * gs + i] = kx * ux;
+            G[(2 * qy + j) * gs + i] = ky * uy;
+        } else {
+            const double k = cf[q], bb = cf[cs + q], s = cf[2 * cs + q];
+            const double ga = adv ? nl[3 * cs + q] * ux : 0.0;
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            G[j * gs + i] = (bb * ux + s * u) + Nv;
+            G[(qy + j) * gs + i] = k * ux;
+        }
+    }
+    __syncthreads();
+
+    // ---- T_t[j][r] = sum_i WTX[dx_t][r][i] G_t[j][i],  dx = (0, 1, 0) ----
+    for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
+        const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy;
+        const double* ax = X + ((t == 1 ? ntx : 0) + r) * xs;
+        const double* g = G + tj * gs;
+        double acc = 0.0;
+        for (int i = 0; i < qx; ++i) acc += ax[i] * g[i];
+        T[tj * ts + r] = acc;
+    }
+    __syncthreads();
+
+    // ---- U[k][r] = sum_t c_t sum_j WTY[dy_t][k][j] T_t[j][r] - F,  dy = (0, 0, 1); masked; loss ----
+    const double J = a.J[e];
+    const double c0 = J, c1 = -(J / a.Jx[e]), c2 = a.dim == 2 ? -(J / a.Jy[e]) : 0.0;
+    const int nax = a.nact ? a.nact[e] : ntx;
+    const int nay = a.nacty ? a.nacty[e] : nty;
+    const double NRa = (double)(nax * nay);
+    double sq = 0.0;
+    for (int idx = tid; idx < NR; idx += 256) {
+        const int k = idx / ntx, r = idx - k * ntx;
+        double v = 0.0;
+        if (r < nax && k < nay) {
+            const double* y0 = Y + k * ys;
+            const double* y1 = Y + (nty + k) * ys;
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            for (int j = 0; j < qy; ++j) {
+                a0 += y0[j] * T[j * ts + r];
+                a1 += y0[j] * T[(qy + j) * ts + r];
+            }
+            if (a.dim == 2)
+                for (int j = 0; j < qy; ++j) a2 += y1[j] * T[(2 * qy + j) * ts + r];
+            v = ((c0 * a0 + c1 * a1) + c2 * a2) - (a.F ? a.F[e * NR + idx] : 0.0);
+        }
+        U[idx] = v;
+        a.R[e * NR + idx] = v;
+        sq += v * v;
+    }
+    sq = nl_block_sum(sq, red);           // (its barriers also order U before the adjoint and T's readers before S's writers)
+    if (tid == 0) a.loss_e[e] = sq / NRa;
+    if (!a.do_adjoint) return;
+
+    // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
+    const double sc = 2.0 / NRa;
+    for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
+        const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
+        const double* y = Y + (t == 2 ? nty * ys : 0) + j;
+        double acc = 0.0;
+        for (int k = 0; k < nty; ++k) acc += y[k * ys] * U[k * ntx + r];
+        T[tj * ts + r] = (t == 0 ? c0 : t == 1 ? c1 : c2) * (sc * acc);
+    }
+    __syncthreads();
+
+    // ---- Gbar_t[j][i] = sum_r WTX[dx_t][r][i] S_t[j][r]; the chain rule at the point; the adjoints of the channels ----
+    for (int q = tid; q < NQ; q += 256) {
+        const int j = q / qx, i = q - j * qx;
+        const double* s0 = T + j * ts;
+        const double* s1 = T + (qy + j) * ts;
+        const double* s2 = T + (2 * qy + j) * ts;
+        double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+        for (int r = 0; r < ntx; ++r) {
+            const double x0 = X[r * xs + i], x1 = X[(ntx + r) * xs + i];
+            g0 += x0 * s0[r];
+            g1 += x1 * s1[r];
+            if (a.dim == 2) g2 += x0 * s2[r];
+        }
+        const double u = a.OUT[base + q], ux = a.OUT[N + base + q];
+        double Nv, dNu;
+        if (a.dim == 2) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double kx = cf[q], ky = cf[cs + q], s = cf[4 * cs + q];
+            double bx = cf[2 * cs + q], by = cf[3 * cs + q], ga = 0.0;
+            if (adv) {
+                const double gx = nl[3 * cs + q], gy = nl[4 * cs + q];
+                ga = gx * ux + gy * uy;
+                bx += gx * u;
+                by += gy * u;
+            }
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            a.GBAR[base + q] = (s + dNu) * g0;
+            a.GBAR[N + base + q] = kx * g1 + bx * g0;
+            a.GBAR[2 * N + base + q] = ky * g2 + by * g0;
+        } else {
+            const double k = cf[q], s = cf[2 * cs + q];
+            double bb = cf[cs + q], ga = 0.0;
+            if (adv) {
+                const double g = nl[3 * cs + q];
+                ga = g * ux;
+                bb += g * u;
+            }
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            a.GBAR[base + q] = (s + dNu) * g0;
+            a.GBAR[N + base + q] = k * g1 + bb * g0;
+        }
+    }
+}
+
+// (the channels are re-read from OUT in the adjoint phase, so nothing is added to k_project_lin's layout)
+size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop_lds_bytes(qx, qy, ntx, nty); }
+
+void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s) {
+    if (n_elem <= 0) return;
+    hipLaunchKernelGGL(k_project_nl, dim3((unsigned)n_elem), dim3(256), hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+}

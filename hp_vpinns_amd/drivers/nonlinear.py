@@ -1,0 +1,128 @@
+"""Three standard nonlinear problems on the variable-coefficient class with a pointwise nonlinear term (VPINNNonlinear), each with an
+exact or manufactured solution and Dirichlet data from it; prints the relative L2 error.
+
+  bratu        u'' + lam exp(u) = 0 on [0, 1], u(0) = u(1) = 0; the lower branch in closed form,
+               u = -2 ln(cosh((x - 1/2) th / 2) / cosh(th / 4)), th the lower root of th = sqrt(2 lam) cosh(th / 4)
+               (lam below the critical 3.5138).  In the class's convention: kappa = 1, exponential = lam, f = 0.
+  burgers      u_t + u u_x - nu u_xx = f in space-time, (x, t) in [-1, 1] x [0, 1] with y = t: kappa = (-nu, 0), beta = (0, 1),
+               advection = (1, 0); u = exp(-t) sin(pi x) manufactured, f from it; data on t = 0 and x = +-1.
+  allen-cahn   eps^2 lap u + u - u^3 = 0 on [-1, 1]^2: kappa = eps^2, sigma = 1, cubic = -1; the exact diagonal front
+               u = tanh((x + y) / (2 eps)) (the 1-D steady front tanh(s / (sqrt(2) eps)) along s = (x + y) / sqrt(2)), f = 0; data on all four sides.
+
+    python -m hp_vpinns_amd.drivers.nonlinear bratu --lam 1.0
+    python -m hp_vpinns_amd.drivers.nonlinear burgers --nu 0.05
+    python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.2
+
+`setup(problem, ...)` builds everything a run needs on the host (no GPU); `run(s, ...)` creates the model from it and trains.
+"""
+import argparse
+
+import numpy as np
+
+# the smallest setting of the Bratu run (tests/test_gpu_nonlinear.py trains it once)
+SMALLEST = dict(problem="bratu", lam=1.0, n_elements=3, n_quad=8, n_test=4, width=8, depth=2)
+
+
+def bratu_theta(lam):
+    """the lower root of th = sqrt(2 lam) cosh(th / 4), by bisection between 0 and the maximum of th - sqrt(2 lam) cosh(th / 4)"""
+    c = np.sqrt(2.0 * float(lam))
+
+    def g(th):
+        return th - c * np.cosh(th / 4.0)
+    lo, hi = 0.0, 4.0 * np.arcsinh(4.0 / c)
+    if not (lam > 0 and g(hi) > 0):
+        raise ValueError("Bratu's problem has its two solutions for 0 < lam < 3.5138 only")
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if g(mid) < 0 else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def bratu_exact(x, lam):
+    th = bratu_theta(lam)
+    x = np.asarray(x, dtype=np.float64)
+    return -2.0 * np.log(np.cosh((x - 0.5) * th / 2.0) / np.cosh(th / 4.0))
+
+
+def _burgers_exact(P):
+    return np.exp(-P[:, 1]) * np.sin(np.pi * P[:, 0])
+
+
+def _allen_cahn_exact(P, eps):
+    return np.tanh((P[:, 0] + P[:, 1]) / (2.0 * eps))
+
+
+def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test=5, width=20, depth=3, n_bound=40, lossb_weight=10.0):
+    """dict(layers, model = the keyword arguments of VPINNNonlinear, X_test, u_test) of one of the three problems"""
+    hidden = [int(width)] * int(depth)
+    if problem == "bratu":
+        ne = 4 if n_elements is None else int(n_elements)
+        X = np.linspace(0.0, 1.0, 401)[:, None]
+        return dict(layers=[1] + hidden + [1], X_test=X, u_test=bratu_exact(X, lam),
+                    model=dict(grid_x=np.linspace(0.0, 1.0, ne + 1), n_quad=int(n_quad), n_test=int(n_test), kappa=1.0, exponential=float(lam), f=0.0,
+                               X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2), lossb_weight=lossb_weight, activation="sin"))
+    ne = 4 if n_elements is None else int(n_elements)
+    t = np.linspace(-1.0, 1.0, int(n_bound))
+    if problem == "burgers":
+        nu = float(nu)
+
+        def f(P):
+            u = _burgers_exact(P)
+            ux = np.pi * np.exp(-P[:, 1]) * np.cos(np.pi * P[:, 0])
+            return -u + u * ux + nu * np.pi ** 2 * u               # u_t + u u_x - nu u_xx
+        s = (t + 1.0) / 2.0
+        Xb = np.concatenate([np.stack([t, 0 * t], 1), np.stack([0 * s - 1.0, s], 1), np.stack([0 * s + 1.0, s], 1)])
+        exact, gy = _burgers_exact, np.linspace(0.0, 1.0, ne + 1)
+        op = dict(kappa=np.array([-nu, 0.0]), beta=np.array([0.0, 1.0]), advection=np.array([1.0, 0.0]), f=f)
+        g = np.stack([v.reshape(-1) for v in np.meshgrid(np.linspace(-1.0, 1.0, 81), np.linspace(0.0, 1.0, 41))], 1)
+    elif problem == "allen-cahn":
+        eps = float(eps)
+
+        def exact(P):
+            return _allen_cahn_exact(P, eps)
+        o = np.ones_like(t)
+        Xb = np.concatenate([np.stack([t, -o], 1), np.stack([t, o], 1), np.stack([-o, t], 1), np.stack([o, t], 1)])
+        gy = np.linspace(-1.0, 1.0, ne + 1)
+        op = dict(kappa=eps ** 2, sigma=1.0, cubic=-1.0, f=0.0)
+        g = np.stack([v.reshape(-1) for v in np.meshgrid(np.linspace(-1.0, 1.0, 81), np.linspace(-1.0, 1.0, 81))], 1)
+    else:
+        raise ValueError("problem is one of bratu, burgers, allen-cahn")
+    return dict(layers=[2] + hidden + [1], X_test=g, u_test=exact(g)[:, None],
+                model=dict(grid_x=np.linspace(-1.0, 1.0, ne + 1), grid_y=gy, n_quad=int(n_quad), n_test=int(n_test), X_u_train=Xb, u_train=exact(Xb),
+                           lossb_weight=lossb_weight, **op))
+
+
+def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True):
+    """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated)."""
+    from ..vpinn import VPINNNonlinear
+    m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, **s["model"])
+    his = None
+    if validate_every:
+        m.set_validation(s["X_test"], s["u_test"])
+        his = m.train_validated(int(n_iter), int(validate_every))
+        if verbose:
+            for it, e2, emax in zip(*his):
+                print("It: %d, relative L2 error %.4e, max error %.4e" % (it, e2, emax))
+    else:
+        m.train(int(n_iter), verbose=verbose)
+    err = m.rel_l2_error(s["X_test"], s["u_test"])
+    if verbose:
+        print("relative L2 error %.4e after %d iterations (%s)" % (err, n_iter, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, history=his, loss_his=np.asarray(m.loss_his))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("problem", choices=["bratu", "burgers", "allen-cahn"])
+    ap.add_argument("--lam", type=float, default=1.0)
+    ap.add_argument("--nu", type=float, default=0.05)
+    ap.add_argument("--eps", type=float, default=0.2)
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--width", type=int, default=20)
+    ap.add_argument("--validate-every", type=int, default=0)
+    a = ap.parse_args(argv)
+    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width), n_iter=a.iters, validate_every=a.validate_every)
+
+
+if __name__ == "__main__":
+    main()

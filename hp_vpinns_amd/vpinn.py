@@ -1398,3 +1398,41 @@ class VPINNLinear(_VPINNBase):
             if verbose and self.rank == 0:
                 print('It: %d, Loss: %.3e' % (it, self.loss_his[-1]))
         self.h.sync()
+
+
+class VPINNNonlinear(VPINNLinear):
+    """`VPINNLinear` with a pointwise nonlinear term (include/hpvpinn.h: hpv_set_nonlinear; the projection runs in k_project_nl):
+
+        div(kappa grad u) + beta . grad u + sigma u + N(x; u, grad u) = f
+        N = quadratic u^2 + cubic u^3 + exponential exp(u) + u (advection . grad u)
+
+    `quadratic`, `cubic`, `exponential`: a constant or a callable of the points (n, dim) returning (n,); `advection` is vector-valued
+    like `beta` (a constant, one (dim,) vector, or a callable returning (n, dim)).  They are evaluated at the rank's own quadrature
+    points with the operator and again in `set_mesh`.  A term that is zero everywhere is not evaluated on the device; with all four
+    zero the model runs exactly what `VPINNLinear` runs.  Steady Bratu is kappa = 1, exponential = lambda; Allen-Cahn kappa = eps^2,
+    sigma = 1, cubic = -1; space-time viscous Burgers (y = t) kappa = (-nu, 0), beta = (0, 1), advection = (1, 0).
+    Everything else is `VPINNLinear`'s, the refusal of the strong form included."""
+
+    def __init__(self, layers, *, quadratic=0.0, cubic=0.0, exponential=0.0, advection=0.0, **kw):
+        self._nl = dict(quadratic=quadratic, cubic=cubic, exponential=exponential, advection=advection)
+        super().__init__(layers, **kw)
+
+    def _hand_nonlinear(self, mesh):
+        """the four terms at this rank's quadrature points as the planes hpv_set_nonlinear takes"""
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        P, d = self._quad_points(mesh, eb, ee), mesh.dim
+        a = [_coef_field(self._nl[k], P, d, k, False) for k in ("quadratic", "cubic", "exponential")]
+        g = _coef_field(self._nl["advection"], P, d, "advection", True)
+        self.h.set_nonlinear(np.concatenate([np.stack(a, 0), g.T], axis=0))
+
+    def _populate_mesh(self, mesh, f):
+        super()._populate_mesh(mesh, f)
+        self._hand_nonlinear(mesh)
+
+    def set_nonlinear(self, quadratic=None, cubic=None, exponential=None, advection=None):
+        """Re-evaluate the nonlinear term on the live model: the coefficients given replace the stored ones (the others stay), all
+        are evaluated at the current mesh's quadrature points and handed to the library.  Parameters and optimizer state stay."""
+        for k, v in (("quadratic", quadratic), ("cubic", cubic), ("exponential", exponential), ("advection", advection)):
+            if v is not None:
+                self._nl[k] = v
+        self._hand_nonlinear(self._mesh)

@@ -139,6 +139,32 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
  * Returns 0; -1 for a handle of another problem, a wrong n, NULL, a non-finite value; -3 before hpv_set_elements; -2 on a HIP error. */
 int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
 
+/* A pointwise nonlinear term on a handle of the class above (HPV_PDE_LINEAR1D / _LINEAR2D).  With L u the operator of
+ * hpv_set_operator and its sign convention unchanged,
+ *     L u + N(x; u, grad u) = f
+ *     N = a2 u^2 + a3 u^3 + ae exp(u) + u (gx u_x + gy u_y)                     1-D:  a2 u^2 + a3 u^3 + ae exp(u) + g u u_x
+ * with a2, a3, ae, gx, gy given at the handle's quadrature points.  N is projected against phi_r phi_k without integration by
+ * parts: it joins the integrand (bx u_x + by u_y + s u) of R above; tables, masking, F, lossv and the loss triple are unchanged,
+ * and the gradient follows by the chain rule at the point (k_project_nl, csrc/kernels_nonlin.hip).
+ * Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
+ * y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
+ * eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
+ * Out of scope: a solution-dependent diffusion coefficient, trainable coefficients, and the strong form (hpv_set_collocation*,
+ * hpv_residual_points, hpv_element_indicators stay refused as for the linear class).  exp(u) is not guarded against overflow.
+ *
+ * coef is [M][n_owned*qx*qy] in planes, M = 4 in 1-D in the order (a2, a3, ae, g), M = 5 in 2-D in the order (a2, a3, ae, gx, gy),
+ * the layout of hpv_set_operator; n = M*n_owned*qx*qy.  A plane that is zero at every owned point switches its term off: it is
+ * not evaluated at all (gx and gy count as one term).  NULL with n = 0, or planes that are all zero, remove the term: the handle
+ * then runs k_project_lin again and computes bit for bit what a handle that never had the term computes.
+ * Everything is copied.  Waits for the handle's stream and drops the captured iteration graphs (like hpv_set_operator).
+ * hpv_set_elements / hpv_set_element_boxes invalidate the planes: a handle that HAD a term then answers -3 from a pass
+ * ("hpv_set_nonlinear has not been called again") until the planes are set again or removed -- it never silently trains the
+ * linear problem.  The planes are not state: hpv_get_state / hpv_set_state do not carry them.
+ * hpv_kernel_variant names the kernel and the active terms, e.g. k_project_nl<6x5/4x3;u2,u3,exp,adv>; hpv_pass_structure stays 0.
+ * Returns 0; -1 for a handle of another problem, a wrong n, a non-finite value, a shape beyond the kernel's LDS; -3 before
+ * hpv_set_elements; -2 on a HIP error. */
+int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n);
+
 /* Boundary / data points of lossb (P1:98, P2:122, P3:184): X is [n][dim] row-major, u is [n].
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
 int hpv_set_data(hpv_handle h, const double* X, const double* u, int n);
