@@ -11,8 +11,15 @@
 //              integrated channels u_x, u_y go to LDS.
 //     phase P  projection of the element from LDS (sum-factorised, P2:98-105), residual R = U - F, element loss
 //              (P2:117-120), adjoint of u_x, u_y back into the same LDS array.
-//     phase R  reverse pass of the same tiles: the tangent pre-activations z_x, z_y are RECOMPUTED from s on the MFMA
-//              pipe (2 channels x (L-1) layer products), then the hand-derived reverse pass of kernels_mfma.hip.
+//     phase R  reverse pass of the same tiles along ONE directional tangent per point.  After phase P the adjoints gx, gy of
+//              u_x, u_y at a point are plain numbers, and first-order Taylor channels are linear in the input tangent:
+//              gx u_x + gy u_y = D_d u with d = (gx, gy).  So the pass carries two channels, not three -- the value (adjoint 0
+//              on element tiles, the data adjoint on boundary / data tiles) and the tangent along d with adjoint 1 on its
+//              output: z_d = gx W1[0,:] + gy W1[1,:] in layer 0, RECOMPUTED from s on the MFMA pipe in the layers above
+//              (ONE product per layer), hbar_d = w_o at the head, zbar_d = s' hbar_d, zbar_0 = s' hbar_0 + s'' z_d hbar_d,
+//              two W zbar^T products and two channels of dW per layer, and dW1[c] += x_c zbar_0 + g_c zbar_d.  (A second-order
+//              channel, NT2 > 0, depends on z_x^2, z_y^2 and keeps the hand-derived pass of kernels_mfma.hip over every channel;
+//              so does the packed quarter tile, whose slot packing is a design of its own.)
 //   The activation store of the two-kernel path (1 120 B/point written by the forward and read by the reverse kernel,
 //   248 MB of HBM traffic per iteration at config 4) does not exist here: per iteration the kernel reads the
 //   coordinates twice (L2-resident), F, the parameters, and writes R, the element losses and one gradient row per
@@ -983,6 +990,121 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             gb[0] = gdat; gb[1] = 0.0; gb[2] = 0.0;
             if constexpr (NT2 > 0) gb[3] = 0.0;
         }
+        if constexpr (NT2 == 0) {
+        // Two channels instead of three.  Without a second tangent the loss reaches a point only through gb[1] u_x + gb[2] u_y, and
+        // first-order Taylor channels are linear in the input tangent: that sum is the ONE directional derivative D_d u along
+        // d = (gb[1], gb[2]), whose output carries the adjoint 1.  So the reverse pass runs over the value channel (adjoint gb[0]:
+        // zero on element tiles) and the tangent channel along d -- z_d = gb[1] z_x + gb[2] z_y in every layer, hbar_d = w_o at the
+        // head -- and the direction comes back only in the first layer's weight gradient.  Boundary / data tiles: d = 0, the tangent
+        // channel's inputs are zeros (its adjoints are not, but they only ever multiply those zeros).
+        // tangent pre-activations along d: layer 0 has z_d = gb[1] W1[0,:] + gb[2] W1[1,:]; layer i: z_d = (sigma'(z_{i-1}) z_d,{i-1}) W_i
+        // (recomputed from s on the matrix pipe: one product per layer)
+        double zd[L][MF_KS];
+#pragma unroll
+        for (int s = 0; s < MF_KS; ++s)
+            zd[0][s] = fma(gb[1], lds[M::W1O + (0 * MF_KS + s) * 64 + lofs], gb[2] * lds[M::W1O + (1 * MF_KS + s) * 64 + lofs]);
+#pragma unroll
+        for (int i = 1; i < L; ++i) {
+            double hd[MF_KS];
+#pragma unroll
+            for (int s = 0; s < MF_KS; ++s) {
+                const double a = sv[(i - 1) * MF_KS + s];
+                hd[s] = (1.0 - a * a) * zd[i - 1][s];
+            }
+            fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hd, zd[i]);
+        }
+
+        FZ_SEG(0);
+        double hbar[2][MF_KS], zbar[2][MF_KS];      // [0] the value channel, [1] the tangent along d
+        // ---- linear head ----
+#pragma unroll
+        for (int s = 0; s < MF_KS; ++s) {
+            const double a = sv[(L - 1) * MF_KS + s], a1 = 1.0 - a * a;
+            const double wo = lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
+            if (k >= n_el) dWo[s] = fma(a, gb[0], dWo[s]);       // (wave-uniform; element tiles have no adjoint of the value channel)
+            dWo[s] = fma(a1, zd[L - 1][s], dWo[s]);
+            hbar[0][s] = gb[0] * wo; hbar[1][s] = wo;
+        }
+        if (q == 0) dbo += gb[0];
+        FZ_SEG(1);
+
+        // ---- hidden layers, last to first ----
+#pragma unroll
+        for (int i = L - 1; i >= 0; --i) {
+#pragma unroll
+            for (int s = 0; s < MF_KS; ++s) {
+                const double a = sv[i * MF_KS + s];
+                const double a1 = 1.0 - a * a, a2 = -2.0 * a * a1;
+                zbar[1][s] = hbar[1][s] * a1;
+                const double zb = hbar[0][s] * a1 + a2 * (hbar[1][s] * zd[i][s]);
+                zbar[0][s] = zb;
+                db[i][s] += zb;
+            }
+            if (i == 0) {
+#pragma unroll
+                for (int s = 0; s < MF_KS; ++s) {
+                    dW1[0][s] += x0 * zbar[0][s] + gb[1] * zbar[1][s];
+                    dW1[1][s] += x1 * zbar[0][s] + gb[2] * zbar[1][s];
+                }
+            } else {
+                // weight gradient dW_i[in][out] = sum_pt sum_ch h_{i-1,ch}[pt][in] zbar_ch[pt][out]: the operands are needed
+                // point-major -> per-wave LDS transpose tiles, both channels written first (one wave-level sync)
+                pj_wave_sync();
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    double* TA = TAB + (2 * ch) * (MF_TRB * MF_LD);
+                    double* TB = TA + MF_TRB * MF_LD;
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) {
+                        const double a = sv[(i - 1) * MF_KS + s], a1 = 1.0 - a * a;
+                        const double hv = ch == 0 ? a : a1 * zd[i - 1][s];
+                        TA[(4 * s + q) * MF_LD + pt] = hv;
+                        TB[(4 * s + q) * MF_LD + pt] = zbar[ch][s];
+                    }
+                }
+                // hbar_{i-1}^T = W_i zbar^T  (independent of the transposes: issued while the LDS writes above land)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+                    double h4 = 0.0;
+                    const double* wrl = lds + M::WRB + (i - 1) * MF_KS * 16 + q * 4 + (lane & 3);
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) {
+                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lds[M::WN + ((i - 1) * MF_KS + s) * 64 + lofs], zbar[ch][s], acc, 0, 0, 0);
+                        h4 = __builtin_amdgcn_mfma_f64_4x4x4f64(wrl[s * 16], zbar[ch][s], h4, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) hbar[ch][s] = acc[s];
+                    hbar[ch][4] = h4;
+                }
+                FZ_SEG(2 + 2 * (L - 1 - i));
+                pj_wave_sync();
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const double* TA = TAB + (2 * ch) * (MF_TRB * MF_LD);
+                    const double* TB = TA + MF_TRB * MF_LD;
+                    double aF[4], bF[4], aS[4], bS[4];
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        aF[kk] = TA[pt * MF_LD + 4 * kk + q];
+                        bF[kk] = TB[pt * MF_LD + 4 * kk + q];
+                        aS[kk] = TA[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
+                        bS[kk] = TB[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        dWacc[i - 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aF[kk], bF[kk], dWacc[i - 1], 0, 0, 0);
+                        dS10[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(aS[kk], bF[kk], dS10[i - 1], 0, 0, 0);
+                        dS01[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(bS[kk], aF[kk], dS01[i - 1], 0, 0, 0);
+                    }
+                    accC[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(TA[(16 + (lane & 3)) * MF_LD + (pt & 12) + q],
+                                                                   TB[(16 + (lane & 3)) * MF_LD + (pt & 12) + q], accC[i - 1], 0, 0, 0);
+                }
+                FZ_SEG(3 + 2 * (L - 1 - i));
+            }
+        }
+        } else {
+        // (NT2 > 0: the mixed second tangent depends on z_x^2 and z_y^2 separately -- every channel on its own)
         // tangent pre-activations of every hidden layer: layer 0 has z_c = W1[c,:]; layer i: z_c = (sigma'(z_{i-1}) z_c,{i-1}) W_i
         // (recomputed from s on the matrix pipe)
         double zc[L][2][MF_KS];
@@ -1061,60 +1183,6 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             } else {
                 // weight gradient dW_i[in][out] = sum_pt sum_ch h_{i-1,ch}[pt][in] zbar_ch[pt][out]: the operands are needed
                 // point-major -> per-wave LDS transpose tiles, all channels written first (one wave-level sync)
-                if constexpr (NT2 == 0) {      // (three channels: ONE pass -- the headline instantiations' text, kept as it was)
-                pj_wave_sync();
-#pragma unroll
-                for (int ch = 0; ch < FZ_C; ++ch) {
-                    double* TA = TAB + (2 * ch) * (MF_TRB * MF_LD);
-                    double* TB = TA + MF_TRB * MF_LD;
-#pragma unroll
-                    for (int s = 0; s < MF_KS; ++s) {
-                        const double a = sv[(i - 1) * MF_KS + s], a1 = 1.0 - a * a;
-                        const double hv = ch == 0 ? a : a1 * ZC(i - 1, ch - 1, s);
-                        TA[(4 * s + q) * MF_LD + pt] = hv;
-                        TB[(4 * s + q) * MF_LD + pt] = zbar[ch][s];
-                    }
-                }
-                // hbar_{i-1}^T = W_i zbar^T  (independent of the transposes: issued while the LDS writes above land)
-#pragma unroll
-                for (int ch = 0; ch < FZ_C; ++ch) {
-                    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
-                    double h4 = 0.0;
-                    const double* wrl = lds + M::WRB + (i - 1) * MF_KS * 16 + q * 4 + (lane & 3);
-#pragma unroll
-                    for (int s = 0; s < MF_KS; ++s) {
-                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lds[M::WN + ((i - 1) * MF_KS + s) * 64 + lofs], zbar[ch][s], acc, 0, 0, 0);
-                        h4 = __builtin_amdgcn_mfma_f64_4x4x4f64(wrl[s * 16], zbar[ch][s], h4, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) hbar[ch][s] = acc[s];
-                    hbar[ch][4] = h4;
-                }
-                FZ_SEG(2 + 2 * (L - 1 - i));
-                pj_wave_sync();
-#pragma unroll
-                for (int ch = 0; ch < FZ_C; ++ch) {
-                    const double* TA = TAB + (2 * ch) * (MF_TRB * MF_LD);
-                    const double* TB = TA + MF_TRB * MF_LD;
-                    double aF[4], bF[4], aS[4], bS[4];
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        aF[kk] = TA[pt * MF_LD + 4 * kk + q];
-                        bF[kk] = TB[pt * MF_LD + 4 * kk + q];
-                        aS[kk] = TA[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
-                        bS[kk] = TB[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
-                    }
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        dWacc[i - 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aF[kk], bF[kk], dWacc[i - 1], 0, 0, 0);
-                        dS10[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(aS[kk], bF[kk], dS10[i - 1], 0, 0, 0);
-                        dS01[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(bS[kk], aF[kk], dS01[i - 1], 0, 0, 0);
-                    }
-                    accC[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(TA[(16 + (lane & 3)) * MF_LD + (pt & 12) + q],
-                                                                   TB[(16 + (lane & 3)) * MF_LD + (pt & 12) + q], accC[i - 1], 0, 0, 0);
-                }
-                FZ_SEG(3 + 2 * (L - 1 - i));
-                } else {
                 pj_wave_sync();
                 // (C > TRG, the four-channel forms: the transposes go through LDS in passes of TRG channels; `put` / `mul` = one pass)
                 auto tr_put = [&](int c0) {
@@ -1184,9 +1252,9 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                     tr_mul();
                 }
                 FZ_SEG(3 + 2 * (L - 1 - i));
-                }
             }
         }
+        }      // (NT2 > 0)
         FZ_SEG(1 + 2 * L);
     };
 #undef ZC
