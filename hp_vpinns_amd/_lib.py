@@ -41,7 +41,9 @@ EXPORTS = [
     "hpv_set_element_boxes", "hpv_element_indicators",
     "hpv_set_flux_data", "hpv_read_flux_loss",
     "hpv_set_operator", "hpv_set_nonlinear",
+    "hpv_create_ex", "hpv_set_trainable",
 ]
+MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
 
@@ -123,6 +125,8 @@ def load():
     lib = C.CDLL(path, mode=C.RTLD_GLOBAL if path == LIB_PATH else C.RTLD_LOCAL)
     h = C.c_void_p
     lib.hpv_create.argtypes = [C.POINTER(h), C.POINTER(HpvConfig)]
+    lib.hpv_create_ex.argtypes = [C.POINTER(h), C.POINTER(HpvConfig), C.c_int]
+    lib.hpv_set_trainable.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_destroy.argtypes = [h]
     lib.hpv_destroy.restype = None
     lib.hpv_last_error.argtypes = [h]
@@ -240,7 +244,8 @@ class Handle:
     """Thin RAII wrapper over an `hpv_handle`; every method maps 1:1 onto a C entry point."""
 
     def __init__(self, pde, var_form, act, layers, lr=1e-3, lossb_weight=1.0, V=1.0, device=0,
-                 backend=BACKEND_AUTO, beta1=0.9, beta2=0.999, eps=1e-8, scheme=SCHEME_VPINN):
+                 backend=BACKEND_AUTO, beta1=0.9, beta2=0.999, eps=1e-8, scheme=SCHEME_VPINN, n_coef=0):
+        """n_coef: trainable coefficients behind the network parameters (hpv_create_ex; linear problems only)."""
         self.lib = load()
         cfg = HpvConfig()
         cfg.pde, cfg.var_form, cfg.act = int(pde), int(var_form), int(act)
@@ -254,12 +259,15 @@ class Handle:
         cfg.lossb_weight, cfg.V = float(lossb_weight), float(V)
         cfg.device, cfg.backend, cfg.scheme = int(device), int(backend), int(scheme)
         self._h = C.c_void_p()
-        rc = self.lib.hpv_create(C.byref(self._h), C.byref(cfg))
+        rc = self.lib.hpv_create_ex(C.byref(self._h), C.byref(cfg), int(n_coef))
         if rc != 0:
             msg = self.lib.hpv_last_error(None)
             self._h = None
-            raise HpvError(f"hpv_create failed ({rc}): {msg.decode() if msg else ''}")
+            err = HpvError(f"hpv_create failed ({rc}): {msg.decode() if msg else ''}")
+            err.code = int(rc)
+            raise err
         self.cfg = cfg
+        self.n_coef = int(n_coef)
         self.layers = layers
         self.n_owned = None        # elements this handle owns (set_elements / set_element_boxes)
         self._keep = []
@@ -373,6 +381,12 @@ class Handle:
         in 1-D, 5 rows (a2, a3, ae, gx, gy) in 2-D, laid out like set_operator's.  None, or all zeros, removes the term."""
         coef = None if coef is None else _c(coef).reshape(-1)
         self._chk(self.lib.hpv_set_nonlinear(self._h, _p(coef), 0 if coef is None else coef.size))
+
+    def set_trainable(self, dirs):
+        """The directions of the trainable coefficients (hpv_set_trainable): (n_coef, K + M, n_owned * qx * qy) -- per coefficient the
+        planes of set_operator followed by those of set_nonlinear, laid out like them."""
+        dirs = None if dirs is None else _c(dirs).reshape(-1)
+        self._chk(self.lib.hpv_set_trainable(self._h, _p(dirs), 0 if dirs is None else dirs.size))
 
     def read_flux_loss(self):
         """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""

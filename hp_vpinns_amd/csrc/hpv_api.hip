@@ -200,6 +200,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
+    if (h->n_coef && !h->have_dirs) return fail(h, -3, "hpv_set_trainable has not been called");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->have_F && !h->d_F && h->n_elem > 0) return fail(h, -3, "internal: F not sliced");
     if (h->batch_dirty) return assemble_batches(h);
@@ -252,9 +253,14 @@ static const char* form_terms(int pde, int vf, double V, ProjDesc& pd, int& nT1,
     return nullptr;
 }
 
-int hpv_create(hpv_handle* out, const hpv_config* cfg) {
+int hpv_create(hpv_handle* out, const hpv_config* cfg) { return hpv_create_ex(out, cfg, 0); }
+
+int hpv_create_ex(hpv_handle* out, const hpv_config* cfg, int n_coef) {
     if (!out || !cfg) return fail(nullptr, -1, "null argument");
     *out = nullptr;
+    if (n_coef < 0 || n_coef > HPV_MAX_COEF) return fail(nullptr, -1, "n_coef = %d not in 0..%d", n_coef, HPV_MAX_COEF);
+    if (n_coef && cfg->pde != HPV_PDE_LINEAR1D && cfg->pde != HPV_PDE_LINEAR2D)
+        return fail(nullptr, -1, "trainable coefficients belong to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
     if (cfg->n_layers < 2 || cfg->n_layers > HPV_MAX_LAYERS) return fail(nullptr, -1, "n_layers out of range");
     const int dim = (cfg->pde == HPV_PDE_POISSON1D || cfg->pde == HPV_PDE_LINEAR1D) ? 1 : 2;
     if (cfg->pde < 0 || cfg->pde > HPV_PDE_LINEAR2D) return fail(nullptr, -1, "unknown pde %d", cfg->pde);
@@ -310,7 +316,8 @@ int hpv_create(hpv_handle* out, const hpv_config* cfg) {
     } else if (cfg->scheme != HPV_SCHEME_VPINN) { delete h; return fail(nullptr, -1, "unknown scheme %d", cfg->scheme); }
     pd.C = h->nd_var.C;
     h->P = h->nd_var.P;
-    h->Ptot = h->P + h->has_eps;
+    h->n_coef = n_coef;
+    h->Ptot = h->P + h->has_eps + n_coef;
 
     int rc = 0;
     rc |= dalloc(h, &h->d_theta, (size_t)h->Ptot);
@@ -346,7 +353,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
+    void* ptrs[] = {h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -461,6 +468,10 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         if (h->nl_mask) h->nl_stale = true;      // a pass must not silently train the linear problem
         h->nl_mask = 0;
         if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
+        h->have_dirs = false;                    // ... nor fixed coefficients
+        h->dir_nl_mask = 0;
+        for (double** p : {&h->d_dirs, &h->d_dcoef_e, &h->d_nl_zero})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
     }
     for (long le = 0; le < ne; ++le) {
         const double* box = boxes + (size_t)(e_begin + le) * bs;
@@ -729,6 +740,41 @@ int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n) {
     if ((rc = dalloc(h, &h->d_nl, n))) return rc;
     if ((rc = upload(h, h->d_nl, coef, n))) return rc;
     h->nl_mask = mask;
+    return 0;
+}
+
+// The directions of the trainable coefficients (include/hpvpinn.h); k_project_id reads them in place.  The masks are decided here, once.
+int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n) {
+    if (!h) return -1;
+    if (!h->n_coef) return fail(h, -1, "the handle was created without trainable coefficients (hpv_create_ex)");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    const size_t K = h->dim == 1 ? 3 : 5, M = h->dim == 1 ? 4 : 5, Nq = (size_t)h->Nq, NP = K + M;
+    if (!dirs || n != (size_t)h->n_coef * NP * Nq)
+        return fail(h, -1, "the directions have %zu entries, expected %d x %zu planes of %ld", n, h->n_coef, NP, h->Nq);
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(dirs[i])) return fail(h, -1, "direction %zu holds a non-finite value in plane %zu at point %zu", i / std::max(NP * Nq, (size_t)1), i / std::max(Nq, (size_t)1) % NP, i % std::max(Nq, (size_t)1));
+    int dm[HPV_MAX_COEF] = {}, nlm = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (dirs[i] != 0.0) {
+            const size_t p = i / Nq % NP;
+            dm[i / (NP * Nq)] |= 1 << p;
+            if (p >= K) nlm |= 1 << std::min(p - K, (size_t)3);      // (gx and gy are one term)
+        }
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old directions)
+    drop_graph(h);
+    h->have_dirs = false;
+    if ((rc = dalloc(h, &h->d_dirs, n))) return rc;
+    if (n && (rc = upload(h, h->d_dirs, dirs, n))) return rc;
+    if ((rc = dalloc(h, &h->d_dcoef_e, (size_t)h->n_coef * (size_t)h->n_elem))) return rc;
+    if (!h->d_dir_mask && (rc = dalloc(h, &h->d_dir_mask, (size_t)HPV_MAX_COEF))) return rc;
+    if ((rc = dalloc(h, &h->d_nl_zero, M * Nq))) return rc;      // (read where hpv_set_nonlinear holds no planes)
+    if (Nq) HIPCHK(h, hipMemsetAsync(h->d_nl_zero, 0, M * Nq * sizeof(double), h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_dir_mask, dm, sizeof dm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::copy_n(dm, HPV_MAX_COEF, h->dir_mask);
+    h->dir_nl_mask = nlm;
+    h->have_dirs = true;
     return 0;
 }
 
@@ -1011,7 +1057,7 @@ int hpv_step_record(hpv_handle h, int n_iters, double* loss3_hist, double* eps_h
         if ((rc = hpv_read_loss(h, loss3_hist + (size_t)3 * (n_iters - 1)))) return rc;
         if (eps_hist) {
             eps_hist[n_iters - 1] = 0.0;
-            if (h->has_eps) {
+            if (h->Ptot > h->P) {      // epsilon of AdvDiff | the first trainable coefficient of a linear handle
                 HIPCHK(h, hipMemcpyAsync(eps_hist + n_iters - 1, h->d_theta + h->P, sizeof(double), hipMemcpyDeviceToHost, h->stream));
                 HIPCHK(h, hipStreamSynchronize(h->stream));
             }

@@ -120,6 +120,16 @@ struct hpv_ctx {
     double* d_nl = nullptr;
     int nl_mask = 0;
     bool nl_stale = false;
+    // trainable coefficients of such a handle (hpv_create_ex, hpv_set_trainable): n_coef slots behind the network in theta, their
+    // directions [n_coef][K + M][Nq], the per-direction masks of the planes that are not zero everywhere (host and device copy), the
+    // HPV_NL_* terms the directions touch, the partials [n_coef][n_elem] of d lossv / d c_m, and -- where hpv_set_nonlinear gave no
+    // planes but a direction touches a term -- zero base planes [M][Nq] for k_project_id to read
+    int n_coef = 0;
+    bool have_dirs = false;    // the directions belong to the current elements
+    double *d_dirs = nullptr, *d_dcoef_e = nullptr, *d_nl_zero = nullptr;
+    int dir_mask[HPV_MAX_COEF] = {};
+    int* d_dir_mask = nullptr;
+    int dir_nl_mask = 0;
     // per-element refinement indicators (hpv_element_indicators): the raw 1-D weights [qx | qy] (uploaded with the quadrature), a
     // forward-only object of the full channel set on the quadrature batch's own X and its buffers; re-created when Nq (sizes d_ind_f),
     // the batch size var.N (sizes d_ind_out and the object) or the owned element count (sizes d_ind) changes

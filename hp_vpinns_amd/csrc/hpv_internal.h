@@ -120,6 +120,22 @@ struct NlProjArgs {
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty);
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s);
 
+// The same launch with trainable coefficients (k_project_id, kernels_ident.hip; hpv_create_ex / hpv_set_trainable): every plane is
+//   base_p + sum_m c_m D_m,p,   p over the operator planes followed by the nonlinear ones,   c = theta[P .. P + n_coef)
+// and the kernel also reduces d lossv / d c_m per element.
+#define HPV_ID_PLANES 10     // 5 + 5 in 2-D (3 + 4 in 1-D)
+struct IdProjArgs {
+    LinProjArgs lin;
+    const double* nl;        // base planes of the nonlinear term (zeros where hpv_set_nonlinear gave none)
+    int mask;                // HPV_NL_* of the terms that are evaluated: the base's and every term a direction touches
+    const double* dirs;      // [n_coef][K + M][coef_stride] directions, the layout of lin.coef
+    const double* c;         // theta + P on the device: read at every launch
+    int n_coef;
+    const int* dmask;        // [n_coef] on the device; bit p: plane p of direction m is not zero everywhere (the others are never read)
+    double* dcoef_e;         // [n_coef][n_elem] partials of d lossv / d c_m (written when lin.do_adjoint; n_elem = the grid)
+};
+void launch_project_id(const IdProjArgs& a, long n_elem, hipStream_t s);
+
 struct AdamArgs {
     double *theta, *m, *v, *state;   // theta == nullptr: no update
     double lr, b1, b2, eps;
@@ -206,12 +222,14 @@ struct FinalizeArgs {
     const double* loss_e;    // [n_loss] loss partials: per element (and row split) / per block of k_pinn_residual
     long n_loss;
     const double* deps_e;    // [n_loss] partials of d loss / d epsilon (nullptr: none)
+    int n_coef;              // trainable coefficients of a linear handle behind the network (hpv_create_ex); 0: none
+    const double* dcoef_e;   // [n_coef][n_loss] partials of d loss / d c_m (k_project_id)
     const double* data_part; // [n_data_part] partial sums of the data term
     int n_data_part;
     double lossb_weight;
     int n_data;
     int P, has_eps;
-    double* RB;              // the packed buffer [grad (P) | (d eps) | lossv | w*lossb | mean square | pad]
+    double* RB;              // the packed buffer [grad (P) | (d eps) | (d c_0 ..) | lossv | w*lossb | mean square | pad]
     int write_grad;          // reverse-mode pass: the gradient rows are summed
     AdamArgs adam;           // the TF1-Adam update applied behind the sums (theta == nullptr: none; ignored without write_grad)
     const int* xerr;         // the handle's sticky failure flag (nullptr: no kernel of the pass can set it)

@@ -112,7 +112,7 @@ static FinalizeArgs pass_finalize_args(hpv_ctx* h, bool backward, int n_data_par
     FinalizeArgs a{};
     a.g[1] = {backward && h->n_data > 0 && !h->merged ? h->data.GPART : nullptr, h->data.rows};
     a.data_part = h->d_data_part; a.n_data_part = n_data_part; a.lossb_weight = h->cfg.lossb_weight; a.n_data = h->n_data;
-    a.P = h->P; a.has_eps = h->has_eps; a.RB = h->d_RB; a.write_grad = backward ? 1 : 0;
+    a.P = h->P; a.has_eps = h->has_eps; a.n_coef = h->n_coef; a.dcoef_e = h->d_dcoef_e; a.RB = h->d_RB; a.write_grad = backward ? 1 : 0;
     if (backward && fuse_adam) a.adam = adam_args(h);
     a.fx = flux_fin(h, backward);
     return a;
@@ -232,7 +232,8 @@ static void pass_separate(hpv_ctx* h, const MfmaPass& p, bool backward, bool use
 // The linear problems (hpv_set_operator): always forward -> k_project_lin -> reverse.  Their integrand carries per-point coefficients
 // and a third term, which neither ProjDesc nor a whole-iteration kernel knows; the layer kernels are the ones every handle of the
 // channel set u, u_x, (u_y) runs, the merged boundary points ride in the forward launch as ever.  With a nonlinear term
-// (hpv_set_nonlinear) k_project_nl takes k_project_lin's place in the same launch slot; nothing else differs.
+// (hpv_set_nonlinear) k_project_nl takes k_project_lin's place in the same launch slot, with trainable coefficients (hpv_set_trainable)
+// k_project_id does; nothing else differs.
 static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_mfma) {
     Batch& v = h->var;
     tstart(h, 0);
@@ -242,7 +243,11 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     tstart(h, 1);
     const LinProjArgs a{v.OUT, v.GBAR, h->d_lin, h->Nq, h->d_F, h->d_R, h->d_loss_e, h->d_wtx, h->d_wty, h->d_jac, h->d_jxy,
                         h->d_jxy + h->n_elem, h->pd.nact, h->pd.nacty, v.N, h->qx, h->qy, h->ntx, h->nty, h->dim, backward ? 1 : 0};
-    if (h->nl_mask) launch_project_nl(NlProjArgs{a, h->d_nl, h->nl_mask}, h->n_elem, h->stream);      // (hpv_set_nonlinear)
+    const int terms_mask = h->nl_mask | (h->n_coef ? h->dir_nl_mask : 0);
+    if (h->n_coef)                                                                                      // (hpv_set_trainable)
+        launch_project_id(IdProjArgs{a, h->nl_mask ? h->d_nl : h->d_nl_zero, terms_mask, h->d_dirs, h->d_theta + h->P + h->has_eps, h->n_coef,
+                                     h->d_dir_mask, h->d_dcoef_e}, h->n_elem, h->stream);
+    else if (h->nl_mask) launch_project_nl(NlProjArgs{a, h->d_nl, h->nl_mask}, h->n_elem, h->stream);      // (hpv_set_nonlinear)
     else launch_project_lin(a, h->n_elem, h->stream);
     tstop(h, 1);
     if (!backward) return;
@@ -250,9 +255,10 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     std::string terms;                               // the active terms of k_project_nl, e.g. ";u2,u3,exp,adv"
     static const char* const term_names[] = {"u2", "u3", "exp", "adv"};
     for (int t = 0; t < 4; ++t)
-        if (h->nl_mask >> t & 1) terms += std::string(terms.empty() ? ";" : ",") + term_names[t];
+        if (terms_mask >> t & 1) terms += std::string(terms.empty() ? ";" : ",") + term_names[t];
+    if (h->n_coef) terms += ";nc=" + std::to_string(h->n_coef);      // e.g. k_project_id<6x5/4x3;u3;nc=2>
     snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
-             h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
+             h->n_coef ? "id" : h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
     tstart(h, 2);
     if (use_mfma) hpv_mfma_backward(v.m, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);
     else run_bwd(h, v);

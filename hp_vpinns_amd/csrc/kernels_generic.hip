@@ -517,7 +517,7 @@ void launch_flux_loss(const double* OUT, long N, int dim, const double* coef, co
 
 // ------------------------------------------------------------------------------------------------
 // Finalize: fixed-order sums of all partials into the packed reduce buffer
-//   RB = [grad (P) | (d eps) | lossv | w*lossb | mean-square of the data term | pad]
+//   RB = [grad (P) | (d eps) | (d c_0 .. d c_{n_coef-1}) | lossv | w*lossb | mean-square of the data term | pad]
 // ------------------------------------------------------------------------------------------------
 // TF1 AdamOptimizer rule (tf.train.AdamOptimizer(LR).minimize, P1:103-104), one parameter:
 //   lr_t = lr sqrt(1-b2^t)/(1-b1^t); m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; theta -= lr_t m/(sqrt(v)+eps)
@@ -547,7 +547,9 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
                                                          double lossb_weight, int n_data, int P, int has_eps,
                                                          double* RB, int write_grad, AdamArgs ad,
                                                          const int* __restrict__ xerr, unsigned int* __restrict__ xiter_bump, int pend,
-                                                         FluxFin fx) {
+                                                         FluxFin fx, int n_coef, const double* __restrict__ dcoef_e) {
+    // n_coef, dcoef_e (the trainable coefficients of a linear handle, k_project_id): n_coef more scalar slots behind the network,
+    // summed and updated by the last block exactly as the epsilon slot is; every branch on n_coef is uniform and not taken at 0
     // fx (the flux term, k_flux_loss): a fourth gradient source and a fourth partial array; both pointers are nullptr on a handle
     // without flux data, and every branch on them is uniform and not taken
     // pend (the multi-GPU iteration in two launches, round 5): `ad` is the update of the PREVIOUS iteration -- its all-reduced
@@ -556,7 +558,7 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
     // failure flag of the reduced buffer was latched into *xerr by that prologue.
     constexpr int FIN_PARTS = FIN_THREADS / FIN_COLS;
     __shared__ double red[FIN_PARTS * FIN_COLS];
-    const int Ptot = P + (has_eps ? 1 : 0);
+    const int Pc = P + (has_eps ? 1 : 0), Ptot = Pc + n_coef;      // Pc: the first coefficient slot
     if (blockIdx.x < gridDim.x - 1) {
         // 16 parameters per block; 64 row-groups summed in parallel (few dependent loads per thread: the kernel is
         // pure latency), then combined in a fixed order
@@ -630,12 +632,14 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
     // dependent ones behind the reductions)
     double s0 = 0.0, s1 = 0.0, eps_th = 0.0, eps_m = 0.0, eps_v = 0.0;
     double old4[4] = {0.0, 0.0, 0.0, 0.0};     // pend: the previous iteration's reduced d-epsilon and losses, read before this one's overwrite them
+    double c_first = 0.0;                      // theta[Pc], the first trainable coefficient as this forward pass used it (the history's fourth column)
     int hidx = -1, failed = 0, failed_now = 0;        // failed: the update this launch applies; failed_now: this iteration (the pad slot)
     if (threadIdx.x == 0 && xerr) { failed_now = *xerr; failed = pend ? xerr[1] : failed_now; }
     if (threadIdx.x == 0 && ad.theta) {
         s0 = ad.state[0]; s1 = ad.state[1];
         if (ad.hist) hidx = *ad.hist_idx;
         if (has_eps) { eps_th = ad.theta[P]; eps_m = ad.m[P]; eps_v = ad.v[P]; }
+        if (n_coef) c_first = ad.theta[Pc];
         if (pend) { old4[0] = has_eps ? RB[P] : 0.0; old4[1] = RB[Ptot]; old4[2] = RB[Ptot + 1]; old4[3] = RB[Ptot + 2]; }
     }
     double lv = 0.0, de = 0.0;
@@ -648,6 +652,28 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
     lv = block_sum(lv, red);
     de = block_sum(de, red);
     sq = block_sum(sq, red);
+    if (n_coef && write_grad) {
+        // row m of dcoef_e over the elements, in the order of loss_e; thread 0 stores the sum and applies the slot's update exactly as
+        // the epsilon slot's below (s0, s1 and `failed` were fetched up front; the slot's own operands are fetched here, one
+        // coefficient after the other in a rolled loop: the kernel keeps the registers it has without coefficients).  Never with pend:
+        // a linear handle's deferred update is applied by k_adam in front of the pass.
+#pragma unroll 1
+        for (int m = 0; m < n_coef; ++m) {
+            double t = 0.0;
+            for (long e = threadIdx.x; e < n_elem; e += blockDim.x) t += dcoef_e[m * n_elem + e];
+            t = block_sum(t, red);
+            if (threadIdx.x == 0) {
+                RB[Pc + m] = t;
+                if (ad.theta && !failed) {
+                    double mi, vi, ti;
+                    hpv_adam_one(ad.lr, ad.b1, ad.b2, ad.eps, s0, s1, t, ad.m[Pc + m], ad.v[Pc + m], ad.theta[Pc + m], mi, vi, ti);
+                    ad.m[Pc + m] = mi;
+                    ad.v[Pc + m] = vi;
+                    ad.theta[Pc + m] = ti;
+                }
+            }
+        }
+    }
     double sf = 0.0;
     if (fx.part) {
         for (int i = threadIdx.x; i < fx.n_part; i += blockDim.x) sf += fx.part[i];
@@ -661,7 +687,8 @@ __global__ void __launch_bounds__(FIN_THREADS) k_finalize(const double* __restri
             lb += fx.w * msf;
             *fx.ms = msf;
         }
-        const double eps_now = (has_eps && ad.theta) ? eps_th : 0.0;   // the coefficient this forward pass used
+        double eps_now = (has_eps && ad.theta) ? eps_th : 0.0;   // the coefficient this forward pass used
+        if (n_coef && ad.theta) eps_now = c_first;                // (a linear handle's first one; has_eps is 0 there)
         if (has_eps && write_grad) {
             RB[P] = de;
             if (ad.theta && !failed) {   // the trainable epsilon (P3:63): adam_update with the operands fetched above
@@ -702,7 +729,7 @@ static void launch_finalize_as(const FinalizeArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_finalize<FIN_THREADS>, dim3(gblocks + 1), dim3(FIN_THREADS), 0, s, a.g[0].GPART, a.g[0].rows, a.g[1].GPART,
                        a.g[1].rows, a.g[2].GPART, a.g[2].rows, a.loss_e, a.n_loss, a.deps_e, a.data_part, a.n_data_part, a.lossb_weight,
                        a.n_data, a.P, a.has_eps, a.RB, a.write_grad, a.write_grad ? a.adam : AdamArgs{}, a.xerr, a.xiter_bump,
-                       a.pending_adam, a.fx);
+                       a.pending_adam, a.fx, a.n_coef, a.dcoef_e);
 }
 void launch_finalize(const FinalizeArgs& a, hipStream_t s) {
     int rows = a.fx.GPART ? a.fx.rows : 0;

@@ -224,6 +224,7 @@ class _VPINNBase:
     _pde = None
     _act = None
     _n_extra = 0
+    _trainable = ()            # VPINNLinear / VPINNNonlinear: the trainable coefficients (dicts: name, init, the direction's fields)
 
     def _create(self, layers, var_form, LR, lossb_weight, V, init_params, seed, backend, device,
                 scheme=_lib.SCHEME_VPINN):
@@ -245,9 +246,11 @@ class _VPINNBase:
         self._handle_args = ((self._pde, var_form, self._act, self._dev_layers),
                              dict(lr=LR, lossb_weight=lossb_weight, V=V, device=device, backend=bk, scheme=scheme))
         self._populate = None      # set by the subclass: hands the problem (rule, tables, elements, F, data) to self.h
+        if self._trainable:
+            self._handle_args[1]["n_coef"] = len(self._trainable)
         self.h = _lib.Handle(*self._handle_args[0], **self._handle_args[1])
         if init_params is None:
-            init_params = xavier_init(self.layers, seed, extra=[1.0] * self._n_extra)
+            init_params = xavier_init(self.layers, seed, extra=[t["init"] for t in self._trainable] if self._trainable else [1.0] * self._n_extra)
         self._init_params = np.asarray(init_params, dtype=np.float64).reshape(-1).copy()
         if self._init_params.size != n_params(self.layers, self._n_extra):
             raise ValueError("init_params has the wrong length")
@@ -560,7 +563,7 @@ class _VPINNBase:
         if n > 0:
             out[n - 1] = self.loss()
             if self._n_extra:
-                eps[n - 1] = self.h.get_params()[-1]
+                eps[n - 1] = self.h.get_params()[-self._n_extra]      # (the first of them: what the history's column holds)
         return out, eps
 
     _RECORD_CHUNK = 1000
@@ -1267,7 +1270,15 @@ class VPINNLinear(_VPINNBase):
     `n_test` the test-function counts of a grid: one number, a pair (x, y), or per-element arrays (one, or a pair in 2-D).
     `kappa`, `beta`, `sigma`, `f`: a constant, or a callable of the points (n, dim); `kappa` and `beta` return (n, dim) -- kappa
     also (n,) when isotropic -- and a constant `beta` may be one vector.  They are evaluated at the handle's own quadrature points;
-    F is assembled on the device (hpv_assemble_rhs).  `X_u_train`, `u_train`: Dirichlet data, weighted by `lossb_weight`."""
+    F is assembled on the device (hpv_assemble_rhs).  `X_u_train`, `u_train`: Dirichlet data, weighted by `lossb_weight`.
+
+    Coefficient identification (hpv_set_trainable): `trainable` is a list of dicts, one per unknown scalar c_m that is trained with
+    the network -- `name`, `init` (its initial value) and any of kappa=, beta=, sigma= (VPINNNonlinear also quadratic=, cubic=,
+    exponential=, advection=), each a constant or a callable with the meaning it has above: together they are the DIRECTION the
+    scalar multiplies, and the coefficients the problem is solved with are the constructor's plus sum_m c_m * direction_m.  An
+    unknown isotropic conductivity is dict(name="kappa", init=1.0, kappa=1.0); two subdomain conductivities are two dicts whose
+    kappa= are the indicator functions; an unknown Burgers viscosity is kappa=(-1.0, 0.0).  The scalars follow the network in
+    `get_params()` and in checkpoints; `coefficients()` returns {name: value}.  At most 8; the fields not named are zero."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1277,8 +1288,10 @@ class VPINNLinear(_VPINNBase):
 
     def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
                  sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
-                 init_params=None, seed=1234, backend="auto", device=None):
+                 init_params=None, seed=1234, backend="auto", device=None, trainable=None):
         dim = int(layers[0])
+        self._trainable = self._check_trainable(trainable)
+        self._n_extra = len(self._trainable)
         if dim not in (1, 2):
             raise ValueError("layers[0] is the dimension of the problem: 1 or 2")
         self._pde = _lib.PDE_LINEAR1D if dim == 1 else _lib.PDE_LINEAR2D
@@ -1343,9 +1356,46 @@ class VPINNLinear(_VPINNBase):
         s = _coef_field(self._op["sigma"], P, d, "sigma", False)
         self.h.set_operator(np.concatenate([k.T, b.T, s[None, :]], axis=0))
 
+    _DIR_FIELDS = ("kappa", "beta", "sigma")      # the fields a direction may name, in this class
+
+    def _check_trainable(self, trainable):
+        out = []
+        for t in (trainable or ()):
+            t = dict(t)
+            unknown = set(t) - {"name", "init"} - set(self._DIR_FIELDS)
+            if unknown or "name" not in t or "init" not in t:
+                raise ValueError(f"a trainable coefficient is dict(name=, init=, and any of {self._DIR_FIELDS}); got {sorted(t)}")
+            t["init"] = float(t["init"])
+            out.append(t)
+        if len(out) > _lib.MAX_COEF or len({t["name"] for t in out}) != len(out):
+            raise ValueError(f"at most {_lib.MAX_COEF} trainable coefficients, with distinct names")
+        return tuple(out)
+
+    def _direction(self, t, P, d):
+        """the planes (K + M, n) of one trainable coefficient's direction at the points P: set_operator's rows, then set_nonlinear's"""
+        k, b = _coef_field(t.get("kappa", 0.0), P, d, "kappa", True), _coef_field(t.get("beta", 0.0), P, d, "beta", True)
+        s = _coef_field(t.get("sigma", 0.0), P, d, "sigma", False)
+        a = [_coef_field(t.get(f, 0.0), P, d, f, False) for f in ("quadratic", "cubic", "exponential")]
+        g = _coef_field(t.get("advection", 0.0), P, d, "advection", True)
+        return np.concatenate([k.T, b.T, s[None, :], np.stack(a, 0), g.T], axis=0)
+
+    def _hand_trainable(self, mesh):
+        """the directions at this rank's quadrature points (after the planes they add to: new elements orphan all of them)"""
+        if not self._trainable:
+            return
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        P = self._quad_points(mesh, eb, ee)
+        self.h.set_trainable(np.stack([self._direction(t, P, mesh.dim) for t in self._trainable], 0))
+
+    def coefficients(self):
+        """{name: current value} of the trainable coefficients"""
+        n = len(self._trainable)
+        return dict(zip((t["name"] for t in self._trainable), (float(v) for v in self.get_params()[-n:]))) if n else {}
+
     def _populate_mesh(self, mesh, f):
         super()._populate_mesh(mesh, f)
         self._hand_operator(mesh)
+        self._hand_trainable(mesh)
 
     def _hand_data(self):
         if self.rank == 0 and self.X_u_train is not None:
@@ -1358,6 +1408,7 @@ class VPINNLinear(_VPINNBase):
             if v is not None:
                 self._op[k] = v
         self._hand_operator(self._mesh)
+        self._hand_trainable(self._mesh)
 
     def set_mesh(self, mesh, f=None):
         """As `_VPINNBase.set_mesh`; the coefficients are re-evaluated on the new elements.  f None keeps the model's own f."""
@@ -1413,6 +1464,8 @@ class VPINNNonlinear(VPINNLinear):
     sigma = 1, cubic = -1; space-time viscous Burgers (y = t) kappa = (-nu, 0), beta = (0, 1), advection = (1, 0).
     Everything else is `VPINNLinear`'s, the refusal of the strong form included."""
 
+    _DIR_FIELDS = VPINNLinear._DIR_FIELDS + ("quadratic", "cubic", "exponential", "advection")
+
     def __init__(self, layers, *, quadratic=0.0, cubic=0.0, exponential=0.0, advection=0.0, **kw):
         self._nl = dict(quadratic=quadratic, cubic=cubic, exponential=exponential, advection=advection)
         super().__init__(layers, **kw)
@@ -1436,3 +1489,4 @@ class VPINNNonlinear(VPINNLinear):
             if v is not None:
                 self._nl[k] = v
         self._hand_nonlinear(self._mesh)
+        self._hand_trainable(self._mesh)

@@ -126,8 +126,8 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
  * builds it), lossv = sum_e mean over the ACTIVE test functions of R^2, loss = lossb_weight * lossb + lossf + lossv.
  * Special cases: k = 1, b = s = 0 is Poisson-2D var_form 1; kx = -eps, ky = 0, bx = V, by = 1 is AdvDiff var_form 1 at a fixed
  * epsilon; 1-D k = -1 is Poisson-1D var_form 2.
- * Such a handle is created with var_form = 1 and HPV_SCHEME_VPINN (anything else is refused), has no trainable coefficient
- * (hpv_num_params counts the network alone) and runs forward -> k_project_lin -> reverse (hpv_pass_structure 0).  Everything
+ * Such a handle is created with var_form = 1 and HPV_SCHEME_VPINN (anything else is refused), has no trainable coefficient unless
+ * it is created with hpv_create_ex (below; hpv_num_params then counts them behind the network) and runs forward -> k_project_lin -> reverse (hpv_pass_structure 0).  Everything
  * else of the variational scheme works on it unchanged; the strong form needs derivatives of k and is refused:
  * hpv_set_collocation*, hpv_residual_points, hpv_element_indicators (negative status, the handle stays usable).
  *
@@ -149,7 +149,7 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
  * Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
  * y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
  * eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
- * Out of scope: a solution-dependent diffusion coefficient, trainable coefficients, and the strong form (hpv_set_collocation*,
+ * Out of scope: a solution-dependent diffusion coefficient and the strong form (trainable coefficients: hpv_set_trainable; hpv_set_collocation*,
  * hpv_residual_points, hpv_element_indicators stay refused as for the linear class).  exp(u) is not guarded against overflow.
  *
  * coef is [M][n_owned*qx*qy] in planes, M = 4 in 1-D in the order (a2, a3, ae, g), M = 5 in 2-D in the order (a2, a3, ae, gx, gy),
@@ -164,6 +164,38 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
  * Returns 0; -1 for a handle of another problem, a wrong n, a non-finite value, a shape beyond the kernel's LDS; -3 before
  * hpv_set_elements; -2 on a HIP error. */
 int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n);
+
+/* Coefficient identification on a handle of the class above: n_coef trainable scalars c_0 .. c_{n_coef-1} follow the network
+ * parameters in theta (1 <= n_coef <= HPV_MAX_COEF) and are trained with them.  Each scalar owns a DIRECTION D_m in the space of
+ * all coefficient planes; the planes the projection uses are
+ *     plane_p(x_q) = base_p(x_q) + sum_m c_m D_m,p(x_q)
+ * with p over the operator planes (k, b, s | kx, ky, bx, by, s) followed by the nonlinear planes (a2, a3, ae, g | a2, a3, ae, gx,
+ * gy) and base what hpv_set_operator / hpv_set_nonlinear hold.  Isotropic conductivity: D = 1 in kx and ky; piecewise-constant
+ * conductivity: indicator functions of subdomains; Burgers viscosity: D = -1 in kx; Bratu lambda: D = 1 in ae; wavenumber squared:
+ * D = 1 in s.  The coefficients enter the variational term only (the data and flux terms add nothing to their gradient), and
+ *     d lossv / d c_m = sum_e sum_q [ (D_s u + D_bx u_x + D_by u_y + D_a2 u^2 + D_a3 u^3 + D_ae e^u + u (D_gx u_x + D_gy u_y)) Gbar_0
+ *                                     + D_kx u_x Gbar_1 + D_ky u_y Gbar_2 ]
+ * with Gbar_t the adjoints of the three integrands (k_project_id, csrc/kernels_ident.hip).
+ * Out of scope: positivity constraints or reparametrised coefficients, coefficients given by a second network, the strong form,
+ * coefficients in the data or flux term.
+ *
+ * hpv_create_ex is hpv_create with n_coef such slots (hpv_create is this call with 0; such a handle computes bit for bit what it
+ * always did).  Ptot = P + (epsilon of AdvDiff) + n_coef: hpv_num_params, hpv_set_params / hpv_get_params, hpv_get_state /
+ * hpv_set_state, the gradient of hpv_loss_and_grad and hpv_reduce_buffer carry the slots behind the network.  The history's fourth
+ * column (eps_hist of hpv_step_record / hpv_history_read) reports theta[P], the FIRST coefficient.  n_coef > 0 is refused (-1) for
+ * any other pde and above HPV_MAX_COEF.
+ *
+ * hpv_set_trainable: dirs is [n_coef][K + M][n_owned*qx*qy] in the plane order above and the layout of hpv_set_operator; n is the
+ * exact count.  Everything is copied.  A (m, p) plane that is zero at every owned point is never read on the device; a direction
+ * that touches a nonlinear plane makes that term active even where its base plane is zero or was never given.  Waits for the
+ * handle's stream and drops the captured iteration graphs.  hpv_set_elements / hpv_set_element_boxes invalidate the directions:
+ * a pass on a handle created with n_coef > 0 answers -3 until they are set (again) -- it never silently trains fixed coefficients.
+ * The directions are not state.  hpv_kernel_variant names the kernel, the active terms and the count, e.g.
+ * k_project_id<6x5/4x3;u3;nc=2>; hpv_pass_structure stays 0.
+ * Returns 0; -1 for a handle without such slots, a wrong n, NULL, a non-finite value; -3 before hpv_set_elements; -2 on a HIP error. */
+#define HPV_MAX_COEF 8
+int hpv_create_ex(hpv_handle* out, const hpv_config* cfg, int n_coef);
+int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n);
 
 /* Boundary / data points of lossb (P1:98, P2:122, P3:184): X is [n][dim] row-major, u is [n].
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
@@ -221,7 +253,7 @@ int hpv_step(hpv_handle h, int n_iters, double* loss3_after);
  * iteration k+1 computes anyway; every training iteration appends it to a device-side history, so only the loss after
  * the last update costs a forward pass.  loss3_hist is [n_iters][3] = {loss, lossb, lossv} after update 1..n_iters;
  * eps_hist (may be NULL) is [n_iters], the trainable diffusion coefficient after each update (P3:318, 0 for the Poisson
- * problems).  hpv_history_reset / hpv_history_read expose the history to callers that drive the iterations themselves
+ * problems; theta[P], the first coefficient, on a handle of hpv_create_ex).  hpv_history_reset / hpv_history_read expose the history to callers that drive the iterations themselves
  * (multi-GPU: entry i = loss / epsilon seen by the i-th forward pass since the reset, global after the all-reduce). */
 int hpv_step_record(hpv_handle h, int n_iters, double* loss3_hist, double* eps_hist);
 int hpv_history_reset(hpv_handle h);
