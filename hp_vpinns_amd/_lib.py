@@ -42,6 +42,7 @@ EXPORTS = [
     "hpv_set_flux_data", "hpv_read_flux_loss",
     "hpv_set_operator", "hpv_set_nonlinear",
     "hpv_create_ex", "hpv_set_trainable",
+    "hpv_set_strong_form", "hpv_linear_indicators",
 ]
 MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
@@ -208,6 +209,8 @@ def load():
     lib.hpv_step_validate.argtypes = [h, C.c_int, C.c_int, _dp, C.c_size_t]
     lib.hpv_set_element_boxes.argtypes = [h, _dp, C.c_int, C.c_int, C.c_int]
     lib.hpv_element_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
+    lib.hpv_set_strong_form.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
+    lib.hpv_linear_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:
@@ -270,6 +273,7 @@ class Handle:
         self.n_coef = int(n_coef)
         self.layers = layers
         self.n_owned = None        # elements this handle owns (set_elements / set_element_boxes)
+        self.n_quad = None         # quadrature points per element (set_quadrature)
         self._keep = []
 
     def _chk(self, rc):
@@ -298,6 +302,7 @@ class Handle:
         xi, wx, yi, wy = _c(xi), _c(wx), _c(yi), _c(wy)
         self._chk(self.lib.hpv_set_quadrature(self._h, _p(xi), _p(wx), xi.size, _p(yi), _p(wy),
                                               1 if yi is None else yi.size))
+        self.n_quad = xi.size * (1 if yi is None else yi.size)      # (points per element: what linear_indicators sizes r by)
 
     def set_tables(self, tx, ty=None, edge_dphi=None):
         """tx / ty: (3, ntest, q) arrays of phi, phi', phi''."""
@@ -335,6 +340,24 @@ class Handle:
         out = np.empty((self.n_owned or 0, IND_N))         # (no elements yet: the library refuses the call)
         self._chk(self.lib.hpv_element_indicators(self._h, _p(f), 0 if f is None else f.size, _p(out), out.size))
         return out
+
+    def set_strong_form(self, Dx=None, Dy=None):
+        """Opt a linear handle into its strong form (hpv_set_strong_form): the (qx, qx) differentiation matrix of the device rule's
+        x nodes on the reference interval and, in 2-D, the (qy, qy) one of its y nodes.  Both None removes them."""
+        Dx, Dy = _c(Dx), _c(Dy)
+        self._chk(self.lib.hpv_set_strong_form(self._h, _p(Dx), 0 if Dx is None else Dx.size, _p(Dy), 0 if Dy is None else Dy.size))
+
+    def linear_indicators(self, f_quad=None, want_r=False):
+        """(n_owned, 5) as `element_indicators`, for a linear handle after `set_strong_form` (hpv_linear_indicators).  want_r: also
+        the strong residual at every owned quadrature point, (n_owned, qx * qy) element-major -- returns (indicators, r)."""
+        f = None if f_quad is None else _c(f_quad).reshape(-1)
+        out = np.empty((self.n_owned or 0, IND_N))
+        r = None
+        if want_r:
+            r = np.empty((self.n_owned or 0, self.n_quad or 0))
+        self._chk(self.lib.hpv_linear_indicators(self._h, _p(f), 0 if f is None else f.size, _p(out), out.size,
+                                                 _p(r), 0 if r is None else r.size))
+        return (out, r) if want_r else out
 
     def set_rhs(self, F):
         F = _c(F)

@@ -353,7 +353,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out,
+    void* ptrs[] = {h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -389,6 +389,7 @@ int hpv_set_quadrature(hpv_handle h, const double* xi, const double* wx, int qx,
         if ((rc = upload(h, h->d_wq, h->wx.data(), (size_t)qx))) return rc;
         if ((rc = upload(h, h->d_wq + qx, h->wy.data(), (size_t)qy))) return rc;
     }
+    if (h->d_sf) { (void)hipFree(h->d_sf); h->d_sf = nullptr; }      // (hpv_set_strong_form: the matrices belong to the old rule)
     h->have_quad = true;
     drop_graph(h);
     h->have_tables = false;  // weighted tables depend on the weights
@@ -1414,6 +1415,91 @@ int hpv_element_indicators(hpv_handle h, const double* f_quad, size_t n, double*
     launch_elem_indicators(h->cfg.pde, a, ne, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The strong form of a linear handle, opted into (include/hpvpinn.h): the differentiation matrices of the current rule, kept on the
+// device for k_lin_indicators alone.  No pass reads them, so the captured iteration graphs stay.
+int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_strong_form belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
+    if (!Dx && !Dy && nx == 0 && ny == 0) {
+        if (h->d_sf) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_sf); h->d_sf = nullptr; }
+        return 0;
+    }
+    if (!h->have_quad) return fail(h, -3, "call hpv_set_quadrature first");
+    const size_t wx = (size_t)h->qx * h->qx, wy = h->dim == 2 ? (size_t)h->qy * h->qy : 0;
+    if (!Dx || nx != wx) return fail(h, -1, "Dx has %zu entries, expected %d x %d of the current rule", nx, h->qx, h->qx);
+    if (h->dim == 1 ? (Dy || ny != 0) : (!Dy || ny != wy))
+        return fail(h, -1, "Dy has %zu entries, expected %zu (1-D: NULL and 0; 2-D: %d x %d of the current rule)", ny, wy, h->qy, h->qy);
+    for (size_t i = 0; i < wx; ++i)
+        if (!std::isfinite(Dx[i])) return fail(h, -1, "Dx holds a non-finite value at entry %zu", i);
+    for (size_t i = 0; i < wy; ++i)
+        if (!std::isfinite(Dy[i])) return fail(h, -1, "Dy holds a non-finite value at entry %zu", i);
+    const size_t lds = hpv_linadapt_lds_bytes(h->dim, h->qx, h->qy);
+    if (lds > 64 * 1024) return fail(h, -1, "rule too large for the linear indicator kernel's LDS (%zu B)", lds);
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = dalloc(h, &h->d_sf, wx + wy))) return rc;
+    if ((rc = upload(h, h->d_sf, Dx, wx))) return rc;
+    if (wy && (rc = upload(h, h->d_sf + wx, Dy, wy))) return rc;
+    return 0;
+}
+
+// hpv_element_indicators for a linear handle with the strong form set; its sequence, its cached buffers under their three-number key:
+//   (1) enqueue_pass(backward = false): forward -> k_project_lin | _nl | _id, which stores R of all owned elements;
+//   (2) one forward-only launch of nd_full on the quadrature batch's own X;
+//   (3) one k_lin_indicators launch, one workgroup per owned element;
+//   (4) one copy of n_owned * HPV_IND_N doubles, and one of the strong residual where the caller asks; one synchronisation.
+int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* out, size_t n_out, double* r_out, size_t n_r) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_linear_indicators belongs to the linear problems (others: hpv_element_indicators)");
+    if (!h->d_sf) return fail(h, -1, "the strong residual of a linear problem needs the rule's differentiation matrices: call hpv_set_strong_form");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    const long ne = h->n_elem, NQ = (long)h->qx * h->qy;
+    if (f_quad && n != (size_t)(ne * NQ)) return fail(h, -1, "f has %zu entries, expected %ld", n, ne * NQ);
+    if (n_out != (size_t)ne * HPV_IND_N || (ne > 0 && !out)) return fail(h, -1, "indicator buffer has %zu entries, expected %zu", n_out, (size_t)ne * HPV_IND_N);
+    if (r_out && n_r != (size_t)(ne * NQ)) return fail(h, -1, "residual buffer has %zu entries, expected %ld", n_r, ne * NQ);
+    const size_t lds = hpv_linadapt_lds_bytes(h->dim, h->qx, h->qy);
+    if (lds > 64 * 1024) return fail(h, -1, "rule too large for the linear indicator kernel's LDS (%zu B)", lds);
+    if (ne == 0) return 0;
+    if (h->ind_Nq != h->Nq || h->ind_N != h->var.N || h->ind_ne != ne) {      // (the key of hpv_element_indicators)
+        if (h->mfma_ind) { hpv_mfma_destroy(h->mfma_ind); h->mfma_ind = nullptr; }
+        h->ind_Nq = h->ind_N = h->ind_ne = -1;
+        if ((rc = dalloc(h, &h->d_ind_out, (size_t)h->nd_full.C * h->var.N))) return rc;
+        if ((rc = dalloc(h, &h->d_ind_f, (size_t)(ne * NQ)))) return rc;
+        if ((rc = dalloc(h, &h->d_ind, (size_t)ne * HPV_IND_N))) return rc;
+        if (h->backend == HPV_BACKEND_MFMA) h->mfma_ind = hpv_mfma_create(h->nd_full, h->var.N, nullptr, false);
+        h->ind_Nq = h->Nq; h->ind_N = h->var.N; h->ind_ne = ne;
+    }
+    if (r_out && h->ind_r_n != h->Nq) {
+        h->ind_r_n = -1;
+        if ((rc = dalloc(h, &h->d_ind_r, (size_t)(ne * NQ)))) return rc;
+        h->ind_r_n = h->Nq;
+    }
+    if (f_quad) HIPCHK(h, hipMemcpyAsync(h->d_ind_f, f_quad, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = enqueue_pass(h, false))) return rc;
+    if (h->mfma_ind) hpv_mfma_forward(h->mfma_ind, h->d_theta, h->var.X, h->d_ind_out, 0, h->stream);
+    else launch_mlp_fwd_generic(h->nd_full, h->d_theta, h->var.X, nullptr, h->d_ind_out, h->var.N, 0, h->stream);
+    const int terms_mask = h->nl_mask | (h->n_coef ? h->dir_nl_mask : 0);      // (what pass_linear hands its projection kernel)
+    const size_t wx = (size_t)h->qx * h->qx;
+    LinIndArgs a{};
+    a.OUT = h->d_ind_out; a.N = h->var.N; a.f = f_quad ? h->d_ind_f : nullptr;
+    a.coef = h->d_lin; a.cs = h->Nq;
+    a.nl = h->nl_mask ? h->d_nl : (h->n_coef ? h->d_nl_zero : nullptr); a.mask = terms_mask;
+    a.dirs = h->n_coef ? h->d_dirs : nullptr; a.c = h->d_theta + h->P + h->has_eps; a.n_coef = h->n_coef; a.dmask = h->d_dir_mask;
+    a.Dx = h->d_sf; a.Dy = h->dim == 2 ? h->d_sf + wx : nullptr;
+    a.wx = h->d_wq; a.wy = h->d_wq + h->qx;
+    a.J = h->d_jac; a.Jx = h->d_jxy; a.Jy = h->d_jxy + h->n_elem;
+    a.R = h->d_R; a.nact = h->pd.nact; a.nacty = h->pd.nacty;
+    a.out = h->d_ind; a.r_out = r_out ? h->d_ind_r : nullptr;
+    a.qx = h->qx; a.qy = h->qy; a.ntx = h->ntx; a.nty = h->nty; a.dim = h->dim;
+    launch_lin_indicators(a, ne, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (r_out) HIPCHK(h, hipMemcpyAsync(r_out, h->d_ind_r, n_r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

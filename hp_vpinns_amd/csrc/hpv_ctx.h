@@ -137,6 +137,12 @@ struct hpv_ctx {
     HpvMfma* mfma_ind = nullptr;
     double *d_ind_out = nullptr, *d_ind_f = nullptr, *d_ind = nullptr;
     long ind_Nq = -1, ind_N = -1, ind_ne = -1;
+    // the strong form of a linear handle (hpv_set_strong_form): the differentiation matrices [qx*qx | qy*qy] of the current rule
+    // (nullptr: not set -- hpv_linear_indicators refuses); they go with the rule (hpv_set_quadrature), nothing a pass reads.
+    // d_ind_r: the strong residual at the owned points for a caller who asks, sized by Nq (ind_r_n)
+    double* d_sf = nullptr;
+    double* d_ind_r = nullptr;
+    long ind_r_n = -1;
     // device-side validation (hpv_eval_points .. hpv_step_validate): forward-only batches at the caller's points
     NetDesc nd_full{};         // the full channel list: u, every first and every second input derivative (hpv_eval_points)
     NetDesc nd_grad{};         // u and the first derivatives (validation against exact gradients)

@@ -306,3 +306,31 @@ struct IndArgs {
     double* out;             // [n_elem][HPV_IND_N]
 };
 void launch_elem_indicators(int pde, const IndArgs& a, long n_elem, hipStream_t s);
+
+// ---- the same for the linear problems (kernels_linadapt.hip; hpv_set_strong_form, hpv_linear_indicators) ----
+struct LinIndArgs {
+    const double* OUT;       // [5 | 3][N] the full channel list at the quadrature batch's points (element-major, q = j * qx + i)
+    long N;
+    const double* f;         // [n_elem * qx * qy] right-hand side at those points, or nullptr (zero)
+    const double* coef;      // the operator planes of LinProjArgs
+    long cs;                 // doubles between two planes (= n_owned * qx * qy)
+    const double* nl;        // base planes of the nonlinear term (NlProjArgs / IdProjArgs), or nullptr when mask == 0
+    int mask;                // HPV_NL_* of the terms that are evaluated
+    const double* dirs;      // [n_coef][K + M][cs] directions of the trainable coefficients, or nullptr
+    const double* c;         // theta + P on the device: read at the launch
+    int n_coef;              // 0: the base planes are the effective ones
+    const int* dmask;        // [n_coef] on the device; bit p: plane p of direction m is not zero everywhere (the others are never read)
+    const double* Dx;        // [qx][qx] differentiation matrix of the rule's x nodes on the reference interval, row-major
+    const double* Dy;        // [qy][qy] (2-D only)
+    const double* wx;        // [qx] raw 1-D weights
+    const double* wy;        // [qy] (1-D problems: one entry, 1.0)
+    const double *J, *Jx, *Jy;   // [n_elem] |J_e| and the half widths per direction (Jy: 2-D only)
+    const double* R;         // [n_elem][nty][ntx] residuals of the most recent pass
+    const int* nact;         // [n_elem] active counts per direction, or nullptr (all)
+    const int* nacty;
+    double* out;             // [n_elem][HPV_IND_N]
+    double* r_out;           // [n_elem * qx * qy] the strong residual at every point, or nullptr (not wanted)
+    int qx, qy, ntx, nty, dim;
+};
+size_t hpv_linadapt_lds_bytes(int dim, int qx, int qy);
+void launch_lin_indicators(const LinIndArgs& a, long n_elem, hipStream_t s);

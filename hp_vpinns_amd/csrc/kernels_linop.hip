@@ -23,6 +23,9 @@
 // Every sum runs in index order in one thread, the block sum of R^2 is a fixed tree: no atomics, the same bits from call to call.
 // A zero-weight padding point has all-zero table columns: it adds exactly 0 to T and receives Gbar = 0.
 // LDS rows are padded to an odd number of doubles, so a lane-per-row access never lands on a power-of-two multiple of the banks.
+// Out of scope: the strong form of the class (it takes derivatives of kx, ky).  hpv_set_collocation*, hpv_residual_points and
+// hpv_element_indicators are refused on these handles; the strong residual at the elements' own quadrature points, for refinement
+// indicators, is an opt-in with a kernel of its own (hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
 #include "hpv_internal.h"
 
 namespace {

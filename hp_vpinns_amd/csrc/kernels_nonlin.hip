@@ -16,8 +16,9 @@
 // Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
 // y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
 // eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
-// Out of scope: a solution-dependent diffusion coefficient kappa(u); the strong form (trainable coefficients: k_project_id, kernels_ident.hip; (hpv_set_collocation*,
-// hpv_residual_points and hpv_element_indicators stay refused as for the linear class).
+// Out of scope: a solution-dependent diffusion coefficient kappa(u); the strong form at arbitrary points (trainable coefficients:
+// k_project_id, kernels_ident.hip; hpv_set_collocation*, hpv_residual_points and hpv_element_indicators stay refused as for the linear
+// class; the strong residual at the elements' own points, for refinement: hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
 //
 // Term mask (HPV_NL_*): a plane that is zero at every owned point is left out of the mask on the host, and its term is not evaluated
 // at all -- the branch is uniform over the grid, an exp nobody asked for is never computed and 0 * inf cannot arise.  exp(u) is

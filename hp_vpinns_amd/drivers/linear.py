@@ -9,6 +9,10 @@ relative L2 error.
 
     python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05
     python -m hp_vpinns_amd.drivers.linear l-shape
+    python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05 --adapt-every 500 --max-elements 16
+
+--adapt-every K: local hp-refinement (VPINNLinear(strong_form="elementwise").train_adaptive) after every K-th update, at most
+--max-elements elements; one (iteration, elements, loss) row is printed per round.
 """
 import argparse
 
@@ -31,19 +35,32 @@ def graded_grid(n, grade=2.0):
     return 1.0 - (1.0 - np.arange(n + 1) / n) ** grade
 
 
+def _train(m, n_iter, adapt_every, max_elements, verbose):
+    """train, or train_adaptive with its rows [(iterations done, elements, loss on the new mesh)] printed like the Poisson-2D driver's"""
+    if not adapt_every:
+        m.train(int(n_iter), verbose=verbose)
+        return []
+    rows = m.train_adaptive(int(n_iter), int(adapt_every), max_elements=max_elements)
+    if verbose:
+        for it, ne, loss in rows:
+            print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
+    return rows
+
+
 def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000, layers=(1, 20, 20, 20, 1), grade=2.0, LR=1e-3,
-                       lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True):
+                       lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None):
     grid = graded_grid(int(n_elements), grade)
     m = VPINNLinear(list(layers), grid_x=grid, n_quad=int(n_quad), n_test=int(n_test), kappa=-float(eps), beta=1.0, sigma=0.0, f=1.0,
                     X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2), lossb_weight=lossb_weight, activation="sin", LR=LR,
-                    seed=seed, backend=backend, device=device)
-    m.train(int(n_iter), verbose=verbose)
+                    seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None)
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     X = np.linspace(0.0, 1.0, 401)[:, None]
     u = boundary_layer_exact(X, eps)
     err = m.rel_l2_error(X, u)
     if verbose:
-        print("boundary layer eps = %g, %d graded elements: relative L2 error %.4e (%s)" % (eps, n_elements, err, m.h.kernel_variant()))
-    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+        print("boundary layer eps = %g, %d elements (%d graded at the start): relative L2 error %.4e (%s)"
+              % (eps, len(m.mesh), n_elements, err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 L_BOXES = np.array([[-1.0, 0.0, -1.0, 0.0], [-1.0, 0.0, 0.0, 1.0], [0.0, 1.0, 0.0, 1.0]])
@@ -69,20 +86,21 @@ def _l_boundary(n):
 
 
 def run_l_shape(n_iter=2000, n_quad=20, n_test=10, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0, seed=1234,
-                backend="auto", device=None, verbose=True):
+                backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None):
     Xb = _l_boundary(int(n_bound))
     m = VPINNLinear(list(layers), mesh=ElementMesh(L_BOXES, int(n_test), int(n_test)), n_quad=int(n_quad),
                     kappa=lambda P: 1.0 + P[:, 0] * P[:, 1], beta=np.array([1.0, -1.0]), sigma=2.0, f=_l_f, X_u_train=Xb, u_train=_l_exact(Xb),
-                    lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device)
-    m.train(int(n_iter), verbose=verbose)
+                    lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device,
+                    strong_form="elementwise" if adapt_every else None)
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     g = np.linspace(-1.0, 1.0, 81)
     X = np.stack([v.reshape(-1) for v in np.meshgrid(g, g)], 1)
     X = X[~((X[:, 0] > 0) & (X[:, 1] < 0))]
     u = _l_exact(X)[:, None]
     err = m.rel_l2_error(X, u)
     if verbose:
-        print("L-shape, kappa = 1 + x y, beta = (1, -1), sigma = 2: relative L2 error %.4e (%s)" % (err, m.h.kernel_variant()))
-    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+        print("L-shape, kappa = 1 + x y, beta = (1, -1), sigma = 2, %d elements: relative L2 error %.4e (%s)" % (len(m.mesh), err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 def main(argv=None):
@@ -94,11 +112,14 @@ def main(argv=None):
     ap.add_argument("--n-quad", type=int, default=20)
     ap.add_argument("--n-test", type=int, default=10)
     ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
+    ap.add_argument("--max-elements", type=int, default=None)
     a = ap.parse_args(argv)
     if a.problem == "boundary-layer":
-        run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade)
+        run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
+                           adapt_every=a.adapt_every, max_elements=a.max_elements)
     else:
-        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test)
+        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements)
 
 
 if __name__ == "__main__":

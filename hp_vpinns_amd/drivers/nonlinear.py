@@ -12,6 +12,10 @@ exact or manufactured solution and Dirichlet data from it; prints the relative L
     python -m hp_vpinns_amd.drivers.nonlinear bratu --lam 1.0
     python -m hp_vpinns_amd.drivers.nonlinear burgers --nu 0.05
     python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.2
+    python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.1 --adapt-every 500 --max-elements 64
+
+--adapt-every K (burgers, allen-cahn): local hp-refinement (VPINNNonlinear(strong_form="elementwise").train_adaptive) after every
+K-th update, at most --max-elements elements; one (iteration, elements, loss) row is printed per round.
 
 `setup(problem, ...)` builds everything a run needs on the host (no GPU); `run(s, ...)` creates the model from it and trains.
 """
@@ -92,12 +96,23 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
                            lossb_weight=lossb_weight, **op))
 
 
-def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True):
-    """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated)."""
+def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None,
+        max_elements=None):
+    """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated); with
+    adapt_every the elements are refined locally (train_adaptive: the model is built with strong_form="elementwise").  The two
+    are not combined: giving both raises ValueError."""
     from ..vpinn import VPINNNonlinear
-    m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, **s["model"])
-    his = None
-    if validate_every:
+    if adapt_every and validate_every:
+        raise ValueError("adapt_every and validate_every cannot be combined: run one or the other")
+    m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None,
+                       **s["model"])
+    his, rows = None, []
+    if adapt_every:
+        rows = m.train_adaptive(int(n_iter), int(adapt_every), max_elements=max_elements)
+        if verbose:
+            for it, ne, loss in rows:
+                print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
+    elif validate_every:
         m.set_validation(s["X_test"], s["u_test"])
         his = m.train_validated(int(n_iter), int(validate_every))
         if verbose:
@@ -108,7 +123,7 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
     err = m.rel_l2_error(s["X_test"], s["u_test"])
     if verbose:
         print("relative L2 error %.4e after %d iterations (%s)" % (err, n_iter, m.h.kernel_variant()))
-    return dict(model=m, rel_l2=err, history=his, loss_his=np.asarray(m.loss_his))
+    return dict(model=m, rel_l2=err, history=his, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 def main(argv=None):
@@ -120,8 +135,11 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--width", type=int, default=20)
     ap.add_argument("--validate-every", type=int, default=0)
+    ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update (not together with --validate-every)")
+    ap.add_argument("--max-elements", type=int, default=None)
     a = ap.parse_args(argv)
-    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width), n_iter=a.iters, validate_every=a.validate_every)
+    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width), n_iter=a.iters, validate_every=a.validate_every,
+        adapt_every=a.adapt_every, max_elements=a.max_elements)
 
 
 if __name__ == "__main__":

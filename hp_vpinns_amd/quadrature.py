@@ -113,3 +113,23 @@ def GaussLobattoJacobiWeights(Q: int, a, b):
     X = np.append(X, 1)
     X = np.append(-1, X)
     return [X, W]
+
+
+def diff_matrix(x):
+    """Differentiation matrix of the distinct nodes `x`: (D v)[i] = p'(x_i) for the polynomial p of degree < len(x) with
+    p(x_m) = v[m].  Barycentric form -- D[i][m] = (lam_m / lam_i) / (x_i - x_m) off the diagonal, lam_i = 1 / prod_{m != i}
+    (x_i - x_m) -- with the diagonal as the negative sum of the row's other entries, which makes the derivative of a constant
+    exactly zero.  Raises ValueError on repeated nodes (e.g. a zero-weight padded rule): their interpolant does not exist."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = x.size
+    if n < 1:
+        raise ValueError("diff_matrix needs at least one node")
+    dx = x[:, None] - x[None, :]
+    np.fill_diagonal(dx, 1.0)
+    if np.any(dx == 0.0):
+        raise ValueError("diff_matrix needs distinct nodes (a padded rule repeats some)")
+    lam = 1.0 / np.prod(dx, axis=1)
+    D = (lam[None, :] / lam[:, None]) / dx
+    np.fill_diagonal(D, 0.0)
+    np.fill_diagonal(D, -D.sum(axis=1))
+    return D

@@ -33,6 +33,7 @@ from . import _lib
 from .adapt import ElementMesh, mark, refine
 from .dist import Reducer, dist_info, shard_range
 from .init import n_params, pad_plan, xavier_init
+from .quadrature import diff_matrix
 from .testfcn import dTest_fcn, tables_1d
 
 
@@ -1278,7 +1279,15 @@ class VPINNLinear(_VPINNBase):
     scalar multiplies, and the coefficients the problem is solved with are the constructor's plus sum_m c_m * direction_m.  An
     unknown isotropic conductivity is dict(name="kappa", init=1.0, kappa=1.0); two subdomain conductivities are two dicts whose
     kappa= are the indicator functions; an unknown Burgers viscosity is kappa=(-1.0, 0.0).  The scalars follow the network in
-    `get_params()` and in checkpoints; `coefficients()` returns {name: value}.  At most 8; the fields not named are zero."""
+    `get_params()` and in checkpoints; `coefficients()` returns {name: value}.  At most 8; the fields not named are zero.
+
+    Local hp-refinement: `strong_form=None` (the default) refuses everything that needs the strong residual -- `element_indicators`,
+    `adapt`, `train_adaptive`, `residual` -- because it takes derivatives of kappa.  `strong_form="elementwise"` differentiates the
+    interpolant of kappa's nodal values on each element's tensor rule (hpv_set_strong_form; one differentiation matrix per
+    direction) and gives `element_indicators(f=None)`, `strong_residual_at_quad()`, `adapt(f=None, **mark_kw)` and `train_adaptive(nIter,
+    adapt_every, f=None, max_elements=None, **mark_kw)` -- the base class's, f None meaning the model's own f; `residual(X)` at arbitrary points stays refused.  ASSUMPTION: kappa is smooth
+    inside each element.  A jump of kappa must lie on element edges; refinement bisects elements, so edges on dyadic positions of
+    the first mesh stay edges.  The rule's nodes must be distinct (no zero-weight padding)."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1288,8 +1297,11 @@ class VPINNLinear(_VPINNBase):
 
     def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
                  sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
-                 init_params=None, seed=1234, backend="auto", device=None, trainable=None):
+                 init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None):
         dim = int(layers[0])
+        if strong_form not in (None, "elementwise"):
+            raise ValueError('strong_form is None or "elementwise"')
+        self._strong_form = strong_form
         self._trainable = self._check_trainable(trainable)
         self._n_extra = len(self._trainable)
         if dim not in (1, 2):
@@ -1394,6 +1406,9 @@ class VPINNLinear(_VPINNBase):
 
     def _populate_mesh(self, mesh, f):
         super()._populate_mesh(mesh, f)
+        if self._strong_form:                              # (set_quadrature dropped the matrices: they belong to the rule)
+            xi, yi = self._dev_rule
+            self.h.set_strong_form(diff_matrix(xi), None if yi is None else diff_matrix(yi))
         self._hand_operator(mesh)
         self._hand_trainable(mesh)
 
@@ -1419,19 +1434,43 @@ class VPINNLinear(_VPINNBase):
 
     def _no_strong_form(self, what):
         raise NotImplementedError(f"{what} needs the strong residual of the problem, which takes derivatives of kappa: "
-                                  "not available for VPINNLinear")
+                                  "not available for VPINNLinear.  strong_form=\"elementwise\" gives it at the elements' own "
+                                  "quadrature points (indicators and adaptivity; residual(X) stays refused).")
+
+    def _owned_f_quad(self, f):
+        mesh = self._mesh
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        return None if ee == eb else self._f_at_quad(mesh, self._f if f is None else f, eb, ee)
 
     def element_indicators(self, f=None):
-        self._no_strong_form("element_indicators")
+        """With strong_form="elementwise": (n_owned, 5) refinement indicators as `_VPINNBase.element_indicators`, column 1 from the
+        strong residual at the elements' own quadrature points (hpv_linear_indicators).  f None: the model's own f."""
+        if not self._strong_form:
+            self._no_strong_form("element_indicators")
+        return self.h.linear_indicators(self._owned_f_quad(f))
+
+    def strong_residual_at_quad(self):
+        """With strong_form="elementwise": (n_owned, qy, qx), the strong residual at this rank's quadrature points."""
+        if not self._strong_form:
+            self._no_strong_form("strong_residual_at_quad")
+        xi, yi = self._dev_rule
+        r = self.h.linear_indicators(self._owned_f_quad(None), want_r=True)[1]
+        return r.reshape(-1, 1 if yi is None else len(yi), len(xi))
 
     def residual(self, X, f=None):
         self._no_strong_form("residual")
 
     def adapt(self, f=None, **mark_kw):
-        self._no_strong_form("adapt")
+        """With strong_form="elementwise": `_VPINNBase.adapt`; f None (the usual call) is the model's own f.  Single GPU only."""
+        if not self._strong_form:
+            self._no_strong_form("adapt")
+        return super().adapt(f, **mark_kw)                 # (element_indicators and set_mesh of this class take f None as self._f)
 
     def train_adaptive(self, nIter, adapt_every, f=None, max_elements=None, **mark_kw):
-        self._no_strong_form("train_adaptive")
+        """With strong_form="elementwise": `_VPINNBase.train_adaptive`; f None is the model's own f.  Single GPU only."""
+        if not self._strong_form:
+            self._no_strong_form("train_adaptive")
+        return super().train_adaptive(nIter, adapt_every, f, max_elements, **mark_kw)
 
     def _train_n(self, n):
         self.train(n)
@@ -1462,7 +1501,8 @@ class VPINNNonlinear(VPINNLinear):
     points with the operator and again in `set_mesh`.  A term that is zero everywhere is not evaluated on the device; with all four
     zero the model runs exactly what `VPINNLinear` runs.  Steady Bratu is kappa = 1, exponential = lambda; Allen-Cahn kappa = eps^2,
     sigma = 1, cubic = -1; space-time viscous Burgers (y = t) kappa = (-nu, 0), beta = (0, 1), advection = (1, 0).
-    Everything else is `VPINNLinear`'s, the refusal of the strong form included."""
+    Everything else is `VPINNLinear`'s: the strong form is refused by default, and `strong_form="elementwise"` opts into the
+    indicators and adaptivity with N in the strong residual (only the terms that are switched on are evaluated)."""
 
     _DIR_FIELDS = VPINNLinear._DIR_FIELDS + ("quadratic", "cubic", "exponential", "advection")
 

@@ -129,7 +129,8 @@ int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n)
  * Such a handle is created with var_form = 1 and HPV_SCHEME_VPINN (anything else is refused), has no trainable coefficient unless
  * it is created with hpv_create_ex (below; hpv_num_params then counts them behind the network) and runs forward -> k_project_lin -> reverse (hpv_pass_structure 0).  Everything
  * else of the variational scheme works on it unchanged; the strong form needs derivatives of k and is refused:
- * hpv_set_collocation*, hpv_residual_points, hpv_element_indicators (negative status, the handle stays usable).
+ * hpv_set_collocation*, hpv_residual_points, hpv_element_indicators (negative status, the handle stays usable).  Refinement
+ * indicators from the strong residual at the elements' own quadrature points are an opt-in: hpv_set_strong_form below.
  *
  * coef is [K][n_owned*qx*qy] in planes, K = 3 in 1-D in the order (k, b, s), K = 5 in 2-D in the order (kx, ky, bx, by, s); each
  * plane element-major over the OWNED elements, q = j*qx + i (the layout of f_quad in hpv_assemble_rhs); n = K*n_owned*qx*qy.
@@ -392,6 +393,39 @@ int hpv_get_residuals(hpv_handle h, double* R, size_t n);   /* R of the owned el
  * without parameters / elements, wrong n or n_out. */
 #define HPV_IND_N 5
 int hpv_element_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, double* out, size_t n_out);
+
+/* Refinement indicators for the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D, with or without hpv_set_nonlinear / hpv_set_trainable).
+ * ADDS an opt-in beside hpv_element_indicators, which stays refused on these handles as do hpv_residual_points and
+ * hpv_set_collocation*; it replaces nothing, and a handle that never calls hpv_set_strong_form behaves as it always did.
+ * The strong residual of the class takes derivatives of the diffusion planes,
+ *     r = kx u_xx + (d kx/dx) u_x + ky u_yy + (d ky/dy) u_y + bx u_x + by u_y + s u + N(u, grad u) - f
+ *     (1-D: r = k u_xx + k' u_x + b u_x + s u + N - f;  N as in hpv_set_nonlinear, only the terms that are switched on),
+ * and the planes are nodal values on each element's tensor rule: the derivative of their interpolant at the element's own points is
+ *     d kx/dx [j][i] = (sum_m Dx[i][m] kx[j][m]) / Jx_e        d ky/dy [j][i] = (sum_m Dy[j][m] ky[m][i]) / Jy_e
+ * with Dx, Dy the differentiation matrices of the rule's nodes on the reference interval and Jx_e, Jy_e the element's half widths.
+ * ASSUMPTION: kappa is smooth inside each element.  Exact for a plane that is a polynomial of degree < q per direction on the
+ * element, spectrally accurate for a smooth one, correct inside every element for a piecewise-constant one whose jumps lie on
+ * element edges.  With trainable coefficients the planes are base + sum_m c_m D_m at the parameters on the device.
+ *
+ * hpv_set_strong_form: Dx is the qx x qx matrix (row-major) of the device rule's x nodes, Dy the qy x qy one; 1-D handles pass
+ * Dy = NULL, ny = 0.  (NULL, 0, NULL, 0) removes them.  Everything is copied.  The matrices belong to the rule: hpv_set_quadrature
+ * drops them, hpv_set_tables / hpv_set_elements / hpv_set_element_boxes do not.  Nothing a pass reads changes: captured iteration
+ * graphs stay, and a handle computes bit for bit what one that never made the call computes.
+ * Returns 0; -1 (the handle stays usable, matrices given earlier stay) for a handle of another problem, sizes that are not the
+ * current rule's, a non-finite entry, a rule whose k_lin_indicators workgroup would need more than 64 KiB of LDS --
+ *     8 * (n_d * qy * (qx|1) + qx * (qx|1) + [2-D: qy * (qy|1)] + 16) bytes,  n_d = 1 in 1-D, 2 in 2-D;
+ * -3 before hpv_set_quadrature; -2 on a HIP error.
+ *
+ * hpv_linear_indicators: out, f_quad and n follow hpv_element_indicators' contract -- [n_owned][HPV_IND_N], the same five columns
+ * with the same meaning, column 1 with the r above.  r_out may be NULL (n_r is then ignored); otherwise it receives r at every
+ * owned quadrature point, n_r = n_owned*qx*qy, element-major, q = j*qx + i.  The launches are hpv_element_indicators' own: the
+ * forward-only pass of hpv_eval_loss (R becomes current), one forward-only launch of the full channel list, one k_lin_indicators
+ * launch (csrc/kernels_linadapt.hip: one workgroup per element, fixed summation order, no atomics -- bitwise reproducible from call
+ * to call), one copy (two with r_out), one synchronisation.  Like hpv_eval_loss it overwrites the loss slots of the packed buffer.
+ * Returns 0; -1 for a handle of another problem, before hpv_set_strong_form (the message names it), wrong n / n_out / n_r; -3
+ * where a pass would (planes, nonlinear term or directions orphaned by new elements, anything not yet set); -2 on a HIP error. */
+int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny);
+int hpv_linear_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, double* out, size_t n_out, double* r_out_or_null, size_t n_r);
 int hpv_backend_in_use(hpv_handle h);                       /* HPV_BACKEND_GENERIC or HPV_BACKEND_MFMA */
 /* Launch structure of the most recent reverse-mode pass over the quadrature batch (tests assert that the kernel they mean to
  * exercise is the one that ran): 0 separate forward / projection / reverse launches, 1 forward + projection-fused reverse,
