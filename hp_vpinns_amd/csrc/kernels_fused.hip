@@ -504,7 +504,10 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         load_x(k0 + NT + 1, xn[1], vn[1], pn[1]);
         int lofs = lane;
         asm volatile("" : "+v"(lofs));       // opaque: the LDS fragment reads stay inside the loop
-        double h[NT][C][MF_KS], sv[NT][NSV];
+        // Without a second tangent only the value channel goes through the layers: u_x, u_y come from ONE adjoint sweep over it (below),
+        // one product per hidden layer instead of the two tangent channels' two.  (NT2 > 0: second tangents need the forward tangents.)
+        constexpr int CF = NT2 > 0 ? C : 1;
+        double h[NT][CF][MF_KS], sv[NT][NSV];
         [[maybe_unused]] double QH[MF_KS], QA[NSV];      // WQ: the packed quarter tile's layer input and its s
         // layer 1 (VALU)
 #pragma unroll
@@ -517,8 +520,11 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 double a, a1, a2;
                 act_fwd<HPV_ACT_TANH>(z, a, a1, a2);
                 sv[t][s] = a;
-                h[t][0][s] = a; h[t][1][s] = a1 * w0; h[t][2][s] = a1 * w1;
-                if constexpr (NT2 > 0) h[t][3][s] = a2 * fma(g.t2w[0], w0 * w0, g.t2w[1] * (w1 * w1));      // (z_cc = 0 in front of the first layer)
+                h[t][0][s] = a;
+                if constexpr (NT2 > 0) {
+                    h[t][1][s] = a1 * w0; h[t][2][s] = a1 * w1;
+                    h[t][3][s] = a2 * fma(g.t2w[0], w0 * w0, g.t2w[1] * (w1 * w1));      // (z_cc = 0 in front of the first layer)
+                }
             }
             if constexpr (WQ) {      // every slot evaluates its own point (the tangent slots share the element point of slot 0)
                 const double z = b1v + qx0 * w0 + qx1 * w1;
@@ -530,14 +536,15 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         }
 #pragma unroll
         for (int i = 1; i < L; ++i) {
-            double z[NT][C][MF_KS];
+            double z[NT][CF][MF_KS];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 fz_layer<true>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, lds + M::BH + (i - 1) * MF_KS * 64, lofs, h[t][0], z[t][0]);
-                fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][1], z[t][1]);
-                fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][2], z[t][2]);
-                if constexpr (NT2 > 0)
+                if constexpr (NT2 > 0) {
+                    fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][1], z[t][1]);
+                    fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][2], z[t][2]);
                     fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, h[t][3], z[t][3]);
+                }
             }
             [[maybe_unused]] double QZ[MF_KS];
             if constexpr (WQ)
@@ -552,9 +559,12 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                     double a, a1, a2;
                     act_fwd<HPV_ACT_TANH>(z[t][0][s], a, a1, a2);
                     sv[t][i * MF_KS + s] = a;
-                    h[t][0][s] = a; h[t][1][s] = a1 * z[t][1][s]; h[t][2][s] = a1 * z[t][2][s];
-                    if constexpr (NT2 > 0)      // h_cc = s'' (w0 z_x^2 + w1 z_y^2) + s' z_cc
+                    h[t][0][s] = a;
+                    if constexpr (NT2 > 0) {
+                        h[t][1][s] = a1 * z[t][1][s]; h[t][2][s] = a1 * z[t][2][s];
+                        // h_cc = s'' (w0 z_x^2 + w1 z_y^2) + s' z_cc
                         h[t][3][s] = a2 * fma(g.t2w[0], z[t][1][s] * z[t][1][s], g.t2w[1] * (z[t][2][s] * z[t][2][s])) + a1 * z[t][3][s];
+                    }
                 }
             if constexpr (WQ) {
 #pragma unroll
@@ -572,6 +582,57 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 }
             }
         }
+        // NT2 == 0: grad_x u of a scalar-output network is one reverse sweep over the value channel, sigma' = 1 - s^2 from the stash:
+        //   abar_L = sigma'(z_L) w_o,  abar_{i-1} = sigma'(z_{i-1}) (W_i abar_i)  (i = L .. 2),  u_x = W1[0,:] . abar_1,  u_y = W1[1,:] . abar_1
+        // on the reverse A fragments M::WN / M::WRB, as the hbar chain of rev_tile.  The tiles of the trip stay independent streams.
+        // (Boundary / data tiles run it too -- nothing reads their u_x, u_y; a wave-uniform skip would cut the straight-line schedule.)
+        [[maybe_unused]] double ogx[NT], ogy[NT];
+        if constexpr (NT2 == 0) {
+            double ab[NT][MF_KS];
+#pragma unroll
+            for (int s = 0; s < MF_KS; ++s) {
+                const double wo = lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const double a = sv[t][(L - 1) * MF_KS + s];
+                    ab[t][s] = (1.0 - a * a) * wo;
+                }
+            }
+#pragma unroll
+            for (int i = L - 1; i >= 1; --i) {
+                const double* wrl = lds + M::WRB + (i - 1) * MF_KS * 16 + (lofs >> 4) * 4 + (lofs & 3);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+                    double h4 = 0.0;
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) {
+                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lds[M::WN + ((i - 1) * MF_KS + s) * 64 + lofs], ab[t][s], acc, 0, 0, 0);
+                        h4 = __builtin_amdgcn_mfma_f64_4x4x4f64(wrl[s * 16], ab[t][s], h4, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) ab[t][s] = acc[s];
+                    ab[t][4] = h4;
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) {
+                        const double a = sv[t][(i - 1) * MF_KS + s];
+                        ab[t][s] *= 1.0 - a * a;
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                double vx = 0.0, vy = 0.0;
+#pragma unroll
+                for (int s = 0; s < MF_KS; ++s) {
+                    vx += ab[t][s] * lds[M::W1O + (0 * MF_KS + s) * 64 + lofs];
+                    vy += ab[t][s] * lds[M::W1O + (1 * MF_KS + s) * 64 + lofs];
+                }
+                vx = xrow_sum16(vx); vx = xrow_sum32(vx);
+                vy = xrow_sum16(vy); vy = xrow_sum32(vy);
+                ogx[t] = vx; ogy[t] = vy;
+            }
+        }
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int k = k0 + t;
@@ -580,7 +641,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
             // (mf_head was tried here: k_iter_fused<2, true, false, 12, 12, 6, 6, false, 0, false> and six of the general
             //  instantiations moved)
 #pragma unroll
-            for (int ch = 0; ch < C; ++ch) {
+            for (int ch = 0; ch < CF; ++ch) {
                 double v = 0.0;
 #pragma unroll
                 for (int s = 0; s < MF_KS; ++s) v += h[t][ch][s] * lds[M::W1O + (2 * MF_KS + s) * 64 + lofs];
@@ -588,6 +649,7 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 v = xrow_sum32(v);
                 o[ch] = v;
             }
+            if constexpr (NT2 == 0) { o[1] = ogx[t]; o[2] = ogy[t]; }
             o[0] += bo;
             if (k < n_el) {
                 if (q == 0) {
