@@ -43,7 +43,9 @@ EXPORTS = [
     "hpv_set_operator", "hpv_set_nonlinear",
     "hpv_create_ex", "hpv_set_trainable",
     "hpv_set_strong_form", "hpv_linear_indicators",
+    "hpv_set_ansatz",
 ]
+ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
 MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
@@ -211,6 +213,7 @@ def load():
     lib.hpv_element_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_set_strong_form.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_linear_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
+    lib.hpv_set_ansatz.argtypes = [h, C.c_int, _dp, C.c_size_t]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:
@@ -410,6 +413,19 @@ class Handle:
         planes of set_operator followed by those of set_nonlinear, laid out like them."""
         dirs = None if dirs is None else _c(dirs).reshape(-1)
         self._chk(self.lib.hpv_set_trainable(self._h, _p(dirs), 0 if dirs is None else dirs.size))
+
+    def set_ansatz(self, which, planes, n=None):
+        """The ansatz u = G + D N of one point set (hpv_set_ansatz): `which` one of ANSATZ_QUAD / _DATA / _FLUX / _VALID, planes
+        (2 * (1 + dim), n) rows (G, G_x[, G_y], D, D_x[, D_y]) at the set's points in the order they were handed over.  None removes the
+        planes of that set.  n: the point count handed to the library (default: the planes' own)."""
+        if planes is None:
+            self._chk(self.lib.hpv_set_ansatz(self._h, int(which), None, 0 if n is None else int(n)))
+            return
+        planes = np.ascontiguousarray(planes, dtype=np.float64)
+        rows = 2 * (1 + self.layers[0])
+        if planes.ndim != 2 or planes.shape[0] != rows:
+            raise ValueError(f"ansatz planes must have shape ({rows}, n), got {planes.shape}")
+        self._chk(self.lib.hpv_set_ansatz(self._h, int(which), _p(planes), planes.shape[1] if n is None else int(n)))
 
     def read_flux_loss(self):
         """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""

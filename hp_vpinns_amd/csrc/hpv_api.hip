@@ -25,6 +25,13 @@ int upload(hpv_ctx* h, double* dst, const double* src, size_t n) {
     return 0;
 }
 
+void drop_ansatz(hpv_ctx* h, int which) {
+    if (h->ans_on[which]) h->batch_dirty = true;      // (whether the data points may ride in the quadrature batch is decided again)
+    if (h->d_ans[which]) { (void)hipFree(h->d_ans[which]); h->d_ans[which] = nullptr; }
+    h->ans_on[which] = false;
+    h->ans_n[which] = 0;
+}
+
 void drop_graph(hpv_ctx* h) {
     if (h->g_stepK) { (void)hipGraphExecDestroy(h->g_stepK); h->g_stepK = nullptr; }
     for (hipGraphExec_t& g : h->g_rem) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -140,7 +147,11 @@ namespace {
 int assemble_batches(hpv_ctx* h) {
     int rc;
     const long N = h->Nq;
-    const int d = h->dim, nd = h->n_data;
+    // a handle with an ansatz (hpv_set_ansatz) keeps its data points out of the quadrature batch: the merged forward launch takes their
+    // loss on raw network values
+    const bool merge = !has_ansatz(h);
+    const int d = h->dim, nd = merge ? h->n_data : 0;
+    bool var_done = false;
     free_batch(h->var);      // (with their objects: none outlives the batch it was sized for)
     free_batch(h->data);
     h->backend = HPV_BACKEND_GENERIC;
@@ -151,7 +162,8 @@ int assemble_batches(hpv_ctx* h) {
         HpvMfma* m = hpv_mfma_create(h->nd_var, Ntot, &why);
         if (m) {
             h->backend = HPV_BACKEND_MFMA;
-            h->merged = true;
+            h->merged = merge;
+            var_done = true;
             h->data_off = Npad;
             hpv_mfma_set_err_flag(m, h->d_xerr);
             hpv_mfma_set_split_ok(m, h->shared_elem_ok);
@@ -182,11 +194,11 @@ int assemble_batches(hpv_ctx* h) {
                                 "generic kernels, which are far slower (hpv_backend_in_use reports HPV_BACKEND_GENERIC)\n", why.c_str());
         }
     }
-    if (!h->merged) {
+    if (!var_done) {
         if ((rc = alloc_batch(h, h->var, h->nd_var, N, true))) return rc;
         if (N > 0 && (rc = upload(h, h->var.X, h->Xq_host.data(), h->Xq_host.size()))) return rc;
-        if ((rc = assemble_data_batch(h))) return rc;
     }
+    if (!h->merged && (rc = assemble_data_batch(h))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->batch_dirty = false;
     return 0;
@@ -359,6 +371,7 @@ void hpv_destroy(hpv_handle h) {
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
                     h->d_nact, h->d_nacty};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (double* p : h->d_ans) if (p) (void)hipFree(p);
     for (auto& t : h->timers) for (auto e : t.ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -464,6 +477,7 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
     std::vector<double> jxy(h->linear ? (size_t)2 * ne : 0, 1.0);
     if (h->linear) {      // the coefficient planes belong to the old elements' points
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        drop_ansatz(h, HPV_ANSATZ_QUAD);         // ... as do the ansatz planes
         h->have_lin = false;
         if (h->d_lin) { (void)hipFree(h->d_lin); h->d_lin = nullptr; }
         if (h->nl_mask) h->nl_stale = true;      // a pass must not silently train the linear problem
@@ -686,6 +700,10 @@ int hpv_set_data(hpv_handle h, const double* X, const double* u, int n) {
     if (!h) return -1;
     if (n < 0 || (n > 0 && (!X || !u))) return fail(h, -1, "bad data arguments");
     int rc;
+    if (h->ans_on[HPV_ANSATZ_DATA]) {           // the ansatz planes belong to the old points
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        drop_ansatz(h, HPV_ANSATZ_DATA);
+    }
     h->n_data = n;
     drop_graph(h);
     h->Xd_host.assign(X, X + (size_t)n * h->dim);
@@ -779,12 +797,46 @@ int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n) {
     return 0;
 }
 
+// The ansatz planes of one point set (include/hpvpinn.h); k_ansatz_fwd / k_ansatz_adj read them in place.
+int hpv_set_ansatz(hpv_handle h, int which, const double* planes, size_t n) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_ansatz belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
+    if (which < HPV_ANSATZ_QUAD || which > HPV_ANSATZ_VALID) return fail(h, -1, "unknown point set %d (0 QUAD .. 3 VALID)", which);
+    if (!planes && n != 0) return fail(h, -1, "NULL planes with n = %zu (NULL and 0 remove the planes)", n);
+    int rc;
+    if (!planes) {
+        if (!h->ans_on[which]) return 0;
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the planes)
+        drop_graph(h);
+        drop_ansatz(h, which);
+        return 0;
+    }
+    if (h->d_sf) return fail(h, -1, "the strong form is active (hpv_set_strong_form): its residual needs second derivatives of G and D, which are not available");
+    if (which == HPV_ANSATZ_QUAD && !h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    const long count[] = {h->Nq, (long)h->n_data, (long)h->n_flux, (long)h->n_val};
+    const size_t np = (size_t)count[which], rows = 2 * (size_t)(1 + h->dim);
+    if (n != np) return fail(h, -1, "the ansatz has n = %zu points, the set has %zu", n, np);
+    for (size_t i = 0; i < rows * np; ++i)
+        if (!std::isfinite(planes[i])) return fail(h, -1, "ansatz plane %zu holds a non-finite value at point %zu", i / np, i % np);
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (an enqueued pass may still read the old planes)
+    drop_graph(h);
+    const bool had = has_ansatz(h);
+    drop_ansatz(h, which);
+    if ((rc = dalloc(h, &h->d_ans[which], rows * np))) return rc;
+    if ((rc = upload(h, h->d_ans[which], planes, rows * np))) return rc;
+    h->ans_on[which] = true;
+    h->ans_n[which] = (long)np;
+    if (!had) h->batch_dirty = true;                     // the first planes of the handle: the data points leave the quadrature batch
+    return 0;
+}
+
 int hpv_set_flux_data(hpv_handle h, const double* X, const double* coef, const double* g, int n, double weight) {
     if (!h) return -1;
     if (n < 0 || (n > 0 && (!X || !coef || !g)) || !std::isfinite(weight)) return fail(h, -1, "bad flux data arguments");
     int rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old set)
     drop_graph(h);
+    drop_ansatz(h, HPV_ANSATZ_FLUX);             // the ansatz planes belong to the old points
     h->n_flux = 0;
     const int d = h->dim;
     const long N = ((long)n + 15) / 16 * 16;      // whole 16-point tiles; the padding sits at the origin and carries zero adjoints
@@ -1101,13 +1153,14 @@ int eval_points_forward(hpv_ctx* h, const double* X, int n) {
 int validation_ready(hpv_ctx* h) {
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->n_val <= 0) return fail(h, -3, "hpv_set_validation has not been called");
-    return 0;
+    return ansatz_ready(h, HPV_ANSATZ_VALID);
 }
 
 // forward over the stored set + the reduction, on the handle's stream; no synchronisation, no host read
 int enqueue_validation(hpv_ctx* h, bool to_history) {
     int rc = forward_only(h, h->valb);
     if (rc) return rc;
+    ansatz_fwd(h, HPV_ANSATZ_VALID, h->valb, h->n_val);
     const int cap = HPV_HIST_CAP;
     double* buf = h->d_val_buf;
     const ValArgs a{h->valb.OUT, h->valb.N, h->d_val_u, h->d_val_du, h->n_val, h->dim, buf + 6 + (size_t)6 * cap,
@@ -1155,6 +1208,7 @@ int hpv_set_validation(hpv_handle h, const double* X, const double* u, const dou
     if (n < 0 || (n > 0 && (!X || !u))) return fail(h, -1, "bad validation arguments");
     int rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued validation may still read the old set)
+    if (h->ans_on[HPV_ANSATZ_VALID]) { drop_ansatz(h, HPV_ANSATZ_VALID); drop_graph(h); }      // the ansatz planes belong to the old points
     h->n_val = 0;
     if ((rc = points_batch(h, h->valb, du ? h->nd_grad : h->nd_val, n))) return rc;
     if ((rc = dalloc(h, &h->d_val_u, (size_t)n))) return rc;
@@ -1428,6 +1482,7 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
         if (h->d_sf) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_sf); h->d_sf = nullptr; }
         return 0;
     }
+    if (has_ansatz(h)) return fail(h, -1, "the handle has an ansatz (hpv_set_ansatz): its strong residual needs second derivatives of G and D, which are not available");
     if (!h->have_quad) return fail(h, -3, "call hpv_set_quadrature first");
     const size_t wx = (size_t)h->qx * h->qx, wy = h->dim == 2 ? (size_t)h->qy * h->qy : 0;
     if (!Dx || nx != wx) return fail(h, -1, "Dx has %zu entries, expected %d x %d of the current rule", nx, h->qx, h->qx);

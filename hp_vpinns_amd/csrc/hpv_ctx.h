@@ -130,6 +130,12 @@ struct hpv_ctx {
     int dir_mask[HPV_MAX_COEF] = {};
     int* d_dir_mask = nullptr;
     int dir_nl_mask = 0;
+    // exact Dirichlet conditions by ansatz u = G + D N (hpv_set_ansatz): per point set (HPV_ANSATZ_QUAD, _DATA, _FLUX, _VALID) the planes
+    // [2 * (1 + dim)][n] = (G, G_x[, G_y], D, D_x[, D_y]) at its points.  ans_on: the set has planes (an empty set's are no allocation);
+    // the point-set calls drop their own.  A handle with any of them keeps its data points in a batch of their own (assemble_batches)
+    bool ans_on[4] = {};
+    double* d_ans[4] = {};
+    long ans_n[4] = {};
     // per-element refinement indicators (hpv_element_indicators): the raw 1-D weights [qx | qy] (uploaded with the quadrature), a
     // forward-only object of the full channel set on the quadrature batch's own X and its buffers; re-created when Nq (sizes d_ind_f),
     // the batch size var.N (sizes d_ind_out and the object) or the owned element count (sizes d_ind) changes
@@ -200,6 +206,12 @@ int upload(hpv_ctx* h, double* dst, const double* src, size_t n);
 void drop_graph(hpv_ctx* h);                 // captured iteration graphs (hpv_api.hip)
 int check_ready(hpv_ctx* h);                 // everything of the variational scheme is set; (re)assembles the device batches (hpv_api.hip)
 int assemble_data_batch(hpv_ctx* h);
+// the ansatz of a point set (hpv_set_ansatz)
+inline bool has_ansatz(const hpv_ctx* h) { return h->ans_on[0] || h->ans_on[1] || h->ans_on[2] || h->ans_on[3]; }
+void drop_ansatz(hpv_ctx* h, int which);     // the planes of one set go (the caller has made sure no enqueued launch reads them)
+int ansatz_ready(hpv_ctx* h, int which);     // -3, naming the set, where a handle with an ansatz has points of that set and no planes for them
+void ansatz_fwd(hpv_ctx* h, int which, Batch& b, long n);      // k_ansatz_fwd on the first n points of b.OUT (no-op without planes)
+void ansatz_adj(hpv_ctx* h, int which, Batch& b, long n);      // k_ansatz_adj on b.GBAR
 // the pass engine (hpv_pass.hip)
 void run_fwd(hpv_ctx* h, Batch& b, int save_act);       // forward launch over a batch
 void enqueue_adam(hpv_ctx* h);

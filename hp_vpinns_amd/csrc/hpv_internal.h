@@ -215,6 +215,11 @@ struct FluxFin {
 int flux_loss_parts(int n);
 void launch_flux_loss(const double* OUT, long N, int dim, const double* coef, const double* g, double* GBAR,
                       double scale_grad, double* part, int n, hipStream_t s);
+// the ansatz u = G + D N on the points [off, off + n) of a batch's channel planes [nch][N] (kernels_ansatz.hip; hpv_set_ansatz): OUT in
+// place behind a forward launch, GBAR in place in front of a reverse launch.  planes: [2 * (1 + dim)][n] = (G, G_x[, G_y], D, D_x[, D_y]);
+// nch: the channels the batch carries, 1 (u alone) or 1 + dim
+void launch_ansatz_fwd(double* OUT, long N, long off, long n, int dim, int nch, const double* planes, hipStream_t s);
+void launch_ansatz_adj(double* GBAR, long N, long off, long n, int dim, int nch, const double* planes, hipStream_t s);
 // All arguments of the finalize launch (k_finalize); a field left at its zero value is an argument that is not there.
 struct GradRows { const double* GPART; int rows; };   // [rows][P] partial gradients of one batch's reverse pass (nullptr: not a source)
 struct FinalizeArgs {

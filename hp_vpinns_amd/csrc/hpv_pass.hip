@@ -40,6 +40,23 @@ static void run_bwd(hpv_ctx* h, Batch& b) {
     else launch_mlp_bwd_generic(b.nd, h->d_theta, b.X, b.ACT, b.GBAR, b.GPART, b.rows, b.N, h->stream);
 }
 
+// ---- the ansatz u = G + D N of a point set (hpv_set_ansatz): k_ansatz_fwd behind the batch's forward launch, k_ansatz_adj in front of its
+// reverse launch, on the first n points of the batch (padding behind them carries zero adjoints and is left alone) ----
+void ansatz_fwd(hpv_ctx* h, int which, Batch& b, long n) {
+    if (h->d_ans[which]) launch_ansatz_fwd(b.OUT, b.N, 0, std::min(n, h->ans_n[which]), h->dim, b.nd.C, h->d_ans[which], h->stream);
+}
+void ansatz_adj(hpv_ctx* h, int which, Batch& b, long n) {
+    if (h->d_ans[which]) launch_ansatz_adj(b.GBAR, b.N, 0, std::min(n, h->ans_n[which]), h->dim, b.nd.C, h->d_ans[which], h->stream);
+}
+int ansatz_ready(hpv_ctx* h, int which) {
+    // (the sets by their short names: tests/test_cabi.py counts the HPV_* words of the binary as environment switches)
+    static const char* const names[] = {"set QUAD (the quadrature points)", "set DATA (the boundary / data points)",
+                                        "set FLUX (the flux points)", "set VALID (the validation set)"};
+    const long count[] = {h->Nq, (long)h->n_data, (long)h->n_flux, (long)h->n_val};
+    if (!has_ansatz(h) || count[which] == 0 || (h->ans_on[which] && h->ans_n[which] == count[which])) return 0;
+    return fail(h, -3, "the handle has an ansatz but no planes for %s: hpv_set_ansatz has not been called for this set", names[which]);
+}
+
 // A batch apart from the quadrature batch (boundary/data points, element edges, flux points, collocation points) moves to the MFMA
 // kernels where they take its shape; its generic activation store is dropped.  required: staying on the generic kernels is an error.
 static int ensure_small_mfma(hpv_ctx* h, Batch& b, bool required = false) {
@@ -74,9 +91,10 @@ static int ensure_small_batches(hpv_ctx* h) {
 static void pass_flux(hpv_ctx* h, bool backward) {
     if (h->n_flux <= 0) return;
     run_fwd(h, h->flux, backward ? 1 : 0);
+    ansatz_fwd(h, HPV_ANSATZ_FLUX, h->flux, h->n_flux);
     launch_flux_loss(h->flux.OUT, h->flux.N, h->dim, h->d_flux_coef, h->d_flux_g, backward ? h->flux.GBAR : nullptr,
                      2.0 * h->w_flux / (double)h->n_flux, h->d_flux_part, h->n_flux, h->stream);
-    if (backward) run_bwd(h, h->flux);
+    if (backward) { ansatz_adj(h, HPV_ANSATZ_FLUX, h->flux, h->n_flux); run_bwd(h, h->flux); }
 }
 static FluxFin flux_fin(hpv_ctx* h, bool backward) {
     if (h->n_flux <= 0) return FluxFin{};
@@ -100,9 +118,10 @@ int launch_check(hpv_ctx* h, const char* what) {
 // ---- the boundary / data term on a batch of its own: forward, k_data_loss, reverse; returns the number of loss partials ----
 static int pass_data(hpv_ctx* h, bool backward) {
     run_fwd(h, h->data, backward ? 1 : 0);
+    ansatz_fwd(h, HPV_ANSATZ_DATA, h->data, h->n_data);
     launch_data_loss(h->data.OUT, h->d_udata, backward ? h->data.GBAR : nullptr, -2.0 * h->cfg.lossb_weight / (double)h->n_data,
                      h->d_data_part, h->n_data, h->stream);
-    if (backward) run_bwd(h, h->data);
+    if (backward) { ansatz_adj(h, HPV_ANSATZ_DATA, h->data, h->n_data); run_bwd(h, h->data); }
     return data_loss_parts(h->n_data);
 }
 
@@ -240,6 +259,7 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     if (use_mfma) hpv_mfma_forward(v.m, h->d_theta, v.X, v.OUT, backward ? 1 : 0, h->stream, p.dt);
     else run_fwd(h, v, backward ? 1 : 0);
     tstop(h, 0);
+    ansatz_fwd(h, HPV_ANSATZ_QUAD, v, h->Nq);      // (outside the timed classes: the plain handle's three figures keep their meaning)
     tstart(h, 1);
     const LinProjArgs a{v.OUT, v.GBAR, h->d_lin, h->Nq, h->d_F, h->d_R, h->d_loss_e, h->d_wtx, h->d_wty, h->d_jac, h->d_jxy,
                         h->d_jxy + h->n_elem, h->pd.nact, h->pd.nacty, v.N, h->qx, h->qy, h->ntx, h->nty, h->dim, backward ? 1 : 0};
@@ -257,8 +277,10 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     for (int t = 0; t < 4; ++t)
         if (terms_mask >> t & 1) terms += std::string(terms.empty() ? ";" : ",") + term_names[t];
     if (h->n_coef) terms += ";nc=" + std::to_string(h->n_coef);      // e.g. k_project_id<6x5/4x3;u3;nc=2>
+    if (has_ansatz(h)) terms += ";ansatz";                           // (hpv_set_ansatz: k_ansatz_fwd / k_ansatz_adj around the projection)
     snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
              h->n_coef ? "id" : h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
+    ansatz_adj(h, HPV_ANSATZ_QUAD, v, h->Nq);
     tstart(h, 2);
     if (use_mfma) hpv_mfma_backward(v.m, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);
     else run_bwd(h, v);
@@ -276,6 +298,7 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam, bool pend) {
     if (h->cfg.scheme == HPV_SCHEME_PINN || !backward) apply_pend();
     if (h->cfg.scheme == HPV_SCHEME_PINN) return enqueue_pinn_pass(h, backward, fuse_adam);
     int rc = check_ready(h);
+    for (int w = HPV_ANSATZ_QUAD; !rc && w <= HPV_ANSATZ_FLUX; ++w) rc = ansatz_ready(h, w);      // (never a pass that mixes u and N)
     if (rc) { apply_pend(); return rc; }
     const bool use_mfma = h->var.m && h->backend == HPV_BACKEND_MFMA;
     // the deferred update can only ride in a whole-iteration kernel that is the ONLY reader of the parameters in this pass (boundary
@@ -423,6 +446,8 @@ int enqueue_iterations(hpv_ctx* h, int n_iters) {
     int rc;
     if (h->use_graph && h->own_stream && !h->timing && n_iters > 0 && h->cfg.scheme == HPV_SCHEME_VPINN) {
         if ((rc = check_ready(h))) return rc;
+        for (int w = HPV_ANSATZ_QUAD; w <= HPV_ANSATZ_FLUX; ++w)      // (before a capture is begun for a pass that would refuse)
+            if ((rc = ansatz_ready(h, w))) return rc;
         // n = a * HPV_GRAPH_ITERS + r: a replays of the K-iteration graph and ONE replay of an r-iteration graph (captured
         // the first time a call leaves that remainder -- callers that time a call run it once untimed before)
         static_assert(HPV_GRAPH_ITERS <= 8, "g_rem size");

@@ -14,6 +14,11 @@ exact or manufactured solution and Dirichlet data from it; prints the relative L
     python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.2
     python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.1 --adapt-every 500 --max-elements 64
 
+    python -m hp_vpinns_amd.drivers.nonlinear burgers --nu 0.05 --hard-bc
+
+--hard-bc (burgers): the initial and boundary conditions are built into the trial function, u = G + D N with D = (1 - x^2) t, which
+vanishes on t = 0 and x = +-1, and G = sin(pi x), the driver's own data there (VPINNNonlinear(hard_bc=...)): no data points, no weight.
+
 --adapt-every K (burgers, allen-cahn): local hp-refinement (VPINNNonlinear(strong_form="elementwise").train_adaptive) after every
 K-th update, at most --max-elements elements; one (iteration, elements, loss) row is printed per round.
 
@@ -56,9 +61,25 @@ def _allen_cahn_exact(P, eps):
     return np.tanh((P[:, 0] + P[:, 1]) / (2.0 * eps))
 
 
-def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test=5, width=20, depth=3, n_bound=40, lossb_weight=10.0):
-    """dict(layers, model = the keyword arguments of VPINNNonlinear, X_test, u_test) of one of the three problems"""
+def burgers_hard_bc():
+    """dict(g=, d=) for VPINNNonlinear(hard_bc=...): D = (1 - x^2) t and G = sin(pi x), each with its gradient (d/dx, d/dt)"""
+    def g(P):
+        x = P[:, 0]
+        return np.stack([np.sin(np.pi * x), np.pi * np.cos(np.pi * x), np.zeros_like(x)], 1)
+
+    def d(P):
+        x, t = P[:, 0], P[:, 1]
+        return np.stack([(1.0 - x * x) * t, -2.0 * x * t, 1.0 - x * x], 1)
+    return dict(g=g, d=d)
+
+
+def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test=5, width=20, depth=3, n_bound=40, lossb_weight=10.0,
+          hard_bc=False):
+    """dict(layers, model = the keyword arguments of VPINNNonlinear, X_test, u_test) of one of the three problems; hard_bc (burgers):
+    the conditions by ansatz instead of data points"""
     hidden = [int(width)] * int(depth)
+    if hard_bc and problem != "burgers":
+        raise ValueError("hard_bc is set up for burgers")
     if problem == "bratu":
         ne = 4 if n_elements is None else int(n_elements)
         X = np.linspace(0.0, 1.0, 401)[:, None]
@@ -91,9 +112,10 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
         g = np.stack([v.reshape(-1) for v in np.meshgrid(np.linspace(-1.0, 1.0, 81), np.linspace(-1.0, 1.0, 81))], 1)
     else:
         raise ValueError("problem is one of bratu, burgers, allen-cahn")
+    bc = dict(hard_bc=burgers_hard_bc()) if hard_bc else dict(X_u_train=Xb, u_train=exact(Xb))
     return dict(layers=[2] + hidden + [1], X_test=g, u_test=exact(g)[:, None],
-                model=dict(grid_x=np.linspace(-1.0, 1.0, ne + 1), grid_y=gy, n_quad=int(n_quad), n_test=int(n_test), X_u_train=Xb, u_train=exact(Xb),
-                           lossb_weight=lossb_weight, **op))
+                model=dict(grid_x=np.linspace(-1.0, 1.0, ne + 1), grid_y=gy, n_quad=int(n_quad), n_test=int(n_test),
+                           lossb_weight=lossb_weight, **bc, **op))
 
 
 def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None,
@@ -137,8 +159,9 @@ def main(argv=None):
     ap.add_argument("--validate-every", type=int, default=0)
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update (not together with --validate-every)")
     ap.add_argument("--max-elements", type=int, default=None)
+    ap.add_argument("--hard-bc", action="store_true", help="burgers: initial and boundary conditions by ansatz instead of data points")
     a = ap.parse_args(argv)
-    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width), n_iter=a.iters, validate_every=a.validate_every,
+    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width, hard_bc=a.hard_bc), n_iter=a.iters, validate_every=a.validate_every,
         adapt_every=a.adapt_every, max_elements=a.max_elements)
 
 

@@ -1258,6 +1258,47 @@ def _coef_field(c, P, dim, what, vector):
     raise ValueError(f"a constant {what} is a scalar" + (f" or a vector of {dim} entries" if vector else ""))
 
 
+_FD_STEP = float(np.finfo(np.float64).eps) ** (1.0 / 3.0)      # ~6.1e-6: the step that balances a central difference's two errors
+_FD_TOL = 1e4 * _FD_STEP ** 2                                 # ~3.7e-7 per unit of scale, see _check_ansatz_field
+
+
+def _ansatz_field(c, P, dim, what):
+    """One field of the ansatz u = G + D N at the points P (n, dim) as (n, 1 + dim): the value and its gradient.  `c` a callable of P
+    returning exactly that, or a constant (zero gradient)."""
+    n = P.shape[0]
+    if callable(c):
+        v = np.asarray(c(P), dtype=np.float64)
+        if v.shape != (n, 1 + dim):
+            raise ValueError(f"hard_bc {what}(points) returned shape {v.shape}; expected {(n, 1 + dim)}: the value and the gradient")
+        return v.copy()
+    v = np.asarray(c, dtype=np.float64)
+    if v.size != 1:
+        raise ValueError(f"a constant hard_bc {what} is a scalar")
+    out = np.zeros((n, 1 + dim))
+    out[:, 0] = float(v.reshape(-1)[0])
+    return out
+
+
+def _check_ansatz_field(c, P, dim, what):
+    """The supplied gradient of a callable field against central differences of its supplied values at the points P.  Step
+    h = eps^(1/3) ~ 6.1e-6: a central difference is off by h^2 |f'''| / 6 (truncation) + eps |f| / h (rounding), both ~ h^2 = 3.7e-11 per
+    unit of |f|, |f'''|.  Tolerance 1e4 h^2 max(1, |f|, |grad f|) ~ 3.7e-7: room for third derivatives four orders above the
+    field itself (a layer-resolving lift), while a wrong sign, a missing factor or swapped columns are off by the gradient itself."""
+    if not callable(c) or P.shape[0] == 0:
+        return
+    v = _ansatz_field(c, P, dim, what)
+    for k in range(dim):
+        e = np.zeros(dim)
+        e[k] = _FD_STEP
+        fd = (_ansatz_field(c, P + e, dim, what)[:, 0] - _ansatz_field(c, P - e, dim, what)[:, 0]) / (2.0 * _FD_STEP)
+        scale = np.maximum(1.0, np.maximum(np.abs(v[:, 0]), np.abs(v[:, 1 + k])))
+        bad = np.abs(fd - v[:, 1 + k]) > _FD_TOL * scale
+        if np.any(bad):
+            i = int(np.argmax(bad))
+            raise ValueError(f"hard_bc field {what!r}: the supplied derivative along coordinate {k} is {v[i, 1 + k]:.6g} at {P[i]}, "
+                             f"central differences of the supplied values give {fd[i]:.6g}")
+
+
 class VPINNLinear(_VPINNBase):
     """Variable-coefficient linear convection-diffusion-reaction problems in 1-D and 2-D (no reference counterpart; the library's
     linear problems, include/hpvpinn.h: hpv_set_operator):
@@ -1287,7 +1328,18 @@ class VPINNLinear(_VPINNBase):
     direction) and gives `element_indicators(f=None)`, `strong_residual_at_quad()`, `adapt(f=None, **mark_kw)` and `train_adaptive(nIter,
     adapt_every, f=None, max_elements=None, **mark_kw)` -- the base class's, f None meaning the model's own f; `residual(X)` at arbitrary points stays refused.  ASSUMPTION: kappa is smooth
     inside each element.  A jump of kappa must lie on element edges; refinement bisects elements, so edges on dyadic positions of
-    the first mesh stay edges.  The rule's nodes must be distinct (no zero-weight padding)."""
+    the first mesh stay edges.  The rule's nodes must be distinct (no zero-weight padding).
+
+    Exact Dirichlet conditions (hpv_set_ansatz): `hard_bc=dict(g=.., d=..)` trains u = G + D N with N the network: `d` a callable
+    of the points (n, dim) returning (n, 1 + dim) = the value and the gradient of a function that vanishes exactly where the
+    condition holds, `g` the same for a function that matches the boundary (and initial) data there, or a constant.  The condition
+    then holds for every parameter vector and `X_u_train` is not needed (it may still be given).  The supplied gradients are compared
+    with central differences of the supplied values at a handful of quadrature points (`_check_ansatz_field`: step eps^(1/3), tolerance
+    1e4 eps^(2/3) ~ 3.7e-7 relative); a mismatch raises a ValueError naming the field.  Planes go to the library with every point
+    set -- the mesh (`set_mesh`, sharding), the data, `set_flux_data`, `set_validation` -- and `set_hard_bc` changes or removes the
+    ansatz of a live model.  `predict`, `rel_l2_error` and `evaluate` apply the map on the host to the raw network channels the
+    library returns; under an ansatz `evaluate` returns `u, u_x[, u_y]` only (second derivatives would need those of G and D).
+    Not together with `strong_form="elementwise"`, for the same reason."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1297,10 +1349,13 @@ class VPINNLinear(_VPINNBase):
 
     def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
                  sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
-                 init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None):
+                 init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None, hard_bc=None):
         dim = int(layers[0])
         if strong_form not in (None, "elementwise"):
             raise ValueError('strong_form is None or "elementwise"')
+        if strong_form and hard_bc is not None:
+            raise ValueError('hard_bc and strong_form="elementwise" do not go together: the strong residual of u = G + D N needs '
+                             "second derivatives of G and D")
         self._strong_form = strong_form
         self._trainable = self._check_trainable(trainable)
         self._n_extra = len(self._trainable)
@@ -1329,6 +1384,8 @@ class VPINNLinear(_VPINNBase):
         self._rule = tuple((np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(w, dtype=np.float64).reshape(-1)) for x, w in rule)
         self._op = dict(kappa=kappa, beta=beta, sigma=sigma)
         self._f = f
+        self._hard_bc = self._check_hard_bc(hard_bc, mesh)
+        self._val_X = None
         self.X_u_train = None if X_u_train is None else np.asarray(X_u_train, dtype=np.float64).reshape(-1, dim)
         self.utrain = None if u_train is None else np.asarray(u_train, dtype=np.float64).reshape(-1)
         self.LR, self.lossb_weight = LR, lossb_weight
@@ -1367,6 +1424,95 @@ class VPINNLinear(_VPINNBase):
         k, b = _coef_field(self._op["kappa"], P, d, "kappa", True), _coef_field(self._op["beta"], P, d, "beta", True)
         s = _coef_field(self._op["sigma"], P, d, "sigma", False)
         self.h.set_operator(np.concatenate([k.T, b.T, s[None, :]], axis=0))
+
+    # -- exact Dirichlet conditions by ansatz u = G + D N (hpv_set_ansatz) ------------------------------------------------------
+    def _check_hard_bc(self, hard_bc, mesh):
+        """hard_bc as dict(g=, d=) with the gradients checked at (up to) five quadrature points spread over the mesh; None stays None"""
+        if hard_bc is None:
+            return None
+        hb = dict(hard_bc)
+        if set(hb) != {"g", "d"} or not callable(hb["d"]):
+            raise ValueError("hard_bc is dict(g=, d=): g a callable or a constant, d a callable, of the points (n, dim) returning (n, 1 + dim)")
+        dim = mesh.dim
+        P = mesh.quad_points(self._rule[0][0], self._rule[1][0] if dim == 2 else None, 0, len(mesh))
+        P = P[np.unique(np.linspace(0, P.shape[0] - 1, 5).astype(int))]
+        for k in ("g", "d"):
+            _check_ansatz_field(hb[k], P, dim, k)
+        return hb
+
+    def _ansatz_planes(self, P):
+        """(2 * (1 + dim), n): the rows (G, G_x[, G_y], D, D_x[, D_y]) of hpv_set_ansatz at the points P"""
+        dim = self.layers[0]
+        P = np.asarray(P, dtype=np.float64).reshape(-1, dim)
+        return np.concatenate([_ansatz_field(self._hard_bc[k], P, dim, k).T for k in ("g", "d")], axis=0)
+
+    def _hand_ansatz(self, which, P):
+        if self._hard_bc is not None and P is not None:
+            self.h.set_ansatz(which, self._ansatz_planes(P))
+
+    def _hand_ansatz_quad(self, mesh):
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        self._hand_ansatz(_lib.ANSATZ_QUAD, self._quad_points(mesh, eb, ee))
+
+    def _hand_flux(self):
+        super()._hand_flux()
+        if self._flux is not None and self.rank == 0:
+            self._hand_ansatz(_lib.ANSATZ_FLUX, self._flux[0])
+
+    def set_validation(self, X=None, u=None, du=None):
+        """As `_VPINNBase.set_validation` (points and exact values are required); under an ansatz the errors are those of u = G + D N."""
+        super().set_validation(X, u, du)
+        self._val_X = np.asarray(X, dtype=np.float64).reshape(-1, self.layers[0]).copy()
+        self._hand_ansatz(_lib.ANSATZ_VALID, self._val_X)
+
+    def clear_validation(self):
+        super().clear_validation()
+        self._val_X = None
+
+    def set_hard_bc(self, g=None, d=None):
+        """Change the ansatz u = G + D N of the live model: the fields given replace the stored ones (a model without an ansatz needs
+        both), they are checked as in the constructor and handed to the library for every point set it holds.  `set_hard_bc()` removes
+        the ansatz: the model trains the raw network again.  Parameters and optimizer state stay."""
+        if self._strong_form:
+            raise ValueError('hard_bc and strong_form="elementwise" do not go together')
+        if g is None and d is None:
+            self._hard_bc = None
+            for which in (_lib.ANSATZ_QUAD, _lib.ANSATZ_DATA, _lib.ANSATZ_FLUX, _lib.ANSATZ_VALID):
+                self.h.set_ansatz(which, None)
+            return
+        old = self._hard_bc or {}
+        hb = dict(g=old.get("g") if g is None else g, d=old.get("d") if d is None else d)
+        if hb["g"] is None or hb["d"] is None:
+            raise ValueError("a model without an ansatz needs both g and d")
+        self._hard_bc = self._check_hard_bc(hb, self._mesh)
+        self._hand_ansatz_quad(self._mesh)
+        if self.rank == 0:
+            self._hand_ansatz(_lib.ANSATZ_DATA, self.X_u_train)
+            if self._flux is not None:
+                self._hand_ansatz(_lib.ANSATZ_FLUX, self._flux[0])
+        self._hand_ansatz(_lib.ANSATZ_VALID, self._val_X)
+
+    def _predict(self, X):
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.layers[0])
+        raw = super()._predict(X)
+        if self._hard_bc is None:
+            return raw
+        pl = self._ansatz_planes(X)
+        return pl[0][:, None] + pl[1 + self.layers[0]][:, None] * raw
+
+    def evaluate(self, X):
+        """As `_VPINNBase.evaluate`.  Under an ansatz: u = G + D N and its first derivatives, keyed `u, u_x[, u_y]` -- the second
+        derivatives would need those of G and D and are not returned."""
+        if self._hard_bc is None:
+            return super().evaluate(X)
+        dim = self.layers[0]
+        X = np.asarray(X, dtype=np.float64).reshape(-1, dim)
+        ch, pl = self.h.eval_points(X), self._ansatz_planes(X)
+        G, D = pl[:1 + dim], pl[1 + dim:]
+        out = {"u": (G[0] + D[0] * ch[0])[:, None]}
+        for c in range(dim):
+            out[self._channel_names[1 + c]] = (G[1 + c] + D[1 + c] * ch[0] + D[0] * ch[1 + c])[:, None]
+        return out
 
     _DIR_FIELDS = ("kappa", "beta", "sigma")      # the fields a direction may name, in this class
 
@@ -1411,10 +1557,12 @@ class VPINNLinear(_VPINNBase):
             self.h.set_strong_form(diff_matrix(xi), None if yi is None else diff_matrix(yi))
         self._hand_operator(mesh)
         self._hand_trainable(mesh)
+        self._hand_ansatz_quad(mesh)
 
     def _hand_data(self):
         if self.rank == 0 and self.X_u_train is not None:
             self.h.set_data(self.X_u_train, self.utrain)
+            self._hand_ansatz(_lib.ANSATZ_DATA, self.X_u_train)
 
     def set_operator(self, kappa=None, beta=None, sigma=None):
         """Re-evaluate the operator on the live model: the coefficients given replace the stored ones (the others stay), all three

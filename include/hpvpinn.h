@@ -426,6 +426,48 @@ int hpv_element_indicators(hpv_handle h, const double* f_quad_or_null, size_t n,
  * where a pass would (planes, nonlinear term or directions orphaned by new elements, anything not yet set); -2 on a HIP error. */
 int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny);
 int hpv_linear_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, double* out, size_t n_out, double* r_out_or_null, size_t n_r);
+
+/* Exact Dirichlet (and initial) conditions by ansatz, for the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D, with or without
+ * hpv_set_nonlinear / hpv_set_trainable).  The trial function is
+ *     u(x) = G(x) + D(x) N(x; theta)
+ * with N the network, G any function that matches the data and D a function that vanishes exactly where the condition holds
+ * (D = (x - a)(b - x) on an interval, D = (1 - x^2) t for space-time Burgers): the condition is met for every theta, and the penalty
+ * lossb_weight * mean((u - u_data)^2) with its weight is not needed (it may still be used: hpv_set_data stays optional).  Every loss
+ * term is taken on u and its first derivatives,
+ *     u_x = G_x + D_x N + D N_x        (same for y),
+ * and the channel adjoints go back through the transposed map,
+ *     Nbar = D ubar + D_x uxbar + D_y uybar        N_xbar = D uxbar        N_ybar = D uybar;
+ * second derivatives of G and D are never needed.  Two pointwise fp64 kernels (csrc/kernels_ansatz.hip) run the map on a batch's channels
+ * in place: k_ansatz_fwd behind the batch's forward launch, k_ansatz_adj in front of its reverse launch -- around k_project_lin | _nl |
+ * _id on the quadrature batch (d loss / d c_m is formed from the transformed channels), around k_data_loss and k_flux_loss, and
+ * between the forward launch and the reduction of hpv_validate / hpv_validate_enqueue / hpv_step_validate.  They are captured into
+ * the iteration graphs like the other launches; one lane per point, no atomics: results are bitwise reproducible.
+ *
+ * hpv_set_ansatz: planes = [2 * (1 + dim)][n] in the order (G, G_x[, G_y], D, D_x[, D_y]) at the points of set `which`, n its exact
+ * point count: HPV_ANSATZ_QUAD the owned quadrature points, element-major, q = j*qx + i (the layout of hpv_set_operator; after
+ * hpv_set_elements / hpv_set_element_boxes), HPV_ANSATZ_DATA the n of hpv_set_data, HPV_ANSATZ_FLUX the n of hpv_set_flux_data,
+ * HPV_ANSATZ_VALID the n of hpv_set_validation, each in the order the points were given.  Everything is copied.  (NULL, 0) removes
+ * the planes of that set; a handle whose planes have all been removed computes bit for bit what one that never had any computes.
+ * Side effects: waits for the handle's stream and drops the captured iteration graphs, like hpv_set_operator.  A handle with any
+ * planes keeps its boundary / data points in a batch of their own (they otherwise ride in the quadrature batch's forward launch,
+ * which takes their loss on raw network values), and hpv_kernel_variant appends ";ansatz" to the projection's name.  The point-set
+ * calls drop their own planes: hpv_set_elements / hpv_set_element_boxes those of QUAD, hpv_set_data, hpv_set_flux_data and
+ * hpv_set_validation those of their set.  A handle that has planes for any set must have them for every non-empty one: a pass
+ * (hpv_loss_and_grad, hpv_step, ...) or a validation otherwise returns -3 with a message naming the set -- u and N are never mixed.
+ * The planes are not state: hpv_get_state / hpv_set_state do not carry them.
+ * hpv_predict, hpv_eval_points and hpv_eval_channels keep returning the RAW network N and its derivatives; the caller applies the map
+ * (the Python classes do so on the host).
+ * Returns 0; -1 (the handle stays usable, planes given earlier stay) for a handle of another problem, an unknown `which`, n that is
+ * not the set's count, a non-finite value, and a handle on which hpv_set_strong_form is active -- the strong residual of u needs
+ * second derivatives of G and D, which is out of scope; hpv_set_strong_form on a handle that has an ansatz is refused likewise; -3
+ * for HPV_ANSATZ_QUAD before the elements are set; -2 on a HIP error.
+ * Out of scope: the problems other than the linear ones and the strong-form scheme (whole-iteration kernels, second derivatives), the
+ * strong-form indicators, ansatz functions with trainable parts, fusing the map into the projection kernels. */
+#define HPV_ANSATZ_QUAD  0
+#define HPV_ANSATZ_DATA  1
+#define HPV_ANSATZ_FLUX  2
+#define HPV_ANSATZ_VALID 3
+int hpv_set_ansatz(hpv_handle h, int which, const double* planes, size_t n);
 int hpv_backend_in_use(hpv_handle h);                       /* HPV_BACKEND_GENERIC or HPV_BACKEND_MFMA */
 /* Launch structure of the most recent reverse-mode pass over the quadrature batch (tests assert that the kernel they mean to
  * exercise is the one that ran): 0 separate forward / projection / reverse launches, 1 forward + projection-fused reverse,
