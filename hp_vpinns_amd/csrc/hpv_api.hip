@@ -424,6 +424,12 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
         if (h->nacty_all[i] > nty)
             return fail(h, -1, "nay[%zu] = %d exceeds the new nty %d (hpv_set_active_tests_2d(NULL, NULL) drops the counts)", i, h->nacty_all[i], nty);
     const int qx = h->qx, qy = h->qy;
+    {   // refused BEFORE anything of the old tables is replaced: a handle that had tables keeps them, with its ntx / nty
+        ProjDesc pd = h->pd;
+        pd.ntx = ntx; pd.nty = nty;
+        const size_t lds = h->linear ? hpv_linop_lds_bytes(qx, qy, ntx, nty) : hpv_proj_lds_bytes(pd);
+        if (lds > 64 * 1024) return fail(h, -1, "element too large for the projection kernel's LDS (%zu B)", lds);
+    }
     std::vector<double> wtx((size_t)3 * ntx * qx), wty((size_t)3 * nty * qy);
     const double* tx[3] = {phix, dphix, d2phix};
     const double* ty[3] = {phiy, dphiy, d2phiy};
@@ -446,8 +452,6 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
     }
     h->ntx = ntx; h->nty = nty;
     h->pd.ntx = ntx; h->pd.nty = nty;
-    const size_t lds = h->linear ? hpv_linop_lds_bytes(qx, qy, ntx, nty) : hpv_proj_lds_bytes(h->pd);
-    if (lds > 64 * 1024) return fail(h, -1, "element too large for the projection kernel's LDS (%zu B)", lds);
     h->have_tables = true;
     drop_graph(h);
     return 0;

@@ -156,8 +156,9 @@ def reference(p, theta=None, planes=None):
     return fr.triple(p["prob"], v["lossv"], d, f), v["grad"] + d["grad"] + f["grad"], v["R"]
 
 
-def conditions(p):
-    """(a) - (c) of the module docstring; returns the figures for the log"""
+def conditions(p, swaps=("q", "nt")):
+    """(a) - (c) of the module docstring; returns the figures for the log.  swaps: the halves of (c) that are asked for -- exchanging
+    two extents of which one is 1 is the same indexing, so a caller with such a shape leaves that half out"""
     v = var_part(p)
     _, g, _ = reference(p)
     total = np.linalg.norm(g)
@@ -170,8 +171,8 @@ def conditions(p):
         moves.append(abs(var_part(p, planes=z)["lossv"] - v["lossv"]) / v["lossv"])
     assert min(moves) > fr.COLUMN_MOVE, ("(b)", moves)
     sw = []
-    if p["dim"] == 2:
-        sw = [abs(var_part(p, swap=w)["lossv"] - v["lossv"]) / v["lossv"] for w in ("q", "nt")]
+    if p["dim"] == 2 and swaps:
+        sw = [abs(var_part(p, swap=w)["lossv"] - v["lossv"]) / v["lossv"] for w in swaps]
         assert min(sw) > fr.COLUMN_MOVE, ("(c)", sw)
     return dict(block_share=min(share.values()), plane=min(moves), swap=min(sw) if sw else None)
 

@@ -154,8 +154,9 @@ def reference(p, theta=None, planes=None, nl=None):
     return fr.triple(p["prob"], v["lossv"], d, f), v["grad"] + d["grad"] + f["grad"], v["R"]
 
 
-def conditions(p, margin=1.0):
-    """(a) - (d) of the module docstring; returns the figures for the log.  margin: the factor (d) is kept by (the seed search uses 2)"""
+def conditions(p, margin=1.0, swaps=("q", "nt")):
+    """(a) - (d) of the module docstring; returns the figures for the log.  margin: the factor (d) is kept by (the seed search uses 2);
+    swaps: the halves of (c) that are asked for, as in linear_reference.conditions"""
     v = var_part(p)
     _, g, _ = reference(p)
     total = np.linalg.norm(g)
@@ -171,8 +172,8 @@ def conditions(p, margin=1.0):
         moves.append(move(planes=z))
     assert min(moves) > fr.COLUMN_MOVE, ("(b)", moves)
     sw = []
-    if p["dim"] == 2:
-        sw = [move(swap=w) for w in ("q", "nt")]
+    if p["dim"] == 2 and swaps:
+        sw = [move(swap=w) for w in swaps]
         assert min(sw) > fr.COLUMN_MOVE, ("(c)", sw)
     nlm = {}
     rows = term_rows(p["dim"])

@@ -37,28 +37,54 @@ def _problem(name, kind="generic"):
 class Dev:
     """the C-ABI on problem dict `p`: a narrow network is zero-padded onto its device width as the Python classes do (init.pad_plan)"""
 
-    def __init__(self, p, ansatz=True):
+    def __init__(self, p, ansatz=True, validation=True):
         from hp_vpinns_amd import _lib
         from hp_vpinns_amd.init import n_params, pad_plan
-        from hp_vpinns_amd.testfcn import tables_1d
         self.p, L, self.nc = p, p["layers"], p["c0"].size
         plan = pad_plan(L, self.nc)
         self.dev_layers, self.idx = plan if plan is not None else (L, None)
         self.n_dev = n_params(self.dev_layers, self.nc)
-        self.h = h = _lib.Handle(_lib.PDE_LINEAR1D if p["dim"] == 1 else _lib.PDE_LINEAR2D, 1, _lib.ACT_SIN if p["act"] == "sin" else _lib.ACT_TANH,
-                                 self.dev_layers, lr=1e-3, lossb_weight=p["lbw"], n_coef=self.nc)
+        self.h = _lib.Handle(_lib.PDE_LINEAR1D if p["dim"] == 1 else _lib.PDE_LINEAR2D, 1, _lib.ACT_SIN if p["act"] == "sin" else _lib.ACT_TANH,
+                             self.dev_layers, lr=1e-3, lossb_weight=p["lbw"], n_coef=self.nc)
+        self.populate(p, ansatz, validation)
+
+    def populate(self, p, ansatz=True, validation=True):
+        """rule, tables, elements, F, counts, planes and point sets of problem dict `p` (same network, same n_coef) on the live handle --
+        a data or flux set the problem lacks is removed, validation=False leaves the handle without a validation set --, the ansatz
+        planes of the sets that exist where p has an ansatz, and p's parameters"""
+        from hp_vpinns_amd.testfcn import tables_1d
+        self.p, h = p, self.h
+        h.set_rhs(None)                                 # (per-grid inputs of an earlier, other mesh)
+        h.set_active_tests(None)
         (xi, wx), yr = p["xr"], p["yr"]
         h.set_quadrature(xi, wx, *(yr if yr is not None else (None, None)))
         h.set_tables(tables_1d(p["ntx"], xi), None if yr is None else tables_1d(p["nty"], yr[0]))
         h.set_element_boxes(p["boxes"], p["eb"], p["ee"])
         h.set_rhs(p["F"].reshape(-1))
+        self.set_counts()
         self.set_planes()
-        h.set_data(*p["data"])
-        h.set_flux_data(p["flux"]["X"], fr.coef(p["flux"]), p["flux"]["g"], fr.W_F)
-        h.set_validation(*p["val"])
-        if ansatz:
-            self.set_ansatz()
+        h.set_data(*(p["data"] if p["data"] is not None else (None, None)))
+        if p["flux"] is not None:
+            h.set_flux_data(p["flux"]["X"], fr.coef(p["flux"]), p["flux"]["g"], fr.W_F)
+        else:
+            h.set_flux_data(None, None, None)
+        self.has_val = validation
+        if validation:
+            h.set_validation(*p["val"])
+        else:
+            h.set_validation(None, None)
+        if ansatz and p["ans"] is not None:
+            self.set_ansatz([k for k in SETS if p["ans"][k] is not None and (k != "val" or validation)])
         self.set_params(p["full"])
+
+    def set_counts(self):
+        p, h = self.p, self.h
+        if p["nax"] is None:
+            h.set_active_tests(None)
+        elif p["dim"] == 1:
+            h.set_active_tests(p["nax"])
+        else:
+            h.set_active_tests_2d(p["nax"], p["nay"])
 
     def set_planes(self):
         p, h = self.p, self.h
