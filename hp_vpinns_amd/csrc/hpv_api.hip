@@ -2,6 +2,7 @@
 // handle = one GPU's shard of elements + a replica of the network parameters.  (The multi-GPU exchanges live in hpv_exchange.hip,
 // the timing / benchmark / debug hooks in hpv_bench.hip; hpv_ctx.h holds the handle and the helpers they share.)
 #include "hpv_ctx.h"
+#include "hpv_dual_norm.h"
 
 using namespace hpvd;
 
@@ -212,6 +213,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
+    if (h->dual_stale) return fail(h, -3, "hpv_set_residual_norm has not been called again: hpv_set_tables dropped the tables of the dual norm");
     if (h->n_coef && !h->have_dirs) return fail(h, -3, "hpv_set_trainable has not been called");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->have_F && !h->d_F && h->n_elem > 0) return fail(h, -3, "internal: F not sliced");
@@ -365,7 +367,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
+    void* ptrs[] = {h->d_dual, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -454,6 +456,12 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
     h->pd.ntx = ntx; h->pd.nty = nty;
     h->have_tables = true;
     drop_graph(h);
+    if (h->d_dual) {      // (hpv_set_residual_norm: its tables belong to the old test functions; a pass must not silently train mean(R^2))
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_dual);
+        h->d_dual = nullptr;
+        h->dual_stale = true;
+    }
     return 0;
 }
 
@@ -763,6 +771,58 @@ int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n) {
     if ((rc = dalloc(h, &h->d_nl, n))) return rc;
     if ((rc = upload(h, h->d_nl, coef, n))) return rc;
     h->nl_mask = mask;
+    return 0;
+}
+
+// The norm the residual is measured in (include/hpvpinn.h); the _dual instantiations of the projection kernels read the tables in place.
+int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx, const double* lamx, const double* Sy, const double* lamy) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -3, "hpv_set_residual_norm belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D): the other classes and the whole-iteration kernels train mean(R^2)");
+    if (h->cfg.scheme == HPV_SCHEME_PINN) return fail(h, -3, "hpv_set_residual_norm belongs to the variational scheme");
+    if (kind != 0 && kind != 1) return fail(h, -1, "unknown residual norm %d (0 l2, 1 dual)", kind);
+    if (kind == 0) {
+        if (!h->d_dual && !h->dual_stale) return 0;
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the tables)
+        drop_graph(h);
+        if (h->d_dual) { (void)hipFree(h->d_dual); h->d_dual = nullptr; }
+        h->dual_stale = false;
+        h->dual_mass = 0.0;
+        return 0;
+    }
+    if (!h->have_tables) return fail(h, -3, "call hpv_set_tables first");
+    const int ntx = h->ntx, nty = h->nty;
+    if (!std::isfinite(mass) || mass < 0.0) return fail(h, -1, "the mass weight of the dual norm is %g; it must be finite and >= 0", mass);
+    if (!Sx || !lamx) return fail(h, -1, "the dual norm needs the x tables");
+    if (h->dim == 1 ? (Sy || lamy) : (!Sy || !lamy)) return fail(h, -1, "the y tables of the dual norm are NULL in 1-D and required in 2-D");
+    const size_t nsx = (size_t)ntx * ntx * ntx, nlx = (size_t)ntx * ntx, nsy = (size_t)nty * nty * nty, nly = (size_t)nty * nty;
+    std::vector<double> tab(hpv_dual_table_doubles(ntx, nty));
+    std::copy_n(Sx, nsx, tab.begin());
+    std::copy_n(lamx, nlx, tab.begin() + nsx);
+    if (h->dim == 2) {
+        std::copy_n(Sy, nsy, tab.begin() + nsx + nlx);
+        std::copy_n(lamy, nly, tab.begin() + nsx + nlx + nsy);
+    } else {      // nty == 1: S_y = 1, lam_y = 0 (d = lam_x / Jx + mass Jx with Jy = 1)
+        tab[nsx + nlx] = 1.0;
+        tab[nsx + nlx + nsy] = 0.0;
+    }
+    for (size_t i = 0; i < tab.size(); ++i)
+        if (!std::isfinite(tab[i])) return fail(h, -1, "the tables of the dual norm hold a non-finite value at entry %zu", i);
+    for (int n = 1; n <= ntx; ++n)      // (the entries behind the count are padding)
+        for (int b = 0; b < n; ++b)
+            if (!(lamx[(size_t)(n - 1) * ntx + b] > 0.0)) return fail(h, -1, "lam_x[%d][%d] = %g; the eigenvalues must be > 0", n - 1, b, lamx[(size_t)(n - 1) * ntx + b]);
+    for (int n = 1; h->dim == 2 && n <= nty; ++n)
+        for (int a = 0; a < n; ++a)
+            if (!(lamy[(size_t)(n - 1) * nty + a] > 0.0)) return fail(h, -1, "lam_y[%d][%d] = %g; the eigenvalues must be > 0", n - 1, a, lamy[(size_t)(n - 1) * nty + a]);
+    const size_t lds = hpv_dual_lds_bytes(h->qx, h->qy, ntx, nty);
+    if (lds > 64 * 1024) return fail(h, -1, "element too large for the dual-norm projection kernels' LDS (%zu B)", lds);
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old tables)
+    drop_graph(h);
+    if (h->d_dual) { (void)hipFree(h->d_dual); h->d_dual = nullptr; }
+    if ((rc = dalloc(h, &h->d_dual, tab.size()))) return rc;
+    if ((rc = upload(h, h->d_dual, tab.data(), tab.size()))) { (void)hipFree(h->d_dual); h->d_dual = nullptr; return rc; }
+    h->dual_mass = mass;
+    h->dual_stale = false;
     return 0;
 }
 
@@ -1555,6 +1615,7 @@ int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* 
     a.R = h->d_R; a.nact = h->pd.nact; a.nacty = h->pd.nacty;
     a.out = h->d_ind; a.r_out = r_out ? h->d_ind_r : nullptr;
     a.qx = h->qx; a.qy = h->qy; a.ntx = h->ntx; a.nty = h->nty; a.dim = h->dim;
+    a.loss_e = h->d_dual ? h->d_loss_e : nullptr;      // (hpv_set_residual_norm: column 0 is the loss the pass above wrote)
     launch_lin_indicators(a, ne, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));

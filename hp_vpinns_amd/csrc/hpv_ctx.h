@@ -120,6 +120,12 @@ struct hpv_ctx {
     double* d_nl = nullptr;
     int nl_mask = 0;
     bool nl_stale = false;
+    // the dual-norm loss of such a handle (hpv_set_residual_norm): the eigen tables of the test functions' Gram matrices (layout:
+    // hpv_dual_norm.h; nullptr: mean(R^2)), the weight of the L2 part, and whether hpv_set_tables has dropped tables that have not
+    // been given again (the tables belong to the test-function tables; a pass then refuses)
+    double* d_dual = nullptr;
+    double dual_mass = 0.0;
+    bool dual_stale = false;
     // trainable coefficients of such a handle (hpv_create_ex, hpv_set_trainable): n_coef slots behind the network in theta, their
     // directions [n_coef][K + M][Nq], the per-direction masks of the planes that are not zero everywhere (host and device copy), the
     // HPV_NL_* terms the directions touch, the partials [n_coef][n_elem] of d lossv / d c_m, and -- where hpv_set_nonlinear gave no

@@ -105,8 +105,11 @@ struct LinProjArgs {
     long N;
     int qx, qy, ntx, nty, dim;
     int do_adjoint;
+    const double* dual;      // the tables of the dual-norm loss (hpv_set_residual_norm; layout: hpv_dual_norm.h), or nullptr: mean(R^2)
+    double dual_mass;        // the weight of the L2 part of its inner product
 };
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty);
+size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty);      // k_project_lin_dual, _nl_dual, _id<.., true>: says whether the scratch is appended
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s);
 
 // The same launch with a pointwise nonlinear term (k_project_nl, kernels_nonlin.hip; hpv_set_nonlinear):
@@ -336,6 +339,7 @@ struct LinIndArgs {
     double* out;             // [n_elem][HPV_IND_N]
     double* r_out;           // [n_elem * qx * qy] the strong residual at every point, or nullptr (not wanted)
     int qx, qy, ntx, nty, dim;
+    const double* loss_e;    // [n_elem] the dual-norm loss the forward-only pass wrote (column 0 under hpv_set_residual_norm), or nullptr
 };
 size_t hpv_linadapt_lds_bytes(int dim, int qx, int qy);
 void launch_lin_indicators(const LinIndArgs& a, long n_elem, hipStream_t s);

@@ -22,6 +22,7 @@
 // whatever finite value its weights take, it adds exactly 0 to every accumulator and every GBAR entry.
 // Registers: profiles/identification.md (no scratch, no VGPR spill; some kernel arguments are parked in VGPR lanes).
 #include "hpv_internal.h"
+#include "hpv_dual_norm.h"
 
 namespace {
 
@@ -96,7 +97,8 @@ __device__ __forceinline__ void id_planes(const IdProjArgs& b, const double* cf,
     }
 }
 
-template <int DIM>
+// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+template <int DIM, bool DUAL>
 __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int K = DIM == 2 ? 5 : 3, M = DIM == 2 ? 5 : 4;
@@ -192,14 +194,21 @@ __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        sq += v * v;
+        if constexpr (!DUAL) sq += v * v;
+    }
+    DualScratch ds{};
+    if constexpr (DUAL) {
+        ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], DIM == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = id_block_sum(sq, red);           // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
     if (!a.do_adjoint) return;
+    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = 2.0 / NRa;
+    const double sc = DUAL ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -275,6 +284,11 @@ __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
 void launch_project_id(const IdProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const size_t lds = hpv_linop_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);      // (nothing is added to k_project_lin's layout)
-    if (a.lin.dim == 2) hipLaunchKernelGGL(k_project_id<2>, dim3((unsigned)n_elem), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(k_project_id<1>, dim3((unsigned)n_elem), dim3(256), lds, s, a);
+    const dim3 grid((unsigned)n_elem), block(256);
+    if (a.lin.dual) {
+        const size_t ldsd = hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
+        if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, true>), grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL((k_project_id<1, true>), grid, block, ldsd, s, a);
+    } else if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, false>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_project_id<1, false>), grid, block, lds, s, a);
 }

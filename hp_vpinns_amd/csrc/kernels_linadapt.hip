@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(LIND_THREADS) k_lin_indicators(LinIndArgs a) {
         v[c] = t;
     }
     double* dst = a.out + e * HPV_IND_N;
-    dst[0] = v[1] / (double)(nax * nay);
+    dst[0] = a.loss_e ? a.loss_e[e] : v[1] / (double)(nax * nay);      // (dual norm: what the forward-only pass wrote)
     dst[1] = a.J[e] * v[0];
     dst[2] = v[1];
     dst[3] = v[2];

@@ -27,6 +27,7 @@
 // hpv_element_indicators are refused on these handles; the strong residual at the elements' own quadrature points, for refinement
 // indicators, is an opt-in with a kernel of its own (hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
 #include "hpv_internal.h"
+#include "hpv_dual_norm.h"
 
 namespace {
 
@@ -42,9 +43,9 @@ __device__ __forceinline__ double lin_block_sum(double v, double* red) {
     return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-}  // namespace
-
-__global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) {
+// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+template <bool DUAL>
+__device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long e = blockIdx.x;
     const int qx = a.qx, qy = a.qy, ntx = a.ntx, nty = a.nty, nt = a.dim + 1;
@@ -122,14 +123,21 @@ __global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        sq += v * v;
+        if constexpr (!DUAL) sq += v * v;
+    }
+    DualScratch ds{};
+    if constexpr (DUAL) {
+        ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], a.dim == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = lin_block_sum(sq, red);          // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
     if (!a.do_adjoint) return;
+    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = 2.0 / NRa;
+    const double sc = DUAL ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -165,12 +173,23 @@ __global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) {
     }
 }
 
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) { project_lin_body<false>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_dual(LinProjArgs a) { project_lin_body<true>(a); }
+
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty) {
     const size_t gs = (size_t)(qx | 1), ts = (size_t)(ntx | 1), ys = (size_t)(qy | 1);
     return (3 * qy * gs + 3 * qy * ts + (size_t)ntx * nty + 2 * ntx * gs + 2 * nty * ys + 4) * sizeof(double);
 }
 
+// the same layout, with the scratch of hpv_dual_norm.h appended where the G region cannot hold it
+size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty) {
+    return hpv_linop_lds_bytes(qx, qy, ntx, nty) + (hpv_dual_aliases_g(qx, qy, ntx, nty) ? 0 : hpv_dual_scratch_doubles(ntx, nty) * sizeof(double));
+}
+
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
-    hipLaunchKernelGGL(k_project_lin, dim3((unsigned)n_elem), dim3(256), hpv_linop_lds_bytes(a.qx, a.qy, a.ntx, a.nty), s, a);
+    if (a.dual) hipLaunchKernelGGL(k_project_lin_dual, dim3((unsigned)n_elem), dim3(256), hpv_dual_lds_bytes(a.qx, a.qy, a.ntx, a.nty), s, a);
+    else hipLaunchKernelGGL(k_project_lin, dim3((unsigned)n_elem), dim3(256), hpv_linop_lds_bytes(a.qx, a.qy, a.ntx, a.nty), s, a);
 }

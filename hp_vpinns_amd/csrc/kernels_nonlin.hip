@@ -30,6 +30,7 @@
 // a fixed tree: no atomics, the same bits from call to call.  A zero-weight padding point has all-zero table columns: whatever finite
 // value N takes there is multiplied by 0 in T, and its Gbar_0 = 0 makes every GBAR entry above 0.
 #include "hpv_internal.h"
+#include "hpv_dual_norm.h"
 
 namespace {
 
@@ -71,9 +72,9 @@ __device__ __forceinline__ void nl_point(int mask, const double* nl, long cs, do
     dNu = d;
 }
 
-}  // namespace
-
-__global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) {
+// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+template <bool DUAL>
+__device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LinProjArgs& a = b.lin;
     const long e = blockIdx.x;
@@ -160,14 +161,21 @@ __global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        sq += v * v;
+        if constexpr (!DUAL) sq += v * v;
+    }
+    DualScratch ds{};
+    if constexpr (DUAL) {
+        ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], a.dim == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = nl_block_sum(sq, red);           // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
     if (!a.do_adjoint) return;
+    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = 2.0 / NRa;
+    const double sc = DUAL ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -221,10 +229,16 @@ __global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) {
     }
 }
 
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) { project_nl_body<false>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_dual(NlProjArgs b) { project_nl_body<true>(b); }
+
 // (the channels are re-read from OUT in the adjoint phase, so nothing is added to k_project_lin's layout)
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop_lds_bytes(qx, qy, ntx, nty); }
 
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
-    hipLaunchKernelGGL(k_project_nl, dim3((unsigned)n_elem), dim3(256), hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+    if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_dual, dim3((unsigned)n_elem), dim3(256), hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+    else hipLaunchKernelGGL(k_project_nl, dim3((unsigned)n_elem), dim3(256), hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
 }

@@ -55,6 +55,19 @@ def interval_hard_bc(a, b, ua, ub):
     return dict(g=g, d=d)
 
 
+def _norm_arg(residual_norm, gram_mass):
+    """the residual_norm= of the classes from the command line's --residual-norm / --gram-mass"""
+    return "l2" if residual_norm == "l2" else dict(kind="dual", mass=float(gram_mass))
+
+
+def _estimator_line(m, h1_err):
+    """sqrt(lossv) beside the H^1-seminorm error the driver knows from its manufactured solution: under residual_norm="dual" the
+    first estimates the second (exactly the projected error's energy for kappa = 1, beta = sigma = 0; up to the operator's
+    continuity and inf-sup constants otherwise), under "l2" it does not"""
+    lossv = float(np.asarray(m.loss())[2])
+    return "sqrt(lossv) %.4e beside the H^1 error %.4e (residual norm %s)" % (np.sqrt(lossv), h1_err, m.residual_norm)
+
+
 def _train(m, n_iter, adapt_every, max_elements, verbose):
     """train, or train_adaptive with its rows [(iterations done, elements, loss on the new mesh)] printed like the Poisson-2D driver's"""
     if not adapt_every:
@@ -68,21 +81,27 @@ def _train(m, n_iter, adapt_every, max_elements, verbose):
 
 
 def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000, layers=(1, 20, 20, 20, 1), grade=2.0, LR=1e-3,
-                       lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, hard_bc=False):
+                       lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, hard_bc=False,
+                       residual_norm="l2"):
     grid = graded_grid(int(n_elements), grade)
     bc = dict(hard_bc=interval_hard_bc(0.0, 1.0, 0.0, 0.0)) if hard_bc else dict(X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2))
     m = VPINNLinear(list(layers), grid_x=grid, n_quad=int(n_quad), n_test=int(n_test), kappa=-float(eps), beta=1.0, sigma=0.0, f=1.0,
                     lossb_weight=lossb_weight, activation="sin", LR=LR,
-                    seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None, **bc)
+                    seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None,
+                    residual_norm=residual_norm, **bc)
     rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     X = np.linspace(0.0, 1.0, 401)[:, None]
     u = boundary_layer_exact(X, eps)
     err = m.rel_l2_error(X, u)
+    ux = 1.0 - np.exp((X[:, 0] - 1.0) / eps) / (eps * (1.0 - np.exp(-1.0 / eps)))
+    d2 = (np.asarray(m.evaluate(X)["u_x"]).reshape(-1) - ux) ** 2
+    h1 = float(np.sqrt(np.sum(0.5 * (d2[1:] + d2[:-1]) * np.diff(X[:, 0]))))      # (trapezoidal rule on the test points)
     bnd = float(np.max(np.abs(m.predict(np.array([[0.0], [1.0]])))))      # (both end values are 0)
     if verbose:
         print("boundary layer eps = %g, %d elements (%d graded at the start), %s: relative L2 error %.4e, boundary error %.3e (%s)"
               % (eps, len(m.mesh), n_elements, "exact conditions (ansatz)" if hard_bc else "penalty", err, bnd, m.h.kernel_variant()))
-    return dict(model=m, rel_l2=err, bnd_err=bnd, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
+        print(_estimator_line(m, h1))
+    return dict(model=m, rel_l2=err, bnd_err=bnd, h1_err=h1, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 L_BOXES = np.array([[-1.0, 0.0, -1.0, 0.0], [-1.0, 0.0, 0.0, 1.0], [0.0, 1.0, 0.0, 1.0]])
@@ -108,21 +127,26 @@ def _l_boundary(n):
 
 
 def run_l_shape(n_iter=2000, n_quad=20, n_test=10, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0, seed=1234,
-                backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None):
+                backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, residual_norm="l2"):
     Xb = _l_boundary(int(n_bound))
     m = VPINNLinear(list(layers), mesh=ElementMesh(L_BOXES, int(n_test), int(n_test)), n_quad=int(n_quad),
                     kappa=lambda P: 1.0 + P[:, 0] * P[:, 1], beta=np.array([1.0, -1.0]), sigma=2.0, f=_l_f, X_u_train=Xb, u_train=_l_exact(Xb),
                     lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device,
-                    strong_form="elementwise" if adapt_every else None)
+                    strong_form="elementwise" if adapt_every else None, residual_norm=residual_norm)
     rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     g = np.linspace(-1.0, 1.0, 81)
     X = np.stack([v.reshape(-1) for v in np.meshgrid(g, g)], 1)
     X = X[~((X[:, 0] > 0) & (X[:, 1] < 0))]
     u = _l_exact(X)[:, None]
     err = m.rel_l2_error(X, u)
+    ev = m.evaluate(X)
+    gx = np.pi * np.cos(np.pi * X[:, 0]) * np.sin(np.pi * X[:, 1]) - np.asarray(ev["u_x"]).reshape(-1)
+    gy = np.pi * np.sin(np.pi * X[:, 0]) * np.cos(np.pi * X[:, 1]) - np.asarray(ev["u_y"]).reshape(-1)
+    h1 = float(np.sqrt(3.0 * np.mean(gx ** 2 + gy ** 2)))      # (the L has area 3; a mean over the uniform test points)
     if verbose:
         print("L-shape, kappa = 1 + x y, beta = (1, -1), sigma = 2, %d elements: relative L2 error %.4e (%s)" % (len(m.mesh), err, m.h.kernel_variant()))
-    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
+        print(_estimator_line(m, h1))
+    return dict(model=m, rel_l2=err, h1_err=h1, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 def main(argv=None):
@@ -137,12 +161,15 @@ def main(argv=None):
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None)
     ap.add_argument("--hard-bc", action="store_true", help="boundary layer: exact Dirichlet conditions by ansatz instead of the penalty")
+    ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
+    ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
+    rn = _norm_arg(a.residual_norm, a.gram_mass)
     if a.problem == "boundary-layer":
         run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
-                           adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc)
+                           adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn)
     else:
-        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements)
+        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn)
 
 
 if __name__ == "__main__":

@@ -119,7 +119,7 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
 
 
 def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None,
-        max_elements=None):
+        max_elements=None, residual_norm="l2"):
     """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated); with
     adapt_every the elements are refined locally (train_adaptive: the model is built with strong_form="elementwise").  The two
     are not combined: giving both raises ValueError."""
@@ -127,7 +127,7 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
     if adapt_every and validate_every:
         raise ValueError("adapt_every and validate_every cannot be combined: run one or the other")
     m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None,
-                       **s["model"])
+                       residual_norm=residual_norm, **s["model"])
     his, rows = None, []
     if adapt_every:
         rows = m.train_adaptive(int(n_iter), int(adapt_every), max_elements=max_elements)
@@ -145,6 +145,8 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
     err = m.rel_l2_error(s["X_test"], s["u_test"])
     if verbose:
         print("relative L2 error %.4e after %d iterations (%s)" % (err, n_iter, m.h.kernel_variant()))
+        # (the test solutions of this driver come without gradients: sqrt(lossv) stands beside the error that is known)
+        print("sqrt(lossv) %.4e (residual norm %s)" % (np.sqrt(float(np.asarray(m.loss())[2])), m.residual_norm))
     return dict(model=m, rel_l2=err, history=his, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
@@ -160,9 +162,12 @@ def main(argv=None):
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update (not together with --validate-every)")
     ap.add_argument("--max-elements", type=int, default=None)
     ap.add_argument("--hard-bc", action="store_true", help="burgers: initial and boundary conditions by ansatz instead of data points")
+    ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
+    ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
     run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width, hard_bc=a.hard_bc), n_iter=a.iters, validate_every=a.validate_every,
-        adapt_every=a.adapt_every, max_elements=a.max_elements)
+        adapt_every=a.adapt_every, max_elements=a.max_elements,
+        residual_norm="l2" if a.residual_norm == "l2" else dict(kind="dual", mass=a.gram_mass))
 
 
 if __name__ == "__main__":

@@ -133,3 +133,43 @@ def diff_matrix(x):
     np.fill_diagonal(D, 0.0)
     np.fill_diagonal(D, -D.sum(axis=1))
     return D
+
+
+# ---- the Gram matrices of the test functions phi_n = P_{n+1} - P_{n-1}, n = 1 .. N, on the reference interval ------------------------
+def gram_1d(n):
+    """(K, M) of the first n test functions, exact closed forms: the stiffness K = int phi_i' phi_j' = diag(2 (2 i + 1)) (because
+    phi_i' = (2 i + 1) P_i) and the mass M = int phi_i phi_j with M_ii = 2 / (2 i + 3) + 2 / (2 i - 1), M_i,i+2 = -2 / (2 i + 3)
+    (indices 1-based)."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("gram_1d needs at least one test function")
+    i = np.arange(1, n + 1, dtype=np.float64)
+    K = np.diag(2.0 * (2.0 * i + 1.0))
+    M = np.diag(2.0 / (2.0 * i + 3.0) + 2.0 / (2.0 * i - 1.0))
+    for j in range(n - 2):
+        M[j, j + 2] = M[j + 2, j] = -2.0 / (2.0 * i[j] + 3.0)
+    return K, M
+
+
+def gram_eig(n):
+    """(S, lam) of the generalised problem K S = M S diag(lam) with S^T M S = I (so S^T K S = diag(lam)), lam ascending: a symmetric
+    eigen-solve of K^{-1/2} M K^{-1/2} = V diag(mu) V^T (K is diagonal), lam = 1 / mu, S = K^{-1/2} V diag(mu^{-1/2})."""
+    K, M = gram_1d(n)
+    k = 1.0 / np.sqrt(np.diag(K))
+    mu, V = np.linalg.eigh(k[:, None] * M * k[None, :])
+    order = np.argsort(-mu)                      # (lam ascending)
+    mu, V = mu[order], V[:, order]
+    S = (k[:, None] * V) / np.sqrt(mu)[None, :]
+    S *= np.where(S[np.argmax(np.abs(S), axis=0), np.arange(S.shape[1])] < 0.0, -1.0, 1.0)[None, :]      # (a fixed sign per column)
+    return S, 1.0 / mu
+
+
+def gram_stacks(nt):
+    """(S_stack (nt, nt, nt), lam_stack (nt, nt)): gram_eig of every count 1 .. nt, count n at [n - 1] in the leading n x n block,
+    zero-padded -- per-element counts use the leading functions, and S of n functions is not a sub-block of S of n + 1
+    (hpv_set_residual_norm)."""
+    nt = int(nt)
+    S, lam = np.zeros((nt, nt, nt)), np.zeros((nt, nt))
+    for n in range(1, nt + 1):
+        S[n - 1, :n, :n], lam[n - 1, :n] = gram_eig(n)
+    return S, lam

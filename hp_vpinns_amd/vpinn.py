@@ -1339,7 +1339,15 @@ class VPINNLinear(_VPINNBase):
     set -- the mesh (`set_mesh`, sharding), the data, `set_flux_data`, `set_validation` -- and `set_hard_bc` changes or removes the
     ansatz of a live model.  `predict`, `rel_l2_error` and `evaluate` apply the map on the host to the raw network channels the
     library returns; under an ansatz `evaluate` returns `u, u_x[, u_y]` only (second derivatives would need those of G and D).
-    Not together with `strong_form="elementwise"`, for the same reason."""
+    Not together with `strong_form="elementwise"`, for the same reason.
+
+    The norm of the residual (hpv_set_residual_norm): `residual_norm="l2"` (the default) is the reference's mean over the test functions
+    of R^2; `"dual"`, or `dict(kind="dual", mass=gamma)`, measures each element's residual functional in the dual norm of its discrete
+    test space, loss_e = R_e^T G_e^{-1} R_e with G_e the Gram matrix of the element's active test functions in (grad v, grad w) +
+    gamma (v, w) -- robust VPINNs.  For kappa = 1, beta = sigma = 0 this is the squared energy norm of the Galerkin projection of
+    the error, so sqrt(loss) estimates the H^1 error, `element_indicators` column 0 is the natural refinement indicator, and loss
+    values compare across `n_test`, element shapes and the meshes of a `train_adaptive` run.  `set_residual_norm` changes it on a
+    live model; checkpoints store the setting.  The data and flux terms keep their mean(square)."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1349,8 +1357,10 @@ class VPINNLinear(_VPINNBase):
 
     def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
                  sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
-                 init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None, hard_bc=None):
+                 init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None, hard_bc=None,
+                 residual_norm="l2"):
         dim = int(layers[0])
+        self._residual_norm = self._check_residual_norm(residual_norm)
         if strong_form not in (None, "elementwise"):
             raise ValueError('strong_form is None or "elementwise"')
         if strong_form and hard_bc is not None:
@@ -1424,6 +1434,55 @@ class VPINNLinear(_VPINNBase):
         k, b = _coef_field(self._op["kappa"], P, d, "kappa", True), _coef_field(self._op["beta"], P, d, "beta", True)
         s = _coef_field(self._op["sigma"], P, d, "sigma", False)
         self.h.set_operator(np.concatenate([k.T, b.T, s[None, :]], axis=0))
+
+    # -- the norm of the residual (hpv_set_residual_norm) ----------------------------------------------------------------------
+    @staticmethod
+    def _check_residual_norm(rn):
+        """("l2" | "dual", mass) of "l2" | "dual" | dict(kind=, mass=)"""
+        d = dict(kind=rn) if isinstance(rn, str) else dict(rn) if isinstance(rn, dict) else None
+        if d is None or set(d) - {"kind", "mass"} or d.get("kind") not in ("l2", "dual"):
+            raise ValueError('residual_norm is "l2", "dual" or dict(kind="dual", mass=gamma)')
+        mass = float(d.get("mass", 0.0))
+        if not np.isfinite(mass) or mass < 0.0 or (d["kind"] == "l2" and mass != 0.0):
+            raise ValueError("residual_norm: mass is a finite number >= 0 and belongs to kind=\"dual\"")
+        return d["kind"], mass
+
+    def _hand_residual_norm(self, mesh):
+        """the eigen tables of the Gram matrices for the counts 1 .. max of the mesh (they go with the test-function tables)"""
+        kind, mass = self._residual_norm
+        if kind == "l2":
+            self.h.set_residual_norm(_lib.NORM_L2)
+            return
+        from .quadrature import gram_stacks
+        sx = gram_stacks(int(mesh.nax.max()))
+        sy = gram_stacks(int(mesh.nay.max())) if mesh.dim == 2 else (None, None)
+        self.h.set_residual_norm(_lib.NORM_DUAL, mass, sx[0], sx[1], sy[0], sy[1])
+
+    def set_residual_norm(self, residual_norm):
+        """Change the norm of the residual on the live model: "l2", "dual" or dict(kind="dual", mass=gamma).  Parameters and optimizer
+        state stay; the loss history goes on in the new norm."""
+        self._residual_norm = self._check_residual_norm(residual_norm)
+        self._hand_residual_norm(self._mesh)
+
+    @property
+    def residual_norm(self):
+        """"l2", or dict(kind="dual", mass=gamma)"""
+        kind, mass = self._residual_norm
+        return "l2" if kind == "l2" else dict(kind="dual", mass=mass)
+
+    def save_checkpoint(self, path):
+        """As `_VPINNBase.save_checkpoint`, with the norm of the residual."""
+        np.savez(self._ckpt_path(path), state=self.h.get_state(), layers=np.asarray(self.layers), dev_layers=np.asarray(self._dev_layers),
+                 cls=type(self).__name__, residual_norm=self._residual_norm[0], residual_norm_mass=self._residual_norm[1])
+
+    def load_checkpoint(self, path):
+        """As `_VPINNBase.load_checkpoint`; a checkpoint that stores the norm of the residual sets it on the model."""
+        super().load_checkpoint(path)
+        d = np.load(self._ckpt_path(path), allow_pickle=False)
+        if "residual_norm" in d:
+            rn = (str(d["residual_norm"]), float(d["residual_norm_mass"]))
+            if rn != self._residual_norm:
+                self.set_residual_norm(dict(kind=rn[0], mass=rn[1]))
 
     # -- exact Dirichlet conditions by ansatz u = G + D N (hpv_set_ansatz) ------------------------------------------------------
     def _check_hard_bc(self, hard_bc, mesh):
@@ -1558,6 +1617,7 @@ class VPINNLinear(_VPINNBase):
         self._hand_operator(mesh)
         self._hand_trainable(mesh)
         self._hand_ansatz_quad(mesh)
+        self._hand_residual_norm(mesh)                     # (set_tables dropped the tables: they belong to the test functions)
 
     def _hand_data(self):
         if self.rank == 0 and self.X_u_train is not None:

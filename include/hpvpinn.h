@@ -468,6 +468,34 @@ int hpv_linear_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, 
 #define HPV_ANSATZ_FLUX  2
 #define HPV_ANSATZ_VALID 3
 int hpv_set_ansatz(hpv_handle h, int which, const double* planes, size_t n);
+
+/* The norm the variational residual is measured in, for the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D, with or without
+ * hpv_set_nonlinear / hpv_set_trainable / hpv_set_ansatz).  kind 0 (the default) is  loss_e = mean over the active functions of R^2,
+ * the Euclidean norm of the residual's coordinates in the basis phi_n = P_{n+1} - P_{n-1}, which is far from orthonormal.  kind 1 is
+ * the dual norm of the element's discrete test space (robust VPINNs),
+ *     loss_e = R_e^T G_e^{-1} R_e,      G_e the Gram matrix of the element's ACTIVE test functions in  (grad v, grad w) + mass (v, w),
+ * not divided by their count; lossv = sum_e loss_e as before.  For kappa = 1, beta = sigma = 0 it is the squared H^1 seminorm (mass 0)
+ * of the Galerkin projection of the error onto the element's bubble space; for the other operators it is equivalent to that up to
+ * the continuity and inf-sup constants.  G_e^{-1} is applied through the tensor structure: with K, M the 1-D stiffness and mass
+ * matrices of n functions on the reference interval and K S = M S Lambda, S^T M S = I,
+ *     G_e^{-1} = (S_y (x) S_x) diag(1 / d) (S_y (x) S_x)^T,      d[a][b] = (Jy/Jx) lam_x[b] + (Jx/Jy) lam_y[a] + mass Jx Jy
+ * on half widths Jx, Jy (1-D: d[b] = lam_x[b] / Jx + mass Jx).  The caller hands the pairs over for EVERY count 1 .. nt (per-element
+ * counts use the leading block, and S of n functions is not a sub-block of S of n + 1): Sx = [ntx][ntx][ntx], entry [n - 1] the
+ * n x n matrix in its leading block, zero-padded; lamx = [ntx][ntx]; Sy, lamy the same for nty, NULL in 1-D.  Everything is copied.
+ * The _dual instantiations of k_project_lin | _nl | _id (csrc/hpv_dual_norm.h) run in the same launch slot; hpv_get_residuals keeps
+ * returning the raw R; d lossv / d c_m, the data and the flux term are unchanged; with hpv_set_strong_form, column 0 of
+ * hpv_linear_indicators is the element's dual-norm loss (columns 1 - 4 stay on the raw R).  hpv_kernel_variant appends ";dual".
+ * The tables belong to the test-function tables: hpv_set_tables drops them, and every pass then returns -3 until this call is
+ * repeated or kind 0 is given -- a handle that had the dual norm never silently trains the other loss.  kind 0 restores the plain
+ * handle bit for bit.  Side effects: waits for the handle's stream and drops the captured iteration graphs, like hpv_set_nonlinear.
+ * The setting is not state: hpv_get_state / hpv_set_state do not carry it.
+ * Returns 0; -3 for a handle of another problem or scheme and before hpv_set_tables; -1 (the handle keeps what it had) for an unknown
+ * kind, mass < 0 or not finite, missing tables, a non-finite entry, an eigenvalue <= 0 inside a count's block, and an element whose
+ * dual-norm kernel would need more than 64 KiB of LDS (the scratch is appended where the integrand region cannot hold it); -2 on a
+ * HIP error.
+ * Out of scope: the other problem classes and the whole-iteration kernels, Gram matrices of a weighted (kappa) inner product,
+ * non-symmetric optimal test norms, the data and flux terms, gathering indicators across GPUs. */
+int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx, const double* lamx, const double* Sy, const double* lamy);
 int hpv_backend_in_use(hpv_handle h);                       /* HPV_BACKEND_GENERIC or HPV_BACKEND_MFMA */
 /* Launch structure of the most recent reverse-mode pass over the quadrature batch (tests assert that the kernel they mean to
  * exercise is the one that ran): 0 separate forward / projection / reverse launches, 1 forward + projection-fused reverse,
