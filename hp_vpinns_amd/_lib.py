@@ -45,6 +45,7 @@ EXPORTS = [
     "hpv_set_strong_form", "hpv_linear_indicators",
     "hpv_set_ansatz",
     "hpv_set_residual_norm",
+    "hpv_set_operator_tensor", "hpv_set_element_points",
 ]
 NORM_L2, NORM_DUAL = 0, 1              # kind of hpv_set_residual_norm
 ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
@@ -145,6 +146,7 @@ def load():
     lib.hpv_set_flux_data.argtypes = [h, _dp, _dp, _dp, C.c_int, C.c_double]
     lib.hpv_read_flux_loss.argtypes = [h, _dp]
     lib.hpv_set_operator.argtypes = [h, _dp, C.c_size_t]
+    lib.hpv_set_operator_tensor.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_nonlinear.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
@@ -212,6 +214,7 @@ def load():
     lib.hpv_validation_read.argtypes = [h, C.c_int, _dp]
     lib.hpv_step_validate.argtypes = [h, C.c_int, C.c_int, _dp, C.c_size_t]
     lib.hpv_set_element_boxes.argtypes = [h, _dp, C.c_int, C.c_int, C.c_int]
+    lib.hpv_set_element_points.argtypes = [h, _dp, C.c_int, C.c_int, C.c_int]
     lib.hpv_element_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_set_strong_form.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_linear_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
@@ -338,6 +341,17 @@ class Handle:
         self._chk(self.lib.hpv_set_element_boxes(self._h, _p(b), b.shape[0], int(e_begin), e_end))
         self.n_owned = e_end - int(e_begin)
 
+    def set_element_points(self, X, e_begin=0, e_end=None):
+        """X: (n, 2, qy * qx) -- per element the physical x and y of its quadrature points, q = j * qx + i: unit elements at the
+        caller's points (hpv_set_element_points; mapped elements whose geometry the caller folds into the planes).  The handle owns
+        the rows [e_begin, e_end)."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 3 or X.shape[1] != 2 or X.shape[2] != (self.n_quad or X.shape[2]):
+            raise ValueError(f"element points must have shape (n, 2, {self.n_quad}), got {X.shape}")
+        e_end = X.shape[0] if e_end is None else int(e_end)
+        self._chk(self.lib.hpv_set_element_points(self._h, _p(X), X.shape[0], int(e_begin), e_end))
+        self.n_owned = e_end - int(e_begin)
+
     def element_indicators(self, f_quad=None):
         """(n_owned, 5): loss_e, eta2_e, sumR2_e, topx_e, topy_e of the owned elements at the current parameters
         (hpv_element_indicators); f_quad: f at the handle's own quadrature points, element-major, or None (zero).  n_owned is what
@@ -405,6 +419,12 @@ class Handle:
         coef = None if coef is None else _c(coef).reshape(-1)
         self._chk(self.lib.hpv_set_operator(self._h, _p(coef), 0 if coef is None else coef.size))
 
+    def set_operator_tensor(self, coef):
+        """The planes of a 2-D linear problem with a full diffusion tensor (hpv_set_operator_tensor): (7, n_owned * qx * qy), rows
+        (kxx, kxy, kyx, kyy, bx, by, s) laid out like set_operator's.  The operator call made last decides which kernels run."""
+        coef = None if coef is None else _c(coef).reshape(-1)
+        self._chk(self.lib.hpv_set_operator_tensor(self._h, _p(coef), 0 if coef is None else coef.size))
+
     def set_nonlinear(self, coef):
         """The planes of the nonlinear term of a linear problem (hpv_set_nonlinear): (M, n_owned * qx * qy), M = 4 rows (a2, a3, ae, g)
         in 1-D, 5 rows (a2, a3, ae, gx, gy) in 2-D, laid out like set_operator's.  None, or all zeros, removes the term."""
@@ -413,7 +433,7 @@ class Handle:
 
     def set_trainable(self, dirs):
         """The directions of the trainable coefficients (hpv_set_trainable): (n_coef, K + M, n_owned * qx * qy) -- per coefficient the
-        planes of set_operator followed by those of set_nonlinear, laid out like them."""
+        planes of set_operator (of set_operator_tensor on a tensor handle) followed by those of set_nonlinear, laid out like them."""
         dirs = None if dirs is None else _c(dirs).reshape(-1)
         self._chk(self.lib.hpv_set_trainable(self._h, _p(dirs), 0 if dirs is None else dirs.size))
 

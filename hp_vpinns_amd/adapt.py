@@ -196,3 +196,138 @@ def refine(mesh, actions, p_max=None):
             if ay == "p":
                 new.raise_p(c, 1, py)
     return new
+
+
+_FD_STEP = float(np.finfo(np.float64).eps) ** (1.0 / 3.0)      # ~6.1e-6: the step that balances a central difference's two errors
+_FD_TOL = 1e4 * _FD_STEP ** 2                                 # ~3.7e-7 per unit of scale, see vpinn._check_ansatz_field
+
+# corners of the reference square in the order of MappedMesh.from_quads, and the bilinear shape functions' signs
+_REF_CORNERS = np.array([[-1.0, -1.0], [1.0, -1.0], [1.0, 1.0], [-1.0, 1.0]])
+
+
+class MappedMesh(ElementMesh):
+    """A 2-D mesh of MAPPED elements: each element is a box in a parameter plane (`boxes`, rows (s0, s1, t0, t1)) plus a map into the
+    physical plane.  Two kinds:
+
+      * `MappedMesh(boxes, nax, nay, map=phi)`: one global map, `phi(P)` returning `(X (n, 2), A (n, 2, 2))` for parameter points
+        P (n, 2) -- the physical points and the Jacobian A[:, a, b] = d x_a / d p_b.  Polar coordinates on (r, theta) boxes are this.
+      * `MappedMesh.from_quads(corners, ntx, nty)`: corners (n, 4, 2), counter-clockwise from the image of (-1, -1); every element
+        has its own bilinear map of the parameter box [-1, 1]^2 (and of the sub-boxes `split` leaves behind).
+
+    The library never sees the maps: `quad_points` returns the PHYSICAL points, so everything evaluated "at the quadrature points"
+    (f, kappa, the ansatz planes) needs no change, and `geometry` returns the Jacobian with respect to each element's REFERENCE
+    coordinates, which the model classes fold into the coefficient planes (include/hpvpinn.h, hpv_set_element_points).
+    `copy`, `split` and `raise_p` keep the geometry; the children of a split tile their parent exactly.  Checked, each failure a
+    ValueError naming the element: finite values and det A > 0 at the corners and the centre of every element (for a bilinear map
+    the determinant is bilinear, so the corners decide) and again at every node `geometry` is asked for; for `map=`, the supplied
+    Jacobian against central differences of the supplied points there.  2-D only; no triangles."""
+
+    def __init__(self, boxes, nax, nay=None, map=None, corners=None):
+        super().__init__(boxes, nax, 1 if nay is None else nay)
+        if self.dim != 2:
+            raise ValueError("a MappedMesh is 2-D: boxes (n, 4) in the parameter plane")
+        if (map is None) == (corners is None):
+            raise ValueError("give either map= (one global map) or corners (MappedMesh.from_quads)")
+        self.map = map
+        self.corners = None if corners is None else np.array(corners, dtype=np.float64).reshape(-1, 4, 2)
+        if self.corners is not None and self.corners.shape[0] != len(self):
+            raise ValueError("one row of four corners per element")
+        self._check()
+
+    @classmethod
+    def from_quads(cls, corners, ntx=1, nty=1):
+        c = np.array(corners, dtype=np.float64).reshape(-1, 4, 2)
+        return cls(np.tile([-1.0, 1.0, -1.0, 1.0], (c.shape[0], 1)), ntx, nty, corners=c)
+
+    def copy(self):
+        return MappedMesh(self.boxes, self.nax, self.nay, map=self.map, corners=self.corners)
+
+    def split(self, e, axis=None):
+        c = None if self.corners is None else self.corners[e]
+        k = super().split(e, axis)                       # (the parameter box is bisected; the map stays)
+        if c is not None:
+            self.corners = np.concatenate([self.corners[:e], np.repeat(c[None], k, 0), self.corners[e + 1:]])
+        return k
+
+    # -- the maps ---------------------------------------------------------------------------------------------------------------
+    def _map_points(self, P, elem):
+        """physical points (n, 2) and Jacobian d x / d p (n, 2, 2) at parameter points P (n, 2) of the elements `elem` (n,)"""
+        if self.map is not None:
+            X, A = self.map(P)
+            X, A = np.asarray(X, dtype=np.float64), np.asarray(A, dtype=np.float64)
+            if X.shape != (P.shape[0], 2) or A.shape != (P.shape[0], 2, 2):
+                raise ValueError(f"map(points) returned shapes {X.shape}, {A.shape}; expected {(P.shape[0], 2)}, {(P.shape[0], 2, 2)}")
+            return X, A
+        c = self.corners[elem]                                               # (n, 4, 2)
+        sg, tg = _REF_CORNERS[:, 0][None, :], _REF_CORNERS[:, 1][None, :]    # (1, 4)
+        s, t = P[:, 0:1], P[:, 1:2]
+        N = (1 + sg * s) * (1 + tg * t) / 4                                  # (n, 4)
+        Ns, Nt = sg * (1 + tg * t) / 4, (1 + sg * s) * tg / 4
+        X = np.einsum("nc,nca->na", N, c)
+        A = np.stack([np.einsum("nc,nca->na", Ns, c), np.einsum("nc,nca->na", Nt, c)], axis=2)
+        return X, A
+
+    def _check_points(self, X, A, elem, what):
+        bad = ~(np.isfinite(X).all(1) & np.isfinite(A).all((1, 2)))
+        if np.any(bad):
+            raise ValueError(f"element {int(elem[np.argmax(bad)])}: the map is not finite at {what}")
+        det = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+        bad = ~(det > 0.0)
+        if np.any(bad):
+            i = int(np.argmax(bad))
+            raise ValueError(f"element {int(elem[i])}: det of the map's Jacobian is {det[i]:.6g} at {what} (physical point {X[i]}); "
+                             "it must be > 0 -- an inverted (clockwise) or non-convex element")
+
+    def _check(self):
+        """corners and centre of every parameter box: finite, det > 0, and for map= the Jacobian against central differences"""
+        b, n = self.boxes, len(self)
+        ref = np.concatenate([_REF_CORNERS, [[0.0, 0.0]]])                   # (5, 2)
+        P = np.stack([b[:, None, 0] + (b[:, None, 1] - b[:, None, 0]) / 2 * (ref[None, :, 0] + 1),
+                      b[:, None, 2] + (b[:, None, 3] - b[:, None, 2]) / 2 * (ref[None, :, 1] + 1)], axis=2).reshape(-1, 2)
+        elem = np.repeat(np.arange(n), ref.shape[0])
+        X, A = self._map_points(P, elem)
+        self._check_points(X, A, elem, "a corner or the centre")
+        if self.map is None:
+            return
+        for k in range(2):
+            e = np.zeros(2)
+            e[k] = _FD_STEP
+            fd = (self._map_points(P + e, elem)[0] - self._map_points(P - e, elem)[0]) / (2.0 * _FD_STEP)       # d x / d p_k
+            scale = np.maximum(1.0, np.maximum(np.abs(X), np.abs(A[:, :, k])))
+            bad = (np.abs(fd - A[:, :, k]) > _FD_TOL * scale).any(1)
+            if np.any(bad):
+                i = int(np.argmax(bad))
+                raise ValueError(f"element {int(elem[i])}: the supplied Jacobian column {k} is {A[i, :, k]} at parameter point {P[i]}, "
+                                 f"central differences of the supplied points give {fd[i]}")
+
+    # -- what the model classes read ----------------------------------------------------------------------------------------------
+    def geometry(self, xi, yi, e_begin=0, e_end=None):
+        """(X (n * NQ, 2), A (n * NQ, 2, 2)) of the elements [e_begin, e_end), element-major with q = j * qx + i: the physical
+        quadrature points and the Jacobian d x / d (xi, eta) with respect to each element's REFERENCE coordinates (the half widths
+        of the parameter box are included).  Finite values and det A > 0 are checked at every node."""
+        e_end = len(self) if e_end is None else e_end
+        P = ElementMesh.quad_points(self, xi, yi, e_begin, e_end)
+        nq = np.size(xi) * np.size(yi)
+        elem = np.repeat(np.arange(e_begin, e_end), nq)
+        if P.shape[0] == 0:
+            return np.zeros((0, 2)), np.zeros((0, 2, 2))
+        X, A = self._map_points(P, elem)
+        b = self.boxes[elem]
+        A = A * np.stack([(b[:, 1] - b[:, 0]) / 2, (b[:, 3] - b[:, 2]) / 2], axis=1)[:, None, :]
+        self._check_points(X, A, elem, "a quadrature node")
+        return X, A
+
+    def quad_points(self, xi, yi=None, e_begin=0, e_end=None):
+        """(n * NQ, 2): the PHYSICAL quadrature points of the elements [e_begin, e_end), in the library's layout"""
+        return self.geometry(xi, yi, e_begin, e_end)[0]
+
+    def jacobians(self):
+        """(n,): 1 -- the library runs mapped elements as unit elements (the determinant lives in the folded planes)"""
+        return np.ones(len(self))
+
+    def area(self, n=8):
+        """the physical area: det A integrated by an n x n Gauss-Legendre rule per element -- exact for bilinear and polar maps"""
+        x, w = np.polynomial.legendre.leggauss(n)
+        A = self.geometry(x, x)[1]
+        det = (A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]).reshape(len(self), n, n)
+        return float(np.einsum("ejk,j,k->", det, w, w))

@@ -468,7 +468,10 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
 // The elements of the whole mesh as boxes [ne_tot][2 * dim] = (x0, x1[, y0, y1]) and the owned slice [e_begin, e_end): the affine map of
 // the reference nodes, |J_e| and the per-term coefficients of every pde / var_form.  Both hpv_set_elements (the boxes of a tensor grid,
 // e = ex * ney + ey) and hpv_set_element_boxes (any list) end here; nothing below this function knows a grid.
-static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, int nex, int ney, int e_begin, int e_end) {
+// points != nullptr (hpv_set_element_points; `boxes` is then nullptr): unit elements, J = Jx = Jy = 1, whose quadrature points are
+// the caller's [ne_tot][2][qy * qx] -- the same slicing, the same buffers, the same invalidation.
+static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, int nex, int ney, int e_begin, int e_end,
+                                   const double* points = nullptr) {
     if (e_begin < 0 || e_end > ne_tot || e_begin > e_end) return fail(h, -1, "bad element range [%d,%d) of %d", e_begin, e_end, ne_tot);
     // per-grid inputs given earlier must fit the new grid: checked BEFORE anything of the old grid is replaced
     if (!h->nact_all.empty() && (int)h->nact_all.size() != ne_tot)
@@ -491,6 +494,7 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         drop_ansatz(h, HPV_ANSATZ_QUAD);         // ... as do the ansatz planes
         h->have_lin = false;
+        h->unit_elems = points != nullptr;
         if (h->d_lin) { (void)hipFree(h->d_lin); h->d_lin = nullptr; }
         if (h->nl_mask) h->nl_stale = true;      // a pass must not silently train the linear problem
         h->nl_mask = 0;
@@ -500,7 +504,13 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         for (double** p : {&h->d_dirs, &h->d_dcoef_e, &h->d_nl_zero})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
     }
-    for (long le = 0; le < ne; ++le) {
+    for (long le = 0; le < ne && points; ++le) {      // (a 2-D linear handle: the caller has made sure)
+        const double* px = points + (size_t)(e_begin + le) * 2 * NQ;
+        std::copy_n(px, NQ, X.begin() + le * NQ);
+        std::copy_n(px + NQ, NQ, X.begin() + N + le * NQ);
+        jac[le] = 1.0;                                    // (jxy is all ones already)
+    }
+    for (long le = 0; le < ne && !points; ++le) {
         const double* box = boxes + (size_t)(e_begin + le) * bs;
         const double gx0 = box[0], gx1 = box[1];
         double gy0 = 0, gy1 = 0;
@@ -608,6 +618,21 @@ int hpv_set_element_boxes(hpv_handle h, const double* boxes, int n_total, int e_
                 return fail(h, -1, "element box %d: [%g, %g] in direction %d is not a finite interval with lower < upper", e, a, b, c);
         }
     return set_elements_from_boxes(h, boxes, n_total, n_total, 1, e_begin, e_end);
+}
+
+// Unit elements at the caller's quadrature points (include/hpvpinn.h): mapped elements whose geometry the host has folded into the planes.
+int hpv_set_element_points(hpv_handle h, const double* X, int n_total, int e_begin, int e_end) {
+    if (!h) return -1;
+    if (!h->linear || h->dim != 2) return fail(h, -1, "hpv_set_element_points belongs to the 2-D problems of the linear class");
+    if (!h->have_quad || !h->have_tables) return fail(h, -3, "call hpv_set_quadrature and hpv_set_tables first");
+    if (!X || n_total < 1) return fail(h, -1, "bad element points");
+    if (h->d_dual || h->dual_stale)
+        return fail(h, -1, "the dual norm is set (hpv_set_residual_norm): the Gram matrix of the reference square is not the physical H^1 inner product of a mapped element");
+    if (h->d_sf) return fail(h, -1, "the strong form is active (hpv_set_strong_form): it is not available on mapped elements");
+    const size_t n = (size_t)n_total * 2 * h->qx * h->qy;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(X[i])) return fail(h, -1, "element %zu holds a non-finite quadrature point (entry %zu)", i / ((size_t)2 * h->qx * h->qy), i);
+    return set_elements_from_boxes(h, nullptr, n_total, n_total, 1, e_begin, e_end, X);
 }
 
 // the device copies of the per-element counts go; the row-split projection (which ignores counts) is on again where it applies
@@ -726,11 +751,10 @@ int hpv_set_data(hpv_handle h, const double* X, const double* u, int n) {
 }
 
 // The coefficient planes of a linear problem at the owned quadrature points (include/hpvpinn.h); k_project_lin reads them in place.
-int hpv_set_operator(hpv_handle h, const double* coef, size_t n) {
-    if (!h) return -1;
-    if (!h->linear) return fail(h, -1, "hpv_set_operator belongs to the linear problems");
+// (both operator calls end here; a change of kind orphans the directions, whose plane count differs)
+static int set_operator_planes(hpv_ctx* h, const double* coef, size_t n, bool tensor) {
     if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
-    const size_t K = h->dim == 1 ? 3 : 5;
+    const size_t K = tensor ? 7 : h->dim == 1 ? 3 : 5;
     if (!coef || n != K * (size_t)h->Nq) return fail(h, -1, "the operator has %zu entries, expected %zu planes of %ld", n, K, h->Nq);
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(coef[i])) return fail(h, -1, "coefficient plane %zu holds a non-finite value at point %zu", i / (size_t)std::max(h->Nq, 1L), i % (size_t)std::max(h->Nq, 1L));
@@ -738,10 +762,30 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n) {
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old planes)
     drop_graph(h);
     h->have_lin = false;
+    if (tensor != h->lin_tensor) {
+        h->have_dirs = false;
+        h->dir_nl_mask = 0;
+        for (double** p : {&h->d_dirs, &h->d_dcoef_e, &h->d_nl_zero})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+    }
+    h->lin_tensor = tensor;
     if ((rc = dalloc(h, &h->d_lin, n))) return rc;
     if ((rc = upload(h, h->d_lin, coef, n))) return rc;
     h->have_lin = true;
     return 0;
+}
+
+int hpv_set_operator(hpv_handle h, const double* coef, size_t n) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_operator belongs to the linear problems");
+    return set_operator_planes(h, coef, n, false);
+}
+
+// The full diffusion tensor of a 2-D linear problem (include/hpvpinn.h); the TENSOR instantiations of the projection kernels read it in place.
+int hpv_set_operator_tensor(hpv_handle h, const double* coef, size_t n) {
+    if (!h) return -1;
+    if (!h->linear || h->dim != 2) return fail(h, -1, "hpv_set_operator_tensor belongs to the 2-D problems of the linear class");
+    return set_operator_planes(h, coef, n, true);
 }
 
 // The planes of the nonlinear term (include/hpvpinn.h); k_project_nl reads them in place.  The mask is decided here, once.
@@ -780,6 +824,8 @@ int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx,
     if (!h->linear) return fail(h, -3, "hpv_set_residual_norm belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D): the other classes and the whole-iteration kernels train mean(R^2)");
     if (h->cfg.scheme == HPV_SCHEME_PINN) return fail(h, -3, "hpv_set_residual_norm belongs to the variational scheme");
     if (kind != 0 && kind != 1) return fail(h, -1, "unknown residual norm %d (0 l2, 1 dual)", kind);
+    if (kind == 1 && h->unit_elems)
+        return fail(h, -1, "the elements are mapped (hpv_set_element_points): the Gram matrix of the reference square is not their physical H^1 inner product");
     if (kind == 0) {
         if (!h->d_dual && !h->dual_stale) return 0;
         HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the tables)
@@ -831,7 +877,7 @@ int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n) {
     if (!h) return -1;
     if (!h->n_coef) return fail(h, -1, "the handle was created without trainable coefficients (hpv_create_ex)");
     if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
-    const size_t K = h->dim == 1 ? 3 : 5, M = h->dim == 1 ? 4 : 5, Nq = (size_t)h->Nq, NP = K + M;
+    const size_t K = h->lin_tensor ? 7 : h->dim == 1 ? 3 : 5, M = h->dim == 1 ? 4 : 5, Nq = (size_t)h->Nq, NP = K + M;
     if (!dirs || n != (size_t)h->n_coef * NP * Nq)
         return fail(h, -1, "the directions have %zu entries, expected %d x %zu planes of %ld", n, h->n_coef, NP, h->Nq);
     for (size_t i = 0; i < n; ++i)
@@ -1547,6 +1593,8 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
         return 0;
     }
     if (has_ansatz(h)) return fail(h, -1, "the handle has an ansatz (hpv_set_ansatz): its strong residual needs second derivatives of G and D, which are not available");
+    if (h->lin_tensor) return fail(h, -1, "the operator is a full tensor (hpv_set_operator_tensor): its strong form needs u_xy, which is not available");
+    if (h->unit_elems) return fail(h, -1, "the elements are mapped (hpv_set_element_points): the strong form is not available on them");
     if (!h->have_quad) return fail(h, -3, "call hpv_set_quadrature first");
     const size_t wx = (size_t)h->qx * h->qx, wy = h->dim == 2 ? (size_t)h->qy * h->qy : 0;
     if (!Dx || nx != wx) return fail(h, -1, "Dx has %zu entries, expected %d x %d of the current rule", nx, h->qx, h->qx);
@@ -1574,6 +1622,8 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
 int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* out, size_t n_out, double* r_out, size_t n_r) {
     if (!h) return -1;
     if (!h->linear) return fail(h, -1, "hpv_linear_indicators belongs to the linear problems (others: hpv_element_indicators)");
+    if (h->lin_tensor) return fail(h, -1, "the operator is a full tensor (hpv_set_operator_tensor): its strong residual needs u_xy, which is not available");
+    if (h->unit_elems) return fail(h, -1, "the elements are mapped (hpv_set_element_points): the strong residual is not available on them");
     if (!h->d_sf) return fail(h, -1, "the strong residual of a linear problem needs the rule's differentiation matrices: call hpv_set_strong_form");
     int rc = check_ready(h);
     if (rc) return rc;

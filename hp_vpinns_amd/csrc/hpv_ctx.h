@@ -115,6 +115,11 @@ struct hpv_ctx {
     bool linear = false;
     bool have_lin = false;     // the planes belong to the current elements
     double *d_lin = nullptr, *d_jxy = nullptr;
+    // hpv_set_operator_tensor: d_lin holds seven planes (kxx, kxy, kyx, kyy, bx, by, s) and the TENSOR instantiations of the three
+    // projection kernels run (2-D only); the operator call made last decides.  hpv_set_element_points: the elements are unit elements
+    // (J = Jx = Jy = 1) at the caller's points -- the host has folded the element maps into the planes
+    bool lin_tensor = false;
+    bool unit_elems = false;
     // the nonlinear term of such a handle (hpv_set_nonlinear): planes [4 | 5][Nq], the HPV_NL_* mask of the planes that are not zero
     // everywhere (0: no term, k_project_lin runs), and whether new elements have orphaned a term that has not been set again or removed
     double* d_nl = nullptr;

@@ -107,6 +107,8 @@ struct LinProjArgs {
     int do_adjoint;
     const double* dual;      // the tables of the dual-norm loss (hpv_set_residual_norm; layout: hpv_dual_norm.h), or nullptr: mean(R^2)
     double dual_mass;        // the weight of the L2 part of its inner product
+    int tensor;              // 2-D, hpv_set_operator_tensor: coef holds seven planes (kxx, kxy, kyx, kyy, bx, by, s) and the TENSOR
+                             // instantiations run: G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y (0: the planes above, the kernels as ever)
 };
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty);
 size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty);      // k_project_lin_dual, _nl_dual, _id<.., true>: says whether the scratch is appended
@@ -126,12 +128,12 @@ void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s);
 // The same launch with trainable coefficients (k_project_id, kernels_ident.hip; hpv_create_ex / hpv_set_trainable): every plane is
 //   base_p + sum_m c_m D_m,p,   p over the operator planes followed by the nonlinear ones,   c = theta[P .. P + n_coef)
 // and the kernel also reduces d lossv / d c_m per element.
-#define HPV_ID_PLANES 10     // 5 + 5 in 2-D (3 + 4 in 1-D)
+#define HPV_ID_PLANES 12     // 7 + 5 with a full diffusion tensor; 5 + 5 in 2-D otherwise (3 + 4 in 1-D)
 struct IdProjArgs {
     LinProjArgs lin;
     const double* nl;        // base planes of the nonlinear term (zeros where hpv_set_nonlinear gave none)
     int mask;                // HPV_NL_* of the terms that are evaluated: the base's and every term a direction touches
-    const double* dirs;      // [n_coef][K + M][coef_stride] directions, the layout of lin.coef
+    const double* dirs;      // [n_coef][K + M][coef_stride] directions, the layout of lin.coef (K = 7 where lin.tensor)
     const double* c;         // theta + P on the device: read at every launch
     int n_coef;
     const int* dmask;        // [n_coef] on the device; bit p: plane p of direction m is not zero everywhere (the others are never read)

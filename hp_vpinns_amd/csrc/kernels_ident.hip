@@ -98,10 +98,14 @@ __device__ __forceinline__ void id_planes(const IdProjArgs& b, const double* cf,
 }
 
 // DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
-template <int DIM, bool DUAL>
+// TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; DIM == 2 only): the operator planes are (kxx, kxy, kyx, kyy, bx,
+// by, s), each base + sum_m c_m D_m like the others; G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y, and d lossv / d c_m weighs
+// D_kxx with u_x Gbar_1, D_kxy with u_y Gbar_1, D_kyx with u_x Gbar_2, D_kyy with u_y Gbar_2
+template <int DIM, bool DUAL, bool TENSOR = false>
 __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
+    static_assert(!TENSOR || DIM == 2, "the tensor operator is 2-D");
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    constexpr int K = DIM == 2 ? 5 : 3, M = DIM == 2 ? 5 : 4;
+    constexpr int K = TENSOR ? 7 : DIM == 2 ? 5 : 3, M = DIM == 2 ? 5 : 4;
     const LinProjArgs& a = b.lin;
     const long e = blockIdx.x;
     const int qx = a.qx, qy = a.qy, ntx = a.ntx, nty = a.nty, nt = DIM + 1;
@@ -141,7 +145,15 @@ __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
         double pl[K + M], Nv, dNu;
         const double w0[K + M] = {};
         id_planes<K, M, false>(b, cf, nl, dirs, cs, q, pl, w0, acc);
-        if constexpr (DIM == 2) {
+        if constexpr (TENSOR) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double bx = pl[4], by = pl[5], s = pl[6];
+            const double ga = (mask & HPV_NL_ADVECTION) ? pl[K + 3] * ux + pl[K + 4] * uy : 0.0;
+            id_nl_point(mask, pl[K], pl[K + 1], pl[K + 2], ex, u, ga, Nv, dNu);
+            G[j * gs + i] = ((bx * ux + by * uy) + s * u) + Nv;
+            G[(qy + j) * gs + i] = pl[0] * ux + pl[1] * uy;
+            G[(2 * qy + j) * gs + i] = pl[2] * ux + pl[3] * uy;
+        } else if constexpr (DIM == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = pl[0], ky = pl[1], bx = pl[2], by = pl[3], s = pl[4];
             const double ga = (mask & HPV_NL_ADVECTION) ? pl[K + 3] * ux + pl[K + 4] * uy : 0.0;
@@ -236,7 +248,24 @@ __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
         const double ex = (mask & HPV_NL_EXP) ? exp(u) : 0.0;
         const double ug0 = u * g0, uug0 = u * ug0;
         double pl[K + M], Nv, dNu;
-        if constexpr (DIM == 2) {
+        if constexpr (TENSOR) {
+            const double uy = a.OUT[2 * N + base + q];
+            // the weight of each plane in d lossv / d c_m: (kxx, kxy, kyx, kyy, bx, by, s | a2, a3, ae, gx, gy)
+            const double w[K + M] = {ux * g1, uy * g1, ux * g2, uy * g2, ux * g0, uy * g0, ug0, uug0, u * uug0, ex * g0, ux * ug0, uy * ug0};
+            id_planes<K, M, true>(b, cf, nl, dirs, cs, q, pl, w, acc);
+            const double s = pl[6];
+            double bx = pl[4], by = pl[5], ga = 0.0;
+            if (mask & HPV_NL_ADVECTION) {
+                const double gx = pl[K + 3], gy = pl[K + 4];
+                ga = gx * ux + gy * uy;
+                bx += gx * u;
+                by += gy * u;
+            }
+            id_nl_point(mask, pl[K], pl[K + 1], pl[K + 2], ex, u, ga, Nv, dNu);
+            a.GBAR[base + q] = (s + dNu) * g0;
+            a.GBAR[N + base + q] = (pl[0] * g1 + pl[2] * g2) + bx * g0;
+            a.GBAR[2 * N + base + q] = (pl[1] * g1 + pl[3] * g2) + by * g0;
+        } else if constexpr (DIM == 2) {
             const double uy = a.OUT[2 * N + base + q];
             // the weight of each plane in d lossv / d c_m: (kx, ky, bx, by, s | a2, a3, ae, gx, gy)
             const double w[K + M] = {ux * g1, uy * g2, ux * g0, uy * g0, ug0, uug0, u * uug0, ex * g0, ux * ug0, uy * ug0};
@@ -285,7 +314,10 @@ void launch_project_id(const IdProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const size_t lds = hpv_linop_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);      // (nothing is added to k_project_lin's layout)
     const dim3 grid((unsigned)n_elem), block(256);
-    if (a.lin.dual) {
+    if (a.lin.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
+        if (a.lin.dual) hipLaunchKernelGGL((k_project_id<2, true, true>), grid, block, hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+        else hipLaunchKernelGGL((k_project_id<2, false, true>), grid, block, lds, s, a);
+    } else if (a.lin.dual) {
         const size_t ldsd = hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
         if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, true>), grid, block, ldsd, s, a);
         else hipLaunchKernelGGL((k_project_id<1, true>), grid, block, ldsd, s, a);

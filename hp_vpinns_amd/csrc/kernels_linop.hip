@@ -44,7 +44,10 @@ __device__ __forceinline__ double lin_block_sum(double v, double* red) {
 }
 
 // DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
-template <bool DUAL>
+// TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; 2-D only): seven planes (kxx, kxy, kyx, kyy, bx, by, s),
+//     G1 = kxx u_x + kxy u_y     G2 = kyx u_x + kyy u_y     GBAR[u_x] = kxx Gbar_1 + kyx Gbar_2 + bx Gbar_0     GBAR[u_y] = kxy Gbar_1 + kyy Gbar_2 + by Gbar_0
+// -- still three integrands, so tables, contractions and LDS are untouched; false is the kernel as it always was
+template <bool DUAL, bool TENSOR = false>
 __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long e = blockIdx.x;
@@ -74,7 +77,14 @@ __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
     for (int q = tid; q < NQ; q += 256) {
         const int j = q / qx, i = q - j * qx;
         const double u = a.OUT[base + q], ux = a.OUT[N + base + q];
-        if (a.dim == 2) {
+        if constexpr (TENSOR) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double kxx = cf[q], kxy = cf[cs + q], kyx = cf[2 * cs + q], kyy = cf[3 * cs + q];
+            const double bx = cf[4 * cs + q], by = cf[5 * cs + q], s = cf[6 * cs + q];
+            G[j * gs + i] = (bx * ux + by * uy) + s * u;
+            G[(qy + j) * gs + i] = kxx * ux + kxy * uy;
+            G[(2 * qy + j) * gs + i] = kyx * ux + kyy * uy;
+        } else if (a.dim == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = cf[q], ky = cf[cs + q], bx = cf[2 * cs + q], by = cf[3 * cs + q], s = cf[4 * cs + q];
             G[j * gs + i] = (bx * ux + by * uy) + s * u;
@@ -160,7 +170,13 @@ __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
             g1 += x1 * s1[r];
             if (a.dim == 2) g2 += x0 * s2[r];
         }
-        if (a.dim == 2) {
+        if constexpr (TENSOR) {
+            const double kxx = cf[q], kxy = cf[cs + q], kyx = cf[2 * cs + q], kyy = cf[3 * cs + q];
+            const double bx = cf[4 * cs + q], by = cf[5 * cs + q], s = cf[6 * cs + q];
+            a.GBAR[base + q] = s * g0;
+            a.GBAR[N + base + q] = (kxx * g1 + kyx * g2) + bx * g0;
+            a.GBAR[2 * N + base + q] = (kxy * g1 + kyy * g2) + by * g0;
+        } else if (a.dim == 2) {
             const double kx = cf[q], ky = cf[cs + q], bx = cf[2 * cs + q], by = cf[3 * cs + q], s = cf[4 * cs + q];
             a.GBAR[base + q] = s * g0;
             a.GBAR[N + base + q] = kx * g1 + bx * g0;
@@ -177,6 +193,8 @@ __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
 
 __global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) { project_lin_body<false>(a); }
 __global__ void __launch_bounds__(256) k_project_lin_dual(LinProjArgs a) { project_lin_body<true>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_tensor(LinProjArgs a) { project_lin_body<false, true>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_tensor_dual(LinProjArgs a) { project_lin_body<true, true>(a); }
 
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty) {
     const size_t gs = (size_t)(qx | 1), ts = (size_t)(ntx | 1), ys = (size_t)(qy | 1);
@@ -190,6 +208,11 @@ size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty) {
 
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
-    if (a.dual) hipLaunchKernelGGL(k_project_lin_dual, dim3((unsigned)n_elem), dim3(256), hpv_dual_lds_bytes(a.qx, a.qy, a.ntx, a.nty), s, a);
-    else hipLaunchKernelGGL(k_project_lin, dim3((unsigned)n_elem), dim3(256), hpv_linop_lds_bytes(a.qx, a.qy, a.ntx, a.nty), s, a);
+    const dim3 grid((unsigned)n_elem), block(256);
+    const size_t lds = a.dual ? hpv_dual_lds_bytes(a.qx, a.qy, a.ntx, a.nty) : hpv_linop_lds_bytes(a.qx, a.qy, a.ntx, a.nty);
+    if (a.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
+        if (a.dual) hipLaunchKernelGGL(k_project_lin_tensor_dual, grid, block, lds, s, a);
+        else hipLaunchKernelGGL(k_project_lin_tensor, grid, block, lds, s, a);
+    } else if (a.dual) hipLaunchKernelGGL(k_project_lin_dual, grid, block, lds, s, a);
+    else hipLaunchKernelGGL(k_project_lin, grid, block, lds, s, a);
 }

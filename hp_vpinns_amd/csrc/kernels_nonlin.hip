@@ -73,7 +73,9 @@ __device__ __forceinline__ void nl_point(int mask, const double* nl, long cs, do
 }
 
 // DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
-template <bool DUAL>
+// TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; 2-D only), as in project_lin_body: the operator has seven planes
+// (kxx, kxy, kyx, kyy, bx, by, s), G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y; the nonlinear planes and N are untouched
+template <bool DUAL, bool TENSOR = false>
 __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LinProjArgs& a = b.lin;
@@ -108,7 +110,16 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
         const int j = q / qx, i = q - j * qx;
         const double u = a.OUT[base + q], ux = a.OUT[N + base + q];
         double Nv, dNu;
-        if (a.dim == 2) {
+        if constexpr (TENSOR) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double kxx = cf[q], kxy = cf[cs + q], kyx = cf[2 * cs + q], kyy = cf[3 * cs + q];
+            const double bx = cf[4 * cs + q], by = cf[5 * cs + q], s = cf[6 * cs + q];
+            const double ga = adv ? nl[3 * cs + q] * ux + nl[4 * cs + q] * uy : 0.0;
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            G[j * gs + i] = ((bx * ux + by * uy) + s * u) + Nv;
+            G[(qy + j) * gs + i] = kxx * ux + kxy * uy;
+            G[(2 * qy + j) * gs + i] = kyx * ux + kyy * uy;
+        } else if (a.dim == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = cf[q], ky = cf[cs + q], bx = cf[2 * cs + q], by = cf[3 * cs + q], s = cf[4 * cs + q];
             const double ga = adv ? nl[3 * cs + q] * ux + nl[4 * cs + q] * uy : 0.0;
@@ -200,7 +211,21 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
         }
         const double u = a.OUT[base + q], ux = a.OUT[N + base + q];
         double Nv, dNu;
-        if (a.dim == 2) {
+        if constexpr (TENSOR) {
+            const double uy = a.OUT[2 * N + base + q];
+            const double kxx = cf[q], kxy = cf[cs + q], kyx = cf[2 * cs + q], kyy = cf[3 * cs + q], s = cf[6 * cs + q];
+            double bx = cf[4 * cs + q], by = cf[5 * cs + q], ga = 0.0;
+            if (adv) {
+                const double gx = nl[3 * cs + q], gy = nl[4 * cs + q];
+                ga = gx * ux + gy * uy;
+                bx += gx * u;
+                by += gy * u;
+            }
+            nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
+            a.GBAR[base + q] = (s + dNu) * g0;
+            a.GBAR[N + base + q] = (kxx * g1 + kyx * g2) + bx * g0;
+            a.GBAR[2 * N + base + q] = (kxy * g1 + kyy * g2) + by * g0;
+        } else if (a.dim == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = cf[q], ky = cf[cs + q], s = cf[4 * cs + q];
             double bx = cf[2 * cs + q], by = cf[3 * cs + q], ga = 0.0;
@@ -233,12 +258,19 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
 
 __global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) { project_nl_body<false>(b); }
 __global__ void __launch_bounds__(256) k_project_nl_dual(NlProjArgs b) { project_nl_body<true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor(NlProjArgs b) { project_nl_body<false, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_dual(NlProjArgs b) { project_nl_body<true, true>(b); }
 
 // (the channels are re-read from OUT in the adjoint phase, so nothing is added to k_project_lin's layout)
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop_lds_bytes(qx, qy, ntx, nty); }
 
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
-    if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_dual, dim3((unsigned)n_elem), dim3(256), hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
-    else hipLaunchKernelGGL(k_project_nl, dim3((unsigned)n_elem), dim3(256), hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+    const dim3 grid((unsigned)n_elem), block(256);
+    const size_t lds = a.lin.dual ? hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty) : hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
+    if (a.lin.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
+        if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_tensor_dual, grid, block, lds, s, a);
+        else hipLaunchKernelGGL(k_project_nl_tensor, grid, block, lds, s, a);
+    } else if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_dual, grid, block, lds, s, a);
+    else hipLaunchKernelGGL(k_project_nl, grid, block, lds, s, a);
 }

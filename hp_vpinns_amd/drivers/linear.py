@@ -1,4 +1,4 @@
-"""Two textbook problems of the variable-coefficient linear class (VPINNLinear), each with a manufactured solution; prints the
+"""Textbook problems of the variable-coefficient linear class (VPINNLinear), each with a manufactured solution; prints the
 relative L2 error.
 
   boundary layer   -eps u'' + u' = 1 on [0, 1], u(0) = u(1) = 0:  u = x - (exp((x - 1) / eps) - exp(-1 / eps)) / (1 - exp(-1 / eps)),
@@ -7,13 +7,20 @@ relative L2 error.
   L-shape          div(kappa grad u) + beta . grad u + sigma u = f on [-1, 1]^2 without its lower right quadrant, as three boxes;
                    kappa = 1 + x y, beta = (1, -1), sigma = 2, u = sin(pi x) sin(pi y) (zero on the whole boundary), f manufactured.
 
+  annulus          lap u = f on the quarter annulus 1 < r < 2, 0 < theta < pi / 2: mapped elements (adapt.MappedMesh, polar map of boxes
+                   in the (r, theta) plane); u = (r - 1)(2 - r) sin(2 theta), zero on all four sides, f manufactured.
+  anisotropic      div(K grad u) = f on [-1, 1]^2 with K = Q diag(1, --ratio) Q^T, Q the rotation by --angle degrees: a full tensor
+                   (hpv_set_operator_tensor); u = sin(pi x) sin(pi y), f manufactured.
+
     python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05
     python -m hp_vpinns_amd.drivers.linear l-shape
+    python -m hp_vpinns_amd.drivers.linear annulus --hard-bc
+    python -m hp_vpinns_amd.drivers.linear anisotropic --angle 30
     python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05 --adapt-every 500 --max-elements 16
 
     python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05 --hard-bc
 
---hard-bc (boundary layer): the Dirichlet conditions are built into the trial function, u = G + D N with D = (x - a)(b - x) and G the
+--hard-bc (boundary layer, annulus): the Dirichlet conditions are built into the trial function, u = G + D N with D = (x - a)(b - x) and G the
 linear interpolant of the end values (VPINNLinear(hard_bc=...)): no boundary points, no penalty weight.
 
 --adapt-every K: local hp-refinement (VPINNLinear(strong_form="elementwise").train_adaptive) after every K-th update, at most
@@ -23,7 +30,7 @@ import argparse
 
 import numpy as np
 
-from ..adapt import ElementMesh
+from ..adapt import ElementMesh, MappedMesh
 from ..vpinn import VPINNLinear
 
 # the smallest setting of the boundary-layer run (tests/test_gpu_linear.py trains it once)
@@ -149,9 +156,112 @@ def run_l_shape(n_iter=2000, n_quad=20, n_test=10, layers=(2, 20, 20, 20, 1), n_
     return dict(model=m, rel_l2=err, h1_err=h1, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
+# the smallest setting of the annulus run (tests/test_gpu_mapped.py trains it once)
+ANNULUS_SMALLEST = dict(n_r=2, n_theta=2, n_quad=8, n_test=4, n_iter=300, layers=[2, 8, 8, 1], LR=5e-3)
+
+
+def polar_map(P):
+    """(r, theta) -> (x, y) = r (cos theta, sin theta) with its Jacobian: the map= of adapt.MappedMesh"""
+    r, t = P[:, 0], P[:, 1]
+    return (np.stack([r * np.cos(t), r * np.sin(t)], 1),
+            np.stack([np.stack([np.cos(t), -r * np.sin(t)], 1), np.stack([np.sin(t), r * np.cos(t)], 1)], 1))
+
+
+def annulus_mesh(n_r, n_theta, n_test):
+    """n_r x n_theta boxes of the (r, theta) plane on 1 < r < 2, 0 < theta < pi / 2 under the polar map"""
+    g = ElementMesh.from_grid(np.linspace(1.0, 2.0, int(n_r) + 1), np.linspace(0.0, np.pi / 2, int(n_theta) + 1))
+    return MappedMesh(g.boxes, int(n_test), int(n_test), map=polar_map)
+
+
+def _annulus_exact(P):
+    x, y = P[:, 0], P[:, 1]
+    r = np.hypot(x, y)
+    return (r - 1.0) * (2.0 - r) * 2.0 * x * y / r ** 2
+
+
+def _annulus_f(P):
+    """the Laplacian of g(r) sin(2 theta), g = (r - 1)(2 - r):  (g'' + g' / r - 4 g / r^2) sin(2 theta)"""
+    x, y = P[:, 0], P[:, 1]
+    r = np.hypot(x, y)
+    return (-2.0 + (3.0 - 2.0 * r) / r - 4.0 * (r - 1.0) * (2.0 - r) / r ** 2) * 2.0 * x * y / r ** 2
+
+
+def annulus_hard_bc():
+    """dict(g=, d=): D = (r - 1)(2 - r) x y vanishes on the two arcs and the two straight sides, G = 0"""
+    def d(P):
+        x, y = P[:, 0], P[:, 1]
+        r = np.hypot(x, y)
+        g, dg = (r - 1.0) * (2.0 - r), 3.0 - 2.0 * r
+        return np.stack([g * x * y, dg * (x / r) * x * y + g * y, dg * (y / r) * x * y + g * x], 1)
+    return dict(g=0.0, d=d)
+
+
+def _annulus_boundary(n):
+    t, r = np.linspace(0.0, np.pi / 2, n), np.linspace(1.0, 2.0, n)
+    z = np.zeros(n)
+    return np.concatenate([np.stack([np.cos(t), np.sin(t)], 1), 2.0 * np.stack([np.cos(t), np.sin(t)], 1), np.stack([r, z], 1), np.stack([z, r], 1)])
+
+
+def run_annulus(n_r=4, n_theta=4, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0,
+                seed=1234, backend="auto", device=None, verbose=True, hard_bc=False, record_every=None):
+    """record_every: also the error curve [(iteration, relative L2 error)], one row per that many updates"""
+    Xb = _annulus_boundary(int(n_bound))
+    bc = dict(hard_bc=annulus_hard_bc()) if hard_bc else dict(X_u_train=Xb, u_train=np.zeros(Xb.shape[0]))
+    m = VPINNLinear(list(layers), mesh=annulus_mesh(n_r, n_theta, n_test), n_quad=int(n_quad), kappa=1.0, f=_annulus_f, lossb_weight=lossb_weight,
+                    LR=LR, seed=seed, backend=backend, device=device, **bc)
+    rr, tt = np.meshgrid(np.linspace(1.0, 2.0, 41), np.linspace(0.0, np.pi / 2, 41))
+    X = np.stack([(rr * np.cos(tt)).reshape(-1), (rr * np.sin(tt)).reshape(-1)], 1)
+    u = _annulus_exact(X)[:, None]
+    curve, it = [], 0
+    while it < int(n_iter):
+        n = min(int(record_every or n_iter), int(n_iter) - it)
+        m.train(n, verbose=False)
+        it += n
+        curve.append((it, m.rel_l2_error(X, u)))
+    err = m.rel_l2_error(X, u)
+    if verbose:
+        for row in curve:
+            print("It: %d, relative L2 error %.4e" % row)
+        print("quarter annulus, %d polar elements (area %.6f), %s: relative L2 error %.4e (%s)"
+              % (len(m.mesh), m.mesh.area(), "exact conditions (ansatz)" if hard_bc else "penalty", err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), curve=curve)
+
+
+def rotated_tensor(angle_deg, ratio):
+    """K = Q diag(1, ratio) Q^T, Q the rotation by angle_deg"""
+    a = np.deg2rad(float(angle_deg))
+    Q = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+    return Q @ np.diag([1.0, float(ratio)]) @ Q.T
+
+
+def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3,
+                    lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True):
+    K = rotated_tensor(angle, ratio)
+
+    def f(P):
+        s, c = np.sin(np.pi * P), np.cos(np.pi * P)
+        return np.pi ** 2 * (-(K[0, 0] + K[1, 1]) * s[:, 0] * s[:, 1] + (K[0, 1] + K[1, 0]) * c[:, 0] * c[:, 1])
+    t = np.linspace(-1.0, 1.0, int(n_bound))
+    o = np.ones_like(t)
+    Xb = np.concatenate([np.stack([t, -o], 1), np.stack([t, o], 1), np.stack([-o, t], 1), np.stack([o, t], 1)])
+    g = np.linspace(-1.0, 1.0, int(n_elements) + 1)
+    m = VPINNLinear(list(layers), grid_x=g, grid_y=g, n_quad=int(n_quad), n_test=int(n_test), kappa=K, f=f, X_u_train=Xb,
+                    u_train=np.zeros(Xb.shape[0]), lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device)
+    m.train(int(n_iter), verbose=False)
+    gg = np.linspace(-1.0, 1.0, 81)
+    X = np.stack([v.reshape(-1) for v in np.meshgrid(gg, gg)], 1)
+    u = _l_exact(X)[:, None]
+    err = m.rel_l2_error(X, u)
+    if verbose:
+        print("rotated anisotropy, angle %g degrees, ratio %g, K = %s: relative L2 error %.4e (%s)" % (angle, ratio, K.round(4).tolist(), err, m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("problem", choices=["boundary-layer", "l-shape"])
+    ap.add_argument("problem", choices=["boundary-layer", "l-shape", "annulus", "anisotropic"])
+    ap.add_argument("--angle", type=float, default=30.0, help="anisotropic: rotation of the tensor's principal axes, degrees")
+    ap.add_argument("--ratio", type=float, default=0.05, help="anisotropic: the smaller principal conductivity (the larger is 1)")
     ap.add_argument("--eps", type=float, default=0.05)
     ap.add_argument("--elements", type=int, default=8)
     ap.add_argument("--grade", type=float, default=2.0)
@@ -160,7 +270,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None)
-    ap.add_argument("--hard-bc", action="store_true", help="boundary layer: exact Dirichlet conditions by ansatz instead of the penalty")
+    ap.add_argument("--hard-bc", action="store_true", help="boundary layer, annulus: exact Dirichlet conditions by ansatz instead of the penalty")
     ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
@@ -168,6 +278,10 @@ def main(argv=None):
     if a.problem == "boundary-layer":
         run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
                            adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn)
+    elif a.problem == "annulus":
+        run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10))
+    elif a.problem == "anisotropic":
+        run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters)
     else:
         run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn)
 

@@ -30,7 +30,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .adapt import ElementMesh, mark, refine
+from .adapt import _FD_STEP, _FD_TOL, ElementMesh, MappedMesh, mark, refine
 from .dist import Reducer, dist_info, shard_range
 from .init import n_params, pad_plan, xavier_init
 from .quadrature import diff_matrix
@@ -763,8 +763,8 @@ class _VPINNBase:
         if mesh.dim == 1 and self.var_form == 3:
             edge = np.ascontiguousarray(dTest_fcn(ntx_dev, np.array([-1.0, 1.0]))[0])
         h.set_tables(tables_1d(ntx_dev, xi), None if mesh.dim == 1 else tables_1d(nty, yi), edge)
-        h.set_element_boxes(mesh.boxes, eb, ee)
         self._dev_rule = (xi, yi)
+        self._hand_elements(mesh, eb, ee)
         if f is not None:
             NR = ntx_dev * nty
             F = np.zeros((n, NR))                          # (only the owned rows are read: hpv_set_rhs slices [eb, ee))
@@ -776,6 +776,11 @@ class _VPINNBase:
                 h.set_active_tests(mesh.nax)
         elif np.any(mesh.nax != ntx) or np.any(mesh.nay != nty):
             h.set_active_tests_2d(mesh.nax, mesh.nay)
+
+    def _hand_elements(self, mesh, eb, ee):
+        if isinstance(mesh, MappedMesh):
+            raise ValueError("mapped elements (adapt.MappedMesh) belong to VPINNLinear / VPINNNonlinear")
+        self.h.set_element_boxes(mesh.boxes, eb, ee)
 
     def set_mesh(self, mesh, f=None):
         """Continue on another set of elements: `mesh` an `adapt.ElementMesh` (any list of boxes with per-element counts), `f` a
@@ -1258,8 +1263,19 @@ def _coef_field(c, P, dim, what, vector):
     raise ValueError(f"a constant {what} is a scalar" + (f" or a vector of {dim} entries" if vector else ""))
 
 
-_FD_STEP = float(np.finfo(np.float64).eps) ** (1.0 / 3.0)      # ~6.1e-6: the step that balances a central difference's two errors
-_FD_TOL = 1e4 * _FD_STEP ** 2                                 # ~3.7e-7 per unit of scale, see _check_ansatz_field
+def _kappa_field(c, P, dim):
+    """kappa at the points P (n, dim): what `_coef_field` returns, (n, dim), for a diagonal or isotropic one; (n, 2, 2) for a full
+    tensor -- in 2-D a constant (2, 2) array or a callable returning (n, 2, 2), rows [[kxx, kxy], [kyx, kyy]], symmetric or not."""
+    n = P.shape[0]
+    if dim == 2 and callable(c):
+        v = np.asarray(c(P), dtype=np.float64)
+        return v.copy() if v.shape == (n, 2, 2) else _coef_field(lambda _P: v, P, dim, "kappa", True)
+    if dim == 2 and np.shape(c) == (2, 2):
+        return np.broadcast_to(np.asarray(c, dtype=np.float64), (n, 2, 2)).copy()
+    return _coef_field(c, P, dim, "kappa", True)
+
+
+# _FD_STEP = eps^(1/3) ~ 6.1e-6 and _FD_TOL = 1e4 _FD_STEP^2 ~ 3.7e-7 per unit of scale (adapt.py): see _check_ansatz_field
 
 
 def _ansatz_field(c, P, dim, what):
@@ -1303,7 +1319,7 @@ class VPINNLinear(_VPINNBase):
     """Variable-coefficient linear convection-diffusion-reaction problems in 1-D and 2-D (no reference counterpart; the library's
     linear problems, include/hpvpinn.h: hpv_set_operator):
 
-        div(kappa grad u) + beta . grad u + sigma u = f        kappa = diag(kx, ky), or one scalar field for both directions
+        div(kappa grad u) + beta . grad u + sigma u = f        kappa = diag(kx, ky), one scalar field for both directions, or a full 2 x 2 tensor
 
     with the sign convention that makes Poisson kappa = 1.  Everything is a keyword argument and nothing is looked up in the
     caller's module.  `layers[0]` (1 or 2) is the dimension.  The elements are a grid per direction (`grid_x`[, `grid_y`]) or an
@@ -1347,7 +1363,18 @@ class VPINNLinear(_VPINNBase):
     gamma (v, w) -- robust VPINNs.  For kappa = 1, beta = sigma = 0 this is the squared energy norm of the Galerkin projection of
     the error, so sqrt(loss) estimates the H^1 error, `element_indicators` column 0 is the natural refinement indicator, and loss
     values compare across `n_test`, element shapes and the meshes of a `train_adaptive` run.  `set_residual_norm` changes it on a
-    live model; checkpoints store the setting.  The data and flux terms keep their mean(square)."""
+    live model; checkpoints store the setting.  The data and flux terms keep their mean(square).
+
+    A full diffusion tensor (hpv_set_operator_tensor): in 2-D `kappa` may also be a constant (2, 2) array or a callable returning
+    (n, 2, 2) = [[kxx, kxy], [kyx, kyy]] per point, symmetric or not; the same holds for `kappa=` in a `trainable` dict.  Mapped
+    elements (hpv_set_element_points): `mesh=adapt.MappedMesh(..)` -- parameter boxes under one global map such as polar
+    coordinates, or one bilinear map per quadrilateral (`MappedMesh.from_quads`).  "The points" of every callable are then the
+    PHYSICAL quadrature points, and the geometry is folded into the planes in one place (`_fold`: K_eff = adj(A) K, everything
+    else times det A, with A the Jacobian of the element's map); the library runs unit elements with a full tensor.  `set_operator`,
+    `set_nonlinear`, `set_mesh` (box to mapped and back, state untouched), checkpoints, sharding, `hard_bc`, `set_flux_data`,
+    validation and `predict` work as on boxes.  Out of scope, each a ValueError that says why: `residual_norm="dual"` with a
+    MappedMesh (the dual norm in the physical metric is not implemented), `strong_form="elementwise"` with a MappedMesh or a tensor
+    kappa, and `adapt` / `train_adaptive` in those cases; also 1-D graded maps, solution-dependent tensors and triangles."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1394,6 +1421,7 @@ class VPINNLinear(_VPINNBase):
         self._rule = tuple((np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(w, dtype=np.float64).reshape(-1)) for x, w in rule)
         self._op = dict(kappa=kappa, beta=beta, sigma=sigma)
         self._f = f
+        self._check_scope(mesh)
         self._hard_bc = self._check_hard_bc(hard_bc, mesh)
         self._val_X = None
         self.X_u_train = None if X_u_train is None else np.asarray(X_u_train, dtype=np.float64).reshape(-1, dim)
@@ -1424,16 +1452,91 @@ class VPINNLinear(_VPINNBase):
         xi, yi = self._dev_rule
         return mesh.quad_points(xi, yi, eb, ee)
 
+    # -- mapped elements and the full diffusion tensor (hpv_set_element_points, hpv_set_operator_tensor) -----------------------------
+    def _hand_elements(self, mesh, eb, ee):
+        if not isinstance(mesh, MappedMesh):
+            self.h.set_element_boxes(mesh.boxes, eb, ee)
+            return
+        xi, yi = self._dev_rule
+        X = mesh.quad_points(xi, yi, 0, len(mesh))          # (the library slices [eb, ee) itself, as it slices boxes)
+        self.h.set_element_points(X.reshape(len(mesh), -1, 2).transpose(0, 2, 1), eb, ee)
+
+    def _geometry(self, mesh, eb, ee):
+        """(P, A): the (physical) quadrature points of the elements [eb, ee) and, for a MappedMesh, the Jacobian of each element's
+        map with respect to its reference coordinates at them (None for boxes, whose geometry the library holds)"""
+        xi, yi = self._dev_rule
+        if isinstance(mesh, MappedMesh):
+            return mesh.geometry(xi, yi, eb, ee)
+        return mesh.quad_points(xi, yi, eb, ee), None
+
+    def _tensor_mode(self, mesh):
+        """whether the handle takes a full diffusion tensor: a mapped mesh (the fold fills it), or a kappa -- the operator's or a
+        direction's -- that is one"""
+        if isinstance(mesh, MappedMesh):
+            return True
+        if mesh.dim != 2:
+            return False
+        P = mesh.quad_points(self._rule[0][0], self._rule[1][0], 0, 1)[:1]
+        return any(_kappa_field(k, P, 2).ndim == 3 for k in [self._op["kappa"]] + [t["kappa"] for t in self._trainable if "kappa" in t])
+
+    @staticmethod
+    def _fold(A, tensor, kappa, scaled):
+        """THE fold of a mapped element onto a unit element (include/hpvpinn.h, hpv_set_element_points), the one place it happens:
+        with A (n, 2, 2) the Jacobian at the points, d = det A and M = adj A = d A^-1,  K_eff = M K  and every other plane times d.
+        kappa: (n, dim), (n, 2, 2) or None; scaled: arrays (n,) or (n, c).  Returns the rows (planes, n): kappa's -- four,
+        (kxx, kxy, kyx, kyy), where `tensor`, else its dim diagonal ones -- then one per column of each of `scaled`.
+        A None (boxes): nothing is folded, the values are only laid out as rows."""
+        rows = []
+        if kappa is not None and tensor:
+            K = kappa
+            if K.ndim == 2:                                 # (a diagonal kappa on a tensor handle)
+                K = np.zeros(K.shape + (2,))
+                K[:, 0, 0], K[:, 1, 1] = kappa[:, 0], kappa[:, 1]
+            if A is not None:
+                M = np.stack([np.stack([A[:, 1, 1], -A[:, 0, 1]], 1), np.stack([-A[:, 1, 0], A[:, 0, 0]], 1)], 1)
+                K = np.einsum("nab,nbc->nac", M, K)
+            rows.append(K.reshape(-1, 4).T)
+        elif kappa is not None:
+            rows.append(kappa.T)
+        d = None if A is None else A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+        for v in scaled:
+            v = v.reshape(v.shape[0], -1)
+            rows.append(v.T if d is None else (v * d[:, None]).T)
+        return np.concatenate(rows, axis=0)
+
+    def _check_scope(self, mesh, residual_norm=None):
+        """what is out of scope on mapped elements and with a full tensor, each refused with its reason"""
+        mapped = isinstance(mesh, MappedMesh)
+        if mapped and (residual_norm or self._residual_norm)[0] == "dual":
+            raise ValueError('residual_norm="dual" on a MappedMesh: the Gram matrix of the reference square is not the physical H^1 '
+                             "inner product of a mapped element (the dual norm in the physical metric is not implemented)")
+        if mapped and self._strong_form:
+            raise ValueError('strong_form="elementwise" on a MappedMesh: the strong residual on mapped elements is not implemented')
+        if self._strong_form and self._tensor_mode(mesh):
+            raise ValueError('strong_form="elementwise" with a full tensor kappa: the strong form of div(K grad u) needs u_xy, '
+                             "which is not available")
+
+    def _no_adapt(self, what):
+        mesh = self._mesh
+        if isinstance(mesh, MappedMesh) or self._tensor_mode(mesh):
+            raise ValueError(f"{what} needs the strong residual, which is not available on a MappedMesh or with a full tensor kappa "
+                             "(it would need the maps' second derivatives / u_xy)")
+
     def _f_at_quad(self, mesh, f, eb, ee):
-        return _coef_field(f, self._quad_points(mesh, eb, ee), mesh.dim, "f", False)
+        P, A = self._geometry(mesh, eb, ee)
+        return self._fold(A, False, None, (_coef_field(f, P, mesh.dim, "f", False),))[0]
 
     def _hand_operator(self, mesh):
-        """kappa, beta, sigma at this rank's quadrature points as the planes hpv_set_operator takes"""
+        """kappa, beta, sigma at this rank's quadrature points as the planes hpv_set_operator (hpv_set_operator_tensor) takes"""
         eb, ee = shard_range(len(mesh), self.rank, self.world)
-        P, d = self._quad_points(mesh, eb, ee), mesh.dim
-        k, b = _coef_field(self._op["kappa"], P, d, "kappa", True), _coef_field(self._op["beta"], P, d, "beta", True)
+        (P, A), d, tensor = self._geometry(mesh, eb, ee), mesh.dim, self._tensor_mode(mesh)
+        k, b = _kappa_field(self._op["kappa"], P, d), _coef_field(self._op["beta"], P, d, "beta", True)
         s = _coef_field(self._op["sigma"], P, d, "sigma", False)
-        self.h.set_operator(np.concatenate([k.T, b.T, s[None, :]], axis=0))
+        planes = self._fold(A, tensor, k, (b, s))
+        if tensor:
+            self.h.set_operator_tensor(planes)
+        else:
+            self.h.set_operator(planes)
 
     # -- the norm of the residual (hpv_set_residual_norm) ----------------------------------------------------------------------
     @staticmethod
@@ -1461,7 +1564,9 @@ class VPINNLinear(_VPINNBase):
     def set_residual_norm(self, residual_norm):
         """Change the norm of the residual on the live model: "l2", "dual" or dict(kind="dual", mass=gamma).  Parameters and optimizer
         state stay; the loss history goes on in the new norm."""
-        self._residual_norm = self._check_residual_norm(residual_norm)
+        rn = self._check_residual_norm(residual_norm)
+        self._check_scope(self._mesh, rn)
+        self._residual_norm = rn
         self._hand_residual_norm(self._mesh)
 
     @property
@@ -1588,21 +1693,22 @@ class VPINNLinear(_VPINNBase):
             raise ValueError(f"at most {_lib.MAX_COEF} trainable coefficients, with distinct names")
         return tuple(out)
 
-    def _direction(self, t, P, d):
-        """the planes (K + M, n) of one trainable coefficient's direction at the points P: set_operator's rows, then set_nonlinear's"""
-        k, b = _coef_field(t.get("kappa", 0.0), P, d, "kappa", True), _coef_field(t.get("beta", 0.0), P, d, "beta", True)
+    def _direction(self, t, P, d, A=None, tensor=False):
+        """the planes (K + M, n) of one trainable coefficient's direction at the points P: set_operator's rows (set_operator_tensor's
+        where `tensor`), then set_nonlinear's -- folded like them"""
+        k, b = _kappa_field(t.get("kappa", 0.0), P, d), _coef_field(t.get("beta", 0.0), P, d, "beta", True)
         s = _coef_field(t.get("sigma", 0.0), P, d, "sigma", False)
         a = [_coef_field(t.get(f, 0.0), P, d, f, False) for f in ("quadratic", "cubic", "exponential")]
         g = _coef_field(t.get("advection", 0.0), P, d, "advection", True)
-        return np.concatenate([k.T, b.T, s[None, :], np.stack(a, 0), g.T], axis=0)
+        return self._fold(A, tensor, k, (b, s, *a, g))
 
     def _hand_trainable(self, mesh):
         """the directions at this rank's quadrature points (after the planes they add to: new elements orphan all of them)"""
         if not self._trainable:
             return
         eb, ee = shard_range(len(mesh), self.rank, self.world)
-        P = self._quad_points(mesh, eb, ee)
-        self.h.set_trainable(np.stack([self._direction(t, P, mesh.dim) for t in self._trainable], 0))
+        (P, A), tensor = self._geometry(mesh, eb, ee), self._tensor_mode(mesh)
+        self.h.set_trainable(np.stack([self._direction(t, P, mesh.dim, A, tensor) for t in self._trainable], 0))
 
     def coefficients(self):
         """{name: current value} of the trainable coefficients"""
@@ -1627,9 +1733,15 @@ class VPINNLinear(_VPINNBase):
     def set_operator(self, kappa=None, beta=None, sigma=None):
         """Re-evaluate the operator on the live model: the coefficients given replace the stored ones (the others stay), all three
         are evaluated at the current mesh's quadrature points and handed to the library.  Parameters and optimizer state stay."""
+        old = dict(self._op)
         for k, v in (("kappa", kappa), ("beta", beta), ("sigma", sigma)):
             if v is not None:
                 self._op[k] = v
+        try:
+            self._check_scope(self._mesh)
+        except ValueError:
+            self._op = old
+            raise
         self._hand_operator(self._mesh)
         self._hand_trainable(self._mesh)
 
@@ -1637,6 +1749,8 @@ class VPINNLinear(_VPINNBase):
         """As `_VPINNBase.set_mesh`; the coefficients are re-evaluated on the new elements.  f None keeps the model's own f."""
         if f is None:
             f = self._f
+        if isinstance(mesh, ElementMesh) and mesh.dim == self.layers[0]:
+            self._check_scope(mesh)
         self._f = f
         super().set_mesh(mesh, f)
 
@@ -1670,12 +1784,14 @@ class VPINNLinear(_VPINNBase):
 
     def adapt(self, f=None, **mark_kw):
         """With strong_form="elementwise": `_VPINNBase.adapt`; f None (the usual call) is the model's own f.  Single GPU only."""
+        self._no_adapt("adapt")
         if not self._strong_form:
             self._no_strong_form("adapt")
         return super().adapt(f, **mark_kw)                 # (element_indicators and set_mesh of this class take f None as self._f)
 
     def train_adaptive(self, nIter, adapt_every, f=None, max_elements=None, **mark_kw):
         """With strong_form="elementwise": `_VPINNBase.train_adaptive`; f None is the model's own f.  Single GPU only."""
+        self._no_adapt("train_adaptive")
         if not self._strong_form:
             self._no_strong_form("train_adaptive")
         return super().train_adaptive(nIter, adapt_every, f, max_elements, **mark_kw)
@@ -1721,10 +1837,10 @@ class VPINNNonlinear(VPINNLinear):
     def _hand_nonlinear(self, mesh):
         """the four terms at this rank's quadrature points as the planes hpv_set_nonlinear takes"""
         eb, ee = shard_range(len(mesh), self.rank, self.world)
-        P, d = self._quad_points(mesh, eb, ee), mesh.dim
+        (P, A), d = self._geometry(mesh, eb, ee), mesh.dim
         a = [_coef_field(self._nl[k], P, d, k, False) for k in ("quadratic", "cubic", "exponential")]
         g = _coef_field(self._nl["advection"], P, d, "advection", True)
-        self.h.set_nonlinear(np.concatenate([np.stack(a, 0), g.T], axis=0))
+        self.h.set_nonlinear(self._fold(A, False, None, (*a, g)))
 
     def _populate_mesh(self, mesh, f):
         super()._populate_mesh(mesh, f)

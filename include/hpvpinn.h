@@ -198,6 +198,44 @@ int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n);
 int hpv_create_ex(hpv_handle* out, const hpv_config* cfg, int n_coef);
 int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n);
 
+/* A full diffusion tensor on a 2-D handle of the class above (HPV_PDE_LINEAR2D only):
+ *     L u = div(K grad u) + bx u_x + by u_y + s u = f          K = [[kxx, kxy], [kyx, kyy]] per quadrature point, not necessarily symmetric
+ * so that media whose principal axes are not the coordinate axes (rotated anisotropy, layers, fibres) can be stated.  Of the three
+ * integrands of hpv_set_operator only two change,
+ *     G1 = kxx u_x + kxy u_y          G2 = kyx u_x + kyy u_y
+ * tables, the constants of the element, masking, F, lossv and the loss triple are unchanged; the TENSOR instantiations of
+ * k_project_lin / k_project_nl / k_project_id run (the same LDS, no atomics, the same bits from call to call) and hpv_kernel_variant
+ * carries ";tensor" inside the brackets, e.g. k_project_lin<6x5/4x3;tensor> or k_project_id<6x5/4x3;u3;tensor;nc=2>.
+ *
+ * coef is [7][n_owned*qx*qy] in the order (kxx, kxy, kyx, kyy, bx, by, s), each plane laid out as in hpv_set_operator, whose contract
+ * this call follows: everything is copied, it waits for the handle's stream and drops the captured iteration graphs, new elements
+ * invalidate the planes.  The operator call made LAST decides which kernels run: a later hpv_set_operator returns the handle to the
+ * diagonal kernels and their exact variant names.  On a tensor handle hpv_set_trainable takes [n_coef][7 + 5][n_owned*qx*qy] (the
+ * seven planes above, then the nonlinear ones) and d lossv / d c_m gains D_kxy u_y Gbar_1 + D_kyx u_x Gbar_2; otherwise [5 + 5].
+ * Switching between the two operator calls invalidates the directions: a pass answers -3 until they are set again.
+ * Out of scope while the operator is a tensor: the strong form -- it would need u_xy -- so hpv_set_strong_form and
+ * hpv_linear_indicators are refused (-1, the handle stays usable); 1-D handles; a solution-dependent tensor.
+ * Returns 0; -1 for a handle of another problem, a wrong n, NULL, a non-finite value; -3 before hpv_set_elements; -2 on a HIP error. */
+int hpv_set_operator_tensor(hpv_handle h, const double* coef, size_t n);
+
+/* Mapped (non-box) elements on a 2-D handle of the class above: the elements are UNIT elements -- J = Jx = Jy = 1 -- whose
+ * quadrature points are the caller's.  X is [n_total][2][qy*qx] (per element the x plane, then the y plane, q = j*qx + i): the
+ * PHYSICAL images of the reference nodes under each element's map.  The geometry is the caller's to fold into the planes: with
+ * A = d(x,y)/d(xi,eta) at a point, d = det A > 0 and M = adj(A), the weak form on the element pulled back to the reference square is
+ * that of a unit element with K_eff = M K (a full tensor: hpv_set_operator_tensor), b_eff = d b, s_eff = d s, a_eff = d a for every
+ * nonlinear plane, D_eff likewise for every direction and f_eff = d f; u, u_x, u_y stay the network's physical derivatives at the
+ * physical points, so the data term, the flux term and hpv_set_ansatz need nothing.  hpv_assemble_rhs on such a handle returns
+ * sum_q w_q f_q phi_r phi_k.  Quadrilaterals with straight or curved sides, polar or any other smooth coordinates are all this call.
+ * Slicing by [e_begin, e_end), preconditions, the re-slicing of F and of the counts, and the invalidation of every plane are those
+ * of hpv_set_element_boxes (both end in one function); hpv_set_elements / hpv_set_element_boxes return the handle to boxes.
+ * The points are checked to be finite; the maps themselves never reach the library and are not checked.
+ * Out of scope on such a handle: the dual norm -- the Gram matrix of the reference square is not the physical H^1 inner product --
+ * so hpv_set_residual_norm(dual) is refused on it and this call is refused while the dual norm is set; the strong form:
+ * hpv_set_strong_form is refused on it and this call is refused while the strong form is set; 1-D handles; triangles.
+ * Returns 0; -1 for another kind of handle, NULL, n_total < 1, a bad range, a non-finite point, the two refusals above; -3 before
+ * hpv_set_quadrature / hpv_set_tables; -2 on a HIP error. */
+int hpv_set_element_points(hpv_handle h, const double* X, int n_total, int e_begin, int e_end);
+
 /* Boundary / data points of lossb (P1:98, P2:122, P3:184): X is [n][dim] row-major, u is [n].
  * The term is weighted by cfg.lossb_weight.  n = 0 disables it (ranks other than 0). */
 int hpv_set_data(hpv_handle h, const double* X, const double* u, int n);
