@@ -44,10 +44,10 @@ EXPORTS = [
     "hpv_create_ex", "hpv_set_trainable",
     "hpv_set_strong_form", "hpv_linear_indicators",
     "hpv_set_ansatz",
-    "hpv_set_residual_norm",
+    "hpv_set_residual_norm", "hpv_set_residual_gram",
     "hpv_set_operator_tensor", "hpv_set_element_points",
 ]
-NORM_L2, NORM_DUAL = 0, 1              # kind of hpv_set_residual_norm
+NORM_L2, NORM_DUAL, NORM_DUAL_DENSE = 0, 1, 2      # kind of hpv_set_residual_norm; HPV_NORM_DUAL_DENSE is what hpv_set_residual_gram sets
 ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
 MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
@@ -220,6 +220,7 @@ def load():
     lib.hpv_linear_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_set_ansatz.argtypes = [h, C.c_int, _dp, C.c_size_t]
     lib.hpv_set_residual_norm.argtypes = [h, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
+    lib.hpv_set_residual_gram.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_build_info.restype = C.c_char_p
     _libs[path] = lib
     if path == LIB_PATH:
@@ -455,6 +456,12 @@ class Handle:
         the L2 part and the stacks of `quadrature.gram_stacks` for ntx (and nty in 2-D): S (nt, nt, nt), lam (nt, nt)."""
         Sx, lamx, Sy, lamy = _c(Sx), _c(lamx), _c(Sy), _c(lamy)
         self._chk(self.lib.hpv_set_residual_norm(self._h, int(kind), float(mass), _p(Sx), _p(lamx), _p(Sy), _p(lamy)))
+
+    def set_residual_gram(self, W):
+        """The dual norm through dense factors (hpv_set_residual_gram): W (n_owned, NR, NR) of `quadrature.gram_factors`, NR = ntx * nty,
+        the inverse Cholesky factor of each owned element's Gram matrix.  set_residual_norm(NORM_L2) removes it."""
+        W = _c(W)
+        self._chk(self.lib.hpv_set_residual_gram(self._h, _p(W), 0 if W is None else W.size))
 
     def read_flux_loss(self):
         """(w_f * msf, msf) of the most recent pass (hpv_read_flux_loss); zeros without the term."""

@@ -3,6 +3,7 @@
 // the timing / benchmark / debug hooks in hpv_bench.hip; hpv_ctx.h holds the handle and the helpers they share.)
 #include "hpv_ctx.h"
 #include "hpv_dual_norm.h"
+#include "hpv_dual_dense.h"
 
 using namespace hpvd;
 
@@ -214,10 +215,22 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
     if (h->dual_stale) return fail(h, -3, "hpv_set_residual_norm has not been called again: hpv_set_tables dropped the tables of the dual norm");
+    if (h->gram_stale) return fail(h, -3, "hpv_set_residual_gram has not been called again: new tables, elements or counts dropped the Gram factors of the dual norm");
     if (h->n_coef && !h->have_dirs) return fail(h, -3, "hpv_set_trainable has not been called");
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
     if (h->have_F && !h->d_F && h->n_elem > 0) return fail(h, -3, "internal: F not sliced");
     if (h->batch_dirty) return assemble_batches(h);
+    return 0;
+}
+
+// The dense Gram factors (hpv_set_residual_gram) belong to the elements, their counts and the test-function tables: whoever changes
+// one of those drops them, and a pass refuses until they are given again -- it must not silently train mean(R^2).
+static int drop_gram(hpv_ctx* h) {
+    if (!h->d_gram) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read them)
+    (void)hipFree(h->d_gram);
+    h->d_gram = nullptr;
+    h->gram_stale = true;
     return 0;
 }
 
@@ -367,7 +380,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dual, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
+    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -462,7 +475,7 @@ int hpv_set_tables(hpv_handle h, const double* phix, const double* dphix, const 
         h->d_dual = nullptr;
         h->dual_stale = true;
     }
-    return 0;
+    return drop_gram(h);
 }
 
 // The elements of the whole mesh as boxes [ne_tot][2 * dim] = (x0, x1[, y0, y1]) and the owned slice [e_begin, e_end): the affine map of
@@ -492,6 +505,7 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
     std::vector<double> jxy(h->linear ? (size_t)2 * ne : 0, 1.0);
     if (h->linear) {      // the coefficient planes belong to the old elements' points
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (int rcg = drop_gram(h)) return rcg;  // ... as do the Gram factors of hpv_set_residual_gram
         drop_ansatz(h, HPV_ANSATZ_QUAD);         // ... as do the ansatz planes
         h->have_lin = false;
         h->unit_elems = points != nullptr;
@@ -650,6 +664,7 @@ static void drop_device_counts(hpv_ctx* h) {
 int hpv_set_active_tests(hpv_handle h, const int* n_active, int n) {
     if (!h) return -1;
     drop_graph(h);
+    if (int rcg = drop_gram(h)) return rcg;      // (hpv_set_residual_gram: the factors are those of the old counts)
     if (!n_active) {
         h->nact_all.clear();
         drop_device_counts(h);
@@ -680,6 +695,7 @@ int hpv_set_active_tests(hpv_handle h, const int* n_active, int n) {
 int hpv_set_active_tests_2d(hpv_handle h, const int* nax, const int* nay, int n) {
     if (!h) return -1;
     drop_graph(h);
+    if (int rcg = drop_gram(h)) return rcg;      // (hpv_set_residual_gram: the factors are those of the old counts)
     if (!nax && !nay) {
         h->nact_all.clear();
         drop_device_counts(h);
@@ -823,14 +839,16 @@ int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx,
     if (!h) return -1;
     if (!h->linear) return fail(h, -3, "hpv_set_residual_norm belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D): the other classes and the whole-iteration kernels train mean(R^2)");
     if (h->cfg.scheme == HPV_SCHEME_PINN) return fail(h, -3, "hpv_set_residual_norm belongs to the variational scheme");
-    if (kind != 0 && kind != 1) return fail(h, -1, "unknown residual norm %d (0 l2, 1 dual)", kind);
+    if (kind != 0 && kind != 1) return fail(h, -1, "unknown residual norm %d (0 l2, 1 dual; 2, the dense factors, is hpv_set_residual_gram's)", kind);
     if (kind == 1 && h->unit_elems)
         return fail(h, -1, "the elements are mapped (hpv_set_element_points): the Gram matrix of the reference square is not their physical H^1 inner product");
     if (kind == 0) {
-        if (!h->d_dual && !h->dual_stale) return 0;
+        if (!h->d_dual && !h->dual_stale && !h->d_gram && !h->gram_stale) return 0;
         HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the tables)
         drop_graph(h);
         if (h->d_dual) { (void)hipFree(h->d_dual); h->d_dual = nullptr; }
+        if (h->d_gram) { (void)hipFree(h->d_gram); h->d_gram = nullptr; }      // (hpv_set_residual_gram)
+        h->gram_stale = false;
         h->dual_stale = false;
         h->dual_mass = 0.0;
         return 0;
@@ -869,6 +887,50 @@ int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx,
     if ((rc = upload(h, h->d_dual, tab.data(), tab.size()))) { (void)hipFree(h->d_dual); h->d_dual = nullptr; return rc; }
     h->dual_mass = mass;
     h->dual_stale = false;
+    if (h->d_gram) { (void)hipFree(h->d_gram); h->d_gram = nullptr; }      // (kind 1 replaces kind 2)
+    h->gram_stale = false;
+    return 0;
+}
+
+// The same norm through one dense inverse Gram factor per owned element (include/hpvpinn.h); the _dense instantiations of the
+// projection kernels read the factors in place (csrc/hpv_dual_dense.h).
+int hpv_set_residual_gram(hpv_handle h, const double* W, size_t n) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -3, "hpv_set_residual_gram belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D): the other classes and the whole-iteration kernels train mean(R^2)");
+    if (h->cfg.scheme == HPV_SCHEME_PINN) return fail(h, -3, "hpv_set_residual_gram belongs to the variational scheme");
+    if (!h->have_tables || !h->have_elems) return fail(h, -3, "call hpv_set_tables and hpv_set_elements first");
+    const int ntx = h->ntx, nty = h->nty;
+    const size_t NR = (size_t)ntx * nty, ne = (size_t)h->n_elem;
+    const size_t lds = hpv_dual_dense_lds_bytes(h->qx, h->qy, ntx, nty);
+    if (lds > 64 * 1024) return fail(h, -1, "element too large for the dense dual-norm projection kernels' LDS (%zu B)", lds);
+    if (!W || n != ne * NR * NR) return fail(h, -1, "the Gram factors have %zu entries, expected %zu x %zu x %zu", W ? n : (size_t)0, ne, NR, NR);
+    for (size_t e = 0; e < ne; ++e) {
+        const int nax = h->nact_all.empty() ? ntx : h->nact_all[h->e_begin + e];
+        const int nay = h->nacty_all.empty() ? nty : h->nacty_all[h->e_begin + e];
+        const double* We = W + e * NR * NR;
+        auto active = [&](size_t i) { return (int)(i % ntx) < nax && (int)(i / ntx) < nay; };
+        for (size_t i = 0; i < NR; ++i)
+            for (size_t j = 0; j < NR; ++j) {
+                const double v = We[i * NR + j];
+                if (!std::isfinite(v)) return fail(h, -1, "the Gram factor of element %zu holds a non-finite value at [%zu][%zu]", h->e_begin + e, i, j);
+                if (j > i && v != 0.0) return fail(h, -1, "the Gram factor of element %zu is not lower triangular: [%zu][%zu] = %g", h->e_begin + e, i, j, v);
+                if (v != 0.0 && (!active(i) || !active(j)))
+                    return fail(h, -1, "the Gram factor of element %zu is %g at [%zu][%zu], in the row or column of an inactive test function (%d x %d active)", h->e_begin + e, v, i, j, nax, nay);
+                if (i == j && active(i) && !(v > 0.0)) return fail(h, -1, "the Gram factor of element %zu has the diagonal entry [%zu] = %g; it must be > 0", h->e_begin + e, i, v);
+            }
+    }
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old factors or tables)
+    drop_graph(h);
+    double* d_new = nullptr;
+    if ((rc = dalloc(h, &d_new, n))) return rc;
+    if (n > 0 && (rc = upload(h, d_new, W, n))) { (void)hipFree(d_new); return rc; }
+    if (h->d_gram) (void)hipFree(h->d_gram);
+    h->d_gram = d_new;
+    h->gram_stale = false;
+    if (h->d_dual) { (void)hipFree(h->d_dual); h->d_dual = nullptr; }      // (kind 2 replaces kind 1)
+    h->dual_stale = false;
+    h->dual_mass = 0.0;
     return 0;
 }
 
@@ -1665,7 +1727,7 @@ int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* 
     a.R = h->d_R; a.nact = h->pd.nact; a.nacty = h->pd.nacty;
     a.out = h->d_ind; a.r_out = r_out ? h->d_ind_r : nullptr;
     a.qx = h->qx; a.qy = h->qy; a.ntx = h->ntx; a.nty = h->nty; a.dim = h->dim;
-    a.loss_e = h->d_dual ? h->d_loss_e : nullptr;      // (hpv_set_residual_norm: column 0 is the loss the pass above wrote)
+    a.loss_e = (h->d_dual || h->d_gram) ? h->d_loss_e : nullptr;      // (hpv_set_residual_norm | _gram: column 0 is the loss the pass above wrote)
     launch_lin_indicators(a, ne, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));

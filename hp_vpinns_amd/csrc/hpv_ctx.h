@@ -131,6 +131,11 @@ struct hpv_ctx {
     double* d_dual = nullptr;
     double dual_mass = 0.0;
     bool dual_stale = false;
+    // the same loss through dense factors (hpv_set_residual_gram): W_e = L_e^{-1} [n_elem][NR][NR] of the owned elements (layout:
+    // hpv_dual_dense.h; nullptr: not set), and whether new tables, elements or counts have dropped factors that have not been given
+    // again (they belong to the elements AND the test functions; a pass then refuses).  At most one of d_dual, d_gram is set.
+    double* d_gram = nullptr;
+    bool gram_stale = false;
     // trainable coefficients of such a handle (hpv_create_ex, hpv_set_trainable): n_coef slots behind the network in theta, their
     // directions [n_coef][K + M][Nq], the per-direction masks of the planes that are not zero everywhere (host and device copy), the
     // HPV_NL_* terms the directions touch, the partials [n_coef][n_elem] of d lossv / d c_m, and -- where hpv_set_nonlinear gave no

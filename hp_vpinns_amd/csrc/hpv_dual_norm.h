@@ -18,6 +18,7 @@
 // scratch aliases it where it is large enough and is appended behind `red` otherwise (hpv_dual_aliases_g).
 // Tables (one device buffer): S_x stack [ntx][ntx][ntx] (count n at [n - 1]: its leading n x n block, zero-padded), lam_x stack
 // [ntx][ntx], S_y stack [nty][nty][nty], lam_y stack [nty][nty].
+// Inner products whose Gram matrix is no Kronecker sum (mapped elements, a kappa-weighted energy product): hpv_dual_dense.h.
 #pragma once
 #include <cstddef>
 #ifdef __HIPCC__

@@ -109,9 +109,12 @@ struct LinProjArgs {
     double dual_mass;        // the weight of the L2 part of its inner product
     int tensor;              // 2-D, hpv_set_operator_tensor: coef holds seven planes (kxx, kxy, kyx, kyy, bx, by, s) and the TENSOR
                              // instantiations run: G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y (0: the planes above, the kernels as ever)
+    int dual_dense;          // hpv_set_residual_gram: `dual` holds the inverse Gram factors W_e [n_elem][NR][NR] (hpv_dual_dense.h) and the
+                             // _dense instantiations run (0: `dual` holds the eigen tables, or is nullptr)
 };
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty);
-size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty);      // k_project_lin_dual, _nl_dual, _id<.., true>: says whether the scratch is appended
+size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty);      // k_project_lin_dual, _nl_dual, _id<.., 1>: says whether the scratch is appended
+size_t hpv_dual_dense_lds_bytes(int qx, int qy, int ntx, int nty);      // k_project_lin_dense, _nl_dense, _id<.., 2>: the same for the NR doubles of y
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s);
 
 // The same launch with a pointwise nonlinear term (k_project_nl, kernels_nonlin.hip; hpv_set_nonlinear):

@@ -263,8 +263,9 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     tstart(h, 1);
     const LinProjArgs a{v.OUT, v.GBAR, h->d_lin, h->Nq, h->d_F, h->d_R, h->d_loss_e, h->d_wtx, h->d_wty, h->d_jac, h->d_jxy,
                         h->d_jxy + h->n_elem, h->pd.nact, h->pd.nacty, v.N, h->qx, h->qy, h->ntx, h->nty, h->dim, backward ? 1 : 0,
-                        h->d_dual, h->dual_mass,                                                        // (hpv_set_residual_norm)
-                        h->lin_tensor ? 1 : 0};                                                         // (hpv_set_operator_tensor)
+                        h->d_gram ? h->d_gram : h->d_dual, h->dual_mass,                                // (hpv_set_residual_norm | _gram)
+                        h->lin_tensor ? 1 : 0,                                                          // (hpv_set_operator_tensor)
+                        h->d_gram ? 1 : 0};                                                             // (hpv_set_residual_gram)
     const int terms_mask = h->nl_mask | (h->n_coef ? h->dir_nl_mask : 0);
     if (h->n_coef)                                                                                      // (hpv_set_trainable)
         launch_project_id(IdProjArgs{a, h->nl_mask ? h->d_nl : h->d_nl_zero, terms_mask, h->d_dirs, h->d_theta + h->P + h->has_eps, h->n_coef,
@@ -282,6 +283,7 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     if (h->n_coef) terms += ";nc=" + std::to_string(h->n_coef);      // e.g. k_project_id<6x5/4x3;u3;nc=2>, k_project_id<6x5/4x3;u3;tensor;nc=2>
     if (has_ansatz(h)) terms += ";ansatz";                           // (hpv_set_ansatz: k_ansatz_fwd / k_ansatz_adj around the projection)
     if (h->d_dual) terms += ";dual";                                 // (hpv_set_residual_norm: the _dual instantiation of the kernel)
+    if (h->d_gram) terms += ";dual=dense";                           // (hpv_set_residual_gram: the _dense instantiation)
     snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
              h->n_coef ? "id" : h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
     ansatz_adj(h, HPV_ANSATZ_QUAD, v, h->Nq);

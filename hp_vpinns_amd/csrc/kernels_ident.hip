@@ -23,6 +23,7 @@
 // Registers: profiles/identification.md (no scratch, no VGPR spill; some kernel arguments are parked in VGPR lanes).
 #include "hpv_internal.h"
 #include "hpv_dual_norm.h"
+#include "hpv_dual_dense.h"
 
 namespace {
 
@@ -97,11 +98,12 @@ __device__ __forceinline__ void id_planes(const IdProjArgs& b, const double* cf,
     }
 }
 
-// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+// DUAL: 1 the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm), 2 that of hpv_dual_dense.h
+// (hpv_set_residual_gram: a dense inverse Gram factor per element); 0 is the kernel as it always was
 // TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; DIM == 2 only): the operator planes are (kxx, kxy, kyx, kyy, bx,
 // by, s), each base + sum_m c_m D_m like the others; G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y, and d lossv / d c_m weighs
 // D_kxx with u_x Gbar_1, D_kxy with u_y Gbar_1, D_kyx with u_x Gbar_2, D_kyy with u_y Gbar_2
-template <int DIM, bool DUAL, bool TENSOR = false>
+template <int DIM, int DUAL, bool TENSOR = false>
 __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
     static_assert(!TENSOR || DIM == 2, "the tensor operator is 2-D");
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -206,21 +208,29 @@ __global__ void __launch_bounds__(256) k_project_id(IdProjArgs b) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        if constexpr (!DUAL) sq += v * v;
+        if constexpr (DUAL == 0) sq += v * v;
     }
     DualScratch ds{};
-    if constexpr (DUAL) {
+    const double* We = nullptr;           // (DUAL == 2) this element's factor and the scratch of y = W_e U
+    double* yd = nullptr;
+    if constexpr (DUAL == 2) {
+        We = a.dual + (size_t)e * NR * NR;
+        yd = hpv_dual_dense_aliases_g(qx, qy, ntx, nty) ? G : red + 4;
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_dense_forward(We, ntx, NR, nax, nay, U, yd);
+    } else if constexpr (DUAL == 1) {
         ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
         __syncthreads();                  // U is complete (G has been dead since T was)
         sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], DIM == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = id_block_sum(sq, red);           // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL != 0 ? sq : sq / NRa;
     if (!a.do_adjoint) return;
-    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 1) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 2) hpv_dual_dense_adjoint(We, ntx, NR, nax, nay, U, yd);
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = DUAL ? 1.0 : 2.0 / NRa;
+    const double sc = DUAL != 0 ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -314,13 +324,20 @@ void launch_project_id(const IdProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const size_t lds = hpv_linop_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);      // (nothing is added to k_project_lin's layout)
     const dim3 grid((unsigned)n_elem), block(256);
+    if (a.lin.dual_dense) {      // (hpv_set_residual_gram)
+        const size_t ldsd = hpv_dual_dense_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
+        if (a.lin.tensor) hipLaunchKernelGGL((k_project_id<2, 2, true>), grid, block, ldsd, s, a);
+        else if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, 2>), grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL((k_project_id<1, 2>), grid, block, ldsd, s, a);
+        return;
+    }
     if (a.lin.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
-        if (a.lin.dual) hipLaunchKernelGGL((k_project_id<2, true, true>), grid, block, hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
-        else hipLaunchKernelGGL((k_project_id<2, false, true>), grid, block, lds, s, a);
+        if (a.lin.dual) hipLaunchKernelGGL((k_project_id<2, 1, true>), grid, block, hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty), s, a);
+        else hipLaunchKernelGGL((k_project_id<2, 0, true>), grid, block, lds, s, a);
     } else if (a.lin.dual) {
         const size_t ldsd = hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
-        if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, true>), grid, block, ldsd, s, a);
-        else hipLaunchKernelGGL((k_project_id<1, true>), grid, block, ldsd, s, a);
-    } else if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, false>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((k_project_id<1, false>), grid, block, lds, s, a);
+        if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, 1>), grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL((k_project_id<1, 1>), grid, block, ldsd, s, a);
+    } else if (a.lin.dim == 2) hipLaunchKernelGGL((k_project_id<2, 0>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_project_id<1, 0>), grid, block, lds, s, a);
 }

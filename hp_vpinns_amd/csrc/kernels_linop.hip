@@ -28,6 +28,7 @@
 // indicators, is an opt-in with a kernel of its own (hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
 #include "hpv_internal.h"
 #include "hpv_dual_norm.h"
+#include "hpv_dual_dense.h"
 
 namespace {
 
@@ -43,11 +44,12 @@ __device__ __forceinline__ double lin_block_sum(double v, double* red) {
     return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+// DUAL: 1 the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm), 2 that of hpv_dual_dense.h
+// (hpv_set_residual_gram: a dense inverse Gram factor per element); 0 is the kernel as it always was
 // TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; 2-D only): seven planes (kxx, kxy, kyx, kyy, bx, by, s),
 //     G1 = kxx u_x + kxy u_y     G2 = kyx u_x + kyy u_y     GBAR[u_x] = kxx Gbar_1 + kyx Gbar_2 + bx Gbar_0     GBAR[u_y] = kxy Gbar_1 + kyy Gbar_2 + by Gbar_0
 // -- still three integrands, so tables, contractions and LDS are untouched; false is the kernel as it always was
-template <bool DUAL, bool TENSOR = false>
+template <int DUAL, bool TENSOR = false>
 __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long e = blockIdx.x;
@@ -133,21 +135,29 @@ __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        if constexpr (!DUAL) sq += v * v;
+        if constexpr (DUAL == 0) sq += v * v;
     }
     DualScratch ds{};
-    if constexpr (DUAL) {
+    const double* We = nullptr;           // (DUAL == 2) this element's factor and the scratch of y = W_e U
+    double* yd = nullptr;
+    if constexpr (DUAL == 2) {
+        We = a.dual + (size_t)e * NR * NR;
+        yd = hpv_dual_dense_aliases_g(qx, qy, ntx, nty) ? G : red + 4;
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_dense_forward(We, ntx, NR, nax, nay, U, yd);
+    } else if constexpr (DUAL == 1) {
         ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
         __syncthreads();                  // U is complete (G has been dead since T was)
         sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], a.dim == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = lin_block_sum(sq, red);          // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL != 0 ? sq : sq / NRa;
     if (!a.do_adjoint) return;
-    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 1) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 2) hpv_dual_dense_adjoint(We, ntx, NR, nax, nay, U, yd);
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = DUAL ? 1.0 : 2.0 / NRa;
+    const double sc = DUAL != 0 ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -191,10 +201,12 @@ __device__ __forceinline__ void project_lin_body(const LinProjArgs& a) {
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) { project_lin_body<false>(a); }
-__global__ void __launch_bounds__(256) k_project_lin_dual(LinProjArgs a) { project_lin_body<true>(a); }
-__global__ void __launch_bounds__(256) k_project_lin_tensor(LinProjArgs a) { project_lin_body<false, true>(a); }
-__global__ void __launch_bounds__(256) k_project_lin_tensor_dual(LinProjArgs a) { project_lin_body<true, true>(a); }
+__global__ void __launch_bounds__(256) k_project_lin(LinProjArgs a) { project_lin_body<0>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_dual(LinProjArgs a) { project_lin_body<1>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_tensor(LinProjArgs a) { project_lin_body<0, true>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_tensor_dual(LinProjArgs a) { project_lin_body<1, true>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_dense(LinProjArgs a) { project_lin_body<2>(a); }
+__global__ void __launch_bounds__(256) k_project_lin_tensor_dense(LinProjArgs a) { project_lin_body<2, true>(a); }
 
 size_t hpv_linop_lds_bytes(int qx, int qy, int ntx, int nty) {
     const size_t gs = (size_t)(qx | 1), ts = (size_t)(ntx | 1), ys = (size_t)(qy | 1);
@@ -206,9 +218,20 @@ size_t hpv_dual_lds_bytes(int qx, int qy, int ntx, int nty) {
     return hpv_linop_lds_bytes(qx, qy, ntx, nty) + (hpv_dual_aliases_g(qx, qy, ntx, nty) ? 0 : hpv_dual_scratch_doubles(ntx, nty) * sizeof(double));
 }
 
+// the same layout, with y of hpv_dual_dense.h (NR doubles) appended where the G region cannot hold it
+size_t hpv_dual_dense_lds_bytes(int qx, int qy, int ntx, int nty) {
+    return hpv_linop_lds_bytes(qx, qy, ntx, nty) + (hpv_dual_dense_aliases_g(qx, qy, ntx, nty) ? 0 : (size_t)ntx * nty * sizeof(double));
+}
+
 void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const dim3 grid((unsigned)n_elem), block(256);
+    if (a.dual_dense) {      // (hpv_set_residual_gram)
+        const size_t ldsd = hpv_dual_dense_lds_bytes(a.qx, a.qy, a.ntx, a.nty);
+        if (a.tensor) hipLaunchKernelGGL(k_project_lin_tensor_dense, grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL(k_project_lin_dense, grid, block, ldsd, s, a);
+        return;
+    }
     const size_t lds = a.dual ? hpv_dual_lds_bytes(a.qx, a.qy, a.ntx, a.nty) : hpv_linop_lds_bytes(a.qx, a.qy, a.ntx, a.nty);
     if (a.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
         if (a.dual) hipLaunchKernelGGL(k_project_lin_tensor_dual, grid, block, lds, s, a);

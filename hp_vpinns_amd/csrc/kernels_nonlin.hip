@@ -31,6 +31,7 @@
 // value N takes there is multiplied by 0 in T, and its Gbar_0 = 0 makes every GBAR entry above 0.
 #include "hpv_internal.h"
 #include "hpv_dual_norm.h"
+#include "hpv_dual_dense.h"
 
 namespace {
 
@@ -72,10 +73,11 @@ __device__ __forceinline__ void nl_point(int mask, const double* nl, long cs, do
     dNu = d;
 }
 
-// DUAL: the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm); false is the kernel as it always was
+// DUAL: 1 the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm), 2 that of hpv_dual_dense.h
+// (hpv_set_residual_gram: a dense inverse Gram factor per element); 0 is the kernel as it always was
 // TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; 2-D only), as in project_lin_body: the operator has seven planes
 // (kxx, kxy, kyx, kyy, bx, by, s), G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y; the nonlinear planes and N are untouched
-template <bool DUAL, bool TENSOR = false>
+template <int DUAL, bool TENSOR = false>
 __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LinProjArgs& a = b.lin;
@@ -172,21 +174,29 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
         }
         U[idx] = v;
         a.R[e * NR + idx] = v;
-        if constexpr (!DUAL) sq += v * v;
+        if constexpr (DUAL == 0) sq += v * v;
     }
     DualScratch ds{};
-    if constexpr (DUAL) {
+    const double* We = nullptr;           // (DUAL == 2) this element's factor and the scratch of y = W_e U
+    double* yd = nullptr;
+    if constexpr (DUAL == 2) {
+        We = a.dual + (size_t)e * NR * NR;
+        yd = hpv_dual_dense_aliases_g(qx, qy, ntx, nty) ? G : red + 4;
+        __syncthreads();                  // U is complete (G has been dead since T was)
+        sq = hpv_dual_dense_forward(We, ntx, NR, nax, nay, U, yd);
+    } else if constexpr (DUAL == 1) {
         ds = hpv_dual_scratch(hpv_dual_aliases_g(qx, qy, ntx, nty) ? G : red + 4, ntx, nty);
         __syncthreads();                  // U is complete (G has been dead since T was)
         sq = hpv_dual_forward(a.dual, a.dual_mass, ntx, nty, nax, nay, a.Jx[e], a.dim == 2 ? a.Jy[e] : 1.0, U, ds);
     }
     sq = nl_block_sum(sq, red);           // (its barriers also order U before the adjoint and T's readers before S's writers)
-    if (tid == 0) a.loss_e[e] = DUAL ? sq : sq / NRa;
+    if (tid == 0) a.loss_e[e] = DUAL != 0 ? sq : sq / NRa;
     if (!a.do_adjoint) return;
-    if constexpr (DUAL) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 1) hpv_dual_adjoint(ntx, nty, nax, nay, U, ds);      // U <- d loss_e / d R: sc = 1 below
+    if constexpr (DUAL == 2) hpv_dual_dense_adjoint(We, ntx, NR, nax, nay, U, yd);
 
     // ---- S_t[j][r] = c_t sum_k WTY[dy_t][k][j] Rbar[k][r],  Rbar = (2 / n_active) R ----
-    const double sc = DUAL ? 1.0 : 2.0 / NRa;
+    const double sc = DUAL != 0 ? 1.0 : 2.0 / NRa;
     for (int idx = tid; idx < nt * qy * ntx; idx += 256) {
         const int tj = idx / ntx, r = idx - tj * ntx, t = tj / qy, j = tj - t * qy;
         const double* y = Y + (t == 2 ? nty * ys : 0) + j;
@@ -256,10 +266,12 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) { project_nl_body<false>(b); }
-__global__ void __launch_bounds__(256) k_project_nl_dual(NlProjArgs b) { project_nl_body<true>(b); }
-__global__ void __launch_bounds__(256) k_project_nl_tensor(NlProjArgs b) { project_nl_body<false, true>(b); }
-__global__ void __launch_bounds__(256) k_project_nl_tensor_dual(NlProjArgs b) { project_nl_body<true, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl(NlProjArgs b) { project_nl_body<0>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_dual(NlProjArgs b) { project_nl_body<1>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor(NlProjArgs b) { project_nl_body<0, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_dual(NlProjArgs b) { project_nl_body<1, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_dense(NlProjArgs b) { project_nl_body<2>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_dense(NlProjArgs b) { project_nl_body<2, true>(b); }
 
 // (the channels are re-read from OUT in the adjoint phase, so nothing is added to k_project_lin's layout)
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop_lds_bytes(qx, qy, ntx, nty); }
@@ -267,6 +279,12 @@ size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const dim3 grid((unsigned)n_elem), block(256);
+    if (a.lin.dual_dense) {      // (hpv_set_residual_gram)
+        const size_t ldsd = hpv_dual_dense_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
+        if (a.lin.tensor) hipLaunchKernelGGL(k_project_nl_tensor_dense, grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL(k_project_nl_dense, grid, block, ldsd, s, a);
+        return;
+    }
     const size_t lds = a.lin.dual ? hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty) : hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
     if (a.lin.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
         if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_tensor_dual, grid, block, lds, s, a);

@@ -62,9 +62,19 @@ def interval_hard_bc(a, b, ua, ub):
     return dict(g=g, d=d)
 
 
-def _norm_arg(residual_norm, gram_mass):
-    """the residual_norm= of the classes from the command line's --residual-norm / --gram-mass"""
-    return "l2" if residual_norm == "l2" else dict(kind="dual", mass=float(gram_mass))
+def _norm_arg(residual_norm, gram_mass, mapped=False):
+    """the residual_norm= of the classes from the command line's --residual-norm / --gram-mass: "dual" is the reference metric on
+    boxes and the physical one on a mapped mesh (dense Gram factors), "energy" the inner product of the problem's own kappa"""
+    if residual_norm == "l2":
+        return "l2"
+    if residual_norm == "energy":
+        return dict(kind="dual", mass=float(gram_mass), metric="energy")
+    return dict(kind="dual", mass=float(gram_mass), metric="physical") if mapped else dict(kind="dual", mass=float(gram_mass))
+
+
+def _loss_line(m, err):
+    """sqrt(lossv) beside the relative L2 error, for the drivers that know no H^1 error of their solution"""
+    return "sqrt(lossv) %.4e beside the relative L2 error %.4e (residual norm %s)" % (np.sqrt(float(np.asarray(m.loss())[2])), err, m.residual_norm)
 
 
 def _estimator_line(m, h1_err):
@@ -203,12 +213,12 @@ def _annulus_boundary(n):
 
 
 def run_annulus(n_r=4, n_theta=4, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0,
-                seed=1234, backend="auto", device=None, verbose=True, hard_bc=False, record_every=None):
+                seed=1234, backend="auto", device=None, verbose=True, hard_bc=False, record_every=None, residual_norm="l2"):
     """record_every: also the error curve [(iteration, relative L2 error)], one row per that many updates"""
     Xb = _annulus_boundary(int(n_bound))
     bc = dict(hard_bc=annulus_hard_bc()) if hard_bc else dict(X_u_train=Xb, u_train=np.zeros(Xb.shape[0]))
     m = VPINNLinear(list(layers), mesh=annulus_mesh(n_r, n_theta, n_test), n_quad=int(n_quad), kappa=1.0, f=_annulus_f, lossb_weight=lossb_weight,
-                    LR=LR, seed=seed, backend=backend, device=device, **bc)
+                    LR=LR, seed=seed, backend=backend, device=device, residual_norm=residual_norm, **bc)
     rr, tt = np.meshgrid(np.linspace(1.0, 2.0, 41), np.linspace(0.0, np.pi / 2, 41))
     X = np.stack([(rr * np.cos(tt)).reshape(-1), (rr * np.sin(tt)).reshape(-1)], 1)
     u = _annulus_exact(X)[:, None]
@@ -224,6 +234,8 @@ def run_annulus(n_r=4, n_theta=4, n_quad=10, n_test=5, n_iter=2000, layers=(2, 2
             print("It: %d, relative L2 error %.4e" % row)
         print("quarter annulus, %d polar elements (area %.6f), %s: relative L2 error %.4e (%s)"
               % (len(m.mesh), m.mesh.area(), "exact conditions (ansatz)" if hard_bc else "penalty", err, m.h.kernel_variant()))
+        if residual_norm != "l2":
+            print(_loss_line(m, err))
     return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), curve=curve)
 
 
@@ -235,7 +247,7 @@ def rotated_tensor(angle_deg, ratio):
 
 
 def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3,
-                    lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True):
+                    lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, residual_norm="l2"):
     K = rotated_tensor(angle, ratio)
 
     def f(P):
@@ -246,7 +258,8 @@ def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n
     Xb = np.concatenate([np.stack([t, -o], 1), np.stack([t, o], 1), np.stack([-o, t], 1), np.stack([o, t], 1)])
     g = np.linspace(-1.0, 1.0, int(n_elements) + 1)
     m = VPINNLinear(list(layers), grid_x=g, grid_y=g, n_quad=int(n_quad), n_test=int(n_test), kappa=K, f=f, X_u_train=Xb,
-                    u_train=np.zeros(Xb.shape[0]), lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device)
+                    u_train=np.zeros(Xb.shape[0]), lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device,
+                    residual_norm=residual_norm)
     m.train(int(n_iter), verbose=False)
     gg = np.linspace(-1.0, 1.0, 81)
     X = np.stack([v.reshape(-1) for v in np.meshgrid(gg, gg)], 1)
@@ -254,6 +267,8 @@ def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n
     err = m.rel_l2_error(X, u)
     if verbose:
         print("rotated anisotropy, angle %g degrees, ratio %g, K = %s: relative L2 error %.4e (%s)" % (angle, ratio, K.round(4).tolist(), err, m.h.kernel_variant()))
+        if residual_norm != "l2":
+            print(_loss_line(m, err))
     return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
 
 
@@ -271,17 +286,21 @@ def main(argv=None):
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None)
     ap.add_argument("--hard-bc", action="store_true", help="boundary layer, annulus: exact Dirichlet conditions by ansatz instead of the penalty")
-    ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
+    ap.add_argument("--residual-norm", choices=["l2", "dual", "energy"], default="l2",
+                    help="dual: each element's residual in the dual norm of its test space (robust VPINNs; on the annulus in the physical metric); "
+                         "energy (l-shape, anisotropic, annulus): that norm in the energy inner product of the problem's own kappa")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
-    rn = _norm_arg(a.residual_norm, a.gram_mass)
+    if a.residual_norm == "energy" and a.problem == "boundary-layer":
+        ap.error("--residual-norm energy belongs to l-shape, anisotropic and annulus")
+    rn = _norm_arg(a.residual_norm, a.gram_mass, mapped=a.problem == "annulus")
     if a.problem == "boundary-layer":
         run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
                            adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn)
     elif a.problem == "annulus":
-        run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10))
+        run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10), residual_norm=rn)
     elif a.problem == "anisotropic":
-        run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters)
+        run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, residual_norm=rn)
     else:
         run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn)
 

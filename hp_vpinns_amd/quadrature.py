@@ -173,3 +173,98 @@ def gram_stacks(nt):
     for n in range(1, nt + 1):
         S[n - 1, :n, :n], lam[n - 1, :n] = gram_eig(n)
     return S, lam
+
+
+# ---- dense Gram factors: the inner products whose Gram matrix is no Kronecker sum (hpv_set_residual_gram) ----------------------------
+def gram_rule(ntx, nty=1, gram_points=None):
+    """(nodes, weights) of the Gram matrices' own Gauss-Legendre rule: max(ntx, nty) + 3 points per direction unless `gram_points`
+    says otherwise -- exact for a constant weight tensor on affine elements (degree 2 nt + 2 <= 2 nt + 5).  Not the handle's Lobatto
+    rule: that one may under-integrate the test functions' products and leave the matrix singular."""
+    n = max(int(ntx), int(nty)) + 3 if gram_points is None else int(gram_points)
+    if n < 1:
+        raise ValueError("gram_points is a positive number of Gauss-Legendre points per direction")
+    return np.polynomial.legendre.leggauss(n)
+
+
+def gram_factors(dim, ntx, nty, nax, nay, A, S=None, mass=0.0, gram_points=None, first=0):
+    """W (n, NR, NR), NR = ntx * nty: per element the inverse Cholesky factor W_e = L_e^{-1} of the Gram matrix G_e = L_e L_e^T of its
+    ACTIVE test functions phi_kr = phi_r(xi) phi_k(eta), r < nax[e], k < nay[e], in the inner product
+
+        G_e[(k, r), (k', r')] = sum_g w_g [ grad^ phi_kr^T C_g grad^ phi_k'r' + m_g phi_kr phi_k'r' ]
+        C = adj(A) S adj(A)^T / det A          m = mass det A                  (1-D: C = S / Jx, m = mass Jx)
+
+    at the points of `gram_rule` (g = j * n_gram + i in 2-D), so that loss_e = |W_e R_e|^2 = R_e^T G_e^{-1} R_e.  W_e is row-major in
+    the full index k * ntx + r (the order of R[k][r]), lower triangular, exactly zero in the rows and columns of inactive functions:
+    a sub-selection of indices keeps its order, so it is a valid inverse factor of the active sub-matrix.
+    A: the Jacobian of each element's map with respect to its reference coordinates at the Gram points -- 2-D (n, n_gram^2, 2, 2),
+    1-D (n, n_gram) (= Jx); boxes are diag(Jx, Jy).  S: the physical weight tensor there, None for the identity (the physical H^1
+    product), else sym(K) of (n, n_gram^2, 2, 2) / the diagonal of (n, n_gram^2, 2) / the scalars of (n, n_gram) in 1-D (the energy
+    product).  Assembled by sum factorisation, numpy only.  ValueError naming the element (numbered from `first`) where S is not
+    positive definite at a Gram point or the Cholesky factorisation fails."""
+    from .testfcn import Test_fcn, dTest_fcn
+    dim, ntx, nty = int(dim), int(ntx), int(nty)
+    x, w = gram_rule(ntx, nty, gram_points)
+    ng = x.size
+    A = np.asarray(A, dtype=np.float64)
+    ne = A.shape[0]
+    if A.shape != ((ne, ng) if dim == 1 else (ne, ng * ng, 2, 2)):
+        raise ValueError(f"A has shape {A.shape}; expected {(ne, ng) if dim == 1 else (ne, ng * ng, 2, 2)}")
+    nax = np.broadcast_to(np.asarray(nax, dtype=np.int64), (ne,))
+    nay = np.broadcast_to(np.asarray(nay, dtype=np.int64), (ne,))
+    NR = ntx * nty
+    W = np.zeros((ne, NR, NR))
+    px, dpx = Test_fcn(ntx, x), dTest_fcn(ntx, x)[0]
+    if dim == 2:
+        py, dpy = Test_fcn(nty, x), dTest_fcn(nty, x)[0]
+        if S is not None:
+            S = np.asarray(S, dtype=np.float64)
+            if S.shape == (ne, ng * ng, 2):
+                S = S[..., None] * np.eye(2)
+            if S.shape != (ne, ng * ng, 2, 2):
+                raise ValueError(f"S has shape {S.shape}; expected {(ne, ng * ng, 2, 2)} or {(ne, ng * ng, 2)}")
+            S = 0.5 * (S + S.transpose(0, 1, 3, 2))
+    elif S is not None:
+        S = np.asarray(S, dtype=np.float64).reshape(ne, ng)
+    I = np.eye(NR)
+    for e in range(ne):
+        na, nb = int(nax[e]), int(nay[e])
+        if dim == 1:
+            s = np.ones(ng) if S is None else S[e]
+            if not np.all(s > 0.0):
+                raise ValueError(f"element {first + e}: kappa is {s.min():.6g} at a Gram point; the energy inner product needs kappa > 0")
+            G = np.einsum("i,ri,si->rs", w * s / A[e], dpx[:na], dpx[:na]) + np.einsum("i,ri,si->rs", w * mass * A[e], px[:na], px[:na])
+        else:
+            a = A[e]
+            det = a[:, 0, 0] * a[:, 1, 1] - a[:, 0, 1] * a[:, 1, 0]
+            adj = np.stack([np.stack([a[:, 1, 1], -a[:, 0, 1]], 1), np.stack([-a[:, 1, 0], a[:, 0, 0]], 1)], 1)
+            if S is None:
+                C = np.einsum("gab,gcb->gac", adj, adj) / det[:, None, None]
+            else:
+                s = S[e]
+                lo = 0.5 * (s[:, 0, 0] + s[:, 1, 1]) - np.sqrt((0.5 * (s[:, 0, 0] - s[:, 1, 1])) ** 2 + s[:, 0, 1] ** 2)
+                if not np.all(lo > 0.0):
+                    raise ValueError(f"element {first + e}: the smallest eigenvalue of sym(kappa) is {lo.min():.6g} at a Gram point; "
+                                     "the energy inner product needs a positive definite kappa")
+                C = np.einsum("gab,gbc,gdc->gad", adj, s, adj) / det[:, None, None]
+            C = C.reshape(ng, ng, 2, 2)                                  # [j][i]
+            m = (mass * det).reshape(ng, ng)
+            X, Y = (px[:na], dpx[:na]), (py[:nb], dpy[:nb])              # [derivative order][function][point]
+            G = np.zeros((nb, na, nb, na))
+            # (a, b): the reference derivative taken of the first / the second function -- 0: d/dxi (x table differentiated), 1: d/deta
+            for ca, cb, c in ((0, 0, C[:, :, 0, 0]), (0, 1, C[:, :, 0, 1]), (1, 0, C[:, :, 1, 0]), (1, 1, C[:, :, 1, 1]), (2, 2, m)):
+                T = np.einsum("ji,ri,si->jrs", c * w[None, :], X[ca == 0], X[cb == 0])      # the x direction, per row j of points
+                G += np.einsum("j,kj,lj,jrs->krls", w, Y[ca == 1], Y[cb == 1], T)
+            G = G.reshape(nb * na, nb * na)
+        try:
+            L = np.linalg.cholesky(0.5 * (G + G.T))
+        except np.linalg.LinAlgError:
+            raise ValueError(f"element {first + e}: the Gram matrix of its {na} x {nb} test functions is not positive definite "
+                             "(Cholesky failed): a degenerate element, or too few gram_points") from None
+        idx = (np.arange(nb)[:, None] * ntx + np.arange(na)[None, :]).reshape(-1)
+        # W_e = L^{-1}: forward substitution against the identity, row by row (numpy has no triangular solve)
+        n = L.shape[0]
+        Wi = np.zeros((n, n))
+        for i in range(n):
+            Wi[i] = (I[i, :n] - L[i, :i] @ Wi[:i]) / L[i, i]
+        W[e][np.ix_(idx, idx)] = np.tril(Wi)
+    return W

@@ -1372,9 +1372,15 @@ class VPINNLinear(_VPINNBase):
     PHYSICAL quadrature points, and the geometry is folded into the planes in one place (`_fold`: K_eff = adj(A) K, everything
     else times det A, with A the Jacobian of the element's map); the library runs unit elements with a full tensor.  `set_operator`,
     `set_nonlinear`, `set_mesh` (box to mapped and back, state untouched), checkpoints, sharding, `hard_bc`, `set_flux_data`,
-    validation and `predict` work as on boxes.  Out of scope, each a ValueError that says why: `residual_norm="dual"` with a
-    MappedMesh (the dual norm in the physical metric is not implemented), `strong_form="elementwise"` with a MappedMesh or a tensor
-    kappa, and `adapt` / `train_adaptive` in those cases; also 1-D graded maps, solution-dependent tensors and triangles."""
+    validation and `predict` work as on boxes.  The dual norm there and in the energy metric (hpv_set_residual_gram):
+    `residual_norm=dict(kind="dual", metric="reference" | "physical" | "energy", mass=gamma, gram_points=None)` -- "reference" (the
+    default, what plain "dual" means) is the H^1 product of the box through the eigen tables; "physical" the H^1 product of the physical
+    element, the tables on boxes and dense Gram factors (`quadrature.gram_factors`) on a MappedMesh; "energy" the product
+    (sym(kappa) grad v, grad w) of the model's own kappa, always dense, re-handed by `set_operator(kappa=)`.  Refused with a reason:
+    "energy" with a trainable kappa or a kappa that is not positive definite at a Gram point, a metric on "l2".  Out of scope, each a
+    ValueError that says why: plain `residual_norm="dual"` with a MappedMesh (metric="physical" is the one that works there),
+    `strong_form="elementwise"` with a MappedMesh or a tensor kappa, and `adapt` / `train_adaptive` in those cases; also 1-D graded
+    maps, solution-dependent tensors and triangles."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1388,6 +1394,7 @@ class VPINNLinear(_VPINNBase):
                  residual_norm="l2"):
         dim = int(layers[0])
         self._residual_norm = self._check_residual_norm(residual_norm)
+        self._norm_metric = self._check_norm_metric(residual_norm)
         if strong_form not in (None, "elementwise"):
             raise ValueError('strong_form is None or "elementwise"')
         if strong_form and hard_bc is not None:
@@ -1458,6 +1465,8 @@ class VPINNLinear(_VPINNBase):
             self.h.set_element_boxes(mesh.boxes, eb, ee)
             return
         xi, yi = self._dev_rule
+        if self._residual_norm[0] == "dual":                # (set_mesh from boxes: the table norm of the boxes is refused on mapped
+            self.h.set_residual_norm(_lib.NORM_L2)          #  elements; _hand_residual_norm hands the dense factors over afterwards)
         X = mesh.quad_points(xi, yi, 0, len(mesh))          # (the library slices [eb, ee) itself, as it slices boxes)
         self.h.set_element_points(X.reshape(len(mesh), -1, 2).transpose(0, 2, 1), eb, ee)
 
@@ -1507,9 +1516,13 @@ class VPINNLinear(_VPINNBase):
     def _check_scope(self, mesh, residual_norm=None):
         """what is out of scope on mapped elements and with a full tensor, each refused with its reason"""
         mapped = isinstance(mesh, MappedMesh)
-        if mapped and (residual_norm or self._residual_norm)[0] == "dual":
+        rn = residual_norm or self._rn4
+        if mapped and rn[0] == "dual" and rn[2] == "reference":
             raise ValueError('residual_norm="dual" on a MappedMesh: the Gram matrix of the reference square is not the physical H^1 '
-                             "inner product of a mapped element (the dual norm in the physical metric is not implemented)")
+                             'inner product of a mapped element; dict(kind="dual", metric="physical") is (dense Gram factors)')
+        if rn[2] == "energy" and any("kappa" in t for t in self._trainable):
+            raise ValueError('metric="energy" with a trainable kappa: the Gram matrix of the energy inner product would move with '
+                             "the unknown coefficient")
         if mapped and self._strong_form:
             raise ValueError('strong_form="elementwise" on a MappedMesh: the strong residual on mapped elements is not implemented')
         if self._strong_form and self._tensor_mode(mesh):
@@ -1538,23 +1551,82 @@ class VPINNLinear(_VPINNBase):
         else:
             self.h.set_operator(planes)
 
-    # -- the norm of the residual (hpv_set_residual_norm) ----------------------------------------------------------------------
+    # -- the norm of the residual (hpv_set_residual_norm, hpv_set_residual_gram) --------------------------------------------------
+    _METRICS = ("reference", "physical", "energy")
+
     @staticmethod
     def _check_residual_norm(rn):
-        """("l2" | "dual", mass) of "l2" | "dual" | dict(kind=, mass=)"""
+        """("l2" | "dual", mass) of "l2" | "dual" | dict(kind=, mass=, metric=, gram_points=); the last two: `_check_norm_metric`"""
         d = dict(kind=rn) if isinstance(rn, str) else dict(rn) if isinstance(rn, dict) else None
-        if d is None or set(d) - {"kind", "mass"} or d.get("kind") not in ("l2", "dual"):
-            raise ValueError('residual_norm is "l2", "dual" or dict(kind="dual", mass=gamma)')
+        if d is None or set(d) - {"kind", "mass", "metric", "gram_points"} or d.get("kind") not in ("l2", "dual"):
+            raise ValueError('residual_norm is "l2", "dual" or dict(kind="dual", metric="reference" | "physical" | "energy", mass=gamma, '
+                             "gram_points=None)")
         mass = float(d.get("mass", 0.0))
         if not np.isfinite(mass) or mass < 0.0 or (d["kind"] == "l2" and mass != 0.0):
             raise ValueError("residual_norm: mass is a finite number >= 0 and belongs to kind=\"dual\"")
+        VPINNLinear._check_norm_metric(d)
         return d["kind"], mass
 
+    @staticmethod
+    def _check_norm_metric(rn):
+        """(metric, gram_points) of a residual_norm= that `_check_residual_norm` has seen: ("reference", None) unless a dict says otherwise"""
+        d = rn if isinstance(rn, dict) else {}
+        if d.get("kind") == "l2" and (d.get("metric") is not None or d.get("gram_points") is not None):
+            raise ValueError('residual_norm: metric and gram_points belong to kind="dual" (the l2 norm has no inner product to choose)')
+        metric = d.get("metric") or "reference"
+        if metric not in VPINNLinear._METRICS:
+            raise ValueError(f"residual_norm: metric is one of {VPINNLinear._METRICS}")
+        gp = d.get("gram_points")
+        if gp is not None and (int(gp) != gp or int(gp) < 1):
+            raise ValueError("residual_norm: gram_points is a positive number of Gauss-Legendre points per direction, or None")
+        return metric, None if gp is None else int(gp)
+
+    @staticmethod
+    def _norm4(rn):
+        """(kind, mass, metric, gram_points) of a residual_norm= argument"""
+        return VPINNLinear._check_residual_norm(rn) + VPINNLinear._check_norm_metric(rn)
+
+    def _dense_norm(self, mesh, rn=None):
+        """whether the dual norm needs dense Gram factors: on mapped elements and in the energy metric -- "physical" on boxes is the
+        inner product of "reference" and takes the tables"""
+        rn = rn or self._rn4
+        return rn[0] == "dual" and (rn[2] == "energy" or isinstance(mesh, MappedMesh))
+
+    def _gram_factors(self, mesh, eb, ee, rn=None):
+        """quadrature.gram_factors of the elements [eb, ee): the geometry and, in the energy metric, sym(kappa) at the Gram rule's points"""
+        from .quadrature import gram_factors, gram_rule
+        _, mass, metric, gp = rn or self._rn4
+        dim = mesh.dim
+        ntx, nty = int(mesh.nax.max()), int(mesh.nay.max()) if dim == 2 else 1
+        x = gram_rule(ntx, nty, gp)[0]
+        ne, ng = ee - eb, x.size
+        if isinstance(mesh, MappedMesh):
+            P, A = mesh.geometry(x, x, eb, ee)
+            A = A.reshape(ne, ng * ng, 2, 2)
+        else:
+            P = mesh.quad_points(x, x if dim == 2 else None, eb, ee)
+            b = mesh.boxes[eb:ee]
+            if dim == 1:
+                A = np.repeat(((b[:, 1] - b[:, 0]) / 2)[:, None], ng, axis=1)
+            else:
+                A = np.zeros((ne, ng * ng, 2, 2))
+                A[:, :, 0, 0], A[:, :, 1, 1] = ((b[:, 1] - b[:, 0]) / 2)[:, None], ((b[:, 3] - b[:, 2]) / 2)[:, None]
+        S = None
+        if metric == "energy":
+            k = _kappa_field(self._op["kappa"], P, dim)
+            S = k[:, 0].reshape(ne, ng) if dim == 1 else k.reshape((ne, ng * ng) + k.shape[1:])
+        return gram_factors(dim, ntx, nty, mesh.nax[eb:ee], mesh.nay[eb:ee] if dim == 2 else 1, A, S, mass, gp, first=eb)
+
     def _hand_residual_norm(self, mesh):
-        """the eigen tables of the Gram matrices for the counts 1 .. max of the mesh (they go with the test-function tables)"""
-        kind, mass = self._residual_norm
+        """the eigen tables of the Gram matrices for the counts 1 .. max of the mesh (they go with the test-function tables), or --
+        mapped elements, the energy metric -- this rank's dense factors (they go with the elements, the counts and kappa too)"""
+        kind, mass = self._residual_norm[:2]
         if kind == "l2":
             self.h.set_residual_norm(_lib.NORM_L2)
+            return
+        if self._dense_norm(mesh):
+            eb, ee = shard_range(len(mesh), self.rank, self.world)
+            self.h.set_residual_gram(self._gram_factors(mesh, eb, ee))
             return
         from .quadrature import gram_stacks
         sx = gram_stacks(int(mesh.nax.max()))
@@ -1562,32 +1634,48 @@ class VPINNLinear(_VPINNBase):
         self.h.set_residual_norm(_lib.NORM_DUAL, mass, sx[0], sx[1], sy[0], sy[1])
 
     def set_residual_norm(self, residual_norm):
-        """Change the norm of the residual on the live model: "l2", "dual" or dict(kind="dual", mass=gamma).  Parameters and optimizer
-        state stay; the loss history goes on in the new norm."""
-        rn = self._check_residual_norm(residual_norm)
+        """Change the norm of the residual on the live model: "l2", "dual" or dict(kind="dual", metric=, mass=gamma, gram_points=).
+        Parameters and optimizer state stay; the loss history goes on in the new norm."""
+        rn = self._norm4(residual_norm)
         self._check_scope(self._mesh, rn)
-        self._residual_norm = rn
+        if self._dense_norm(self._mesh, rn):               # (a kappa that is not positive definite is refused before anything changes)
+            eb, ee = shard_range(len(self._mesh), self.rank, self.world)
+            self._gram_factors(self._mesh, eb, ee, rn)
+        self._residual_norm, self._norm_metric = rn[:2], rn[2:]
         self._hand_residual_norm(self._mesh)
 
     @property
     def residual_norm(self):
-        """"l2", or dict(kind="dual", mass=gamma)"""
-        kind, mass = self._residual_norm
-        return "l2" if kind == "l2" else dict(kind="dual", mass=mass)
+        """"l2", dict(kind="dual", mass=gamma) in the reference metric with the default rule, else dict(kind="dual", mass=gamma,
+        metric=, gram_points=)"""
+        kind, mass, metric, gp = self._rn4
+        if kind == "l2":
+            return "l2"
+        return dict(kind="dual", mass=mass) if (metric, gp) == ("reference", None) else dict(kind="dual", mass=mass, metric=metric, gram_points=gp)
+
+    @property
+    def _rn4(self):
+        return tuple(self._residual_norm) + tuple(self._norm_metric)
 
     def save_checkpoint(self, path):
         """As `_VPINNBase.save_checkpoint`, with the norm of the residual."""
+        kind, mass, metric, gp = self._rn4
         np.savez(self._ckpt_path(path), state=self.h.get_state(), layers=np.asarray(self.layers), dev_layers=np.asarray(self._dev_layers),
-                 cls=type(self).__name__, residual_norm=self._residual_norm[0], residual_norm_mass=self._residual_norm[1])
+                 cls=type(self).__name__, residual_norm=kind, residual_norm_mass=mass, residual_norm_metric=metric,
+                 residual_norm_gram_points=0 if gp is None else gp)
 
     def load_checkpoint(self, path):
-        """As `_VPINNBase.load_checkpoint`; a checkpoint that stores the norm of the residual sets it on the model."""
+        """As `_VPINNBase.load_checkpoint`; a checkpoint that stores the norm of the residual sets it on the model (one written before
+        the metrics existed is "reference")."""
         super().load_checkpoint(path)
         d = np.load(self._ckpt_path(path), allow_pickle=False)
         if "residual_norm" in d:
-            rn = (str(d["residual_norm"]), float(d["residual_norm_mass"]))
-            if rn != self._residual_norm:
-                self.set_residual_norm(dict(kind=rn[0], mass=rn[1]))
+            kind = str(d["residual_norm"])
+            metric = str(d["residual_norm_metric"]) if "residual_norm_metric" in d else "reference"
+            gp = int(d["residual_norm_gram_points"]) if "residual_norm_gram_points" in d else 0
+            rn = (kind, float(d["residual_norm_mass"]), metric, gp or None)
+            if rn != self._rn4:
+                self.set_residual_norm("l2" if kind == "l2" else dict(kind=kind, mass=rn[1], metric=metric, gram_points=rn[3]))
 
     # -- exact Dirichlet conditions by ansatz u = G + D N (hpv_set_ansatz) ------------------------------------------------------
     def _check_hard_bc(self, hard_bc, mesh):
@@ -1737,13 +1825,19 @@ class VPINNLinear(_VPINNBase):
         for k, v in (("kappa", kappa), ("beta", beta), ("sigma", sigma)):
             if v is not None:
                 self._op[k] = v
+        energy = self._norm_metric[0] == "energy"
         try:
             self._check_scope(self._mesh)
+            if energy:                                     # (a kappa that is not positive definite is refused before anything changes)
+                eb, ee = shard_range(len(self._mesh), self.rank, self.world)
+                W = self._gram_factors(self._mesh, eb, ee)
         except ValueError:
             self._op = old
             raise
         self._hand_operator(self._mesh)
         self._hand_trainable(self._mesh)
+        if energy:                                         # (the Gram matrix of the energy inner product is kappa's)
+            self.h.set_residual_gram(W)
 
     def set_mesh(self, mesh, f=None):
         """As `_VPINNBase.set_mesh`; the coefficients are re-evaluated on the new elements.  f None keeps the model's own f."""

@@ -229,8 +229,9 @@ int hpv_set_operator_tensor(hpv_handle h, const double* coef, size_t n);
  * Slicing by [e_begin, e_end), preconditions, the re-slicing of F and of the counts, and the invalidation of every plane are those
  * of hpv_set_element_boxes (both end in one function); hpv_set_elements / hpv_set_element_boxes return the handle to boxes.
  * The points are checked to be finite; the maps themselves never reach the library and are not checked.
- * Out of scope on such a handle: the dual norm -- the Gram matrix of the reference square is not the physical H^1 inner product --
- * so hpv_set_residual_norm(dual) is refused on it and this call is refused while the dual norm is set; the strong form:
+ * Out of scope on such a handle: the TABLE dual norm -- the Gram matrix of the reference square is not the physical H^1 inner product --
+ * so hpv_set_residual_norm(dual) is refused on it and this call is refused while that norm is set (the dense factors of
+ * hpv_set_residual_gram carry the physical product: under them this call is accepted and drops the factors); the strong form:
  * hpv_set_strong_form is refused on it and this call is refused while the strong form is set; 1-D handles; triangles.
  * Returns 0; -1 for another kind of handle, NULL, n_total < 1, a bad range, a non-finite point, the two refusals above; -3 before
  * hpv_set_quadrature / hpv_set_tables; -2 on a HIP error. */
@@ -531,9 +532,36 @@ int hpv_set_ansatz(hpv_handle h, int which, const double* planes, size_t n);
  * kind, mass < 0 or not finite, missing tables, a non-finite entry, an eigenvalue <= 0 inside a count's block, and an element whose
  * dual-norm kernel would need more than 64 KiB of LDS (the scratch is appended where the integrand region cannot hold it); -2 on a
  * HIP error.
- * Out of scope: the other problem classes and the whole-iteration kernels, Gram matrices of a weighted (kappa) inner product,
- * non-symmetric optimal test norms, the data and flux terms, gathering indicators across GPUs. */
+ * Out of scope: the other problem classes and the whole-iteration kernels, non-symmetric optimal test norms, the data and flux terms,
+ * gathering indicators across GPUs.  Gram matrices of a weighted (kappa) inner product and of mapped elements: hpv_set_residual_gram. */
 int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx, const double* lamx, const double* Sy, const double* lamy);
+
+/* The same dual norm through one DENSE inverse Gram factor per owned element (kind 2), for the inner products whose Gram matrix is no
+ * Kronecker sum: the physical H^1 product of a mapped element (hpv_set_element_points) and the energy product
+ * (sym(K) grad v, grad w) + mass (v, w) of a variable or full-tensor kappa.  The caller factors G_e = L_e L_e^T of each element's ACTIVE
+ * test functions once (hp_vpinns_amd/quadrature.py: gram_factors, a Gauss-Legendre rule of the Gram matrix's own) and hands over
+ * W_e = L_e^{-1}: W is [n_owned][NR][NR], NR = ntx*nty, row-major in the full index k*ntx + r of R[k][r], lower triangular, exactly zero
+ * in the rows and columns of inactive functions.  Then
+ *     loss_e = |W_e R_e|^2 = R_e^T G_e^{-1} R_e          d loss_e / d R = 2 W_e^T (W_e R_e)
+ * in the _dense instantiations of k_project_lin | _nl | _id, with and without the tensor operator (csrc/hpv_dual_dense.h: one
+ * workgroup per element, W_e read in place twice per pass, no atomics, the same bits from call to call), in the launch slot of
+ * kind 1.  It follows the contract of hpv_set_residual_norm: linear problems and the variational scheme only; 1-D, 2-D and mapped
+ * handles; everything is copied; it waits for the handle's stream and drops the captured iteration graphs; it replaces kind 1 if
+ * that was set (and hpv_set_residual_norm(h, 1, ..) replaces it); hpv_set_residual_norm(h, 0, ..) removes it and restores the plain
+ * handle bit for bit.  hpv_kernel_variant appends ";dual=dense"; hpv_get_residuals keeps returning the raw R; with
+ * hpv_set_strong_form on boxes, column 0 of hpv_linear_indicators is the dense dual loss.  The setting is not state.
+ * The factors belong to the elements, their counts and the test-function tables: hpv_set_tables, hpv_set_elements,
+ * hpv_set_element_boxes, hpv_set_element_points and hpv_set_active_tests* drop them, and every pass then returns -3 until this call
+ * is repeated or kind 0 is given -- a handle that had a dual norm never silently trains mean(R^2).  On mapped handles kind 1 stays
+ * refused and hpv_set_element_points stays refused while kind 1 is set; while kind 2 is set it is accepted and drops the factors.
+ * Returns 0; -3 for a handle of another problem or scheme and before hpv_set_tables / the elements; -1 (the handle keeps what it
+ * had) for an element whose kernel would need more than 64 KiB of LDS (y = W_e R_e, NR doubles, is appended where the integrand
+ * region cannot hold it), a wrong n, NULL, a non-finite entry, a non-zero entry above the diagonal or in an inactive row or column,
+ * a diagonal entry <= 0 on an active index; -2 on a HIP error.
+ * Out of scope: the other problem classes and the whole-iteration kernels, non-symmetric optimal test norms, the data and flux terms,
+ * a Gram matrix that follows a trainable coefficient, gathering indicators across GPUs. */
+#define HPV_NORM_DUAL_DENSE 2
+int hpv_set_residual_gram(hpv_handle h, const double* W, size_t n);
 int hpv_backend_in_use(hpv_handle h);                       /* HPV_BACKEND_GENERIC or HPV_BACKEND_MFMA */
 /* Launch structure of the most recent reverse-mode pass over the quadrature batch (tests assert that the kernel they mean to
  * exercise is the one that ran): 0 separate forward / projection / reverse launches, 1 forward + projection-fused reverse,
