@@ -42,7 +42,7 @@ EXPORTS = [
     "hpv_set_flux_data", "hpv_read_flux_loss",
     "hpv_set_operator", "hpv_set_nonlinear",
     "hpv_create_ex", "hpv_set_trainable",
-    "hpv_set_strong_form", "hpv_linear_indicators",
+    "hpv_set_strong_form", "hpv_linear_indicators", "hpv_set_strong_form_div",
     "hpv_set_ansatz",
     "hpv_set_residual_norm", "hpv_set_residual_gram",
     "hpv_set_operator_tensor", "hpv_set_element_points",
@@ -218,6 +218,7 @@ def load():
     lib.hpv_element_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_set_strong_form.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_linear_indicators.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
+    lib.hpv_set_strong_form_div.argtypes = [h, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_size_t]
     lib.hpv_set_ansatz.argtypes = [h, C.c_int, _dp, C.c_size_t]
     lib.hpv_set_residual_norm.argtypes = [h, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
     lib.hpv_set_residual_gram.argtypes = [h, _dp, C.c_size_t]
@@ -367,6 +368,13 @@ class Handle:
         x nodes on the reference interval and, in 2-D, the (qy, qy) one of its y nodes.  Both None removes them."""
         Dx, Dy = _c(Dx), _c(Dy)
         self._chk(self.lib.hpv_set_strong_form(self._h, _p(Dx), 0 if Dx is None else Dx.size, _p(Dy), 0 if Dy is None else Dy.size))
+
+    def set_strong_form_div(self, Dx=None, Dy=None, inv_det=None):
+        """Opt a linear handle into its strong form in divergence form (hpv_set_strong_form_div): the matrices of `set_strong_form`
+        and, on unit (mapped) elements, 1 / det A at the owned quadrature points, element-major.  All None removes it."""
+        Dx, Dy, d = _c(Dx), _c(Dy), None if inv_det is None else _c(inv_det).reshape(-1)
+        self._chk(self.lib.hpv_set_strong_form_div(self._h, _p(Dx), 0 if Dx is None else Dx.size, _p(Dy), 0 if Dy is None else Dy.size,
+                                                   _p(d), 0 if d is None else d.size))
 
     def linear_indicators(self, f_quad=None, want_r=False):
         """(n_owned, 5) as `element_indicators`, for a linear handle after `set_strong_form` (hpv_linear_indicators).  want_r: also

@@ -225,6 +225,15 @@ int hpvd::check_ready(hpv_ctx* h) {
 
 // The dense Gram factors (hpv_set_residual_gram) belong to the elements, their counts and the test-function tables: whoever changes
 // one of those drops them, and a pass refuses until they are given again -- it must not silently train mean(R^2).
+// the divergence form's matrices and 1 / det A (hpv_set_strong_form_div) belong to the rule and the elements: new ones orphan them
+// (the caller has made sure no enqueued launch reads them: k_div_indicators runs only inside hpv_linear_indicators, which synchronises)
+static void drop_strong_form_div(hpv_ctx* h) {
+    if (!h->d_sfd) return;
+    (void)hipFree(h->d_sfd); h->d_sfd = nullptr;
+    if (h->d_inv_det) { (void)hipFree(h->d_inv_det); h->d_inv_det = nullptr; }
+    h->sfd_stale = true;
+}
+
 static int drop_gram(hpv_ctx* h) {
     if (!h->d_gram) return 0;
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read them)
@@ -380,7 +389,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_ind_r,
+    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_sfd, h->d_inv_det, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -418,6 +427,7 @@ int hpv_set_quadrature(hpv_handle h, const double* xi, const double* wx, int qx,
         if ((rc = upload(h, h->d_wq + qx, h->wy.data(), (size_t)qy))) return rc;
     }
     if (h->d_sf) { (void)hipFree(h->d_sf); h->d_sf = nullptr; }      // (hpv_set_strong_form: the matrices belong to the old rule)
+    drop_strong_form_div(h);                                         // (hpv_set_strong_form_div: as do these, and -3 says so)
     h->have_quad = true;
     drop_graph(h);
     h->have_tables = false;  // weighted tables depend on the weights
@@ -507,6 +517,7 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (int rcg = drop_gram(h)) return rcg;  // ... as do the Gram factors of hpv_set_residual_gram
         drop_ansatz(h, HPV_ANSATZ_QUAD);         // ... as do the ansatz planes
+        drop_strong_form_div(h);                 // ... and 1 / det A of the divergence form
         h->have_lin = false;
         h->unit_elems = points != nullptr;
         if (h->d_lin) { (void)hipFree(h->d_lin); h->d_lin = nullptr; }
@@ -1657,6 +1668,7 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
     if (has_ansatz(h)) return fail(h, -1, "the handle has an ansatz (hpv_set_ansatz): its strong residual needs second derivatives of G and D, which are not available");
     if (h->lin_tensor) return fail(h, -1, "the operator is a full tensor (hpv_set_operator_tensor): its strong form needs u_xy, which is not available");
     if (h->unit_elems) return fail(h, -1, "the elements are mapped (hpv_set_element_points): the strong form is not available on them");
+    if (h->d_sfd || h->sfd_stale) return fail(h, -1, "the divergence form is active (hpv_set_strong_form_div): remove it first, the two kinds exclude each other");
     if (!h->have_quad) return fail(h, -3, "call hpv_set_quadrature first");
     const size_t wx = (size_t)h->qx * h->qx, wy = h->dim == 2 ? (size_t)h->qy * h->qy : 0;
     if (!Dx || nx != wx) return fail(h, -1, "Dx has %zu entries, expected %d x %d of the current rule", nx, h->qx, h->qx);
@@ -1671,8 +1683,103 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
     int rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if ((rc = dalloc(h, &h->d_sf, wx + wy))) return rc;
+    h->ind_Nq = h->ind_N = h->ind_ne = -1;      // (the indicator buffers of the divergence kind hold no channel list)
     if ((rc = upload(h, h->d_sf, Dx, wx))) return rc;
     if (wy && (rc = upload(h, h->d_sf + wx, Dy, wy))) return rc;
+    return 0;
+}
+
+// The strong form in divergence form (include/hpvpinn.h): the same matrices and, on unit elements, 1 / det A at the owned points,
+// kept on the device for k_div_indicators alone.  No pass reads them, so the captured iteration graphs stay.
+int hpv_set_strong_form_div(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny, const double* inv_det, size_t n_det) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -1, "hpv_set_strong_form_div belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
+    if (!Dx && !Dy && !inv_det && nx == 0 && ny == 0 && n_det == 0) {
+        if (h->d_sfd) { HIPCHK(h, hipStreamSynchronize(h->stream)); drop_strong_form_div(h); }
+        h->sfd_stale = false;
+        return 0;
+    }
+    if (h->d_sf) return fail(h, -1, "the elementwise strong form is active (hpv_set_strong_form): remove it first, the two kinds exclude each other");
+    if (!h->have_quad) return fail(h, -3, "call hpv_set_quadrature first");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first (1 / det A belongs to the elements)");
+    const size_t wx = (size_t)h->qx * h->qx, wy = h->dim == 2 ? (size_t)h->qy * h->qy : 0;
+    if (!Dx || nx != wx) return fail(h, -1, "Dx has %zu entries, expected %d x %d of the current rule", nx, h->qx, h->qx);
+    if (h->dim == 1 ? (Dy || ny != 0) : (!Dy || ny != wy))
+        return fail(h, -1, "Dy has %zu entries, expected %zu (1-D: NULL and 0; 2-D: %d x %d of the current rule)", ny, wy, h->qy, h->qy);
+    const size_t nd = h->unit_elems ? (size_t)h->Nq : 0;
+    if (h->unit_elems ? (!inv_det || n_det != nd) : (inv_det || n_det != 0))
+        return fail(h, -1, "inv_det has %zu entries, expected %zu (boxes: NULL and 0; unit elements: 1 / det A at the n_owned * qx * qy points)", n_det, nd);
+    for (size_t i = 0; i < wx; ++i)
+        if (!std::isfinite(Dx[i])) return fail(h, -1, "Dx holds a non-finite value at entry %zu", i);
+    for (size_t i = 0; i < wy; ++i)
+        if (!std::isfinite(Dy[i])) return fail(h, -1, "Dy holds a non-finite value at entry %zu", i);
+    for (size_t i = 0; i < nd; ++i)
+        if (!std::isfinite(inv_det[i]) || !(inv_det[i] > 0.0)) return fail(h, -1, "inv_det is not finite and > 0 at point %zu", i);
+    const size_t lds = hpv_div_lds_bytes(h->dim, h->qx, h->qy);
+    if (lds > 64 * 1024) return fail(h, -1, "rule too large for the divergence-form indicator kernel's LDS (%zu B)", lds);
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = dalloc(h, &h->d_sfd, wx + wy))) return rc;
+    if ((rc = upload(h, h->d_sfd, Dx, wx))) return rc;
+    if (wy && (rc = upload(h, h->d_sfd + wx, Dy, wy))) return rc;
+    if ((rc = dalloc(h, &h->d_inv_det, nd))) return rc;
+    if (nd && (rc = upload(h, h->d_inv_det, inv_det, nd))) return rc;
+    h->sfd_stale = false;
+    h->ind_Nq = h->ind_N = h->ind_ne = -1;      // (the indicator buffers of the other kind hold the full channel list)
+    return 0;
+}
+
+// hpv_linear_indicators with the divergence form set; its sequence, on the handle's stream with one synchronisation:
+//   (1) enqueue_pass(backward = false): forward -> (k_ansatz_fwd) -> k_project_lin | _nl | _id, which stores R and loss_e of all owned
+//       elements and leaves u, u_x[, u_y] -- post-ansatz -- in the quadrature batch's OUT;
+//   (2) one k_div_indicators launch on exactly those channels: no further forward launch, and no nd_full object;
+//   (3) one copy of n_owned * HPV_IND_N doubles, and one of the strong residual where the caller asks.
+static int div_indicators(hpv_ctx* h, const double* f_quad, size_t n, double* out, size_t n_out, double* r_out, size_t n_r) {
+    if (!h->d_sfd) return fail(h, -3, "new elements or a new rule have orphaned the divergence form: hand the strong form over again (hpv_set_strong_form_div)");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    const long ne = h->n_elem, NQ = (long)h->qx * h->qy;
+    if (f_quad && n != (size_t)(ne * NQ)) return fail(h, -1, "f has %zu entries, expected %ld", n, ne * NQ);
+    if (n_out != (size_t)ne * HPV_IND_N || (ne > 0 && !out)) return fail(h, -1, "indicator buffer has %zu entries, expected %zu", n_out, (size_t)ne * HPV_IND_N);
+    if (r_out && n_r != (size_t)(ne * NQ)) return fail(h, -1, "residual buffer has %zu entries, expected %ld", n_r, ne * NQ);
+    if (ne == 0) return 0;
+    // d_ind_f and d_ind under hpv_element_indicators' key; the full-channel buffer and its object are not needed and not made (both
+    // hpv_set_strong_form* calls reset the key, so the elementwise kind never finds it without them)
+    if (h->ind_Nq != h->Nq || h->ind_N != h->var.N || h->ind_ne != ne) {
+        if (h->mfma_ind) { hpv_mfma_destroy(h->mfma_ind); h->mfma_ind = nullptr; }
+        h->ind_Nq = h->ind_N = h->ind_ne = -1;
+        if ((rc = dalloc(h, &h->d_ind_out, 0))) return rc;
+        if ((rc = dalloc(h, &h->d_ind_f, (size_t)(ne * NQ)))) return rc;
+        if ((rc = dalloc(h, &h->d_ind, (size_t)ne * HPV_IND_N))) return rc;
+        h->ind_Nq = h->Nq; h->ind_N = h->var.N; h->ind_ne = ne;
+    }
+    if (r_out && h->ind_r_n != h->Nq) {
+        h->ind_r_n = -1;
+        if ((rc = dalloc(h, &h->d_ind_r, (size_t)(ne * NQ)))) return rc;
+        h->ind_r_n = h->Nq;
+    }
+    if (f_quad) HIPCHK(h, hipMemcpyAsync(h->d_ind_f, f_quad, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = enqueue_pass(h, false))) return rc;
+    const int terms_mask = h->nl_mask | (h->n_coef ? h->dir_nl_mask : 0);      // (what pass_linear hands its projection kernel)
+    const size_t wx = (size_t)h->qx * h->qx;
+    LinIndArgs a{};
+    a.OUT = h->var.OUT; a.N = h->var.N; a.f = f_quad ? h->d_ind_f : nullptr;
+    a.coef = h->d_lin; a.cs = h->Nq;
+    a.nl = h->nl_mask ? h->d_nl : (h->n_coef ? h->d_nl_zero : nullptr); a.mask = terms_mask;
+    a.dirs = h->n_coef ? h->d_dirs : nullptr; a.c = h->d_theta + h->P + h->has_eps; a.n_coef = h->n_coef; a.dmask = h->d_dir_mask;
+    a.Dx = h->d_sfd; a.Dy = h->dim == 2 ? h->d_sfd + wx : nullptr;
+    a.wx = h->d_wq; a.wy = h->d_wq + h->qx;
+    a.J = h->d_jac; a.Jx = h->d_jxy; a.Jy = h->d_jxy + h->n_elem;
+    a.R = h->d_R; a.nact = h->pd.nact; a.nacty = h->pd.nacty;
+    a.out = h->d_ind; a.r_out = r_out ? h->d_ind_r : nullptr;
+    a.qx = h->qx; a.qy = h->qy; a.ntx = h->ntx; a.nty = h->nty; a.dim = h->dim;
+    a.loss_e = (h->d_dual || h->d_gram) ? h->d_loss_e : nullptr;
+    a.inv_det = h->d_inv_det; a.tensor = h->lin_tensor ? 1 : 0;
+    launch_div_indicators(a, ne, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->d_ind, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (r_out) HIPCHK(h, hipMemcpyAsync(r_out, h->d_ind_r, n_r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -1684,6 +1791,7 @@ int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double*
 int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* out, size_t n_out, double* r_out, size_t n_r) {
     if (!h) return -1;
     if (!h->linear) return fail(h, -1, "hpv_linear_indicators belongs to the linear problems (others: hpv_element_indicators)");
+    if (h->d_sfd || h->sfd_stale) return div_indicators(h, f_quad, n, out, n_out, r_out, n_r);
     if (h->lin_tensor) return fail(h, -1, "the operator is a full tensor (hpv_set_operator_tensor): its strong residual needs u_xy, which is not available");
     if (h->unit_elems) return fail(h, -1, "the elements are mapped (hpv_set_element_points): the strong residual is not available on them");
     if (!h->d_sf) return fail(h, -1, "the strong residual of a linear problem needs the rule's differentiation matrices: call hpv_set_strong_form");

@@ -163,6 +163,11 @@ struct hpv_ctx {
     // (nullptr: not set -- hpv_linear_indicators refuses); they go with the rule (hpv_set_quadrature), nothing a pass reads.
     // d_ind_r: the strong residual at the owned points for a caller who asks, sized by Nq (ind_r_n)
     double* d_sf = nullptr;
+    // the same in divergence form (hpv_set_strong_form_div; at most one of d_sf, d_sfd is set): the matrices, and on unit elements
+    // 1 / det A at the owned points [n_elem * qx * qy] (nullptr on boxes).  Both belong to the rule AND the elements: a new rule,
+    // new boxes or new points drop them and set sfd_stale, and hpv_linear_indicators answers -3 until they are handed over again
+    double *d_sfd = nullptr, *d_inv_det = nullptr;
+    bool sfd_stale = false;
     double* d_ind_r = nullptr;
     long ind_r_n = -1;
     // device-side validation (hpv_eval_points .. hpv_step_validate): forward-only batches at the caller's points

@@ -345,6 +345,11 @@ struct LinIndArgs {
     double* r_out;           // [n_elem * qx * qy] the strong residual at every point, or nullptr (not wanted)
     int qx, qy, ntx, nty, dim;
     const double* loss_e;    // [n_elem] the dual-norm loss the forward-only pass wrote (column 0 under hpv_set_residual_norm), or nullptr
+    // k_div_indicators only (hpv_set_strong_form_div): OUT is then [3 | 2][N] = u, u_x[, u_y] of the quadrature batch after the pass
+    const double* inv_det;   // [n_elem * qx * qy] 1 / det A at every point of the unit (mapped) elements, or nullptr (boxes: 1)
+    int tensor;              // coef holds seven planes (hpv_set_operator_tensor)
 };
 size_t hpv_linadapt_lds_bytes(int dim, int qx, int qy);
 void launch_lin_indicators(const LinIndArgs& a, long n_elem, hipStream_t s);
+size_t hpv_div_lds_bytes(int dim, int qx, int qy);
+void launch_div_indicators(const LinIndArgs& a, long n_elem, hipStream_t s);

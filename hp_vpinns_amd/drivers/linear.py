@@ -23,8 +23,13 @@ relative L2 error.
 --hard-bc (boundary layer, annulus): the Dirichlet conditions are built into the trial function, u = G + D N with D = (x - a)(b - x) and G the
 linear interpolant of the end values (VPINNLinear(hard_bc=...)): no boundary points, no penalty weight.
 
---adapt-every K: local hp-refinement (VPINNLinear(strong_form="elementwise").train_adaptive) after every K-th update, at most
---max-elements elements; one (iteration, elements, loss) row is printed per round.
+--adapt-every K: local hp-refinement (VPINNLinear(strong_form=...).train_adaptive) after every K-th update, at most
+--max-elements elements; one (iteration, elements, loss) row is printed per round.  boundary-layer and l-shape take the strong
+residual elementwise ("elementwise"); the annulus (mapped elements), anisotropic (a full tensor) and boundary-layer --hard-bc (an
+ansatz) take it in divergence form ("divergence"), which needs no second derivatives.
+
+    python -m hp_vpinns_amd.drivers.linear annulus --adapt-every 500 --max-elements 40
+    python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05 --hard-bc --adapt-every 500 --max-elements 16
 """
 import argparse
 
@@ -104,7 +109,8 @@ def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000
     bc = dict(hard_bc=interval_hard_bc(0.0, 1.0, 0.0, 0.0)) if hard_bc else dict(X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2))
     m = VPINNLinear(list(layers), grid_x=grid, n_quad=int(n_quad), n_test=int(n_test), kappa=-float(eps), beta=1.0, sigma=0.0, f=1.0,
                     lossb_weight=lossb_weight, activation="sin", LR=LR,
-                    seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None,
+                    seed=seed, backend=backend, device=device,
+                    strong_form=("divergence" if hard_bc else "elementwise") if adapt_every else None,      # (the ansatz has no second derivatives)
                     residual_norm=residual_norm, **bc)
     rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     X = np.linspace(0.0, 1.0, 401)[:, None]
@@ -213,17 +219,21 @@ def _annulus_boundary(n):
 
 
 def run_annulus(n_r=4, n_theta=4, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0,
-                seed=1234, backend="auto", device=None, verbose=True, hard_bc=False, record_every=None, residual_norm="l2"):
-    """record_every: also the error curve [(iteration, relative L2 error)], one row per that many updates"""
+                seed=1234, backend="auto", device=None, verbose=True, hard_bc=False, record_every=None, residual_norm="l2",
+                adapt_every=None, max_elements=None):
+    """record_every: also the error curve [(iteration, relative L2 error)], one row per that many updates (runs without adapt_every);
+    adapt_every: local hp-refinement of the polar elements from the strong residual in divergence form"""
     Xb = _annulus_boundary(int(n_bound))
     bc = dict(hard_bc=annulus_hard_bc()) if hard_bc else dict(X_u_train=Xb, u_train=np.zeros(Xb.shape[0]))
     m = VPINNLinear(list(layers), mesh=annulus_mesh(n_r, n_theta, n_test), n_quad=int(n_quad), kappa=1.0, f=_annulus_f, lossb_weight=lossb_weight,
-                    LR=LR, seed=seed, backend=backend, device=device, residual_norm=residual_norm, **bc)
+                    LR=LR, seed=seed, backend=backend, device=device, residual_norm=residual_norm,
+                    strong_form="divergence" if adapt_every else None, **bc)
     rr, tt = np.meshgrid(np.linspace(1.0, 2.0, 41), np.linspace(0.0, np.pi / 2, 41))
     X = np.stack([(rr * np.cos(tt)).reshape(-1), (rr * np.sin(tt)).reshape(-1)], 1)
     u = _annulus_exact(X)[:, None]
     curve, it = [], 0
-    while it < int(n_iter):
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose) if adapt_every else []
+    while not adapt_every and it < int(n_iter):
         n = min(int(record_every or n_iter), int(n_iter) - it)
         m.train(n, verbose=False)
         it += n
@@ -236,7 +246,7 @@ def run_annulus(n_r=4, n_theta=4, n_quad=10, n_test=5, n_iter=2000, layers=(2, 2
               % (len(m.mesh), m.mesh.area(), "exact conditions (ansatz)" if hard_bc else "penalty", err, m.h.kernel_variant()))
         if residual_norm != "l2":
             print(_loss_line(m, err))
-    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), curve=curve)
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), curve=curve, adapt_rows=rows)
 
 
 def rotated_tensor(angle_deg, ratio):
@@ -247,7 +257,8 @@ def rotated_tensor(angle_deg, ratio):
 
 
 def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3,
-                    lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, residual_norm="l2"):
+                    lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, residual_norm="l2", adapt_every=None,
+                    max_elements=None):
     K = rotated_tensor(angle, ratio)
 
     def f(P):
@@ -259,17 +270,18 @@ def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n
     g = np.linspace(-1.0, 1.0, int(n_elements) + 1)
     m = VPINNLinear(list(layers), grid_x=g, grid_y=g, n_quad=int(n_quad), n_test=int(n_test), kappa=K, f=f, X_u_train=Xb,
                     u_train=np.zeros(Xb.shape[0]), lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device,
-                    residual_norm=residual_norm)
-    m.train(int(n_iter), verbose=False)
+                    residual_norm=residual_norm, strong_form="divergence" if adapt_every else None)
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     gg = np.linspace(-1.0, 1.0, 81)
     X = np.stack([v.reshape(-1) for v in np.meshgrid(gg, gg)], 1)
     u = _l_exact(X)[:, None]
     err = m.rel_l2_error(X, u)
     if verbose:
-        print("rotated anisotropy, angle %g degrees, ratio %g, K = %s: relative L2 error %.4e (%s)" % (angle, ratio, K.round(4).tolist(), err, m.h.kernel_variant()))
+        print("rotated anisotropy, angle %g degrees, ratio %g, K = %s, %d elements: relative L2 error %.4e (%s)"
+              % (angle, ratio, K.round(4).tolist(), len(m.mesh), err, m.h.kernel_variant()))
         if residual_norm != "l2":
             print(_loss_line(m, err))
-    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+    return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
 def main(argv=None):
@@ -298,9 +310,11 @@ def main(argv=None):
         run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
                            adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn)
     elif a.problem == "annulus":
-        run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10), residual_norm=rn)
+        run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10), residual_norm=rn,
+                    adapt_every=a.adapt_every, max_elements=a.max_elements)
     elif a.problem == "anisotropic":
-        run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, residual_norm=rn)
+        run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, residual_norm=rn,
+                        adapt_every=a.adapt_every, max_elements=a.max_elements)
     else:
         run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn)
 

@@ -20,7 +20,8 @@ exact or manufactured solution and Dirichlet data from it; prints the relative L
 vanishes on t = 0 and x = +-1, and G = sin(pi x), the driver's own data there (VPINNNonlinear(hard_bc=...)): no data points, no weight.
 
 --adapt-every K (burgers, allen-cahn): local hp-refinement (VPINNNonlinear(strong_form="elementwise").train_adaptive) after every
-K-th update, at most --max-elements elements; one (iteration, elements, loss) row is printed per round.
+K-th update, at most --max-elements elements; one (iteration, elements, loss) row is printed per round.  Together with --hard-bc the
+strong residual is taken in divergence form (strong_form="divergence"): the ansatz has no second derivatives to offer.
 
 `setup(problem, ...)` builds everything a run needs on the host (no GPU); `run(s, ...)` creates the model from it and trains.
 """
@@ -121,12 +122,13 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
 def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None,
         max_elements=None, residual_norm="l2"):
     """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated); with
-    adapt_every the elements are refined locally (train_adaptive: the model is built with strong_form="elementwise").  The two
-    are not combined: giving both raises ValueError."""
+    adapt_every the elements are refined locally (train_adaptive: the model is built with strong_form="elementwise", or
+    "divergence" where the setup has an ansatz).  The two are not combined: giving both raises ValueError."""
     from ..vpinn import VPINNNonlinear
     if adapt_every and validate_every:
         raise ValueError("adapt_every and validate_every cannot be combined: run one or the other")
-    m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, strong_form="elementwise" if adapt_every else None,
+    kind = "divergence" if "hard_bc" in s["model"] else "elementwise"
+    m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, strong_form=kind if adapt_every else None,
                        residual_norm=residual_norm, **s["model"])
     his, rows = None, []
     if adapt_every:

@@ -1345,6 +1345,12 @@ class VPINNLinear(_VPINNBase):
     adapt_every, f=None, max_elements=None, **mark_kw)` -- the base class's, f None meaning the model's own f; `residual(X)` at arbitrary points stays refused.  ASSUMPTION: kappa is smooth
     inside each element.  A jump of kappa must lie on element edges; refinement bisects elements, so edges on dyadic positions of
     the first mesh stay edges.  The rule's nodes must be distinct (no zero-weight padding).
+    `strong_form="divergence"` (hpv_set_strong_form_div) gives the same five entry points from the residual in divergence form:
+    the fluxes kappa grad u at the element's own points -- which the projection forms anyway -- are interpolated on the tensor rule
+    and the interpolant's divergence is taken with the same differentiation matrices.  That needs no second derivative of the
+    network, of an element map or of the ansatz functions, so it also works on a `MappedMesh` (the Piola-transformed fluxes of
+    `_fold`, the result divided by det A: `_inv_det`), with a full tensor kappa, trainable or not, and under `hard_bc`.  ASSUMPTION:
+    the flux is smooth inside each element.
 
     Exact Dirichlet conditions (hpv_set_ansatz): `hard_bc=dict(g=.., d=..)` trains u = G + D N with N the network: `d` a callable
     of the points (n, dim) returning (n, 1 + dim) = the value and the gradient of a function that vanishes exactly where the
@@ -1355,7 +1361,7 @@ class VPINNLinear(_VPINNBase):
     set -- the mesh (`set_mesh`, sharding), the data, `set_flux_data`, `set_validation` -- and `set_hard_bc` changes or removes the
     ansatz of a live model.  `predict`, `rel_l2_error` and `evaluate` apply the map on the host to the raw network channels the
     library returns; under an ansatz `evaluate` returns `u, u_x[, u_y]` only (second derivatives would need those of G and D).
-    Not together with `strong_form="elementwise"`, for the same reason.
+    Not together with `strong_form="elementwise"`, for the same reason; `strong_form="divergence"` goes with it.
 
     The norm of the residual (hpv_set_residual_norm): `residual_norm="l2"` (the default) is the reference's mean over the test functions
     of R^2; `"dual"`, or `dict(kind="dual", mass=gamma)`, measures each element's residual functional in the dual norm of its discrete
@@ -1379,7 +1385,8 @@ class VPINNLinear(_VPINNBase):
     (sym(kappa) grad v, grad w) of the model's own kappa, always dense, re-handed by `set_operator(kappa=)`.  Refused with a reason:
     "energy" with a trainable kappa or a kappa that is not positive definite at a Gram point, a metric on "l2".  Out of scope, each a
     ValueError that says why: plain `residual_norm="dual"` with a MappedMesh (metric="physical" is the one that works there),
-    `strong_form="elementwise"` with a MappedMesh or a tensor kappa, and `adapt` / `train_adaptive` in those cases; also 1-D graded
+    `strong_form="elementwise"` with a MappedMesh or a tensor kappa, and `adapt` / `train_adaptive` in those cases unless
+    `strong_form="divergence"`; `residual(X)` at arbitrary points and `adapt` on several GPUs under either kind; also 1-D graded
     maps, solution-dependent tensors and triangles."""
 
     _n_extra = 0
@@ -1395,9 +1402,9 @@ class VPINNLinear(_VPINNBase):
         dim = int(layers[0])
         self._residual_norm = self._check_residual_norm(residual_norm)
         self._norm_metric = self._check_norm_metric(residual_norm)
-        if strong_form not in (None, "elementwise"):
-            raise ValueError('strong_form is None or "elementwise"')
-        if strong_form and hard_bc is not None:
+        if strong_form not in (None, "elementwise", "divergence"):
+            raise ValueError('strong_form is None, "elementwise" or "divergence"')
+        if strong_form == "elementwise" and hard_bc is not None:
             raise ValueError('hard_bc and strong_form="elementwise" do not go together: the strong residual of u = G + D N needs '
                              "second derivatives of G and D")
         self._strong_form = strong_form
@@ -1478,6 +1485,12 @@ class VPINNLinear(_VPINNBase):
             return mesh.geometry(xi, yi, eb, ee)
         return mesh.quad_points(xi, yi, eb, ee), None
 
+    def _inv_det(self, mesh, eb, ee):
+        """1 / det A at the quadrature points of the elements [eb, ee), element-major: what hpv_set_strong_form_div takes on mapped
+        elements to turn the residual of the folded planes into the physical one (None for boxes)"""
+        A = self._geometry(mesh, eb, ee)[1]
+        return None if A is None else 1.0 / (A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0])
+
     def _tensor_mode(self, mesh):
         """whether the handle takes a full diffusion tensor: a mapped mesh (the fold fills it), or a kappa -- the operator's or a
         direction's -- that is one"""
@@ -1523,14 +1536,16 @@ class VPINNLinear(_VPINNBase):
         if rn[2] == "energy" and any("kappa" in t for t in self._trainable):
             raise ValueError('metric="energy" with a trainable kappa: the Gram matrix of the energy inner product would move with '
                              "the unknown coefficient")
-        if mapped and self._strong_form:
+        if mapped and self._strong_form == "elementwise":
             raise ValueError('strong_form="elementwise" on a MappedMesh: the strong residual on mapped elements is not implemented')
-        if self._strong_form and self._tensor_mode(mesh):
+        if self._strong_form == "elementwise" and self._tensor_mode(mesh):
             raise ValueError('strong_form="elementwise" with a full tensor kappa: the strong form of div(K grad u) needs u_xy, '
                              "which is not available")
 
     def _no_adapt(self, what):
         mesh = self._mesh
+        if self._strong_form == "divergence":              # (the divergence form needs neither the maps' second derivatives nor u_xy)
+            return
         if isinstance(mesh, MappedMesh) or self._tensor_mode(mesh):
             raise ValueError(f"{what} needs the strong residual, which is not available on a MappedMesh or with a full tensor kappa "
                              "(it would need the maps' second derivatives / u_xy)")
@@ -1725,7 +1740,7 @@ class VPINNLinear(_VPINNBase):
         """Change the ansatz u = G + D N of the live model: the fields given replace the stored ones (a model without an ansatz needs
         both), they are checked as in the constructor and handed to the library for every point set it holds.  `set_hard_bc()` removes
         the ansatz: the model trains the raw network again.  Parameters and optimizer state stay."""
-        if self._strong_form:
+        if self._strong_form == "elementwise":
             raise ValueError('hard_bc and strong_form="elementwise" do not go together')
         if g is None and d is None:
             self._hard_bc = None
@@ -1807,7 +1822,12 @@ class VPINNLinear(_VPINNBase):
         super()._populate_mesh(mesh, f)
         if self._strong_form:                              # (set_quadrature dropped the matrices: they belong to the rule)
             xi, yi = self._dev_rule
-            self.h.set_strong_form(diff_matrix(xi), None if yi is None else diff_matrix(yi))
+            Dx, Dy = diff_matrix(xi), None if yi is None else diff_matrix(yi)
+            if self._strong_form == "divergence":          # (... and the new elements 1 / det A)
+                eb, ee = shard_range(len(mesh), self.rank, self.world)
+                self.h.set_strong_form_div(Dx, Dy, self._inv_det(mesh, eb, ee))
+            else:
+                self.h.set_strong_form(Dx, Dy)
         self._hand_operator(mesh)
         self._hand_trainable(mesh)
         self._hand_ansatz_quad(mesh)
@@ -1859,14 +1879,15 @@ class VPINNLinear(_VPINNBase):
         return None if ee == eb else self._f_at_quad(mesh, self._f if f is None else f, eb, ee)
 
     def element_indicators(self, f=None):
-        """With strong_form="elementwise": (n_owned, 5) refinement indicators as `_VPINNBase.element_indicators`, column 1 from the
+        """With strong_form="elementwise" | "divergence": (n_owned, 5) refinement indicators as `_VPINNBase.element_indicators`, column 1 from the
         strong residual at the elements' own quadrature points (hpv_linear_indicators).  f None: the model's own f."""
         if not self._strong_form:
             self._no_strong_form("element_indicators")
         return self.h.linear_indicators(self._owned_f_quad(f))
 
     def strong_residual_at_quad(self):
-        """With strong_form="elementwise": (n_owned, qy, qx), the strong residual at this rank's quadrature points."""
+        """With strong_form="elementwise" | "divergence": (n_owned, qy, qx), the strong residual at this rank's quadrature points
+        (on a MappedMesh the physical one)."""
         if not self._strong_form:
             self._no_strong_form("strong_residual_at_quad")
         xi, yi = self._dev_rule
@@ -1877,14 +1898,14 @@ class VPINNLinear(_VPINNBase):
         self._no_strong_form("residual")
 
     def adapt(self, f=None, **mark_kw):
-        """With strong_form="elementwise": `_VPINNBase.adapt`; f None (the usual call) is the model's own f.  Single GPU only."""
+        """With strong_form="elementwise" | "divergence": `_VPINNBase.adapt`; f None (the usual call) is the model's own f.  Single GPU only."""
         self._no_adapt("adapt")
         if not self._strong_form:
             self._no_strong_form("adapt")
         return super().adapt(f, **mark_kw)                 # (element_indicators and set_mesh of this class take f None as self._f)
 
     def train_adaptive(self, nIter, adapt_every, f=None, max_elements=None, **mark_kw):
-        """With strong_form="elementwise": `_VPINNBase.train_adaptive`; f None is the model's own f.  Single GPU only."""
+        """With strong_form="elementwise" | "divergence": `_VPINNBase.train_adaptive`; f None is the model's own f.  Single GPU only."""
         self._no_adapt("train_adaptive")
         if not self._strong_form:
             self._no_strong_form("train_adaptive")
@@ -1919,7 +1940,7 @@ class VPINNNonlinear(VPINNLinear):
     points with the operator and again in `set_mesh`.  A term that is zero everywhere is not evaluated on the device; with all four
     zero the model runs exactly what `VPINNLinear` runs.  Steady Bratu is kappa = 1, exponential = lambda; Allen-Cahn kappa = eps^2,
     sigma = 1, cubic = -1; space-time viscous Burgers (y = t) kappa = (-nu, 0), beta = (0, 1), advection = (1, 0).
-    Everything else is `VPINNLinear`'s: the strong form is refused by default, and `strong_form="elementwise"` opts into the
+    Everything else is `VPINNLinear`'s: the strong form is refused by default, and `strong_form="elementwise"` | `"divergence"` opts into the
     indicators and adaptivity with N in the strong residual (only the terms that are switched on are evaluated)."""
 
     _DIR_FIELDS = VPINNLinear._DIR_FIELDS + ("quadratic", "cubic", "exponential", "advection")

@@ -213,8 +213,9 @@ int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n);
  * diagonal kernels and their exact variant names.  On a tensor handle hpv_set_trainable takes [n_coef][7 + 5][n_owned*qx*qy] (the
  * seven planes above, then the nonlinear ones) and d lossv / d c_m gains D_kxy u_y Gbar_1 + D_kyx u_x Gbar_2; otherwise [5 + 5].
  * Switching between the two operator calls invalidates the directions: a pass answers -3 until they are set again.
- * Out of scope while the operator is a tensor: the strong form -- it would need u_xy -- so hpv_set_strong_form and
- * hpv_linear_indicators are refused (-1, the handle stays usable); 1-D handles; a solution-dependent tensor.
+ * Out of scope while the operator is a tensor: the ELEMENTWISE strong form -- it would need u_xy -- so hpv_set_strong_form is refused
+ * (-1, the handle stays usable), and hpv_linear_indicators unless the divergence form is set (hpv_set_strong_form_div, which needs
+ * no u_xy); 1-D handles; a solution-dependent tensor.
  * Returns 0; -1 for a handle of another problem, a wrong n, NULL, a non-finite value; -3 before hpv_set_elements; -2 on a HIP error. */
 int hpv_set_operator_tensor(hpv_handle h, const double* coef, size_t n);
 
@@ -231,8 +232,9 @@ int hpv_set_operator_tensor(hpv_handle h, const double* coef, size_t n);
  * The points are checked to be finite; the maps themselves never reach the library and are not checked.
  * Out of scope on such a handle: the TABLE dual norm -- the Gram matrix of the reference square is not the physical H^1 inner product --
  * so hpv_set_residual_norm(dual) is refused on it and this call is refused while that norm is set (the dense factors of
- * hpv_set_residual_gram carry the physical product: under them this call is accepted and drops the factors); the strong form:
- * hpv_set_strong_form is refused on it and this call is refused while the strong form is set; 1-D handles; triangles.
+ * hpv_set_residual_gram carry the physical product: under them this call is accepted and drops the factors); the ELEMENTWISE strong
+ * form: hpv_set_strong_form is refused on it and this call is refused while that form is set (the divergence form,
+ * hpv_set_strong_form_div, works on such a handle: this call then orphans its 1 / det A); 1-D handles; triangles.
  * Returns 0; -1 for another kind of handle, NULL, n_total < 1, a bad range, a non-finite point, the two refusals above; -3 before
  * hpv_set_quadrature / hpv_set_tables; -2 on a HIP error. */
 int hpv_set_element_points(hpv_handle h, const double* X, int n_total, int e_begin, int e_end);
@@ -466,6 +468,36 @@ int hpv_element_indicators(hpv_handle h, const double* f_quad_or_null, size_t n,
 int hpv_set_strong_form(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny);
 int hpv_linear_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, double* out, size_t n_out, double* r_out_or_null, size_t n_r);
 
+/* The strong residual of the linear problems in DIVERGENCE form: the second kind hpv_linear_indicators can run, and the one that works
+ * on every linear handle -- 1-D, diagonal, full tensor (hpv_set_operator_tensor), unit elements (hpv_set_element_points), with or
+ * without an ansatz (hpv_set_ansatz), a dual norm or trainable coefficients.  The projection kernels already form the flux planes
+ *     G1 = kxx u_x + kxy u_y      G2 = kyx u_x + kyy u_y      (diagonal: kx u_x, ky u_y; 1-D: k u')      G0 = bx u_x + by u_y + s u
+ * at every quadrature point from u, u_x, u_y alone; the divergence of their nodal interpolant on the element's tensor rule is
+ *     r_ref[j][i] = (1/Jx) sum_m Dx[i][m] G1[j][m] + (1/Jy) sum_m Dy[j][m] G2[m][i] + G0[j][i] + N[j][i] - f[j][i]
+ * with the planes as the handle holds them (after the caller's fold, base + sum_m c_m D_m with trainable coefficients), N as in
+ * hpv_set_nonlinear (only the terms that are switched on), Jx = Jy = 1 on unit elements, and u, u_x, u_y the values after the ansatz
+ * where there is one.  No second derivative of the network, of an element map, of G or of D is needed.  On unit elements the planes
+ * carry adj(A) and det A, so G1, G2 are the Piola-transformed fluxes and r_ref = det A * r: the physical residual is r = m r_ref with
+ * m = inv_det = 1 / det A per point (m = 1 on boxes).  Column 1 of hpv_linear_indicators is J_e sum_q w_x[i] w_y[j] m_q r_ref_q^2,
+ * the quadrature of int r^2 dx over the element; columns 0, 2, 3, 4 are what the elementwise kind writes (column 0 the dual-norm
+ * loss_e under hpv_set_residual_norm / _gram); r_out receives r.  Exact where every flux component is a polynomial of degree < q per
+ * direction on the element, spectrally accurate for smooth fluxes.
+ *
+ * Dx, nx, Dy, ny: as hpv_set_strong_form.  inv_det: NULL and 0 on a handle with boxes; on unit elements 1 / det A at the owned points,
+ * n_det = n_owned*qx*qy, element-major, finite and > 0.  All NULL / 0 removes the form.  Everything is copied.  The two kinds exclude
+ * each other: either call is refused (-1, with the reason) while the other kind is set.  Matrices and inv_det belong to the rule AND
+ * the elements: hpv_set_quadrature, hpv_set_elements, hpv_set_element_boxes and hpv_set_element_points drop them, and
+ * hpv_linear_indicators answers -3 ("hand the strong form over again") until this call is made again.  While this kind is set,
+ * hpv_set_element_points and hpv_set_ansatz are accepted.  Nothing a pass reads changes: captured iteration graphs stay.
+ * hpv_linear_indicators then runs the forward-only pass of hpv_eval_loss and ONE k_div_indicators launch (csrc/kernels_linadapt.hip)
+ * on the channels u, u_x[, u_y] that pass left in the quadrature batch -- no further forward launch --, one copy (two with r_out), one
+ * synchronisation; fixed summation order, no atomics: bitwise reproducible from call to call.
+ * Returns 0; -1 (the handle stays usable, what was given earlier stays) for a handle of another problem, the other kind being set,
+ * sizes that are not the current rule's / elements', a non-finite entry, an inv_det entry that is not > 0, inv_det on boxes or none on
+ * unit elements, a rule whose k_div_indicators workgroup would need more than 64 KiB of LDS (the formula of hpv_set_strong_form);
+ * -3 before hpv_set_quadrature / the elements; -2 on a HIP error. */
+int hpv_set_strong_form_div(hpv_handle h, const double* Dx, size_t nx, const double* Dy, size_t ny, const double* inv_det_or_null, size_t n_det);
+
 /* Exact Dirichlet (and initial) conditions by ansatz, for the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D, with or without
  * hpv_set_nonlinear / hpv_set_trainable).  The trial function is
  *     u(x) = G(x) + D(x) N(x; theta)
@@ -498,7 +530,8 @@ int hpv_linear_indicators(hpv_handle h, const double* f_quad_or_null, size_t n, 
  * (the Python classes do so on the host).
  * Returns 0; -1 (the handle stays usable, planes given earlier stay) for a handle of another problem, an unknown `which`, n that is
  * not the set's count, a non-finite value, and a handle on which hpv_set_strong_form is active -- the strong residual of u needs
- * second derivatives of G and D, which is out of scope; hpv_set_strong_form on a handle that has an ansatz is refused likewise; -3
+ * second derivatives of G and D, which is out of scope; hpv_set_strong_form on a handle that has an ansatz is refused likewise (the
+ * divergence form, hpv_set_strong_form_div, needs none of them and goes together with an ansatz); -3
  * for HPV_ANSATZ_QUAD before the elements are set; -2 on a HIP error.
  * Out of scope: the problems other than the linear ones and the strong-form scheme (whole-iteration kernels, second derivatives), the
  * strong-form indicators, ansatz functions with trainable parts, fusing the map into the projection kernels. */
