@@ -46,6 +46,7 @@ EXPORTS = [
     "hpv_set_ansatz",
     "hpv_set_residual_norm", "hpv_set_residual_gram",
     "hpv_set_operator_tensor", "hpv_set_element_points",
+    "hpv_set_quasilinear",
 ]
 NORM_L2, NORM_DUAL, NORM_DUAL_DENSE = 0, 1, 2      # kind of hpv_set_residual_norm; HPV_NORM_DUAL_DENSE is what hpv_set_residual_gram sets
 ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
@@ -148,6 +149,7 @@ def load():
     lib.hpv_set_operator.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_operator_tensor.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_nonlinear.argtypes = [h, _dp, C.c_size_t]
+    lib.hpv_set_quasilinear.argtypes = [h, _dp, C.c_size_t, C.c_double]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
     lib.hpv_num_params.restype = C.c_size_t
@@ -439,6 +441,12 @@ class Handle:
         in 1-D, 5 rows (a2, a3, ae, gx, gy) in 2-D, laid out like set_operator's.  None, or all zeros, removes the term."""
         coef = None if coef is None else _c(coef).reshape(-1)
         self._chk(self.lib.hpv_set_nonlinear(self._h, _p(coef), 0 if coef is None else coef.size))
+
+    def set_quasilinear(self, planes, exponent=0.0):
+        """The multiplier mu = (m0 + m1 u + m2 u^2) (delta + |grad u|^2)^exponent on the diffusive flux of a linear problem
+        (hpv_set_quasilinear): (4, n_owned * qx * qy), rows (m0, m1, m2, delta) laid out like set_operator's.  None removes the term."""
+        planes = None if planes is None else _c(planes).reshape(-1)
+        self._chk(self.lib.hpv_set_quasilinear(self._h, _p(planes), 0 if planes is None else planes.size, float(exponent)))
 
     def set_trainable(self, dirs):
         """The directions of the trainable coefficients (hpv_set_trainable): (n_coef, K + M, n_owned * qx * qy) -- per coefficient the

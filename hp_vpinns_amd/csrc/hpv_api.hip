@@ -214,6 +214,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (!h->have_elems) return fail(h, -3, "hpv_set_elements has not been called");
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
+    if (h->q_stale) return fail(h, -3, "hpv_set_quasilinear has not been called again");
     if (h->dual_stale) return fail(h, -3, "hpv_set_residual_norm has not been called again: hpv_set_tables dropped the tables of the dual norm");
     if (h->gram_stale) return fail(h, -3, "hpv_set_residual_gram has not been called again: new tables, elements or counts dropped the Gram factors of the dual norm");
     if (h->n_coef && !h->have_dirs) return fail(h, -3, "hpv_set_trainable has not been called");
@@ -389,7 +390,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_sfd, h->d_inv_det, h->d_ind_r,
+    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_qp, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_sfd, h->d_inv_det, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -524,6 +525,9 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         if (h->nl_mask) h->nl_stale = true;      // a pass must not silently train the linear problem
         h->nl_mask = 0;
         if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
+        if (h->q_mask) h->q_stale = true;        // ... nor the constant-diffusion one (hpv_set_quasilinear)
+        h->q_mask = 0;
+        if (h->d_qp) { (void)hipFree(h->d_qp); h->d_qp = nullptr; }
         h->have_dirs = false;                    // ... nor fixed coefficients
         h->dir_nl_mask = 0;
         for (double** p : {&h->d_dirs, &h->d_dcoef_e, &h->d_nl_zero})
@@ -845,6 +849,49 @@ int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n) {
     return 0;
 }
 
+// The multiplier mu = P(u) B(|grad u|^2) on the diffusive flux (include/hpvpinn.h); the _q instantiations of k_project_nl read the planes
+// in place.  The two mask bits are decided here, once; with both clear nothing is kept and the handle launches what it did before.
+int hpv_set_quasilinear(hpv_handle h, const double* planes, size_t n, double exponent) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -3, "hpv_set_quasilinear belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
+    if (h->n_coef) return fail(h, -3, "hpv_set_quasilinear on a handle with trainable coefficients: k_project_id does not carry the multiplier");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    const size_t Nq = (size_t)h->Nq;
+    if ((!planes && n != 0) || (planes && n != 4 * Nq))
+        return fail(h, -1, "the quasilinear term has %zu entries, expected 4 planes (m0, m1, m2, delta) of %ld (NULL and 0 remove it)", n, h->Nq);
+    if (!planes) n = 0;
+    static const char* const names[] = {"m0", "m1", "m2", "delta"};
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(planes[i])) return fail(h, -1, "quasilinear plane %s holds a non-finite value at point %zu", names[i / std::max(Nq, (size_t)1)], i % std::max(Nq, (size_t)1));
+    if (!std::isfinite(exponent)) return fail(h, -1, "the exponent of the quasilinear term is not finite");
+    int mask = 0;
+    if (n && exponent != 0.0) {
+        mask |= HPV_NL_DIFF_GRAD;
+        for (size_t i = 0; i < Nq; ++i)
+            if (!(planes[3 * Nq + i] > 0.0))
+                return fail(h, -1, "quasilinear plane delta = %g at point %zu; it must be > 0 where the exponent is not 0", planes[3 * Nq + i], i);
+    }
+    for (size_t i = 0; i < Nq && n; ++i)
+        if (planes[i] != 1.0 || planes[Nq + i] != 0.0 || planes[2 * Nq + i] != 0.0) { mask |= HPV_NL_DIFF_U; break; }
+    if (mask && hpv_nonlin_lds_bytes(h->qx, h->qy, h->ntx, h->nty) > 64 * 1024)
+        return fail(h, -1, "element too large for the nonlinear projection kernel's LDS (%zu B)", hpv_nonlin_lds_bytes(h->qx, h->qy, h->ntx, h->nty));
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old planes)
+    drop_graph(h);
+    h->q_mask = 0;
+    h->q_stale = false;
+    h->q_exp = 0.0;
+    if (!mask) {                                     // no multiplier: the handle launches what it launched before the first call
+        if (h->d_qp) { (void)hipFree(h->d_qp); h->d_qp = nullptr; }
+        return 0;
+    }
+    if ((rc = dalloc(h, &h->d_qp, n))) return rc;
+    if ((rc = upload(h, h->d_qp, planes, n))) return rc;
+    h->q_mask = mask;
+    h->q_exp = exponent;
+    return 0;
+}
+
 // The norm the residual is measured in (include/hpvpinn.h); the _dual instantiations of the projection kernels read the tables in place.
 int hpv_set_residual_norm(hpv_handle h, int kind, double mass, const double* Sx, const double* lamx, const double* Sy, const double* lamy) {
     if (!h) return -1;
@@ -948,6 +995,7 @@ int hpv_set_residual_gram(hpv_handle h, const double* W, size_t n) {
 // The directions of the trainable coefficients (include/hpvpinn.h); k_project_id reads them in place.  The masks are decided here, once.
 int hpv_set_trainable(hpv_handle h, const double* dirs, size_t n) {
     if (!h) return -1;
+    if (h->q_mask || h->q_stale) return fail(h, -3, "hpv_set_trainable on a handle with the quasilinear term (hpv_set_quasilinear): k_project_id does not carry the multiplier");
     if (!h->n_coef) return fail(h, -1, "the handle was created without trainable coefficients (hpv_create_ex)");
     if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
     const size_t K = h->lin_tensor ? 7 : h->dim == 1 ? 3 : 5, M = h->dim == 1 ? 4 : 5, Nq = (size_t)h->Nq, NP = K + M;
@@ -1765,7 +1813,8 @@ static int div_indicators(hpv_ctx* h, const double* f_quad, size_t n, double* ou
     LinIndArgs a{};
     a.OUT = h->var.OUT; a.N = h->var.N; a.f = f_quad ? h->d_ind_f : nullptr;
     a.coef = h->d_lin; a.cs = h->Nq;
-    a.nl = h->nl_mask ? h->d_nl : (h->n_coef ? h->d_nl_zero : nullptr); a.mask = terms_mask;
+    a.nl = h->nl_mask ? h->d_nl : (h->n_coef ? h->d_nl_zero : nullptr); a.mask = terms_mask | h->q_mask;
+    a.qp = h->q_mask ? h->d_qp : nullptr; a.qr = h->q_exp;      // (hpv_set_quasilinear: the QUASI instantiation)
     a.dirs = h->n_coef ? h->d_dirs : nullptr; a.c = h->d_theta + h->P + h->has_eps; a.n_coef = h->n_coef; a.dmask = h->d_dir_mask;
     a.Dx = h->d_sfd; a.Dy = h->dim == 2 ? h->d_sfd + wx : nullptr;
     a.wx = h->d_wq; a.wy = h->d_wq + h->qx;
@@ -1792,6 +1841,8 @@ int hpv_linear_indicators(hpv_handle h, const double* f_quad, size_t n, double* 
     if (!h) return -1;
     if (!h->linear) return fail(h, -1, "hpv_linear_indicators belongs to the linear problems (others: hpv_element_indicators)");
     if (h->d_sfd || h->sfd_stale) return div_indicators(h, f_quad, n, out, n_out, r_out, n_r);
+    if (h->q_mask || h->q_stale)
+        return fail(h, -3, "the quasilinear term is set (hpv_set_quasilinear): the elementwise strong residual would need the derivative of mu along the element; the divergence form (hpv_set_strong_form_div) carries it");
     if (h->lin_tensor) return fail(h, -1, "the operator is a full tensor (hpv_set_operator_tensor): its strong residual needs u_xy, which is not available");
     if (h->unit_elems) return fail(h, -1, "the elements are mapped (hpv_set_element_points): the strong residual is not available on them");
     if (!h->d_sf) return fail(h, -1, "the strong residual of a linear problem needs the rule's differentiation matrices: call hpv_set_strong_form");

@@ -125,6 +125,13 @@ struct hpv_ctx {
     double* d_nl = nullptr;
     int nl_mask = 0;
     bool nl_stale = false;
+    // the flux multiplier of such a handle (hpv_set_quasilinear): planes [4][Nq] = m0, m1, m2, delta, the exponent, the bits
+    // HPV_NL_DIFF_U | _DIFF_GRAD of the factors that are not identically 1 (0: no multiplier, the planes are freed; the launch ORs
+    // them into nl_mask, and either one selects k_project_nl's _q instantiations), and the same orphan rule as nl_stale
+    double* d_qp = nullptr;
+    double q_exp = 0.0;
+    int q_mask = 0;
+    bool q_stale = false;
     // the dual-norm loss of such a handle (hpv_set_residual_norm): the eigen tables of the test functions' Gram matrices (layout:
     // hpv_dual_norm.h; nullptr: mean(R^2)), the weight of the L2 part, and whether hpv_set_tables has dropped tables that have not
     // been given again (the tables belong to the test-function tables; a pass then refuses)

@@ -119,11 +119,16 @@ void launch_project_lin(const LinProjArgs& a, long n_elem, hipStream_t s);
 
 // The same launch with a pointwise nonlinear term (k_project_nl, kernels_nonlin.hip; hpv_set_nonlinear):
 //   L u + a2 u^2 + a3 u^3 + ae exp(u) + u (gx u_x + gy u_y) = f.   A term outside `mask` is not evaluated and its plane not read.
-enum { HPV_NL_QUADRATIC = 1, HPV_NL_CUBIC = 2, HPV_NL_EXP = 4, HPV_NL_ADVECTION = 8 };
+// Quasilinear diffusion (hpv_set_quasilinear): div(mu K grad u) with mu = P(u) B(|grad u|^2), P = m0 + m1 u + m2 u^2, B = (delta + s)^r;
+// the bits HPV_NL_DIFF_U / _DIFF_GRAD say which factor is not identically 1, and either one selects the _q instantiations.
+enum { HPV_NL_QUADRATIC = 1, HPV_NL_CUBIC = 2, HPV_NL_EXP = 4, HPV_NL_ADVECTION = 8, HPV_NL_DIFF_U = 16, HPV_NL_DIFF_GRAD = 32 };
 struct NlProjArgs {
     LinProjArgs lin;
-    const double* nl;        // planes (a2, a3, ae, g) in 1-D, (a2, a3, ae, gx, gy) in 2-D; layout and stride of lin.coef
+    const double* nl;        // planes (a2, a3, ae, g) in 1-D, (a2, a3, ae, gx, gy) in 2-D; layout and stride of lin.coef; may be nullptr
+                             // where the mask holds none of the four pointwise terms
     int mask;                // HPV_NL_* of the planes that are not zero everywhere (never 0: such a handle launches k_project_lin)
+    const double* qp;        // planes (m0, m1, m2, delta) of the multiplier, layout and stride of lin.coef; nullptr without a DIFF bit
+    double qr;               // the exponent r of B
 };
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty);
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s);
@@ -348,6 +353,8 @@ struct LinIndArgs {
     // k_div_indicators only (hpv_set_strong_form_div): OUT is then [3 | 2][N] = u, u_x[, u_y] of the quadrature batch after the pass
     const double* inv_det;   // [n_elem * qx * qy] 1 / det A at every point of the unit (mapped) elements, or nullptr (boxes: 1)
     int tensor;              // coef holds seven planes (hpv_set_operator_tensor)
+    const double* qp;        // planes (m0, m1, m2, delta) of the flux multiplier (hpv_set_quasilinear; NlProjArgs), stride cs, or nullptr:
+    double qr;               // then mask holds neither HPV_NL_DIFF_U nor _DIFF_GRAD.  qr: the exponent of B
 };
 size_t hpv_linadapt_lds_bytes(int dim, int qx, int qy);
 void launch_lin_indicators(const LinIndArgs& a, long n_elem, hipStream_t s);

@@ -270,7 +270,8 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     if (h->n_coef)                                                                                      // (hpv_set_trainable)
         launch_project_id(IdProjArgs{a, h->nl_mask ? h->d_nl : h->d_nl_zero, terms_mask, h->d_dirs, h->d_theta + h->P + h->has_eps, h->n_coef,
                                      h->d_dir_mask, h->d_dcoef_e}, h->n_elem, h->stream);
-    else if (h->nl_mask) launch_project_nl(NlProjArgs{a, h->d_nl, h->nl_mask}, h->n_elem, h->stream);      // (hpv_set_nonlinear)
+    else if (h->nl_mask | h->q_mask)                                                                    // (hpv_set_nonlinear | hpv_set_quasilinear)
+        launch_project_nl(NlProjArgs{a, h->nl_mask ? h->d_nl : nullptr, h->nl_mask | h->q_mask, h->q_mask ? h->d_qp : nullptr, h->q_exp}, h->n_elem, h->stream);
     else launch_project_lin(a, h->n_elem, h->stream);
     tstop(h, 1);
     if (!backward) return;
@@ -279,13 +280,14 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     static const char* const term_names[] = {"u2", "u3", "exp", "adv"};
     for (int t = 0; t < 4; ++t)
         if (terms_mask >> t & 1) terms += std::string(terms.empty() ? ";" : ",") + term_names[t];
+    if (h->q_mask) terms += ";quasi";                                // (hpv_set_quasilinear: the _q instantiation of k_project_nl)
     if (h->lin_tensor) terms += ";tensor";                           // (hpv_set_operator_tensor: the TENSOR instantiation of the kernel)
     if (h->n_coef) terms += ";nc=" + std::to_string(h->n_coef);      // e.g. k_project_id<6x5/4x3;u3;nc=2>, k_project_id<6x5/4x3;u3;tensor;nc=2>
     if (has_ansatz(h)) terms += ";ansatz";                           // (hpv_set_ansatz: k_ansatz_fwd / k_ansatz_adj around the projection)
     if (h->d_dual) terms += ";dual";                                 // (hpv_set_residual_norm: the _dual instantiation of the kernel)
     if (h->d_gram) terms += ";dual=dense";                           // (hpv_set_residual_gram: the _dense instantiation)
     snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
-             h->n_coef ? "id" : h->nl_mask ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
+             h->n_coef ? "id" : (h->nl_mask | h->q_mask) ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
     ansatz_adj(h, HPV_ANSATZ_QUAD, v, h->Nq);
     tstart(h, 2);
     if (use_mfma) hpv_mfma_backward(v.m, h->d_theta, v.X, v.GBAR, v.GPART, &v.rows, h->stream);

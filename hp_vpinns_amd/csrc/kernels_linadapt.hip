@@ -177,7 +177,10 @@ __global__ void __launch_bounds__(LIND_THREADS) k_lin_indicators(LinIndArgs a) {
     dst[4] = v[3];
 }
 
-template <int DIM, bool TENSOR>
+// QUASI (hpv_set_quasilinear): stage 1 multiplies both flux planes by mu = P(u) B(|grad u|^2) of project_nl_body (kernels_nonlin.hip) at
+// the point -- the channels are physical on mapped elements too, so nothing else changes; false is the kernel as it always was.  Only
+// this form carries the multiplier: k_lin_indicators would need the derivative of mu along the element.
+template <int DIM, bool TENSOR, bool QUASI = false>
 __global__ void __launch_bounds__(LIND_THREADS) k_div_indicators(LinIndArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int K = TENSOR ? 7 : DIM == 2 ? 5 : 3, M = DIM == 2 ? 5 : 4, NP = K + M;
@@ -212,17 +215,26 @@ __global__ void __launch_bounds__(LIND_THREADS) k_div_indicators(LinIndArgs a) {
         const int j = q / qx, i = q - j * qx;
         const long p = base + q;
         const double ux = OUT[N + p];
+        double mu = 1.0;
+        if constexpr (QUASI) {
+            const double u = OUT[p], uy = DIM == 2 ? OUT[2 * N + p] : 0.0;
+            const double* qp = a.qp + p;
+            double P = 1.0, B = 1.0;
+            if (mask & HPV_NL_DIFF_U) P = (qp[0] + qp[cs] * u) + qp[2 * cs] * (u * u);
+            if (mask & HPV_NL_DIFF_GRAD) B = pow(qp[3 * cs] + (ux * ux + uy * uy), a.qr);
+            mu = P * B;
+        }
         if constexpr (TENSOR) {
             const double uy = OUT[2 * N + p];
             const double kxx = eff_plane<NP>(a, dirs, 0, cf[q], q), kxy = eff_plane<NP>(a, dirs, 1, cf[cs + q], q);
             const double kyx = eff_plane<NP>(a, dirs, 2, cf[2 * cs + q], q), kyy = eff_plane<NP>(a, dirs, 3, cf[3 * cs + q], q);
-            G1[j * ks + i] = kxx * ux + kxy * uy;
-            G2[j * ks + i] = kyx * ux + kyy * uy;
+            G1[j * ks + i] = QUASI ? mu * (kxx * ux + kxy * uy) : kxx * ux + kxy * uy;
+            G2[j * ks + i] = QUASI ? mu * (kyx * ux + kyy * uy) : kyx * ux + kyy * uy;
         } else if (DIM == 2) {
-            G1[j * ks + i] = eff_plane<NP>(a, dirs, 0, cf[q], q) * ux;
-            G2[j * ks + i] = eff_plane<NP>(a, dirs, 1, cf[cs + q], q) * OUT[2 * N + p];
+            G1[j * ks + i] = QUASI ? mu * (eff_plane<NP>(a, dirs, 0, cf[q], q) * ux) : eff_plane<NP>(a, dirs, 0, cf[q], q) * ux;
+            G2[j * ks + i] = QUASI ? mu * (eff_plane<NP>(a, dirs, 1, cf[cs + q], q) * OUT[2 * N + p]) : eff_plane<NP>(a, dirs, 1, cf[cs + q], q) * OUT[2 * N + p];
         } else {
-            G1[i] = eff_plane<NP>(a, dirs, 0, cf[q], q) * ux;
+            G1[i] = QUASI ? mu * (eff_plane<NP>(a, dirs, 0, cf[q], q) * ux) : eff_plane<NP>(a, dirs, 0, cf[q], q) * ux;
         }
     }
     __syncthreads();
@@ -326,6 +338,12 @@ void launch_div_indicators(const LinIndArgs& a, long n_elem, hipStream_t s) {
     if (n_elem < 1) return;
     const size_t lds = hpv_div_lds_bytes(a.dim, a.qx, a.qy);
     const dim3 grid((unsigned)n_elem), block(LIND_THREADS);
+    if (a.mask & (HPV_NL_DIFF_U | HPV_NL_DIFF_GRAD)) {      // (hpv_set_quasilinear)
+        if (a.dim == 1) hipLaunchKernelGGL((k_div_indicators<1, false, true>), grid, block, lds, s, a);
+        else if (a.tensor) hipLaunchKernelGGL((k_div_indicators<2, true, true>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((k_div_indicators<2, false, true>), grid, block, lds, s, a);
+        return;
+    }
     if (a.dim == 1) hipLaunchKernelGGL((k_div_indicators<1, false>), grid, block, lds, s, a);
     else if (a.tensor) hipLaunchKernelGGL((k_div_indicators<2, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((k_div_indicators<2, false>), grid, block, lds, s, a);

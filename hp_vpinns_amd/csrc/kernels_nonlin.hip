@@ -16,9 +16,22 @@
 // Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
 // y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
 // eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
-// Out of scope: a solution-dependent diffusion coefficient kappa(u); the strong form at arbitrary points (trainable coefficients:
+// Quasilinear diffusion (hpv_set_quasilinear; the QUASI instantiations, k_project_nl*_q): the flux is scaled by a multiplier at the point,
+//     div(mu K grad u) + ..      mu = P(u) B(s)      P = m0 + m1 u + m2 u^2      B = (delta + s)^r      s = |grad u|^2 = u_x^2 [+ u_y^2]
+// with m0, m1, m2, delta given per quadrature point and r one scalar per handle.  With F1, F2 the flux values above (kx u_x, ky u_y;
+// kxx u_x + kxy u_y, kyx u_x + kyy u_y with a full tensor; k u' in 1-D) the integrands are G1 = mu F1, G2 = mu F2, and the chain rule
+// after the adjoint contractions gains, with h = F1 Gbar_1 + F2 Gbar_2, mu_u = (m1 + 2 m2 u) B and mu_s = r P (delta + s)^(r-1),
+//     GBAR[u]   += mu_u h       GBAR[u_x] = mu (kxx Gbar_1 + kyx Gbar_2) + .. + 2 u_x mu_s h       GBAR[u_y] likewise with u_y.
+// u_x, u_y are physical derivatives on mapped elements too (the fold puts the geometry into K_eff), so s is the physical |grad u|^2.
+// B costs one pow per point and phase, (delta + s)^(r-1) = B / (delta + s) one division; mu is recomputed in the adjoint phase from the
+// channels re-read from OUT, as exp(u) is.  HPV_NL_DIFF_U / HPV_NL_DIFF_GRAD select the factors: without DIFF_GRAD pow is never called
+// and delta never read, without DIFF_U m0, m1, m2 are never read.  P(u) > 0 is not checked; delta > 0 is the host's duty wherever
+// r != 0, at padding points as well (their mu is then finite, multiplied by 0 forward and by Gbar = 0 backward).
+// Out of scope: a diffusion coefficient outside that family (exp-type k(u)), solution-dependent anisotropy, trainable coefficients
+// together with the multiplier; the strong form at arbitrary points (trainable coefficients:
 // k_project_id, kernels_ident.hip; hpv_set_collocation*, hpv_residual_points and hpv_element_indicators stay refused as for the linear
-// class; the strong residual at the elements' own points, for refinement: hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
+// class; the strong residual at the elements' own points, for refinement: hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip;
+// with the multiplier only the divergence form, k_div_indicators).
 //
 // Term mask (HPV_NL_*): a plane that is zero at every owned point is left out of the mask on the host, and its term is not evaluated
 // at all -- the branch is uniform over the grid, an exp nobody asked for is never computed and 0 * inf cannot arise.  exp(u) is
@@ -73,11 +86,31 @@ __device__ __forceinline__ void nl_point(int mask, const double* nl, long cs, do
     dNu = d;
 }
 
+// mu = P(u) B(s) at one point and its partials mu_u, mu_s; qp the planes m0, m1, m2, delta at the point.  A factor outside the mask is 1
+// and its planes are not touched.
+__device__ __forceinline__ void quasi_point(int mask, const double* qp, long cs, double r, double u, double s, double& mu, double& mu_u, double& mu_s) {
+    double P = 1.0, dP = 0.0, B = 1.0, dB = 0.0;
+    if (mask & HPV_NL_DIFF_U) {
+        const double m0 = qp[0], m1 = qp[cs], m2 = qp[2 * cs];
+        P = (m0 + m1 * u) + m2 * (u * u);
+        dP = m1 + 2.0 * (m2 * u);
+    }
+    if (mask & HPV_NL_DIFF_GRAD) {
+        const double t = qp[3 * cs] + s;
+        B = pow(t, r);
+        dB = r * (B / t);
+    }
+    mu = P * B;
+    mu_u = dP * B;
+    mu_s = P * dB;
+}
+
 // DUAL: 1 the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm), 2 that of hpv_dual_dense.h
 // (hpv_set_residual_gram: a dense inverse Gram factor per element); 0 is the kernel as it always was
 // TENSOR: a full diffusion tensor per point (hpv_set_operator_tensor; 2-D only), as in project_lin_body: the operator has seven planes
 // (kxx, kxy, kyx, kyy, bx, by, s), G1 = kxx u_x + kxy u_y, G2 = kyx u_x + kyy u_y; the nonlinear planes and N are untouched
-template <int DUAL, bool TENSOR = false>
+// QUASI: the multiplier mu on the two flux integrands (hpv_set_quasilinear; the file header); false is the kernel as it always was
+template <int DUAL, bool TENSOR = false, bool QUASI = false>
 __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const LinProjArgs& a = b.lin;
@@ -95,8 +128,10 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
     const long base = e * NQ, N = a.N;
     const long cs = a.coef_stride;
     const double* cf = a.coef + base;
-    const double* nl = b.nl + base;            // planes a2, a3, ae, gx, (gy), the stride of the operator's
-    const int mask = b.mask;
+    const double* nl = QUASI && !b.nl ? nullptr : b.nl + base;      // planes a2, a3, ae, gx, (gy), the stride of the operator's (QUASI: none
+    const int mask = b.mask;                                        //  where the mask holds no pointwise term -- nl_point reads nothing then)
+    const double* qp = QUASI ? b.qp + base : nullptr;               // planes m0, m1, m2, delta, the same stride
+    const double qr = b.qr;
     const bool adv = mask & HPV_NL_ADVECTION;
 
     // ---- stage the tables and the three integrands ----
@@ -119,22 +154,42 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
             const double ga = adv ? nl[3 * cs + q] * ux + nl[4 * cs + q] * uy : 0.0;
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
             G[j * gs + i] = ((bx * ux + by * uy) + s * u) + Nv;
-            G[(qy + j) * gs + i] = kxx * ux + kxy * uy;
-            G[(2 * qy + j) * gs + i] = kyx * ux + kyy * uy;
+            double f1 = kxx * ux + kxy * uy, f2 = kyx * ux + kyy * uy;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux + uy * uy, mu, mu_u, mu_s);
+                f1 *= mu;
+                f2 *= mu;
+            }
+            G[(qy + j) * gs + i] = f1;
+            G[(2 * qy + j) * gs + i] = f2;
         } else if (a.dim == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = cf[q], ky = cf[cs + q], bx = cf[2 * cs + q], by = cf[3 * cs + q], s = cf[4 * cs + q];
             const double ga = adv ? nl[3 * cs + q] * ux + nl[4 * cs + q] * uy : 0.0;
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
             G[j * gs + i] = ((bx * ux + by * uy) + s * u) + Nv;
-            G[(qy + j) * gs + i] = kx * ux;
-            G[(2 * qy + j) * gs + i] = ky * uy;
+            double f1 = kx * ux, f2 = ky * uy;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux + uy * uy, mu, mu_u, mu_s);
+                f1 *= mu;
+                f2 *= mu;
+            }
+            G[(qy + j) * gs + i] = f1;
+            G[(2 * qy + j) * gs + i] = f2;
         } else {
             const double k = cf[q], bb = cf[cs + q], s = cf[2 * cs + q];
             const double ga = adv ? nl[3 * cs + q] * ux : 0.0;
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
             G[j * gs + i] = (bb * ux + s * u) + Nv;
-            G[(qy + j) * gs + i] = k * ux;
+            double f1 = k * ux;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux, mu, mu_u, mu_s);
+                f1 *= mu;
+            }
+            G[(qy + j) * gs + i] = f1;
         }
     }
     __syncthreads();
@@ -232,9 +287,18 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
                 by += gy * u;
             }
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
-            a.GBAR[base + q] = (s + dNu) * g0;
-            a.GBAR[N + base + q] = (kxx * g1 + kyx * g2) + bx * g0;
-            a.GBAR[2 * N + base + q] = (kxy * g1 + kyy * g2) + by * g0;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux + uy * uy, mu, mu_u, mu_s);
+                const double h = (kxx * ux + kxy * uy) * g1 + (kyx * ux + kyy * uy) * g2;
+                a.GBAR[base + q] = (s + dNu) * g0 + mu_u * h;
+                a.GBAR[N + base + q] = (mu * (kxx * g1 + kyx * g2) + bx * g0) + 2.0 * ux * (mu_s * h);
+                a.GBAR[2 * N + base + q] = (mu * (kxy * g1 + kyy * g2) + by * g0) + 2.0 * uy * (mu_s * h);
+            } else {
+                a.GBAR[base + q] = (s + dNu) * g0;
+                a.GBAR[N + base + q] = (kxx * g1 + kyx * g2) + bx * g0;
+                a.GBAR[2 * N + base + q] = (kxy * g1 + kyy * g2) + by * g0;
+            }
         } else if (a.dim == 2) {
             const double uy = a.OUT[2 * N + base + q];
             const double kx = cf[q], ky = cf[cs + q], s = cf[4 * cs + q];
@@ -246,9 +310,18 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
                 by += gy * u;
             }
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
-            a.GBAR[base + q] = (s + dNu) * g0;
-            a.GBAR[N + base + q] = kx * g1 + bx * g0;
-            a.GBAR[2 * N + base + q] = ky * g2 + by * g0;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux + uy * uy, mu, mu_u, mu_s);
+                const double h = (kx * ux) * g1 + (ky * uy) * g2;
+                a.GBAR[base + q] = (s + dNu) * g0 + mu_u * h;
+                a.GBAR[N + base + q] = (mu * (kx * g1) + bx * g0) + 2.0 * ux * (mu_s * h);
+                a.GBAR[2 * N + base + q] = (mu * (ky * g2) + by * g0) + 2.0 * uy * (mu_s * h);
+            } else {
+                a.GBAR[base + q] = (s + dNu) * g0;
+                a.GBAR[N + base + q] = kx * g1 + bx * g0;
+                a.GBAR[2 * N + base + q] = ky * g2 + by * g0;
+            }
         } else {
             const double k = cf[q], s = cf[2 * cs + q];
             double bb = cf[cs + q], ga = 0.0;
@@ -258,8 +331,16 @@ __device__ __forceinline__ void project_nl_body(const NlProjArgs& b) {
                 bb += g * u;
             }
             nl_point(mask, nl + q, cs, u, ga, Nv, dNu);
-            a.GBAR[base + q] = (s + dNu) * g0;
-            a.GBAR[N + base + q] = k * g1 + bb * g0;
+            if constexpr (QUASI) {
+                double mu, mu_u, mu_s;
+                quasi_point(mask, qp + q, cs, qr, u, ux * ux, mu, mu_u, mu_s);
+                const double h = (k * ux) * g1;
+                a.GBAR[base + q] = (s + dNu) * g0 + mu_u * h;
+                a.GBAR[N + base + q] = (mu * (k * g1) + bb * g0) + 2.0 * ux * (mu_s * h);
+            } else {
+                a.GBAR[base + q] = (s + dNu) * g0;
+                a.GBAR[N + base + q] = k * g1 + bb * g0;
+            }
         }
     }
 }
@@ -272,6 +353,13 @@ __global__ void __launch_bounds__(256) k_project_nl_tensor(NlProjArgs b) { proje
 __global__ void __launch_bounds__(256) k_project_nl_tensor_dual(NlProjArgs b) { project_nl_body<1, true>(b); }
 __global__ void __launch_bounds__(256) k_project_nl_dense(NlProjArgs b) { project_nl_body<2>(b); }
 __global__ void __launch_bounds__(256) k_project_nl_tensor_dense(NlProjArgs b) { project_nl_body<2, true>(b); }
+// (hpv_set_quasilinear: the same six with the multiplier on the flux)
+__global__ void __launch_bounds__(256) k_project_nl_q(NlProjArgs b) { project_nl_body<0, false, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_dual_q(NlProjArgs b) { project_nl_body<1, false, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_q(NlProjArgs b) { project_nl_body<0, true, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_dual_q(NlProjArgs b) { project_nl_body<1, true, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_dense_q(NlProjArgs b) { project_nl_body<2, false, true>(b); }
+__global__ void __launch_bounds__(256) k_project_nl_tensor_dense_q(NlProjArgs b) { project_nl_body<2, true, true>(b); }
 
 // (the channels are re-read from OUT in the adjoint phase, so nothing is added to k_project_lin's layout)
 size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop_lds_bytes(qx, qy, ntx, nty); }
@@ -279,16 +367,17 @@ size_t hpv_nonlin_lds_bytes(int qx, int qy, int ntx, int nty) { return hpv_linop
 void launch_project_nl(const NlProjArgs& a, long n_elem, hipStream_t s) {
     if (n_elem <= 0) return;
     const dim3 grid((unsigned)n_elem), block(256);
+    const bool quasi = a.mask & (HPV_NL_DIFF_U | HPV_NL_DIFF_GRAD);      // (hpv_set_quasilinear: the _q instantiations, the same LDS)
     if (a.lin.dual_dense) {      // (hpv_set_residual_gram)
         const size_t ldsd = hpv_dual_dense_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
-        if (a.lin.tensor) hipLaunchKernelGGL(k_project_nl_tensor_dense, grid, block, ldsd, s, a);
-        else hipLaunchKernelGGL(k_project_nl_dense, grid, block, ldsd, s, a);
+        if (a.lin.tensor) hipLaunchKernelGGL(quasi ? k_project_nl_tensor_dense_q : k_project_nl_tensor_dense, grid, block, ldsd, s, a);
+        else hipLaunchKernelGGL(quasi ? k_project_nl_dense_q : k_project_nl_dense, grid, block, ldsd, s, a);
         return;
     }
     const size_t lds = a.lin.dual ? hpv_dual_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty) : hpv_nonlin_lds_bytes(a.lin.qx, a.lin.qy, a.lin.ntx, a.lin.nty);
     if (a.lin.tensor) {      // (hpv_set_operator_tensor: 2-D only, the host has made sure)
-        if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_tensor_dual, grid, block, lds, s, a);
-        else hipLaunchKernelGGL(k_project_nl_tensor, grid, block, lds, s, a);
-    } else if (a.lin.dual) hipLaunchKernelGGL(k_project_nl_dual, grid, block, lds, s, a);
-    else hipLaunchKernelGGL(k_project_nl, grid, block, lds, s, a);
+        if (a.lin.dual) hipLaunchKernelGGL(quasi ? k_project_nl_tensor_dual_q : k_project_nl_tensor_dual, grid, block, lds, s, a);
+        else hipLaunchKernelGGL(quasi ? k_project_nl_tensor_q : k_project_nl_tensor, grid, block, lds, s, a);
+    } else if (a.lin.dual) hipLaunchKernelGGL(quasi ? k_project_nl_dual_q : k_project_nl_dual, grid, block, lds, s, a);
+    else hipLaunchKernelGGL(quasi ? k_project_nl_q : k_project_nl, grid, block, lds, s, a);
 }

@@ -1,5 +1,6 @@
-"""Three standard nonlinear problems on the variable-coefficient class with a pointwise nonlinear term (VPINNNonlinear), each with an
-exact or manufactured solution and Dirichlet data from it; prints the relative L2 error.
+"""Standard nonlinear problems on the variable-coefficient class (VPINNNonlinear): three with a pointwise nonlinear term, three with a
+solution-dependent diffusion coefficient; each with an exact or manufactured solution and Dirichlet data from it; prints the relative
+L2 error.
 
   bratu        u'' + lam exp(u) = 0 on [0, 1], u(0) = u(1) = 0; the lower branch in closed form,
                u = -2 ln(cosh((x - 1/2) th / 2) / cosh(th / 4)), th the lower root of th = sqrt(2 lam) cosh(th / 4)
@@ -8,8 +9,17 @@ exact or manufactured solution and Dirichlet data from it; prints the relative L
                advection = (1, 0); u = exp(-t) sin(pi x) manufactured, f from it; data on t = 0 and x = +-1.
   allen-cahn   eps^2 lap u + u - u^3 = 0 on [-1, 1]^2: kappa = eps^2, sigma = 1, cubic = -1; the exact diagonal front
                u = tanh((x + y) / (2 eps)) (the 1-D steady front tanh(s / (sqrt(2) eps)) along s = (x + y) / sqrt(2)), f = 0; data on all four sides.
+  heat-ku      div((1 + u^2) grad u) = f on [-1, 1]^2: diffusivity poly = (1, 0, 1); u = 0.8 sin(pi x / 2 + 0.3) cos(pi y / 2 - 0.2)
+               manufactured, f from it; data on all four sides.
+  p-laplace    div((eps^2 + |grad u|^2)^((p - 2) / 2) grad u) = f, the regularised p-Laplacian: diffusivity shift = eps^2,
+               power = (p - 2) / 2; the same manufactured u.
+  minimal-surface   div(grad u / sqrt(1 + |grad u|^2)) = 0 on [-1, 1]^2: diffusivity shift = 1, power = -1/2; Scherk's surface
+               u = log(cos x) - log(cos y), Dirichlet data from it, f = 0.
 
     python -m hp_vpinns_amd.drivers.nonlinear bratu --lam 1.0
+    python -m hp_vpinns_amd.drivers.nonlinear heat-ku
+    python -m hp_vpinns_amd.drivers.nonlinear p-laplace --p 3 --eps 0.1
+    python -m hp_vpinns_amd.drivers.nonlinear minimal-surface --adapt-every 500 --max-elements 64
     python -m hp_vpinns_amd.drivers.nonlinear burgers --nu 0.05
     python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.2
     python -m hp_vpinns_amd.drivers.nonlinear allen-cahn --eps 0.1 --adapt-every 500 --max-elements 64
@@ -19,9 +29,10 @@ exact or manufactured solution and Dirichlet data from it; prints the relative L
 --hard-bc (burgers): the initial and boundary conditions are built into the trial function, u = G + D N with D = (1 - x^2) t, which
 vanishes on t = 0 and x = +-1, and G = sin(pi x), the driver's own data there (VPINNNonlinear(hard_bc=...)): no data points, no weight.
 
---adapt-every K (burgers, allen-cahn): local hp-refinement (VPINNNonlinear(strong_form="elementwise").train_adaptive) after every
+--adapt-every K (burgers, allen-cahn and the quasilinear three): local hp-refinement (VPINNNonlinear(strong_form="elementwise").train_adaptive) after every
 K-th update, at most --max-elements elements; one (iteration, elements, loss) row is printed per round.  Together with --hard-bc the
-strong residual is taken in divergence form (strong_form="divergence"): the ansatz has no second derivatives to offer.
+strong residual is taken in divergence form (strong_form="divergence"): the ansatz has no second derivatives to offer.  The three
+quasilinear problems always take the divergence form: the elementwise one would need the derivative of mu along the element.
 
 `setup(problem, ...)` builds everything a run needs on the host (no GPU); `run(s, ...)` creates the model from it and trains.
 """
@@ -31,6 +42,9 @@ import numpy as np
 
 # the smallest setting of the Bratu run (tests/test_gpu_nonlinear.py trains it once)
 SMALLEST = dict(problem="bratu", lam=1.0, n_elements=3, n_quad=8, n_test=4, width=8, depth=2)
+# ... and of the minimal-surface run (tests/test_gpu_quasilinear.py)
+SMALLEST_QUASI = dict(problem="minimal-surface", n_elements=2, n_quad=6, n_test=3, width=8, depth=2, n_bound=12)
+QUASI = ("heat-ku", "p-laplace", "minimal-surface")
 
 
 def bratu_theta(lam):
@@ -62,6 +76,51 @@ def _allen_cahn_exact(P, eps):
     return np.tanh((P[:, 0] + P[:, 1]) / (2.0 * eps))
 
 
+def manufactured(P):
+    """u, grad u (n, 2), Hessian (n, 2, 2) of the manufactured solution of heat-ku and p-laplace"""
+    a, b = np.pi / 2 * P[:, 0] + 0.3, np.pi / 2 * P[:, 1] - 0.2
+    c, h = 0.8, np.pi / 2
+    u = c * np.sin(a) * np.cos(b)
+    du = np.stack([c * h * np.cos(a) * np.cos(b), -c * h * np.sin(a) * np.sin(b)], 1)
+    uxy = -c * h * h * np.cos(a) * np.sin(b)
+    H = np.stack([np.stack([-h * h * u, uxy], 1), np.stack([uxy, -h * h * u], 1)], 1)
+    return u, du, H
+
+
+def scherk(P):
+    """Scherk's surface u = log(cos x) - log(cos y), |x|, |y| < pi / 2, with its gradient and Hessian"""
+    x, y = P[:, 0], P[:, 1]
+    z = np.zeros_like(x)
+    return (np.log(np.cos(x)) - np.log(np.cos(y)), np.stack([-np.tan(x), np.tan(y)], 1),
+            np.stack([np.stack([-1.0 / np.cos(x) ** 2, z], 1), np.stack([z, 1.0 / np.cos(y) ** 2], 1)], 1))
+
+
+def quasi_mu(poly, shift, power, u, s):
+    """mu = (m0 + m1 u + m2 u^2) (shift + s)^power and its partials (mu, mu_u, mu_s) for constants poly, shift, power"""
+    m0, m1, m2 = poly
+    Pu, B = m0 + m1 * u + m2 * u * u, (shift + s) ** power
+    return Pu * B, (m1 + 2.0 * m2 * u) * B, power * Pu * (shift + s) ** (power - 1.0)
+
+
+def quasi_rhs(diffusivity, exact, P):
+    """f = div(mu grad u) of an exact solution: mu lap u + mu_u |grad u|^2 + 2 mu_s grad u^T H grad u"""
+    u, du, H = exact(P)
+    s = np.sum(du * du, axis=1)
+    mu, mu_u, mu_s = quasi_mu(diffusivity["poly"], diffusivity["shift"], diffusivity["power"], u, s)
+    return mu * (H[:, 0, 0] + H[:, 1, 1]) + mu_u * s + 2.0 * mu_s * np.einsum("na,nab,nb->n", du, H, du)
+
+
+def quasi_diffusivity(problem, p=3.0, eps=0.1):
+    """the diffusivity= of the three quasilinear problems, all keys filled in"""
+    if problem == "heat-ku":
+        return dict(poly=(1.0, 0.0, 1.0), shift=1.0, power=0.0)
+    if problem == "p-laplace":
+        if not (p > 1.0 and eps > 0.0):
+            raise ValueError("p-laplace needs p > 1 and eps > 0")
+        return dict(poly=(1.0, 0.0, 0.0), shift=float(eps) ** 2, power=(float(p) - 2.0) / 2.0)
+    return dict(poly=(1.0, 0.0, 0.0), shift=1.0, power=-0.5)
+
+
 def burgers_hard_bc():
     """dict(g=, d=) for VPINNNonlinear(hard_bc=...): D = (1 - x^2) t and G = sin(pi x), each with its gradient (d/dx, d/dt)"""
     def g(P):
@@ -75,10 +134,25 @@ def burgers_hard_bc():
 
 
 def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test=5, width=20, depth=3, n_bound=40, lossb_weight=10.0,
-          hard_bc=False):
-    """dict(layers, model = the keyword arguments of VPINNNonlinear, X_test, u_test) of one of the three problems; hard_bc (burgers):
+          hard_bc=False, p=3.0):
+    """dict(layers, model = the keyword arguments of VPINNNonlinear, X_test, u_test) of one of the problems; hard_bc (burgers):
     the conditions by ansatz instead of data points"""
     hidden = [int(width)] * int(depth)
+    if problem in QUASI:
+        if hard_bc:
+            raise ValueError("hard_bc is set up for burgers")
+        ne = 4 if n_elements is None else int(n_elements)
+        dif = quasi_diffusivity(problem, p, eps)
+        exact = scherk if problem == "minimal-surface" else manufactured
+        t = np.linspace(-1.0, 1.0, int(n_bound))
+        o = np.ones_like(t)
+        Xb = np.concatenate([np.stack([t, -o], 1), np.stack([t, o], 1), np.stack([-o, t], 1), np.stack([o, t], 1)])
+        g = np.stack([v.reshape(-1) for v in np.meshgrid(np.linspace(-1.0, 1.0, 81), np.linspace(-1.0, 1.0, 81))], 1)
+        f = 0.0 if problem == "minimal-surface" else (lambda P: quasi_rhs(dif, exact, P))
+        grid = np.linspace(-1.0, 1.0, ne + 1)
+        return dict(layers=[2] + hidden + [1], X_test=g, u_test=exact(g)[0][:, None], exact=exact,
+                    model=dict(grid_x=grid, grid_y=grid, n_quad=int(n_quad), n_test=int(n_test), lossb_weight=lossb_weight, kappa=1.0,
+                               diffusivity=dif, f=f, X_u_train=Xb, u_train=exact(Xb)[0]))
     if hard_bc and problem != "burgers":
         raise ValueError("hard_bc is set up for burgers")
     if problem == "bratu":
@@ -112,7 +186,7 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
         op = dict(kappa=eps ** 2, sigma=1.0, cubic=-1.0, f=0.0)
         g = np.stack([v.reshape(-1) for v in np.meshgrid(np.linspace(-1.0, 1.0, 81), np.linspace(-1.0, 1.0, 81))], 1)
     else:
-        raise ValueError("problem is one of bratu, burgers, allen-cahn")
+        raise ValueError("problem is one of bratu, burgers, allen-cahn, heat-ku, p-laplace, minimal-surface")
     bc = dict(hard_bc=burgers_hard_bc()) if hard_bc else dict(X_u_train=Xb, u_train=exact(Xb))
     return dict(layers=[2] + hidden + [1], X_test=g, u_test=exact(g)[:, None],
                 model=dict(grid_x=np.linspace(-1.0, 1.0, ne + 1), grid_y=gy, n_quad=int(n_quad), n_test=int(n_test),
@@ -127,7 +201,7 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
     from ..vpinn import VPINNNonlinear
     if adapt_every and validate_every:
         raise ValueError("adapt_every and validate_every cannot be combined: run one or the other")
-    kind = "divergence" if "hard_bc" in s["model"] else "elementwise"
+    kind = "divergence" if "hard_bc" in s["model"] or "diffusivity" in s["model"] else "elementwise"
     m = VPINNNonlinear(s["layers"], LR=LR, seed=seed, backend=backend, device=device, strong_form=kind if adapt_every else None,
                        residual_norm=residual_norm, **s["model"])
     his, rows = None, []
@@ -154,10 +228,11 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("problem", choices=["bratu", "burgers", "allen-cahn"])
+    ap.add_argument("problem", choices=["bratu", "burgers", "allen-cahn", "heat-ku", "p-laplace", "minimal-surface"])
     ap.add_argument("--lam", type=float, default=1.0)
     ap.add_argument("--nu", type=float, default=0.05)
-    ap.add_argument("--eps", type=float, default=0.2)
+    ap.add_argument("--eps", type=float, default=None, help="allen-cahn: the front width (default 0.2); p-laplace: the regularisation (default 0.1)")
+    ap.add_argument("--p", type=float, default=3.0, help="p-laplace: the exponent p > 1")
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--width", type=int, default=20)
     ap.add_argument("--validate-every", type=int, default=0)
@@ -167,7 +242,9 @@ def main(argv=None):
     ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
-    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width, hard_bc=a.hard_bc), n_iter=a.iters, validate_every=a.validate_every,
+    if a.eps is None:
+        a.eps = 0.1 if a.problem == "p-laplace" else 0.2
+    run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width, hard_bc=a.hard_bc, p=a.p), n_iter=a.iters, validate_every=a.validate_every,
         adapt_every=a.adapt_every, max_elements=a.max_elements,
         residual_norm="l2" if a.residual_norm == "l2" else dict(kind="dual", mass=a.gram_mass))
 

@@ -1941,13 +1941,70 @@ class VPINNNonlinear(VPINNLinear):
     zero the model runs exactly what `VPINNLinear` runs.  Steady Bratu is kappa = 1, exponential = lambda; Allen-Cahn kappa = eps^2,
     sigma = 1, cubic = -1; space-time viscous Burgers (y = t) kappa = (-nu, 0), beta = (0, 1), advection = (1, 0).
     Everything else is `VPINNLinear`'s: the strong form is refused by default, and `strong_form="elementwise"` | `"divergence"` opts into the
-    indicators and adaptivity with N in the strong residual (only the terms that are switched on are evaluated)."""
+    indicators and adaptivity with N in the strong residual (only the terms that are switched on are evaluated).
+
+    Quasilinear diffusion (hpv_set_quasilinear; the _q instantiations of k_project_nl): `diffusivity=dict(poly=(m0, m1, m2), shift=delta,
+    power=r)` turns the operator into
+
+        div(mu kappa grad u) + ..        mu = (m0 + m1 u + m2 u^2) (delta + |grad u|^2)^r
+
+    with m0, m1, m2, delta each a constant or a callable of the points returning (n,); the defaults are (1, 0, 0), 1.0 and 0.0, and a
+    factor that is identically 1 is not evaluated on the device.  k(u) = 1 + u^2 is poly=(1, 0, 1); the regularised p-Laplacian
+    shift=eps^2, power=(p - 2) / 2; the minimal-surface equation shift=1, power=-1/2.  |grad u|^2 is the physical one on a
+    MappedMesh too.  `set_nonlinear(diffusivity=...)` changes it on a live model.  `hard_bc` applies before mu (mu sees u = G + D N);
+    data and flux terms, validation, `predict`, checkpoints, graphs, sharding and `strong_form="divergence"` (indicators, `adapt`,
+    `train_adaptive`) work as without it.  `residual_norm` with metric="energy" keeps using kappa alone for its Gram matrices, never
+    mu kappa.  No check is made that the polynomial stays positive at the solution: a mu that changes sign makes the problem
+    ill-posed without any error.  Refused with a reason: `trainable=` together with `diffusivity`, `strong_form="elementwise"`
+    together with it, and power != 0 with a shift that is not positive at some quadrature point.  Out of scope: exp-type k(u) and
+    solution-dependent anisotropy (mu is a scalar on kappa)."""
 
     _DIR_FIELDS = VPINNLinear._DIR_FIELDS + ("quadratic", "cubic", "exponential", "advection")
 
-    def __init__(self, layers, *, quadratic=0.0, cubic=0.0, exponential=0.0, advection=0.0, **kw):
+    def __init__(self, layers, *, quadratic=0.0, cubic=0.0, exponential=0.0, advection=0.0, diffusivity=None, **kw):
         self._nl = dict(quadratic=quadratic, cubic=cubic, exponential=exponential, advection=advection)
+        self._diffusivity = self._check_diffusivity(diffusivity, kw.get("trainable"), kw.get("strong_form"))
         super().__init__(layers, **kw)
+
+    # -- quasilinear diffusion (hpv_set_quasilinear) ----------------------------------------------------------------------------------
+    @staticmethod
+    def _check_diffusivity(diffusivity, trainable, strong_form):
+        """dict(poly=(m0, m1, m2), shift=, power=) with the defaults filled in, or None; what does not go with it is refused here"""
+        if diffusivity is None:
+            return None
+        d = dict(diffusivity)
+        if set(d) - {"poly", "shift", "power"}:
+            raise ValueError("diffusivity is dict(poly=(m0, m1, m2), shift=delta, power=r): mu = (m0 + m1 u + m2 u^2) (delta + |grad u|^2)^r")
+        poly = tuple(d.get("poly", (1.0, 0.0, 0.0)))
+        power = float(d.get("power", 0.0))
+        if len(poly) != 3 or not np.isfinite(power):
+            raise ValueError("diffusivity: poly holds the three coefficients (m0, m1, m2), power is a finite number")
+        if trainable:
+            raise ValueError("diffusivity and trainable= do not go together: the identification kernel (k_project_id) does not carry "
+                             "the multiplier mu(u, |grad u|^2)")
+        if strong_form == "elementwise":
+            raise ValueError('diffusivity and strong_form="elementwise" do not go together: the elementwise strong residual would need '
+                             'the derivative of mu along the element; strong_form="divergence" carries it')
+        return dict(poly=poly, shift=d.get("shift", 1.0), power=power)
+
+    def _quasi_planes(self, mesh, eb, ee):
+        """(4, n): the rows (m0, m1, m2, delta) of hpv_set_quasilinear at the (physical) quadrature points of the elements [eb, ee) --
+        plain rows also on a MappedMesh: mu multiplies K_eff, which already carries the geometry, so nothing is times det A here"""
+        d, dim = self._diffusivity, mesh.dim
+        P = self._geometry(mesh, eb, ee)[0]
+        rows = [_coef_field(c, P, dim, "diffusivity poly[%d]" % i, False) for i, c in enumerate(d["poly"])]
+        rows.append(_coef_field(d["shift"], P, dim, "diffusivity shift", False))
+        if d["power"] != 0.0 and np.any(rows[3] <= 0.0):
+            i = int(np.argmin(rows[3]))
+            raise ValueError(f"diffusivity: power = {d['power']} needs shift > 0 at every point, but shift = {rows[3][i]} at {P[i]}")
+        return self._fold(None, False, None, rows)
+
+    def _hand_quasilinear(self, mesh):
+        """the multiplier at this rank's quadrature points, next to `_hand_nonlinear` (new elements orphan the planes of both)"""
+        if self._diffusivity is None:
+            return
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        self.h.set_quasilinear(self._quasi_planes(mesh, eb, ee), self._diffusivity["power"])
 
     def _hand_nonlinear(self, mesh):
         """the four terms at this rank's quadrature points as the planes hpv_set_nonlinear takes"""
@@ -1960,12 +2017,25 @@ class VPINNNonlinear(VPINNLinear):
     def _populate_mesh(self, mesh, f):
         super()._populate_mesh(mesh, f)
         self._hand_nonlinear(mesh)
+        self._hand_quasilinear(mesh)
 
-    def set_nonlinear(self, quadratic=None, cubic=None, exponential=None, advection=None):
+    def set_nonlinear(self, quadratic=None, cubic=None, exponential=None, advection=None, diffusivity=None):
         """Re-evaluate the nonlinear term on the live model: the coefficients given replace the stored ones (the others stay), all
-        are evaluated at the current mesh's quadrature points and handed to the library.  Parameters and optimizer state stay."""
+        are evaluated at the current mesh's quadrature points and handed to the library.  `diffusivity=dict(poly=, shift=, power=)`
+        replaces the multiplier as a whole (keys left out take their defaults, so `diffusivity={}` removes it).  Parameters and
+        optimizer state stay."""
+        if diffusivity is not None:
+            new = self._check_diffusivity(diffusivity, self._trainable, self._strong_form)
+            old, self._diffusivity = self._diffusivity, new
+            try:
+                eb, ee = shard_range(len(self._mesh), self.rank, self.world)
+                self._quasi_planes(self._mesh, eb, ee)
+            except ValueError:
+                self._diffusivity = old
+                raise
         for k, v in (("quadratic", quadratic), ("cubic", cubic), ("exponential", exponential), ("advection", advection)):
             if v is not None:
                 self._nl[k] = v
         self._hand_nonlinear(self._mesh)
+        self._hand_quasilinear(self._mesh)
         self._hand_trainable(self._mesh)

@@ -150,7 +150,7 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
  * Special cases: space-time viscous Burgers u_t + u u_x - nu u_xx = 0 is kx = -nu, ky = 0, by = 1, gx = 1 on a 2-D handle with
  * y = t (the AdvDiff special case with V replaced by u); Bratu u'' + lambda e^u = 0 is k = 1, ae = lambda; Allen-Cahn
  * eps^2 lap u + u - u^3 = f is k = eps^2, s = 1, a3 = -1.
- * Out of scope: a solution-dependent diffusion coefficient and the strong form (trainable coefficients: hpv_set_trainable; hpv_set_collocation*,
+ * Out of scope: the strong form (a solution-dependent diffusion coefficient: hpv_set_quasilinear; trainable coefficients: hpv_set_trainable; hpv_set_collocation*,
  * hpv_residual_points, hpv_element_indicators stay refused as for the linear class).  exp(u) is not guarded against overflow.
  *
  * coef is [M][n_owned*qx*qy] in planes, M = 4 in 1-D in the order (a2, a3, ae, g), M = 5 in 2-D in the order (a2, a3, ae, gx, gy),
@@ -165,6 +165,34 @@ int hpv_set_operator(hpv_handle h, const double* coef, size_t n);
  * Returns 0; -1 for a handle of another problem, a wrong n, a non-finite value, a shape beyond the kernel's LDS; -3 before
  * hpv_set_elements; -2 on a HIP error. */
 int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n);
+
+/* Quasilinear diffusion on a handle of the class above: the diffusive flux is scaled by a multiplier that depends on the solution,
+ *
+ *     div( mu(x; u, s) K grad u ) + b . grad u + s u + N(x; u, grad u) = f
+ *     s = |grad u|^2 = u_x^2 [+ u_y^2]       mu = P(u) B(s)       P = m0 + m1 u + m2 u^2       B = (delta + s)^r
+ *
+ * with K the scalar, diagonal or full tensor of hpv_set_operator / hpv_set_operator_tensor, m0, m1, m2, delta given per quadrature
+ * point and r one scalar per handle.  k(u) = 1 + u^2 is m = (1, 0, 1), r = 0; the regularised p-Laplacian m = (1, 0, 0),
+ * delta = eps^2, r = (p - 2) / 2; the minimal-surface equation delta = 1, r = -1/2.  On unit elements (hpv_set_element_points) u_x,
+ * u_y are the physical derivatives and the geometry sits in the folded tensor, so s is the physical |grad u|^2 and the planes are
+ * handed as they are, NOT times det A.  mu multiplies the two flux integrands of R; the gradient follows by the chain rule at the
+ * point (the _q instantiations of k_project_nl, csrc/kernels_nonlin.hip; the same LDS, no further launch).
+ *
+ * planes is [4][n_owned*qx*qy] in the order (m0, m1, m2, delta), the layout of hpv_set_operator; n = 4*n_owned*qx*qy.  The factor P is
+ * evaluated unless m0 == 1 and m1 == m2 == 0 at every owned point, the factor B iff exponent != 0 (then delta > 0 is required at
+ * every point, zero-weight padding points included; otherwise delta is not read).  NULL with n = 0, or planes and an exponent that
+ * leave both factors 1, remove the term: nothing is kept and the handle launches bit for bit what it launched before the call.
+ * No check is made that P(u) stays positive.
+ * Everything is copied.  Waits for the handle's stream and drops the captured iteration graphs, like hpv_set_nonlinear.
+ * hpv_set_elements / hpv_set_element_boxes / hpv_set_element_points invalidate the planes: a handle that HAD the term then answers -3
+ * from a pass ("hpv_set_quasilinear has not been called again") until the planes are set again or removed.  The planes are not state.
+ * hpv_kernel_variant carries ";quasi", e.g. k_project_nl<6x5/4x3;u3;quasi;tensor>.  The divergence-form strong residual
+ * (hpv_set_strong_form_div, hpv_linear_indicators) carries the multiplier; the elementwise one (hpv_set_strong_form) refuses with -3
+ * while the term is set, and hpv_residual_norm's energy metric is the caller's choice of Gram factors as before.
+ * Returns 0; -1 for a wrong n, a non-finite plane entry (named) or exponent, exponent != 0 with a delta <= 0 (named), a shape beyond the
+ * kernel's LDS; -3 for a handle of another problem, a handle with trainable coefficients (hpv_create_ex with n_coef > 0; and
+ * hpv_set_trainable refuses with -3 on a handle with the term), or before hpv_set_elements; -2 on a HIP error. */
+int hpv_set_quasilinear(hpv_handle h, const double* planes, size_t n, double exponent);
 
 /* Coefficient identification on a handle of the class above: n_coef trainable scalars c_0 .. c_{n_coef-1} follow the network
  * parameters in theta (1 <= n_coef <= HPV_MAX_COEF) and are trained with them.  Each scalar owns a DIRECTION D_m in the space of
