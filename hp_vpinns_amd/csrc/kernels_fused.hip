@@ -55,6 +55,8 @@
 #define FZ_STAMP(I) fz_t[I] = clock64()
 // segments of the reverse tile body, accumulated over the wave's tiles: [0] fetch + tangent recompute, [1] head,
 // [2 + 2 (L-1-i)] layer i: zbar + transposes + hbar chain, [3 + 2 (L-1-i)] layer i: dW products (layer 0: dW1)
+// (rev_tile's DWE text, L = 3 without SPLIT: [0] also carries the stores of every layer's input operands and most of the head's
+//  algebra, and the compiler issues most dW products in front of the stamp that closes [2] / [4] -- read [2] + [3] and [4] + [5] as pairs)
 #define FZ_SEG(I) do { const long long t_ = clock64(); fz_seg[I] += t_ - fz_last; fz_last = t_; } while (0)
 #else
 #define FZ_STAMP(I)
@@ -1061,6 +1063,20 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         // channel's inputs are zeros (its adjoints are not, but they only ever multiply those zeros).
         // tangent pre-activations along d: layer 0 has z_d = gb[1] W1[0,:] + gb[2] W1[1,:]; layer i: z_d = (sigma'(z_{i-1}) z_d,{i-1}) W_i
         // (recomputed from s on the matrix pipe: one product per layer)
+        //
+        // DWE (three hidden layers, one workgroup per element or more): the dW operands' LDS round trips are taken off the adjoint chain.
+        // Transpose tiles then (the per-wave region holds 2 TRG = 6 tiles; this text carries two channels): tiles 0, 1 = zbar of the value
+        // / tangent channel (TB: the only operands that follow the chain, one layer at a time), tiles 2 + 2 (i - 1) + ch = the inputs
+        // h_{i-1} = s and hdot_{i-1} = sigma'(z_{i-1}) z_d,{i-1} of layer i (TA).  The inputs of EVERY layer are known once the recompute
+        // below has formed them -- hd[] IS hdot_{i-1} -- so they are written there, once per tile, under the recompute products, and
+        // each layer reads them back before its zbar exists.  Every ordering of these tiles is "LDS serves a wave in order" plus a
+        // compiler-only fence (pj_wave_sync): reads of tile k before the stores of tile k + 1, stores before the reads that follow.
+        // Not DWE (L = 2: one layer to pay the stores back; SPLIT: the exchange sets the wall clock -- both measured level or slower,
+        // profiles/reverse_dw_latency.md): per layer, both channels' inputs and zbar into tiles 2 ch, 2 ch + 1 and back, as before.
+        constexpr bool DWE = L == 3 && !SPLIT;
+        constexpr int TRT = MF_TRB * MF_LD;
+        static_assert(!DWE || (2 + 2 * LH) * TRT <= M::TR_WAVE, "the inputs of every hidden layer and one layer's zbar fit the per-wave transpose region");
+        if constexpr (DWE) pj_wave_sync();      // (the previous tile's operand reads are issued; LDS serves a wave in order)
         double zd[L][MF_KS];
 #pragma unroll
         for (int s = 0; s < MF_KS; ++s)
@@ -1074,7 +1090,17 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                 hd[s] = (1.0 - a * a) * zd[i - 1][s];
             }
             fz_layer<false>(lds + M::WT + (i - 1) * MF_KS * 64, lds + M::WR + (i - 1) * MF_KS * 16, nullptr, lofs, hd, zd[i]);
+            if constexpr (DWE) {
+                // (behind the layer's own fragment reads: the stores land under its products)
+                double* TA = TAB + (2 + 2 * (i - 1)) * TRT;
+#pragma unroll
+                for (int s = 0; s < MF_KS; ++s) {
+                    TA[(4 * s + q) * MF_LD + pt] = sv[(i - 1) * MF_KS + s];
+                    TA[TRT + (4 * s + q) * MF_LD + pt] = hd[s];
+                }
+            }
         }
+        if constexpr (DWE) pj_wave_sync();      // (every layer's inputs are in their tiles)
 
         FZ_SEG(0);
         double hbar[2][MF_KS], zbar[2][MF_KS];      // [0] the value channel, [1] the tangent along d
@@ -1093,6 +1119,24 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
         // ---- hidden layers, last to first ----
 #pragma unroll
         for (int i = L - 1; i >= 0; --i) {
+            // What layer i's products read that does not follow the adjoint chain, requested before its zbar is formed: the fragments of
+            // W_i (the chain below waits for them alone) and BOTH channels' input operands of the dW products.
+            [[maybe_unused]] double wn[MF_KS], wr[MF_KS], aF[2][4], aS[2][4], aC[2];
+            if (DWE && i > 0) {
+                const double* wrl = lds + M::WRB + (i - 1) * MF_KS * 16 + q * 4 + (lane & 3);
+#pragma unroll
+                for (int s = 0; s < MF_KS; ++s) { wn[s] = lds[M::WN + ((i - 1) * MF_KS + s) * 64 + lofs]; wr[s] = wrl[s * 16]; }
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const double* TA = TAB + (2 + 2 * (i - 1) + ch) * TRT;
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        aF[ch][kk] = TA[pt * MF_LD + 4 * kk + q];
+                        aS[ch][kk] = TA[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
+                    }
+                    aC[ch] = TA[(16 + (lane & 3)) * MF_LD + (pt & 12) + q];
+                }
+            }
 #pragma unroll
             for (int s = 0; s < MF_KS; ++s) {
                 const double a = sv[i * MF_KS + s];
@@ -1108,6 +1152,56 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                     dW1[0][s] += x0 * zbar[0][s] + gb[1] * zbar[1][s];
                     dW1[1][s] += x1 * zbar[0][s] + gb[2] * zbar[1][s];
                 }
+            } else if constexpr (DWE) {
+                // weight gradient dW_i[in][out] = sum_pt sum_ch h_{i-1,ch}[pt][in] zbar_ch[pt][out]: the operands are needed
+                // point-major -> per-wave LDS transpose tiles.  The inputs' tiles were written behind the recompute; only zbar goes in here
+                // (LDS serves a wave in order: these writes land behind the previous layer's operand reads of the same tiles)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    double* TB = TAB + ch * TRT;
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) TB[(4 * s + q) * MF_LD + pt] = zbar[ch][s];
+                }
+                pj_wave_sync();
+                // both channels' zbar operands: one round trip per layer, paid under the chain instead of in front of the products
+                double bF[2][4], bS[2][4], bC[2];
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const double* TB = TAB + ch * TRT;
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        bF[ch][kk] = TB[pt * MF_LD + 4 * kk + q];
+                        bS[ch][kk] = TB[(16 + (lane & 3)) * MF_LD + 4 * kk + q];
+                    }
+                    bC[ch] = TB[(16 + (lane & 3)) * MF_LD + (pt & 12) + q];
+                }
+                pj_wave_sync();      // (keeps the requests in front of the chain: a compiler-only ordering, no wait)
+                // hbar_{i-1}^T = W_i zbar^T  (independent of the transposes: issued while the operand reads above are in flight)
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+                    double h4 = 0.0;
+#pragma unroll
+                    for (int s = 0; s < MF_KS; ++s) {
+                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wn[s], zbar[ch][s], acc, 0, 0, 0);
+                        h4 = __builtin_amdgcn_mfma_f64_4x4x4f64(wr[s], zbar[ch][s], h4, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) hbar[ch][s] = acc[s];
+                    hbar[ch][4] = h4;
+                }
+                FZ_SEG(2 + 2 * (L - 1 - i));
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        dWacc[i - 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aF[ch][kk], bF[ch][kk], dWacc[i - 1], 0, 0, 0);
+                        dS10[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(aS[ch][kk], bF[ch][kk], dS10[i - 1], 0, 0, 0);
+                        dS01[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(bS[ch][kk], aF[ch][kk], dS01[i - 1], 0, 0, 0);
+                    }
+                    accC[i - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(aC[ch], bC[ch], accC[i - 1], 0, 0, 0);
+                }
+                FZ_SEG(3 + 2 * (L - 1 - i));
             } else {
                 // weight gradient dW_i[in][out] = sum_pt sum_ch h_{i-1,ch}[pt][in] zbar_ch[pt][out]: the operands are needed
                 // point-major -> per-wave LDS transpose tiles, both channels written first (one wave-level sync)
@@ -1394,7 +1488,8 @@ __global__ void __launch_bounds__(FZ_BLOCK, 1) k_iter_fused(MfmaArgs g) {
                     dW1[1][s] = fma(c1, ZB[s], dW1[1][s]);
                 }
             } else {
-                pj_wave_sync();
+                pj_wave_sync();      // (also orders these stores behind the last whole tile's operand reads: its input tiles 2..5 may still be
+                                     //  in flight, tiles 0, 1 were its zbar's -- rev_tile's DWE plan)
                 double* TA = TAB;
                 double* TB = TA + MF_TRB * MF_LD;
 #pragma unroll
