@@ -47,9 +47,11 @@ EXPORTS = [
     "hpv_set_residual_norm", "hpv_set_residual_gram",
     "hpv_set_operator_tensor", "hpv_set_element_points",
     "hpv_set_quasilinear",
+    "hpv_set_moments", "hpv_read_moments",
 ]
 NORM_L2, NORM_DUAL, NORM_DUAL_DENSE = 0, 1, 2      # kind of hpv_set_residual_norm; HPV_NORM_DUAL_DENSE is what hpv_set_residual_gram sets
 ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
+MAX_MOMENTS = 8          # HPV_MAX_MOMENTS of include/hpvpinn.h: integral constraints of a linear handle
 MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
@@ -150,6 +152,8 @@ def load():
     lib.hpv_set_operator_tensor.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_nonlinear.argtypes = [h, _dp, C.c_size_t]
     lib.hpv_set_quasilinear.argtypes = [h, _dp, C.c_size_t, C.c_double]
+    lib.hpv_set_moments.argtypes = [h, C.c_int, C.POINTER(C.c_int), _dp, C.c_size_t, _dp, _dp]
+    lib.hpv_read_moments.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_set_collocation.argtypes = [h, _dp, _dp, C.c_int]
     lib.hpv_num_params.argtypes = [h]
     lib.hpv_num_params.restype = C.c_size_t
@@ -447,6 +451,25 @@ class Handle:
         (hpv_set_quasilinear): (4, n_owned * qx * qy), rows (m0, m1, m2, delta) laid out like set_operator's.  None removes the term."""
         planes = None if planes is None else _c(planes).reshape(-1)
         self._chk(self.lib.hpv_set_quasilinear(self._h, _p(planes), 0 if planes is None else planes.size, float(exponent)))
+
+    def set_moments(self, power, measure, target, weight):
+        """The integral constraints of a linear problem (hpv_set_moments): per term the power (1 or 2), the measure plane
+        (n_owned * qx * qy,) laid out like set_operator's, the target and the weight of w (I - c)^2.  power None removes the terms."""
+        if power is None:
+            self._chk(self.lib.hpv_set_moments(self._h, 0, None, None, 0, None, None))
+            return
+        power = np.ascontiguousarray(power, dtype=np.int32).reshape(-1)
+        K = power.size
+        measure, target, weight = _c(measure).reshape(-1), _c(target).reshape(-1), _c(weight).reshape(-1)
+        if target.size != K or weight.size != K:
+            raise ValueError("one target and one weight per term")
+        self._chk(self.lib.hpv_set_moments(self._h, K, power.ctypes.data_as(C.POINTER(C.c_int)), _p(measure), measure.size, _p(target), _p(weight)))
+
+    def read_moments(self, n_terms):
+        """(I_k, pen_k) of the most recent pass (hpv_read_moments), two arrays of n_terms."""
+        I, pen = np.zeros(max(int(n_terms), 1)), np.zeros(max(int(n_terms), 1))
+        self._chk(self.lib.hpv_read_moments(self._h, _p(I), _p(pen), int(n_terms)))
+        return I[:int(n_terms)], pen[:int(n_terms)]
 
     def set_trainable(self, dirs):
         """The directions of the trainable coefficients (hpv_set_trainable): (n_coef, K + M, n_owned * qx * qy) -- per coefficient the

@@ -13,7 +13,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $HPV_EXTRA_FLAGS"   # e.g. HPV_EXTRA_FLAGS=-DHPV_FZ_TIMING
-SRCS="kernels_mfma kernels_fused kernels_fused_gen kernels_project kernels_tile kernels_tall kernels_generic kernels_validate kernels_adapt kernels_linadapt kernels_linop kernels_nonlin kernels_ident kernels_ansatz hpv_api hpv_pass hpv_exchange hpv_bench"
+SRCS="kernels_mfma kernels_fused kernels_fused_gen kernels_project kernels_tile kernels_tall kernels_generic kernels_validate kernels_adapt kernels_linadapt kernels_linop kernels_nonlin kernels_ident kernels_moment kernels_ansatz hpv_api hpv_pass hpv_exchange hpv_bench"
 ELEM_SHAPES="20,20,10,10 16,16,8,8 12,12,6,6"             # kernels_elem.hip: one object per element shape (= HPV_ELEM_SHAPES of hpv_mfma_dev.h)
 WIDE_WIDTHS="64 32 48 24 40"                            # kernels_wide.hip: one object per hidden width and dimension (= HPV_WIDE_WIDTHS of hpv_mfma.h)
 # the sources whose text depends on HPV_TEST_HOOKS, their own or through HPV_XDEBUG_SKIP of hpv_mfma_dev.h (built twice)

@@ -27,6 +27,13 @@ int upload(hpv_ctx* h, double* dst, const double* src, size_t n) {
     return 0;
 }
 
+// the integral constraints of hpv_set_moments and their buffers
+void drop_moments(hpv_ctx* h) {
+    h->n_mom = 0;
+    for (double** p : {&h->d_mom, &h->d_mom_part, &h->d_mom_res, &h->d_mom_dcoef})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+}
+
 void drop_ansatz(hpv_ctx* h, int which) {
     if (h->ans_on[which]) h->batch_dirty = true;      // (whether the data points may ride in the quadrature batch is decided again)
     if (h->d_ans[which]) { (void)hipFree(h->d_ans[which]); h->d_ans[which] = nullptr; }
@@ -215,6 +222,7 @@ int hpvd::check_ready(hpv_ctx* h) {
     if (h->linear && !h->have_lin) return fail(h, -3, "hpv_set_operator has not been called");
     if (h->nl_stale) return fail(h, -3, "hpv_set_nonlinear has not been called again");
     if (h->q_stale) return fail(h, -3, "hpv_set_quasilinear has not been called again");
+    if (h->mom_stale) return fail(h, -3, "hpv_set_moments has not been called again: new elements dropped the measure planes of the integral constraints");
     if (h->dual_stale) return fail(h, -3, "hpv_set_residual_norm has not been called again: hpv_set_tables dropped the tables of the dual norm");
     if (h->gram_stale) return fail(h, -3, "hpv_set_residual_gram has not been called again: new tables, elements or counts dropped the Gram factors of the dual norm");
     if (h->n_coef && !h->have_dirs) return fail(h, -3, "hpv_set_trainable has not been called");
@@ -390,7 +398,7 @@ void hpv_destroy(hpv_handle h) {
     if (h->mfma_ind) hpv_mfma_destroy(h->mfma_ind);
     p2p_release(h);
     rccl_release(h);
-    void* ptrs[] = {h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_qp, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_sfd, h->d_inv_det, h->d_ind_r,
+    void* ptrs[] = {h->d_mom, h->d_mom_part, h->d_mom_res, h->d_mom_dcoef, h->d_dual, h->d_gram, h->d_dirs, h->d_dcoef_e, h->d_nl_zero, h->d_dir_mask, h->d_nl, h->d_qp, h->d_lin, h->d_jxy, h->d_flux_coef, h->d_flux_g, h->d_flux_part, h->d_eval_out, h->d_fcol, h->d_col_part, h->d_jac, h->d_wq, h->d_ind_out, h->d_sf, h->d_sfd, h->d_inv_det, h->d_ind_r,
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
@@ -528,6 +536,8 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
         if (h->q_mask) h->q_stale = true;        // ... nor the constant-diffusion one (hpv_set_quasilinear)
         h->q_mask = 0;
         if (h->d_qp) { (void)hipFree(h->d_qp); h->d_qp = nullptr; }
+        if (h->n_mom) h->mom_stale = true;       // ... nor without its integral constraints (hpv_set_moments)
+        drop_moments(h);
         h->have_dirs = false;                    // ... nor fixed coefficients
         h->dir_nl_mask = 0;
         for (double** p : {&h->d_dirs, &h->d_dcoef_e, &h->d_nl_zero})
@@ -587,14 +597,16 @@ static int set_elements_from_boxes(hpv_ctx* h, const double* boxes, int ne_tot, 
     const bool tall = h->pd.qx == 80 && h->pd.qy == 80 && h->pd.ntx == 5 && h->pd.nty == 5 && h->cfg.backend != HPV_BACKEND_GENERIC && ne <= 128;
     const size_t nred = (size_t)ne * std::max(h->proj_split, tall ? 64 : 1);
     h->n_red_alloc = (long)nred;
-    if ((rc = dalloc(h, &h->d_loss_e, nred))) return rc;
-    if ((rc = dalloc(h, &h->d_deps_e, nred))) return rc;
+    // (HPV_MAX_MOMENTS spare entries: the penalties of hpv_set_moments follow the element losses; deps_e's are zeroed with the rest)
+    if ((rc = dalloc(h, &h->d_loss_e, nred + HPV_MAX_MOMENTS))) return rc;
+    if ((rc = dalloc(h, &h->d_deps_e, nred + HPV_MAX_MOMENTS))) return rc;
     if ((rc = dalloc(h, &h->d_upart, h->proj_split > 1 ? (size_t)ne * h->proj_split * h->ntx * h->nty : 0))) return rc;
     h->Xq_host = X;
     h->batch_dirty = true;
     if (N > 0) {
         if ((rc = upload(h, h->d_coef, coef.data(), coef.size()))) return rc;
-        HIPCHK(h, hipMemsetAsync(h->d_deps_e, 0, nred * sizeof(double), h->stream));
+        const size_t nzero = nred + HPV_MAX_MOMENTS;      // (a name of its own: HIPCHK's message quotes the call)
+        HIPCHK(h, hipMemsetAsync(h->d_deps_e, 0, nzero * sizeof(double), h->stream));
     }
     if (h->pd.edge) {
         if ((rc = alloc_batch(h, h->edge, h->nd_val, 2 * ne, true))) return rc;
@@ -889,6 +901,60 @@ int hpv_set_quasilinear(hpv_handle h, const double* planes, size_t n, double exp
     if ((rc = upload(h, h->d_qp, planes, n))) return rc;
     h->q_mask = mask;
     h->q_exp = exponent;
+    return 0;
+}
+
+// Integral constraints (include/hpvpinn.h; kernels_moment.hip).  Everything is decided here; with n_terms == 0 nothing is kept and the
+// handle launches what it launched before.
+int hpv_set_moments(hpv_handle h, int n_terms, const int* power, const double* measure, size_t n, const double* target, const double* weight) {
+    if (!h) return -1;
+    if (!h->linear) return fail(h, -3, "hpv_set_moments belongs to the linear problems (HPV_PDE_LINEAR1D / _LINEAR2D)");
+    // (removing terms is harmless on any handle: only SETTING them is refused under an exchange)
+    if (n_terms > 0 && (h->rccl_on || h->p2p_on))
+        return fail(h, -3, "hpv_set_moments on a handle with an exchange connected: the moments are integrals over the whole domain and there is no collective before the adjoint");
+    if (!h->have_elems) return fail(h, -3, "call hpv_set_elements first");
+    if (n_terms < 0 || n_terms > HPV_MAX_MOMENTS) return fail(h, -1, "n_terms = %d not in 0..%d", n_terms, HPV_MAX_MOMENTS);
+    const size_t Nq = (size_t)h->Nq;
+    if (n_terms > 0 && (!power || !measure || !target || !weight)) return fail(h, -1, "hpv_set_moments: a NULL array with n_terms = %d", n_terms);
+    if (n != (size_t)n_terms * Nq) return fail(h, -1, "the measure has %zu entries, expected %d planes of %ld", n, n_terms, h->Nq);
+    for (int k = 0; k < n_terms; ++k) {
+        if (power[k] != 1 && power[k] != 2) return fail(h, -1, "term %d has power %d; 1 and 2 are supported", k, power[k]);
+        if (!std::isfinite(target[k])) return fail(h, -1, "term %d has a non-finite target", k);
+        if (!std::isfinite(weight[k])) return fail(h, -1, "term %d has a non-finite weight", k);
+        if (weight[k] < 0.0) return fail(h, -1, "term %d has the negative weight %g", k, weight[k]);
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(measure[i])) return fail(h, -1, "the measure of term %zu holds a non-finite value at point %zu", i / std::max(Nq, (size_t)1), i % std::max(Nq, (size_t)1));
+    if (n_terms == 0 && !h->n_mom && !h->mom_stale) return 0;      // nothing was set: nothing to wait for, no graph to drop
+    int rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (an enqueued pass may still read the old planes)
+    drop_graph(h);
+    drop_moments(h);
+    h->mom_stale = false;
+    if (n_terms == 0 || h->n_elem == 0) return 0;
+    if ((rc = dalloc(h, &h->d_mom, n))) return rc;
+    if ((rc = upload(h, h->d_mom, measure, n))) return rc;
+    if ((rc = dalloc(h, &h->d_mom_part, (size_t)n_terms * (size_t)h->n_elem))) return rc;
+    const size_t nres = (size_t)3 * HPV_MAX_MOMENTS;      // (a name of its own: HIPCHK's message quotes the call)
+    if ((rc = dalloc(h, &h->d_mom_res, nres))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->d_mom_res, 0, nres * sizeof(double), h->stream));
+    if (h->n_coef && (rc = dalloc(h, &h->d_mom_dcoef, (size_t)h->n_coef * ((size_t)h->n_elem + n_terms)))) return rc;
+    std::copy_n(power, n_terms, h->mom_power);
+    std::copy_n(target, n_terms, h->mom_target);
+    std::copy_n(weight, n_terms, h->mom_weight);
+    h->n_mom = n_terms;
+    return 0;
+}
+
+int hpv_read_moments(hpv_handle h, double* values, double* penalties, int n_terms) {
+    if (!h || !values || !penalties) return -1;
+    if (n_terms != h->n_mom) return fail(h, -1, "hpv_read_moments: n_terms = %d but the handle has %d terms", n_terms, h->n_mom);
+    if (n_terms == 0) return 0;
+    double res[3 * HPV_MAX_MOMENTS];
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(res, h->d_mom_res, sizeof res, hipMemcpyDeviceToHost));
+    std::copy_n(res, n_terms, values);
+    std::copy_n(res + HPV_MAX_MOMENTS, n_terms, penalties);
     return 0;
 }
 

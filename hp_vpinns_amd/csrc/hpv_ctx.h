@@ -132,6 +132,15 @@ struct hpv_ctx {
     double q_exp = 0.0;
     int q_mask = 0;
     bool q_stale = false;
+    // the integral constraints of such a handle (hpv_set_moments): n_mom terms (0: none, everything below is freed and the handle launches
+    // what it launched before), their powers, targets and weights, the measure planes [n_mom][Nq], the per-element partials
+    // [n_mom][n_elem], the results [3][HPV_MAX_MOMENTS] of the last pass (MomentArgs::res), with trainable coefficients the rows
+    // [n_coef][n_elem + n_mom] k_finalize reads in place of d_dcoef_e, and the same orphan rule as nl_stale
+    int n_mom = 0;
+    int mom_power[HPV_MAX_MOMENTS] = {};
+    double mom_target[HPV_MAX_MOMENTS] = {}, mom_weight[HPV_MAX_MOMENTS] = {};
+    double *d_mom = nullptr, *d_mom_part = nullptr, *d_mom_res = nullptr, *d_mom_dcoef = nullptr;
+    bool mom_stale = false;
     // the dual-norm loss of such a handle (hpv_set_residual_norm): the eigen tables of the test functions' Gram matrices (layout:
     // hpv_dual_norm.h; nullptr: mean(R^2)), the weight of the L2 part, and whether hpv_set_tables has dropped tables that have not
     // been given again (the tables belong to the test-function tables; a pass then refuses)
@@ -236,6 +245,7 @@ int check_ready(hpv_ctx* h);                 // everything of the variational sc
 int assemble_data_batch(hpv_ctx* h);
 // the ansatz of a point set (hpv_set_ansatz)
 inline bool has_ansatz(const hpv_ctx* h) { return h->ans_on[0] || h->ans_on[1] || h->ans_on[2] || h->ans_on[3]; }
+void drop_moments(hpv_ctx* h);               // the constraint terms and their buffers go (the caller has made sure no enqueued launch reads them)
 void drop_ansatz(hpv_ctx* h, int which);     // the planes of one set go (the caller has made sure no enqueued launch reads them)
 int ansatz_ready(hpv_ctx* h, int which);     // -3, naming the set, where a handle with an ansatz has points of that set and no planes for them
 void ansatz_fwd(hpv_ctx* h, int which, Batch& b, long n);      // k_ansatz_fwd on the first n points of b.OUT (no-op without planes)

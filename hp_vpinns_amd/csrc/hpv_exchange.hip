@@ -102,6 +102,7 @@ extern "C" {
 int hpv_p2p_export(hpv_handle h, int world, int rank, void* handles128) {
     if (!h || !handles128 || world < 1 || world > HPV_P2P_MAX || rank < 0 || rank >= world) return -1;
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");
+    if (h->n_mom || h->mom_stale) return fail(h, -3, "the handle has integral constraints (hpv_set_moments): %s", "the moments are integrals over the whole domain and there is no collective before the adjoint");
     p2p_release(h);
     drop_graph(h);
     const int n = h->Ptot + 4;
@@ -135,6 +136,7 @@ int hpv_p2p_export(hpv_handle h, int world, int rank, void* handles128) {
 
 int hpv_p2p_connect(hpv_handle h, const void* handles) {
     if (!h || !handles || !h->d_inbox) return -1;
+    if (h->n_mom || h->mom_stale) return fail(h, -3, "the handle has integral constraints (hpv_set_moments): %s", "the moments are integrals over the whole domain and there is no collective before the adjoint");
     const int W = h->pp.world, me = h->pp.rank;
     for (int r = 0; r < W; ++r) {
         if (r == me) { h->pp.inbox[r] = h->d_inbox; h->pp.flag[r] = h->d_flag; continue; }
@@ -201,6 +203,7 @@ int hpv_rccl_unique_id(hpv_handle h, void* id128) {
 
 int hpv_rccl_connect(hpv_handle h, int world, int rank, const void* id128) {
     if (!h || !id128 || world < 1 || rank < 0 || rank >= world) return -1;
+    if (h->n_mom || h->mom_stale) return fail(h, -3, "the handle has integral constraints (hpv_set_moments): %s", "the moments are integrals over the whole domain and there is no collective before the adjoint");
     if (h->rccl_abandoned.load()) return fail(h, -6, "this handle abandoned an RCCL call earlier (hpv_rccl_abandon)");
     if (!rccl_api().ok) return fail(h, -6, "librccl.so could not be loaded: %s", rccl_api().why.c_str());
     if (!h->have_params) return fail(h, -3, "hpv_set_params has not been called");

@@ -149,6 +149,26 @@ struct IdProjArgs {
 };
 void launch_project_id(const IdProjArgs& a, long n_elem, hipStream_t s);
 
+// Integral constraints (hpv_set_moments; kernels_moment.hip): K weighted moments I_k = sum_q m_k[q] u_q^p_k of the value channel and a
+// penalty w_k (I_k - c_k)^2 on each, between the projection kernel and the reverse launch of a linear handle's pass.
+struct MomentArgs {
+    const double* OUT;       // the quadrature batch's channels; the value channel's first Nq entries are read
+    double* GBAR;            // ... their adjoints; the same entries take the += (adjoint launches only)
+    const double* m;         // [K][Nq] measure planes, the layout of LinProjArgs::coef
+    long Nq, n_elem;
+    int NQ, K;               // points per element, active terms (1 .. HPV_MAX_MOMENTS)
+    int power[HPV_MAX_MOMENTS];
+    double target[HPV_MAX_MOMENTS], weight[HPV_MAX_MOMENTS];
+    double* part;            // [K][n_elem] per-element partial sums
+    double* res;             // [3][HPV_MAX_MOMENTS] I_k | pen_k | 2 w_k (I_k - c_k) of this pass
+    double* loss_e;          // pen_k -> loss_e[n_elem + k]
+    int n_coef;              // trainable coefficients: dcoef_src [n_coef][n_elem] is laid out again as dcoef_dst [n_coef][n_elem + K],
+    const double* dcoef_src; // zero tails, for k_finalize (whose rows are n_loss = n_elem + K long); dcoef_dst == nullptr: nothing to do
+    double* dcoef_dst;
+};
+// k_moment_part, k_moment_close and, where adjoint, k_moment_adj
+void launch_moments(const MomentArgs& a, bool adjoint, hipStream_t s);
+
 struct AdamArgs {
     double *theta, *m, *v, *state;   // theta == nullptr: no update
     double lr, b1, b2, eps;

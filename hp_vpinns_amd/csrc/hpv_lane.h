@@ -54,3 +54,13 @@ template <int SP>
 __device__ __forceinline__ double group_sum(double v) { return group_reduce<SP>(v, [](double x, double y) { return x + y; }); }
 // the 16 lanes of a DPP row (= the 16 points of a neuron group)
 __device__ __forceinline__ double row_sum16(double v) { return group_sum<16>(v); }
+// sum over the 256 threads of a workgroup, fixed order: butterfly inside each wave, the four wave sums added in wave order; every
+// thread gets it.  red: four doubles of LDS; the leading barrier lets a caller use it again at once
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[w] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}

@@ -131,7 +131,7 @@ static FinalizeArgs pass_finalize_args(hpv_ctx* h, bool backward, int n_data_par
     FinalizeArgs a{};
     a.g[1] = {backward && h->n_data > 0 && !h->merged ? h->data.GPART : nullptr, h->data.rows};
     a.data_part = h->d_data_part; a.n_data_part = n_data_part; a.lossb_weight = h->cfg.lossb_weight; a.n_data = h->n_data;
-    a.P = h->P; a.has_eps = h->has_eps; a.n_coef = h->n_coef; a.dcoef_e = h->d_dcoef_e; a.RB = h->d_RB; a.write_grad = backward ? 1 : 0;
+    a.P = h->P; a.has_eps = h->has_eps; a.n_coef = h->n_coef; a.dcoef_e = h->n_mom ? h->d_mom_dcoef : h->d_dcoef_e; a.RB = h->d_RB; a.write_grad = backward ? 1 : 0;
     if (backward && fuse_adam) a.adam = adam_args(h);
     a.fx = flux_fin(h, backward);
     return a;
@@ -274,6 +274,14 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
         launch_project_nl(NlProjArgs{a, h->nl_mask ? h->d_nl : nullptr, h->nl_mask | h->q_mask, h->q_mask ? h->d_qp : nullptr, h->q_exp}, h->n_elem, h->stream);
     else launch_project_lin(a, h->n_elem, h->stream);
     tstop(h, 1);
+    if (h->n_mom) {                                  // (hpv_set_moments; outside the timed classes, like the ansatz)
+        MomentArgs ma{v.OUT, v.GBAR, h->d_mom, h->Nq, h->n_elem, h->qx * h->qy, h->n_mom, {}, {}, {}, h->d_mom_part, h->d_mom_res, h->d_loss_e,
+                      h->n_coef, h->d_dcoef_e, backward && h->n_coef ? h->d_mom_dcoef : nullptr};
+        std::copy_n(h->mom_power, HPV_MAX_MOMENTS, ma.power);
+        std::copy_n(h->mom_target, HPV_MAX_MOMENTS, ma.target);
+        std::copy_n(h->mom_weight, HPV_MAX_MOMENTS, ma.weight);
+        launch_moments(ma, backward, h->stream);
+    }
     if (!backward) return;
     h->pass_structure = 0;
     std::string terms;                               // the active terms of k_project_nl, e.g. ";u2,u3,exp,adv"
@@ -286,6 +294,7 @@ static void pass_linear(hpv_ctx* h, const MfmaPass& p, bool backward, bool use_m
     if (has_ansatz(h)) terms += ";ansatz";                           // (hpv_set_ansatz: k_ansatz_fwd / k_ansatz_adj around the projection)
     if (h->d_dual) terms += ";dual";                                 // (hpv_set_residual_norm: the _dual instantiation of the kernel)
     if (h->d_gram) terms += ";dual=dense";                           // (hpv_set_residual_gram: the _dense instantiation)
+    if (h->n_mom) terms += ";mom=" + std::to_string(h->n_mom);       // (hpv_set_moments: k_moment_part, _close, _adj behind the kernel)
     snprintf(h->variant, sizeof h->variant, "%s + k_project_%s<%dx%d/%dx%d%s> + %s", use_mfma ? hpv_mfma_variant(v.m, 1) : "k_mlp_fwd_generic",
              h->n_coef ? "id" : (h->nl_mask | h->q_mask) ? "nl" : "lin", h->qx, h->qy, h->ntx, h->nty, terms.c_str(), use_mfma ? hpv_mfma_variant(v.m, 2) : "k_mlp_bwd_generic");
     ansatz_adj(h, HPV_ANSATZ_QUAD, v, h->Nq);
@@ -325,7 +334,7 @@ int enqueue_pass(hpv_ctx* h, bool backward, bool fuse_adam, bool pend) {
         const MfmaDataTerm dt = pass_data_term(h, backward);
         const ProjArgs pa = pass_proj_args(h, backward);
         const MfmaPass p = pass_mfma(h, dt, pa);
-        if (h->linear) pass_linear(h, p, backward, use_mfma);
+        if (h->linear) { pass_linear(h, p, backward, use_mfma); pl.n_loss += h->n_mom; }      // (hpv_set_moments: pen_k behind the element losses)
         else if (!(backward && use_mfma && pass_whole_iteration(h, p, fuse_adam, pend, pl))) pass_separate(h, p, backward, use_mfma);
     }
     // --- boundary / data term: inside the quadrature batch (one partial per 16-point data tile), or its own small batch ---

@@ -27,6 +27,7 @@
 // hpv_element_indicators are refused on these handles; the strong residual at the elements' own quadrature points, for refinement
 // indicators, is an opt-in with a kernel of its own (hpv_set_strong_form, k_lin_indicators, kernels_linadapt.hip).
 #include "hpv_internal.h"
+#include "hpv_lane.h"
 #include "hpv_dual_norm.h"
 #include "hpv_dual_dense.h"
 
@@ -35,14 +36,8 @@ namespace {
 __device__ __forceinline__ int odd(int n) { return n | 1; }
 
 // sum over the 256 threads, fixed order: butterfly inside each wave, the four wave sums added in wave order; every thread gets it
-__device__ __forceinline__ double lin_block_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+// (block_sum256 of hpv_lane.h, which k_moment_part shares)
+__device__ __forceinline__ double lin_block_sum(double v, double* red) { return block_sum256(v, red); }
 
 // DUAL: 1 the dual-norm loss of hpv_dual_norm.h between the two halves (hpv_set_residual_norm), 2 that of hpv_dual_dense.h
 // (hpv_set_residual_gram: a dense inverse Gram factor per element); 0 is the kernel as it always was

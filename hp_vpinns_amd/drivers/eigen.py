@@ -1,0 +1,115 @@
+"""Dirichlet eigenvalue problems of the Laplacian on VPINNLinear: lap u + lambda u = 0 with lambda a trainable scalar on sigma
+(trainable=[dict(name="lambda", sigma=1.0, ..)]), the conditions exact by ansatz (hard_bc), and the integral constraints of
+VPINNLinear(constraints=) doing what no local loss term can: the normalisation int u^2 = 1, without which the minimiser is u = 0, and
+the deflation integrals int u v_k = 0 against the modes already found, without which only one eigenpair can be reached.  Modes 1..n
+are trained one after the other; the densities v_k are the earlier models, evaluated at the quadrature points.
+
+  laplace-1d   u'' + lambda u = 0 on (0, 1):               lambda_k = k^2 pi^2
+  laplace-2d   lap u + lambda u = 0 on the unit square:    lambda = 2 pi^2, 5 pi^2, 5 pi^2, 8 pi^2, ..
+  annulus      the same on the quarter annulus 1 < r < 2, 0 < theta < pi / 2 (adapt.MappedMesh, polar map): u = g(r) sin(2 m theta),
+               lambda from the radial problem g'' + g' / r - (2 m)^2 g / r^2 + lambda g = 0, g(1) = g(2) = 0, solved here by finite
+               differences for the value printed beside the trained one
+
+    python -m hp_vpinns_amd.drivers.eigen laplace-1d --modes 3
+    python -m hp_vpinns_amd.drivers.eigen laplace-2d
+    python -m hp_vpinns_amd.drivers.eigen annulus
+
+Each run prints lambda beside the known value, int u^2 and the deflation integrals.  Nothing here guarantees convergence: the loss
+has a zero at every eigenpair the deflation does not exclude, and which one a run reaches depends on where lambda starts (`lambda0`)."""
+import argparse
+
+import numpy as np
+
+from ..vpinn import VPINNLinear
+from .linear import annulus_hard_bc, annulus_mesh
+
+
+def box_hard_bc(dim):
+    """dict(g=, d=): D = x (1 - x) [y (1 - y)] vanishes on the boundary of the unit interval / square, G = 0"""
+    def d(P):
+        x = P[:, 0]
+        a, da = x * (1.0 - x), 1.0 - 2.0 * x
+        if dim == 1:
+            return np.stack([a, da], 1)
+        y = P[:, 1]
+        b, db = y * (1.0 - y), 1.0 - 2.0 * y
+        return np.stack([a * b, da * b, a * db], 1)
+    return dict(g=0.0, d=d)
+
+
+def annulus_eigenvalues(n_modes, n=1500):
+    """the smallest eigenvalues of the quarter annulus: over the angular numbers nu = 2, 4, .. the radial problem on (1, 2) by second-order
+    finite differences with Richardson extrapolation"""
+    def radial(nu, n):
+        r = np.linspace(1.0, 2.0, n + 1)[1:-1]
+        h = 1.0 / n
+        A = (np.diag(2.0 / h ** 2 + nu ** 2 / r ** 2) + np.diag(-1.0 / h ** 2 - 1.0 / (2 * h * r[:-1]), 1) + np.diag(-1.0 / h ** 2 + 1.0 / (2 * h * r[1:]), -1))
+        return np.sort(np.linalg.eigvals(A).real)[:n_modes]
+    lam = np.concatenate([(4.0 * radial(nu, n) - radial(nu, n // 2)) / 3.0 for nu in range(2, 2 + 2 * n_modes, 2)])
+    return np.sort(lam)[:n_modes]
+
+
+def known(problem, n_modes):
+    if problem == "laplace-1d":
+        return np.array([(k * np.pi) ** 2 for k in range(1, n_modes + 1)])
+    if problem == "laplace-2d":
+        return np.sort([(i * i + j * j) * np.pi ** 2 for i in range(1, n_modes + 2) for j in range(1, n_modes + 2)])[:n_modes]
+    return annulus_eigenvalues(n_modes)
+
+
+def _model(problem, lambda0, constraints, layers, n_elements, n_quad, n_test, LR, seed, backend, device):
+    tr = [dict(name="lambda", init=float(lambda0), sigma=1.0)]
+    kw = dict(n_quad=int(n_quad), kappa=1.0, sigma=0.0, f=0.0, trainable=tr, constraints=constraints, LR=LR, seed=seed, backend=backend, device=device)
+    if problem == "annulus":
+        return VPINNLinear([2] + list(layers) + [1], mesh=annulus_mesh(n_elements, n_elements, n_test), hard_bc=annulus_hard_bc(), **kw)
+    g = np.linspace(0.0, 1.0, int(n_elements) + 1)
+    if problem == "laplace-2d":
+        return VPINNLinear([2] + list(layers) + [1], grid_x=g, grid_y=g, n_test=int(n_test), hard_bc=box_hard_bc(2), **kw)
+    return VPINNLinear([1] + list(layers) + [1], grid_x=g, n_test=int(n_test), hard_bc=box_hard_bc(1), activation="sin", **kw)
+
+
+def run(problem="laplace-1d", n_modes=3, n_iter=3000, layers=(20, 20), n_elements=None, n_quad=10, n_test=5, LR=2e-3, weight=100.0, lambda0=None,
+        seed=1234, backend="auto", device=None, verbose=True):
+    """modes 1..n_modes by deflation; returns a list of dict(model, lam, known, iterations, norm2, deflation) -- lam the trained
+    lambda, norm2 = int u^2 and deflation = [int u v_k] at the end.  lambda0: the start of lambda per mode (default: 5 for the first,
+    2.5 times the previous mode's lambda after it); weight: the penalty weight of every constraint."""
+    n_elements = n_elements or (4 if problem == "laplace-1d" else 2)
+    ref, out, prev = known(problem, n_modes), [], []
+    for k in range(n_modes):
+        cons = [dict(name="norm", kind="l2", target=1.0, weight=weight)]
+        for j, pm in enumerate(prev):
+            cons.append(dict(name="v%d" % (j + 1), kind="moment", power=1, target=0.0, weight=weight, density=lambda P, pm=pm: pm.predict(P).reshape(-1)))
+        l0 = (lambda0[k] if lambda0 is not None else (5.0 if k == 0 else 2.5 * out[-1]["lam"]))
+        m = _model(problem, l0, cons, layers, n_elements, n_quad, n_test, LR, seed + k, backend, device)
+        m.train(int(n_iter), verbose=False)
+        m.loss()
+        c, lam = m.constraints(), m.coefficients()["lambda"]
+        row = dict(model=m, lam=lam, known=float(ref[k]), iterations=int(n_iter), norm2=c["norm"][0], deflation=[c["v%d" % (j + 1)][0] for j in range(k)],
+                   lossv=float(np.asarray(m.loss())[2]))
+        out.append(row)
+        prev.append(m)
+        if verbose:
+            print("%s mode %d: %d iterations, lambda %.6f beside %.6f (relative error %.2e); int u^2 = %.6f; deflation integrals %s; lossv %.3e (%s)"
+                  % (problem, k + 1, n_iter, lam, ref[k], abs(lam - ref[k]) / ref[k], row["norm2"], ["%.2e" % v for v in row["deflation"]], row["lossv"],
+                     m.h.kernel_variant()))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("problem", choices=["laplace-1d", "laplace-2d", "annulus"])
+    ap.add_argument("--modes", type=int, default=None, help="modes 1..n by deflation (default: 3 in 1-D, 1 otherwise)")
+    ap.add_argument("--iters", type=int, default=3000)
+    ap.add_argument("--n-quad", type=int, default=10)
+    ap.add_argument("--n-test", type=int, default=5)
+    ap.add_argument("--weight", type=float, default=100.0, help="penalty weight of the normalisation and the deflation integrals")
+    ap.add_argument("--lambda0", type=float, nargs="*", default=None, help="where lambda starts, one value per mode")
+    a = ap.parse_args(argv)
+    n = a.modes or (3 if a.problem == "laplace-1d" else 1)
+    if a.lambda0 is not None and len(a.lambda0) != n:
+        ap.error("--lambda0 takes one value per mode")
+    run(a.problem, n_modes=n, n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, weight=a.weight, lambda0=a.lambda0)
+
+
+if __name__ == "__main__":
+    main()

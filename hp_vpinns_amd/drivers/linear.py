@@ -12,7 +12,12 @@ relative L2 error.
   anisotropic      div(K grad u) = f on [-1, 1]^2 with K = Q diag(1, --ratio) Q^T, Q the rotation by --angle degrees: a full tensor
                    (hpv_set_operator_tensor); u = sin(pi x) sin(pi y), f manufactured.
 
+  neumann          lap u = f on the unit square with du/dn = g on all four sides (set_flux_data) and no Dirichlet data: the solution is
+                   fixed only up to a constant, which the integral constraint int u = c (constraints=[dict(kind="mean", ..)]) picks;
+                   u = cos(pi x) cos(pi y) + 0.3 x^2 - 0.2 y + 0.5 (mean 0.5), f and g manufactured.  --no-mean leaves the constraint out.
+
     python -m hp_vpinns_amd.drivers.linear boundary-layer --eps 0.05
+    python -m hp_vpinns_amd.drivers.linear neumann
     python -m hp_vpinns_amd.drivers.linear l-shape
     python -m hp_vpinns_amd.drivers.linear annulus --hard-bc
     python -m hp_vpinns_amd.drivers.linear anisotropic --angle 30
@@ -284,16 +289,55 @@ def run_anisotropic(angle=30.0, ratio=0.05, n_elements=2, n_quad=10, n_test=5, n
     return dict(model=m, rel_l2=err, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his), adapt_rows=rows)
 
 
+def _neumann_exact(P):
+    x, y = P[:, 0], P[:, 1]
+    return np.cos(np.pi * x) * np.cos(np.pi * y) + 0.3 * x ** 2 - 0.2 * y + 0.5
+
+
+def _neumann_grad(P):
+    x, y = P[:, 0], P[:, 1]
+    return np.stack([-np.pi * np.sin(np.pi * x) * np.cos(np.pi * y) + 0.6 * x, -np.pi * np.cos(np.pi * x) * np.sin(np.pi * y) - 0.2], 1)
+
+
+def run_neumann(n_elements=2, n_quad=10, n_test=5, n_iter=2000, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, flux_weight=10.0, mean_weight=10.0,
+                with_mean=True, seed=1234, backend="auto", device=None, verbose=True):
+    """pure-Neumann Poisson: flux data on all sides and the mean of u (0.5 over the unit square) as an integral constraint; with_mean
+    False leaves the constant free, and the error shows it"""
+    t = np.linspace(0.0, 1.0, int(n_bound))
+    o, z = np.ones_like(t), np.zeros_like(t)
+    Xb = np.concatenate([np.stack([t, z], 1), np.stack([t, o], 1), np.stack([z, t], 1), np.stack([o, t], 1)])
+    nb = np.concatenate([np.tile([0.0, -1.0], (t.size, 1)), np.tile([0.0, 1.0], (t.size, 1)), np.tile([-1.0, 0.0], (t.size, 1)), np.tile([1.0, 0.0], (t.size, 1))])
+    g = np.linspace(0.0, 1.0, int(n_elements) + 1)
+    cons = [dict(name="mean", kind="mean", target=0.5, weight=float(mean_weight))] if with_mean else None
+    m = VPINNLinear(list(layers), grid_x=g, grid_y=g, n_quad=int(n_quad), n_test=int(n_test), kappa=1.0,
+                    f=lambda P: -2.0 * np.pi ** 2 * np.cos(np.pi * P[:, 0]) * np.cos(np.pi * P[:, 1]) + 0.6, constraints=cons,
+                    LR=LR, seed=seed, backend=backend, device=device)
+    m.set_flux_data(Xb, g=np.sum(_neumann_grad(Xb) * nb, axis=1), b=nb, weight=flux_weight)
+    m.train(int(n_iter), verbose=False)
+    gg = np.linspace(0.0, 1.0, 41)
+    X = np.stack([v.reshape(-1) for v in np.meshgrid(gg, gg)], 1)
+    u = _neumann_exact(X)[:, None]
+    err = m.rel_l2_error(X, u)
+    d = m.predict(X).reshape(-1) - u.reshape(-1)
+    err0 = float(np.linalg.norm(d - d.mean()) / np.linalg.norm(u))      # (the error once the best constant is taken out)
+    m.loss()
+    if verbose:
+        print("pure Neumann, %s: relative L2 error %.4e (%.4e up to a constant); constraints %s (%s)"
+              % ("int u = 0.5 imposed" if with_mean else "no mean constraint", err, err0, m.constraints(), m.h.kernel_variant()))
+    return dict(model=m, rel_l2=err, rel_l2_mod_const=err0, X_test=X, u_test=u, loss_his=np.asarray(m.loss_his))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("problem", choices=["boundary-layer", "l-shape", "annulus", "anisotropic"])
+    ap.add_argument("problem", choices=["boundary-layer", "l-shape", "annulus", "anisotropic", "neumann"])
+    ap.add_argument("--no-mean", action="store_true", help="neumann: leave the mean constraint out")
     ap.add_argument("--angle", type=float, default=30.0, help="anisotropic: rotation of the tensor's principal axes, degrees")
     ap.add_argument("--ratio", type=float, default=0.05, help="anisotropic: the smaller principal conductivity (the larger is 1)")
     ap.add_argument("--eps", type=float, default=0.05)
     ap.add_argument("--elements", type=int, default=8)
     ap.add_argument("--grade", type=float, default=2.0)
-    ap.add_argument("--n-quad", type=int, default=20)
-    ap.add_argument("--n-test", type=int, default=10)
+    ap.add_argument("--n-quad", type=int, default=None, help="quadrature points per direction (default: 20; neumann: 10)")
+    ap.add_argument("--n-test", type=int, default=None, help="test functions per direction (default: 10; neumann: 5)")
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None)
@@ -303,6 +347,8 @@ def main(argv=None):
                          "energy (l-shape, anisotropic, annulus): that norm in the energy inner product of the problem's own kappa")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
     a = ap.parse_args(argv)
+    dq, dt = (10, 5) if a.problem == "neumann" else (20, 10)
+    a.n_quad, a.n_test = a.n_quad or dq, a.n_test or dt
     if a.residual_norm == "energy" and a.problem == "boundary-layer":
         ap.error("--residual-norm energy belongs to l-shape, anisotropic and annulus")
     rn = _norm_arg(a.residual_norm, a.gram_mass, mapped=a.problem == "annulus")
@@ -312,6 +358,8 @@ def main(argv=None):
     elif a.problem == "annulus":
         run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10), residual_norm=rn,
                     adapt_every=a.adapt_every, max_elements=a.max_elements)
+    elif a.problem == "neumann":
+        run_neumann(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, with_mean=not a.no_mean)
     elif a.problem == "anisotropic":
         run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, residual_norm=rn,
                         adapt_every=a.adapt_every, max_elements=a.max_elements)

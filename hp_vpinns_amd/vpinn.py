@@ -1387,7 +1387,20 @@ class VPINNLinear(_VPINNBase):
     ValueError that says why: plain `residual_norm="dual"` with a MappedMesh (metric="physical" is the one that works there),
     `strong_form="elementwise"` with a MappedMesh or a tensor kappa, and `adapt` / `train_adaptive` in those cases unless
     `strong_form="divergence"`; `residual(X)` at arbitrary points and `adapt` on several GPUs under either kind; also 1-D graded
-    maps, solution-dependent tensors and triangles."""
+    maps, solution-dependent tensors and triangles.
+
+    Integral constraints (hpv_set_moments): `constraints=[dict(name=, kind="mean" | "l2" | "moment", density=None | callable | array,
+    power=, target=, weight=)]` adds, per entry, weight * (I - target)^2 with I = int density u^power over the domain (power 1 or 2; at
+    most 8 entries) -- "mean" is power 1, "l2" power 2, both with density 1, "moment" takes everything explicitly; a callable density is
+    evaluated at the (physical) quadrature points, an array holds its values there.  This is the normalisation int u^2 = 1 and the
+    deflation int u v_k = 0 of an eigenvalue problem (lambda a trainable scalar on sigma), the constant of a pure-Neumann problem, a
+    prescribed mass.  `set_constraints(list | None)` changes them on a live model, `constraints()` returns {name: (value, penalty)};
+    the penalties are part of the variational loss the model reports.  `set_mesh` / `adapt` re-evaluate callables and refuse an array
+    density (hand it over again on the new mesh); checkpoints store kinds, powers, targets, weights and the density values, and
+    `load_checkpoint` restores "mean" and "l2" entries as they were and every "moment" entry -- a callable density too -- with the ARRAY
+    of its values on the checkpoint's mesh, so such an entry must be handed over again before the mesh changes.  One GPU only:
+    the moments are integrals over the whole domain and there is no collective before the adjoint.  Out of scope: powers above 2,
+    moments of grad u, inequality constraints, multiplier updates."""
 
     _n_extra = 0
     _val_default = ("X_test", "utest")
@@ -1398,8 +1411,10 @@ class VPINNLinear(_VPINNBase):
     def __init__(self, layers, *, grid_x=None, grid_y=None, mesh=None, n_quad=10, rule=None, n_test=5, kappa=1.0, beta=0.0,
                  sigma=0.0, f=0.0, X_u_train=None, u_train=None, lossb_weight=1.0, activation="tanh", LR=0.001,
                  init_params=None, seed=1234, backend="auto", device=None, trainable=None, strong_form=None, hard_bc=None,
-                 residual_norm="l2"):
+                 residual_norm="l2", constraints=None):
         dim = int(layers[0])
+        self._constraints = self._check_constraints(constraints)
+        self._con_rho, self._con_handed = None, False
         self._residual_norm = self._check_residual_norm(residual_norm)
         self._norm_metric = self._check_norm_metric(residual_norm)
         if strong_form not in (None, "elementwise", "divergence"):
@@ -1444,6 +1459,7 @@ class VPINNLinear(_VPINNBase):
         self.loss_his = []
         self._backend_arg = backend
         self._create(layers, 1, LR, lossb_weight, 1.0, init_params, seed, backend, device)
+        self._no_constraints_on_several_gpus(self._constraints)
         mesh = mesh.copy()
         self._mesh = mesh
 
@@ -1677,7 +1693,15 @@ class VPINNLinear(_VPINNBase):
         kind, mass, metric, gp = self._rn4
         np.savez(self._ckpt_path(path), state=self.h.get_state(), layers=np.asarray(self.layers), dev_layers=np.asarray(self._dev_layers),
                  cls=type(self).__name__, residual_norm=kind, residual_norm_mass=mass, residual_norm_metric=metric,
-                 residual_norm_gram_points=0 if gp is None else gp)
+                 residual_norm_gram_points=0 if gp is None else gp, **self._constraints_ckpt())
+
+    def _constraints_ckpt(self):
+        """the constraints as arrays: names, powers, targets, weights and the unfolded density values at the quadrature points"""
+        c = self._constraints
+        if not c:
+            return {}
+        return dict(con_name=np.asarray([k["name"] for k in c]), con_kind=np.asarray([k.get("kind", "moment") for k in c]), con_power=np.asarray([k["power"] for k in c]),
+                    con_target=np.asarray([k["target"] for k in c]), con_weight=np.asarray([k["weight"] for k in c]), con_density=self._con_rho)
 
     def load_checkpoint(self, path):
         """As `_VPINNBase.load_checkpoint`; a checkpoint that stores the norm of the residual sets it on the model (one written before
@@ -1691,6 +1715,11 @@ class VPINNLinear(_VPINNBase):
             rn = (kind, float(d["residual_norm_mass"]), metric, gp or None)
             if rn != self._rn4:
                 self.set_residual_norm("l2" if kind == "l2" else dict(kind=kind, mass=rn[1], metric=metric, gram_points=rn[3]))
+        if "con_power" in d:                               # (the densities as the arrays they were on the checkpoint's mesh)
+            kinds = d["con_kind"] if "con_kind" in d else ["moment"] * len(d["con_power"])
+            self.set_constraints([dict(name=str(n), kind=str(k), target=float(t), weight=float(w)) if str(k) != "moment" else
+                                  dict(name=str(n), kind="moment", density=np.asarray(r), power=int(p), target=float(t), weight=float(w))
+                                  for n, k, r, p, t, w in zip(d["con_name"], kinds, d["con_density"], d["con_power"], d["con_target"], d["con_weight"])])
 
     # -- exact Dirichlet conditions by ansatz u = G + D N (hpv_set_ansatz) ------------------------------------------------------
     def _check_hard_bc(self, hard_bc, mesh):
@@ -1832,6 +1861,116 @@ class VPINNLinear(_VPINNBase):
         self._hand_trainable(mesh)
         self._hand_ansatz_quad(mesh)
         self._hand_residual_norm(mesh)                     # (set_tables dropped the tables: they belong to the test functions)
+        self._hand_constraints(mesh)                       # (the new elements orphaned the measure planes)
+
+    # -- integral constraints (hpv_set_moments) -----------------------------------------------------------------------------------
+    _CON_KINDS = {"mean": 1, "l2": 2}
+
+    @staticmethod
+    def _check_constraints(constraints):
+        """the list of dict(name=, kind="mean" | "l2" | "moment", density=, power=, target=, weight=) with kind resolved: "mean" is
+        power 1, "l2" power 2, both with density 1; "moment" takes everything explicitly.  None and [] are no constraints."""
+        out = []
+        for c in constraints or ():
+            c = dict(c)
+            kind = c.get("kind", "moment")
+            if kind not in ("mean", "l2", "moment") or set(c) - {"name", "kind", "density", "power", "target", "weight"} or "name" not in c:
+                raise ValueError('a constraint is dict(name=, kind="mean" | "l2" | "moment", density=, power=, target=, weight=)')
+            if kind != "moment":
+                if c.get("density") is not None or c.get("power", VPINNLinear._CON_KINDS[kind]) != VPINNLinear._CON_KINDS[kind]:
+                    raise ValueError(f'kind="{kind}" fixes density 1 and power {VPINNLinear._CON_KINDS[kind]}; kind="moment" takes them explicitly')
+                c["power"], c["density"] = VPINNLinear._CON_KINDS[kind], None
+            elif "power" not in c:
+                raise ValueError('kind="moment" needs power=1 or power=2')
+            if c["power"] not in (1, 2):
+                raise ValueError("constraints: power is 1 or 2 (higher powers and moments of grad u are out of scope)")
+            c["target"], c["weight"] = float(c.get("target", 0.0)), float(c.get("weight", 1.0))
+            if not (np.isfinite(c["target"]) and np.isfinite(c["weight"]) and c["weight"] >= 0.0):
+                raise ValueError("constraints: target is finite, weight is finite and not negative (the penalty is weight * (I - target)^2)")
+            d = c.get("density")
+            c["density"] = d if d is None or callable(d) else np.asarray(d, dtype=np.float64)
+            out.append(c)
+        if len(out) > _lib.MAX_MOMENTS:
+            raise ValueError(f"at most {_lib.MAX_MOMENTS} constraints")
+        if len({c["name"] for c in out}) != len(out):
+            raise ValueError("constraints: the names must differ")
+        return out
+
+    def _no_constraints_on_several_gpus(self, constraints):
+        if constraints and self.world > 1:
+            raise ValueError("constraints on several GPUs: the moments are integrals over the whole domain and there is no collective "
+                             "before the adjoint")
+
+    def _measure(self, mesh, eb, ee, constraints):
+        """THE measure planes of the constraints, the one place they are built: (rho (K, n), m (K, n)) at the quadrature points of the
+        elements [eb, ee) -- rho the density's values there (the physical points on a MappedMesh), m = rho x tensor quadrature
+        weight x the element's Jacobian (the half widths' product of a box) x det A on a MappedMesh.  A zero-weight padding point
+        gets m = 0 exactly."""
+        P, A = self._geometry(mesh, eb, ee)
+        n, dim = P.shape[0], mesh.dim
+        w = self._rule[0][1] if dim == 1 else np.outer(self._rule[1][1], self._rule[0][1]).reshape(-1)
+        if A is not None:
+            jac = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+        else:
+            b = np.asarray(mesh.boxes, dtype=np.float64)[eb:ee]
+            jac = np.repeat(np.prod([(b[:, 2 * a + 1] - b[:, 2 * a]) / 2 for a in range(dim)], axis=0), w.size)
+        rho = np.ones((len(constraints), n))
+        for k, c in enumerate(constraints):
+            d = c["density"]
+            if callable(d):
+                rho[k] = _coef_field(d, P, dim, "density of constraint %r" % c["name"], False)
+            elif d is not None:
+                if d.size != n:
+                    raise ValueError(f"constraint {c['name']!r}: the density array has {d.size} values but the mesh has {n} quadrature "
+                                     "points; an array belongs to the mesh it was sampled on -- hand it over again (set_constraints)")
+                rho[k] = d.reshape(-1)
+        return rho, self._fold_measure(rho, w, jac)
+
+    @staticmethod
+    def _fold_measure(rho, w, jac):
+        """rho (K, n) density values, w (NQ,) the tensor rule's weights, jac (n,) the Jacobian at the points: m = rho w jac, and
+        exactly 0 where the weight is 0 (whatever the density is there)"""
+        wj = np.tile(w, jac.size // w.size) * jac
+        m = rho * wj[None, :]
+        m[:, wj == 0.0] = 0.0
+        return m
+
+    def _hand_constraints(self, mesh):
+        if not self._constraints:                          # (a model that never had constraints never calls the library for them)
+            self._con_rho = None
+            if self._con_handed:
+                self.h.set_moments(None, None, None, None)
+            self._con_handed = False
+            return
+        eb, ee = shard_range(len(mesh), self.rank, self.world)
+        c = self._constraints
+        self._con_rho, m = self._measure(mesh, eb, ee, c)
+        self._con_handed = True                            # (before the call: a refusal may have removed the old terms already)
+        self.h.set_moments([k["power"] for k in c], m, [k["target"] for k in c], [k["weight"] for k in c])
+
+    def set_constraints(self, constraints):
+        """Replace the integral constraints on the live model (None or [] removes them); densities are evaluated at the current mesh's
+        quadrature points.  Parameters and optimizer state stay."""
+        new = self._check_constraints(constraints)
+        self._no_constraints_on_several_gpus(new)
+        old, self._constraints = self._constraints, new
+        try:
+            self._hand_constraints(self._mesh)
+        except Exception:                                  # (a ValueError of a density, a refusal of the library: the old terms again)
+            self._constraints = old
+            try:
+                self._hand_constraints(self._mesh)
+            except Exception:                              # (the handle refuses them too: the model then has none, as the handle has)
+                self._constraints, self._con_rho = [], None
+            raise
+
+    def constraints(self):
+        """{name: (value, penalty)}: I_k = int density u^power and weight (I_k - target)^2 of the most recent pass.  The penalties are
+        part of the loss the model reports as its variational part (the last entry of the loss triple, `loss_his`)."""
+        if not self._constraints:
+            return {}
+        I, pen = self.h.read_moments(len(self._constraints))
+        return {c["name"]: (float(I[k]), float(pen[k])) for k, c in enumerate(self._constraints)}
 
     def _hand_data(self):
         if self.rank == 0 and self.X_u_train is not None:
@@ -1865,6 +2004,10 @@ class VPINNLinear(_VPINNBase):
             f = self._f
         if isinstance(mesh, ElementMesh) and mesh.dim == self.layers[0]:
             self._check_scope(mesh)
+        for c in self._constraints:
+            if isinstance(c["density"], np.ndarray):
+                raise ValueError(f"constraint {c['name']!r} has an array density, which belongs to the mesh it was sampled on: remove it "
+                                 "(set_constraints) before the mesh changes and hand it over again afterwards")
         self._f = f
         super().set_mesh(mesh, f)
 

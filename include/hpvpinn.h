@@ -194,6 +194,34 @@ int hpv_set_nonlinear(hpv_handle h, const double* coef, size_t n);
  * hpv_set_trainable refuses with -3 on a handle with the term), or before hpv_set_elements; -2 on a HIP error. */
 int hpv_set_quasilinear(hpv_handle h, const double* planes, size_t n, double exponent);
 
+/* Integral constraints on a handle of the class above: up to HPV_MAX_MOMENTS weighted moments of u over the handle's Nq = n_owned*qx*qy
+ * quadrature points and a quadratic penalty on each,
+ *     I_k   = sum_q m_k[q] u_q^p_k            p_k in {1, 2}
+ *     pen_k = w_k (I_k - c_k)^2               lossv += sum_k pen_k
+ *     d loss / d u_q += 2 w_k (I_k - c_k) p_k u_q^(p_k - 1) m_k[q]
+ * u is what the projection kernel reads (with hpv_set_ansatz: G + D N).  m_k is a ready-made measure plane in the layout of
+ * hpv_set_operator: density x tensor quadrature weight x |J_e| (x det A on unit elements, hpv_set_element_points); the caller builds
+ * it.  A zero-weight padding point has m_k = 0: it adds 0 to I_k and receives exactly 0.  A prescribed mean or mass, the
+ * normalisation int u^2 = 1 and the deflation integrals int u v_j = 0 of an eigenvalue problem are all this term.
+ * Three launches follow the projection kernel (k_moment_part, k_moment_close, k_moment_adj; csrc/kernels_moment.hip; the first two in
+ * hpv_eval_loss), inside the captured iteration graphs; no atomics, the same bits from call to call.  The penalties are part of the
+ * first entry of the loss triple.  hpv_kernel_variant carries ";mom=K" in the projection kernel's bracket.
+ *
+ * power, target, weight are [n_terms]; measure is [n_terms][Nq], n = n_terms*Nq.  n_terms == 0 (the arrays may be NULL) removes the
+ * terms: nothing is kept, and the handle launches bit for bit what a handle that never had terms launches.
+ * Everything is copied.  Waits for the handle's stream and drops the captured iteration graphs, like hpv_set_nonlinear.
+ * hpv_set_elements / hpv_set_element_boxes / hpv_set_element_points invalidate the planes: a handle that HAD terms then answers -3
+ * from a pass ("hpv_set_moments has not been called again") until they are set again or removed.  The terms are not state.
+ * Returns 0; -1 for n_terms outside 0..HPV_MAX_MOMENTS, a power outside {1, 2}, a negative weight, a wrong n, a non-finite target,
+ * weight or measure entry; -3 for a handle of another problem (a linear handle exists under the variational scheme only: hpv_create), before hpv_set_elements, and with n_terms > 0 on a handle with
+ * an exchange connected (hpv_rccl_connect, hpv_p2p_export / _connect -- which in turn refuse with -3 while terms are set: I_k is a
+ * global integral and there is no collective before the adjoint; n_terms == 0 is accepted there, and where no terms are set it touches
+ * nothing); -2 on a HIP error. */
+#define HPV_MAX_MOMENTS 8
+int hpv_set_moments(hpv_handle h, int n_terms, const int* power, const double* measure, size_t n, const double* target, const double* weight);
+/* I_k and pen_k of the most recent pass (waits for the handle's stream); n_terms must equal the handle's count.  Returns 0; -1 otherwise. */
+int hpv_read_moments(hpv_handle h, double* values, double* penalties, int n_terms);
+
 /* Coefficient identification on a handle of the class above: n_coef trainable scalars c_0 .. c_{n_coef-1} follow the network
  * parameters in theta (1 <= n_coef <= HPV_MAX_COEF) and are trained with them.  Each scalar owns a DIRECTION D_m in the space of
  * all coefficient planes; the planes the projection uses are
