@@ -48,11 +48,15 @@ EXPORTS = [
     "hpv_set_operator_tensor", "hpv_set_element_points",
     "hpv_set_quasilinear",
     "hpv_set_moments", "hpv_read_moments",
+    "hpv_lbfgs_step", "hpv_lbfgs_reset",
 ]
 NORM_L2, NORM_DUAL, NORM_DUAL_DENSE = 0, 1, 2      # kind of hpv_set_residual_norm; HPV_NORM_DUAL_DENSE is what hpv_set_residual_gram sets
 ANSATZ_QUAD, ANSATZ_DATA, ANSATZ_FLUX, ANSATZ_VALID = 0, 1, 2, 3      # HPV_ANSATZ_* of include/hpvpinn.h: the point sets of hpv_set_ansatz
 MAX_MOMENTS = 8          # HPV_MAX_MOMENTS of include/hpvpinn.h: integral constraints of a linear handle
 MAX_COEF = 8             # HPV_MAX_COEF of include/hpvpinn.h: trainable coefficients of a linear handle
+LBFGS_MAX_HISTORY = 64   # HPV_LBFGS_MAX_HISTORY of csrc/hpv_internal.h: pairs the ring of hpv_lbfgs_step holds at most
+# HPV_LBFGS_* of include/hpvpinn.h: why hpv_lbfgs_step stopped
+LBFGS_REASONS = ("max_iter", "max_eval", "tolerance_grad", "tolerance_change", "tolerance_direction", "max_ls", "non_finite")
 IND_N = 5                # HPV_IND_N of include/hpvpinn.h: loss_e, eta2_e, sumR2_e, topx_e, topy_e
 
 
@@ -84,6 +88,11 @@ class HpvConfig(C.Structure):
         ("lossb_weight", C.c_double), ("V", C.c_double),
         ("device", C.c_int), ("backend", C.c_int), ("scheme", C.c_int),
     ]
+
+
+class HpvLbfgsOpts(C.Structure):
+    _fields_ = [("history", C.c_int), ("max_iter", C.c_int), ("max_eval", C.c_int),
+                ("lr", C.c_double), ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double)]
 
 
 class HpvError(RuntimeError):
@@ -228,7 +237,13 @@ def load():
     lib.hpv_set_ansatz.argtypes = [h, C.c_int, _dp, C.c_size_t]
     lib.hpv_set_residual_norm.argtypes = [h, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
     lib.hpv_set_residual_gram.argtypes = [h, _dp, C.c_size_t]
+    lib.hpv_lbfgs_step.argtypes = [h, C.POINTER(HpvLbfgsOpts), _dp, C.POINTER(C.c_int)]
+    lib.hpv_lbfgs_reset.argtypes = [h]
     lib.hpv_build_info.restype = C.c_char_p
+    if path == TEST_HOOKS_LIB_PATH:      # the kernel-level hooks of the L-BFGS stage (csrc/hpv_lbfgs.hip)
+        _ip = C.POINTER(C.c_int)
+        lib.hpv_test_lbfgs_direction.argtypes = [C.c_int] * 4 + [_dp, _dp, _dp, C.c_double, _dp, _dp, _dp]
+        lib.hpv_test_lbfgs_push.argtypes = [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     _libs[path] = lib
     if path == LIB_PATH:
         _lib = lib
@@ -766,6 +781,22 @@ class Handle:
         n = C.c_longlong(0)
         self._chk(self.lib.hpv_updates_applied(self._h, C.byref(n)))
         return int(n.value)
+
+    def lbfgs_step(self, max_iter, history=20, lr=1.0, tolerance_grad=1e-7, tolerance_change=1e-9, max_eval=None):
+        """hpv_lbfgs_step: ((iters + 1, 3) array {loss, lossb, lossv} at the start and after every accepted iteration,
+        {"iters", "func_evals", "pairs_skipped", "reason"})."""
+        o = HpvLbfgsOpts(int(history), int(max_iter), 0 if max_eval is None else int(max_eval), float(lr), float(tolerance_grad),
+                         float(tolerance_change))
+        if max_eval is not None and int(max_eval) < 1:
+            raise ValueError("max_eval must be at least 1")
+        hist = np.zeros((max(int(max_iter), 0) + 1, 3))
+        info = (C.c_int * 4)()
+        self._chk(self.lib.hpv_lbfgs_step(self._h, C.byref(o), _p(hist), info))
+        return hist[:info[0] + 1], {"iters": int(info[0]), "func_evals": int(info[1]), "pairs_skipped": int(info[2]),
+                                    "reason": LBFGS_REASONS[info[3]]}
+
+    def lbfgs_reset(self):
+        self._chk(self.lib.hpv_lbfgs_reset(self._h))
 
     def shared_element_kernels(self):
         """False once the handle stays on launch structures without an in-kernel exchange (set, or after a timeout fallback)."""

@@ -13,11 +13,11 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $HPV_EXTRA_FLAGS"   # e.g. HPV_EXTRA_FLAGS=-DHPV_FZ_TIMING
-SRCS="kernels_mfma kernels_fused kernels_fused_gen kernels_project kernels_tile kernels_tall kernels_generic kernels_validate kernels_adapt kernels_linadapt kernels_linop kernels_nonlin kernels_ident kernels_moment kernels_ansatz hpv_api hpv_pass hpv_exchange hpv_bench"
+SRCS="kernels_mfma kernels_fused kernels_fused_gen kernels_project kernels_tile kernels_tall kernels_generic kernels_validate kernels_adapt kernels_linadapt kernels_linop kernels_nonlin kernels_ident kernels_moment kernels_ansatz kernels_lbfgs hpv_api hpv_pass hpv_exchange hpv_bench hpv_lbfgs"
 ELEM_SHAPES="20,20,10,10 16,16,8,8 12,12,6,6"             # kernels_elem.hip: one object per element shape (= HPV_ELEM_SHAPES of hpv_mfma_dev.h)
 WIDE_WIDTHS="64 32 48 24 40"                            # kernels_wide.hip: one object per hidden width and dimension (= HPV_WIDE_WIDTHS of hpv_mfma.h)
 # the sources whose text depends on HPV_TEST_HOOKS, their own or through HPV_XDEBUG_SKIP of hpv_mfma_dev.h (built twice)
-HOOKED="kernels_fused kernels_fused_gen kernels_tile kernels_tall hpv_api hpv_pass hpv_exchange"
+HOOKED="kernels_fused kernels_fused_gen kernels_tile kernels_tall hpv_api hpv_pass hpv_exchange hpv_lbfgs"
 TH_FLAGS="-DHPV_TEST_HOOKS"
 CHK="python3 ../../scripts/check_agpr.py"
 # objects are cached by mtime; a change of flags must invalidate them (.flags remembers what the objects were built with)
@@ -50,11 +50,23 @@ guarded_compile() {   # guarded_compile <source stem> <object> <extra flags> <fi
   $HIPCC $FLAGS $XF $add $extra -c $f.hip -o $obj      # (the guard tripped: once more, without the offending instantiations)
 }
 
+# The reducing kernels of the L-BFGS stage run 1024 threads on 128 registers each: the same check, on their assembly, that none of
+# them spills (no hand-managed registers there: base 256).
+spill_checked_compile() {   # spill_checked_compile <source stem> <object> <extra flags> <kernel-name substring>
+  local f=$1 obj=$2 extra=$3 key=$4 tmp=.tmp_${2%.o}
+  rm -rf $tmp; mkdir -p $tmp
+  $HIPCC $FLAGS $extra -save-temps=obj -c $f.hip -o $tmp/$f.o || { rm -rf $tmp; return 1; }
+  cp $tmp/$f-hip-amdgcn-amd-amdhsa-gfx950.s ${obj%.o}.s || { echo "build.sh: ERROR -- no device assembly behind $f.hip" >&2; rm -rf $tmp; return 1; }
+  $CHK ${obj%.o}.s $key 256 >/dev/null || { echo "build.sh: ERROR -- a kernel of $f.hip spills to scratch memory (or could not be checked)" >&2; rm -rf $tmp; return 1; }
+  mv $tmp/$f.o $obj; rm -rf $tmp
+}
+
 compile_one() {   # compile_one <source stem> <object> <extra flags>
   local f=$1 obj=$2 extra=$3
   if [ $f = kernels_fused ]; then guarded_compile $f $obj "$extra" "$HPV_FUSED_EXTRA"      # (A/B builds: flags for this file only, scripts/build_variant.sh --fused-only)
   elif [ $f = kernels_fused_gen ]; then guarded_compile $f $obj "$extra" "$HPV_FUSED_EXTRA"
   elif [ $f = kernels_tall ]; then guarded_compile $f $obj "$extra" ""
+  elif [ $f = kernels_lbfgs ]; then spill_checked_compile $f $obj "$extra" k_lbfgs
   else $HIPCC $FLAGS $extra -c $f.hip -o $obj; fi
 }
 

@@ -402,7 +402,7 @@ void hpv_destroy(hpv_handle h) {
                     h->d_ind_f, h->d_ind, h->d_res_f, h->d_res_r, h->d_val_u, h->d_val_du, h->d_val_buf, h->d_val_idx, h->d_upart,
                     h->d_wtx, h->d_wty, h->d_edge_dphi, h->d_coef, h->d_edge_coef, h->d_F, h->d_R, h->d_loss_e, h->d_deps_e, h->d_udata,
                     h->d_data_part, h->d_theta, h->d_m, h->d_v, h->d_state, h->d_RB, h->d_hist, h->d_hist_idx, h->d_xerr, h->d_nupd,
-                    h->d_nact, h->d_nacty};
+                    h->d_nact, h->d_nacty, h->d_lb, h->d_lb_ring};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (double* p : h->d_ans) if (p) (void)hipFree(p);
     for (auto& t : h->timers) for (auto e : t.ev) (void)hipEventDestroy(e);
@@ -1199,7 +1199,7 @@ int hpv_set_params(hpv_handle h, const double* theta, size_t n) {
     for (size_t i = 0; i < st.size(); i += 2) { st[i] = h->cfg.beta1; st[i + 1] = h->cfg.beta2; }   // beta^1, every copy
     if ((rc = upload(h, h->d_state, st.data(), st.size()))) return rc;
     h->have_params = true;
-    return 0;
+    return lbfgs_drop(h);      // (curvature pairs gathered along another trajectory say nothing about these parameters)
 }
 
 int hpv_get_params(hpv_handle h, double* theta, size_t n) {
@@ -1622,7 +1622,7 @@ int hpv_set_state(hpv_handle h, const double* buf, size_t n) {
     for (size_t i = 0; i < st.size(); i += 2) { st[i] = buf[3 * P]; st[i + 1] = buf[3 * P + 1]; }
     if ((rc = upload(h, h->d_state, st.data(), st.size()))) return rc;
     h->have_params = true;
-    return 0;
+    return lbfgs_drop(h);      // (curvature pairs gathered along another trajectory say nothing about these parameters)
 }
 
 // F_ext[e][k][r] = J_e sum_q w_x phi_r w_y phi_k f(x_q)  (P1:289, P2:405-407) for the owned elements, from

@@ -196,6 +196,13 @@ struct hpv_ctx {
     double *d_val_u = nullptr, *d_val_du = nullptr;     // exact values [n], exact gradients [dim][n] (nullptr: none given)
     double* d_val_buf = nullptr;   // [6] result of hpv_validate | [HPV_HIST_CAP][6] history | [HPV_VAL_MAX_BLOCKS][5] partials
     int* d_val_idx = nullptr;      // [0] history index, [1] the reduction's ticket counter
+    // L-BFGS stage (hpv_lbfgs_step; hpv_lbfgs.hip): one allocation d_lb = [theta0 | g | d | three gradient slots of the line search |
+    // S[m] | Y[m]] (Ptot each) | rho[m] | h_diag | scal[8], the ring's counters d_lb_ring[4], the capacity lb_m the buffers were made
+    // for (0: none yet) and the iterations taken since the history was last dropped (the first one steps along -g with its own length)
+    double* d_lb = nullptr;
+    int* d_lb_ring = nullptr;
+    int lb_m = 0;
+    long long lb_iters = 0;
     // in-library exchange of the packed buffer between the ranks of a node (hpv_p2p_*)
     P2PArgs pp{};
     bool p2p_on = false;
@@ -261,6 +268,7 @@ int enqueue_iterations(hpv_ctx* h, int n_iters);
 MfmaDataTerm pass_data_term(hpv_ctx* h, bool backward);
 ProjArgs pass_proj_args(hpv_ctx* h, bool backward, bool edge = false);
 MfmaPass pass_mfma(hpv_ctx* h, const MfmaDataTerm& dt, const ProjArgs& pa);
+int lbfgs_drop(hpv_ctx* h);                  // the L-BFGS history goes: new parameters were handed in (hpv_lbfgs.hip)
 void p2p_release(hpv_ctx* h);                // hpv_exchange.hip
 void rccl_release(hpv_ctx* h);
 int p2p_check(hpv_ctx* h);

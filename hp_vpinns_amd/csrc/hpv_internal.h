@@ -326,6 +326,31 @@ void launch_validate_reduce(const ValArgs& a, int blocks, hipStream_t s);
 void launch_residual_points(int pde, const double* OUT, long N, const double* f_or_null, const double* eps_ptr, double V, int n,
                             double* r, hipStream_t s);
 
+// ---- L-BFGS stage (kernels_lbfgs.hip; hpv_lbfgs_step) ----
+// The device-resident state of the optimiser: every vector has P entries and stays on the device; only `scal` travels.  The ring
+// holds n_hist <= m pairs (s_i, y_i) at the slots head, head + 1, .. (mod m), oldest first.
+#define HPV_LBFGS_MAX_HISTORY 64
+#define HPV_LBFGS_YS_MIN 1e-10    // a pair with y . s at or below this is skipped (the curvature test of the reference implementation)
+struct LbfgsArgs {
+    int P, m;
+    double *S, *Y;           // [m][P] the rings of steps s = t d and gradient differences y
+    double* rho;             // [m] 1 / (y_i . s_i)
+    double* h_diag;          // [1] (y . s) / (y . y) of the newest pair; 1 while there is none
+    int* ring;               // [4] head, n_hist, pairs skipped so far, unused
+    double* g;               // [P] gradient at theta0 (the accepted iterate): g_prev of the next pair
+    double* d;               // [P] search direction
+    double* theta0;          // [P] the accepted iterate
+    double* theta;           // [P] the handle's live parameters (what a pass reads)
+    double* scal;            // [8]: k_lbfgs_direction writes [0..3] = g . d, max|g|, sum|g|, max|d|;
+                             //      k_lbfgs_probe writes [4..7] = loss, g_new . d, max|g_new|, 0
+};
+void launch_lbfgs_direction(const LbfgsArgs& a, hipStream_t s);
+void launch_lbfgs_trial(const LbfgsArgs& a, double t, hipStream_t s);
+// RB = [grad (P) | lossv | w*lossb | ..] of the pass just run; the gradient is copied to g_keep [P] (a: nothing to project on --
+// the call's first evaluation -- when with_d == 0; g . d is then 0)
+void launch_lbfgs_probe(const LbfgsArgs& a, const double* RB, double* g_keep, int with_d, hipStream_t s);
+void launch_lbfgs_push(const LbfgsArgs& a, double t, const double* g_new, hipStream_t s);
+
 // ---- per-element refinement indicators (kernels_adapt.hip; hpv_element_indicators) ----
 struct IndArgs {
     const double* OUT;       // [5 | 3][N] the full channel list at the quadrature batch's points (element-major, q = j * qx + i)

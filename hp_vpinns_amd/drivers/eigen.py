@@ -69,8 +69,8 @@ def _model(problem, lambda0, constraints, layers, n_elements, n_quad, n_test, LR
 
 
 def run(problem="laplace-1d", n_modes=3, n_iter=3000, layers=(20, 20), n_elements=None, n_quad=10, n_test=5, LR=2e-3, weight=100.0, lambda0=None,
-        seed=1234, backend="auto", device=None, verbose=True):
-    """modes 1..n_modes by deflation; returns a list of dict(model, lam, known, iterations, norm2, deflation) -- lam the trained
+        seed=1234, backend="auto", device=None, verbose=True, lbfgs=0):
+    """lbfgs=N: every mode gets an L-BFGS stage of N iterations after its Adam iterations (the known error is lambda's).  modes 1..n_modes by deflation; returns a list of dict(model, lam, known, iterations, norm2, deflation) -- lam the trained
     lambda, norm2 = int u^2 and deflation = [int u v_k] at the end.  lambda0: the start of lambda per mode (default: 5 for the first,
     2.5 times the previous mode's lambda after it); weight: the penalty weight of every constraint."""
     n_elements = n_elements or (4 if problem == "laplace-1d" else 2)
@@ -82,6 +82,8 @@ def run(problem="laplace-1d", n_modes=3, n_iter=3000, layers=(20, 20), n_element
         l0 = (lambda0[k] if lambda0 is not None else (5.0 if k == 0 else 2.5 * out[-1]["lam"]))
         m = _model(problem, l0, cons, layers, n_elements, n_quad, n_test, LR, seed + k, backend, device)
         m.train(int(n_iter), verbose=False)
+        from . import lbfgs_stage
+        lbfgs_stage(m, lbfgs, lambda: abs(m.coefficients()["lambda"] - ref[k]) / ref[k], what="relative error of lambda", verbose=verbose)
         m.loss()
         c, lam = m.constraints(), m.coefficients()["lambda"]
         row = dict(model=m, lam=lam, known=float(ref[k]), iterations=int(n_iter), norm2=c["norm"][0], deflation=[c["v%d" % (j + 1)][0] for j in range(k)],
@@ -104,11 +106,12 @@ def main(argv=None):
     ap.add_argument("--n-test", type=int, default=5)
     ap.add_argument("--weight", type=float, default=100.0, help="penalty weight of the normalisation and the deflation integrals")
     ap.add_argument("--lambda0", type=float, nargs="*", default=None, help="where lambda starts, one value per mode")
+    ap.add_argument("--lbfgs", type=int, default=0, help="L-BFGS iterations after the Adam iterations of every mode")
     a = ap.parse_args(argv)
     n = a.modes or (3 if a.problem == "laplace-1d" else 1)
     if a.lambda0 is not None and len(a.lambda0) != n:
         ap.error("--lambda0 takes one value per mode")
-    run(a.problem, n_modes=n, n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, weight=a.weight, lambda0=a.lambda0)
+    run(a.problem, n_modes=n, n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, weight=a.weight, lambda0=a.lambda0, lbfgs=a.lbfgs)
 
 
 if __name__ == "__main__":

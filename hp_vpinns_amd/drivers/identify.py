@@ -82,11 +82,14 @@ def setup(problem, k1=1.0, k2=2.0, nu=0.1, init=None, n_elements=None, n_quad=10
     raise ValueError("problem is one of conductivity, burgers-nu")
 
 
-def run(s, n_iter=5000, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True):
-    """Train the problem of `setup`'s dict; returns dict(model, coefficients, true, rel_l2, loss_his)"""
+def run(s, n_iter=5000, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, lbfgs=0):
+    """Train the problem of `setup`'s dict (lbfgs=N: N L-BFGS iterations after the Adam iterations; the coefficients move with the network); returns dict(model, coefficients, true, rel_l2, loss_his)"""
     from ..vpinn import VPINNLinear, VPINNNonlinear
     m = (VPINNNonlinear if s["nonlinear"] else VPINNLinear)(s["layers"], LR=LR, seed=seed, backend=backend, device=device, **s["model"])
     m.train(int(n_iter), verbose=verbose)
+    from . import lbfgs_stage
+    lbfgs_stage(m, lbfgs, lambda: max(abs(v - s["true"][k]) / abs(s["true"][k]) for k, v in m.coefficients().items()),
+                what="largest relative coefficient error", verbose=verbose)
     c = m.coefficients()
     err = m.rel_l2_error(s["X_test"], s["u_test"])
     if verbose:
@@ -106,8 +109,9 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=5000)
     ap.add_argument("--width", type=int, default=20)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--lbfgs", type=int, default=0, help="L-BFGS iterations after the Adam iterations")
     a = ap.parse_args(argv)
-    run(setup(a.problem, k1=a.k1, k2=a.k2, nu=a.nu, init=a.init, width=a.width), n_iter=a.iters, LR=a.lr)
+    run(setup(a.problem, k1=a.k1, k2=a.k2, nu=a.nu, init=a.init, width=a.width), n_iter=a.iters, LR=a.lr, lbfgs=a.lbfgs)
 
 
 if __name__ == "__main__":

@@ -95,21 +95,25 @@ def _estimator_line(m, h1_err):
     return "sqrt(lossv) %.4e beside the H^1 error %.4e (residual norm %s)" % (np.sqrt(lossv), h1_err, m.residual_norm)
 
 
-def _train(m, n_iter, adapt_every, max_elements, verbose):
-    """train, or train_adaptive with its rows [(iterations done, elements, loss on the new mesh)] printed like the Poisson-2D driver's"""
+def _train(m, n_iter, adapt_every, max_elements, verbose, lbfgs=0, test=None):
+    """train, or train_adaptive with its rows [(iterations done, elements, loss on the new mesh)] printed like the Poisson-2D driver's;
+    then lbfgs iterations of the L-BFGS stage, the error on the points test = (X, u) printed before and after"""
+    from . import lbfgs_stage
     if not adapt_every:
         m.train(int(n_iter), verbose=verbose)
+        lbfgs_stage(m, lbfgs, (lambda: m.rel_l2_error(*test)) if test is not None else None, verbose=verbose)
         return []
     rows = m.train_adaptive(int(n_iter), int(adapt_every), max_elements=max_elements)
     if verbose:
         for it, ne, loss in rows:
             print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
+    lbfgs_stage(m, lbfgs, (lambda: m.rel_l2_error(*test)) if test is not None else None, verbose=verbose)
     return rows
 
 
 def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000, layers=(1, 20, 20, 20, 1), grade=2.0, LR=1e-3,
                        lossb_weight=10.0, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, hard_bc=False,
-                       residual_norm="l2"):
+                       residual_norm="l2", lbfgs=0):
     grid = graded_grid(int(n_elements), grade)
     bc = dict(hard_bc=interval_hard_bc(0.0, 1.0, 0.0, 0.0)) if hard_bc else dict(X_u_train=np.array([[0.0], [1.0]]), u_train=np.zeros(2))
     m = VPINNLinear(list(layers), grid_x=grid, n_quad=int(n_quad), n_test=int(n_test), kappa=-float(eps), beta=1.0, sigma=0.0, f=1.0,
@@ -117,9 +121,9 @@ def run_boundary_layer(eps=0.05, n_elements=8, n_quad=20, n_test=10, n_iter=2000
                     seed=seed, backend=backend, device=device,
                     strong_form=("divergence" if hard_bc else "elementwise") if adapt_every else None,      # (the ansatz has no second derivatives)
                     residual_norm=residual_norm, **bc)
-    rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     X = np.linspace(0.0, 1.0, 401)[:, None]
     u = boundary_layer_exact(X, eps)
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose, lbfgs, (X, u))
     err = m.rel_l2_error(X, u)
     ux = 1.0 - np.exp((X[:, 0] - 1.0) / eps) / (eps * (1.0 - np.exp(-1.0 / eps)))
     d2 = (np.asarray(m.evaluate(X)["u_x"]).reshape(-1) - ux) ** 2
@@ -155,17 +159,17 @@ def _l_boundary(n):
 
 
 def run_l_shape(n_iter=2000, n_quad=20, n_test=10, layers=(2, 20, 20, 20, 1), n_bound=40, LR=1e-3, lossb_weight=10.0, seed=1234,
-                backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, residual_norm="l2"):
+                backend="auto", device=None, verbose=True, adapt_every=None, max_elements=None, residual_norm="l2", lbfgs=0):
     Xb = _l_boundary(int(n_bound))
     m = VPINNLinear(list(layers), mesh=ElementMesh(L_BOXES, int(n_test), int(n_test)), n_quad=int(n_quad),
                     kappa=lambda P: 1.0 + P[:, 0] * P[:, 1], beta=np.array([1.0, -1.0]), sigma=2.0, f=_l_f, X_u_train=Xb, u_train=_l_exact(Xb),
                     lossb_weight=lossb_weight, LR=LR, seed=seed, backend=backend, device=device,
                     strong_form="elementwise" if adapt_every else None, residual_norm=residual_norm)
-    rows = _train(m, n_iter, adapt_every, max_elements, verbose)
     g = np.linspace(-1.0, 1.0, 81)
     X = np.stack([v.reshape(-1) for v in np.meshgrid(g, g)], 1)
     X = X[~((X[:, 0] > 0) & (X[:, 1] < 0))]
     u = _l_exact(X)[:, None]
+    rows = _train(m, n_iter, adapt_every, max_elements, verbose, lbfgs, (X, u))
     err = m.rel_l2_error(X, u)
     ev = m.evaluate(X)
     gx = np.pi * np.cos(np.pi * X[:, 0]) * np.sin(np.pi * X[:, 1]) - np.asarray(ev["u_x"]).reshape(-1)
@@ -346,7 +350,10 @@ def main(argv=None):
                     help="dual: each element's residual in the dual norm of its test space (robust VPINNs; on the annulus in the physical metric); "
                          "energy (l-shape, anisotropic, annulus): that norm in the energy inner product of the problem's own kappa")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
+    ap.add_argument("--lbfgs", type=int, default=0, help="boundary-layer, l-shape: L-BFGS iterations after the Adam iterations")
     a = ap.parse_args(argv)
+    if a.lbfgs and a.problem not in ("boundary-layer", "l-shape"):
+        ap.error("--lbfgs belongs to boundary-layer and l-shape")
     dq, dt = (10, 5) if a.problem == "neumann" else (20, 10)
     a.n_quad, a.n_test = a.n_quad or dq, a.n_test or dt
     if a.residual_norm == "energy" and a.problem == "boundary-layer":
@@ -354,7 +361,7 @@ def main(argv=None):
     rn = _norm_arg(a.residual_norm, a.gram_mass, mapped=a.problem == "annulus")
     if a.problem == "boundary-layer":
         run_boundary_layer(eps=a.eps, n_elements=a.elements, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, grade=a.grade,
-                           adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn)
+                           adapt_every=a.adapt_every, max_elements=a.max_elements, hard_bc=a.hard_bc, residual_norm=rn, lbfgs=a.lbfgs)
     elif a.problem == "annulus":
         run_annulus(n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, hard_bc=a.hard_bc, record_every=max(1, a.iters // 10), residual_norm=rn,
                     adapt_every=a.adapt_every, max_elements=a.max_elements)
@@ -364,7 +371,8 @@ def main(argv=None):
         run_anisotropic(angle=a.angle, ratio=a.ratio, n_quad=a.n_quad, n_test=a.n_test, n_iter=a.iters, residual_norm=rn,
                         adapt_every=a.adapt_every, max_elements=a.max_elements)
     else:
-        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn)
+        run_l_shape(n_iter=a.iters, n_quad=a.n_quad, n_test=a.n_test, adapt_every=a.adapt_every, max_elements=a.max_elements, residual_norm=rn,
+                    lbfgs=a.lbfgs)
 
 
 if __name__ == "__main__":

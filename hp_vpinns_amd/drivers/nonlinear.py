@@ -194,8 +194,8 @@ def setup(problem, lam=1.0, nu=0.05, eps=0.2, n_elements=None, n_quad=10, n_test
 
 
 def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", device=None, verbose=True, adapt_every=None,
-        max_elements=None, residual_norm="l2"):
-    """Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated); with
+        max_elements=None, residual_norm="l2", lbfgs=0):
+    """lbfgs=N: an L-BFGS stage of N iterations after the Adam iterations.  Train the problem of `setup`'s dict; with validate_every the error history is sampled on the device (train_validated); with
     adapt_every the elements are refined locally (train_adaptive: the model is built with strong_form="elementwise", or
     "divergence" where the setup has an ansatz).  The two are not combined: giving both raises ValueError."""
     from ..vpinn import VPINNNonlinear
@@ -218,6 +218,8 @@ def run(s, n_iter=2000, validate_every=0, LR=1e-3, seed=1234, backend="auto", de
                 print("It: %d, relative L2 error %.4e, max error %.4e" % (it, e2, emax))
     else:
         m.train(int(n_iter), verbose=verbose)
+    from . import lbfgs_stage
+    lbfgs_stage(m, lbfgs, lambda: m.rel_l2_error(s["X_test"], s["u_test"]), verbose=verbose)
     err = m.rel_l2_error(s["X_test"], s["u_test"])
     if verbose:
         print("relative L2 error %.4e after %d iterations (%s)" % (err, n_iter, m.h.kernel_variant()))
@@ -241,12 +243,13 @@ def main(argv=None):
     ap.add_argument("--hard-bc", action="store_true", help="burgers: initial and boundary conditions by ansatz instead of data points")
     ap.add_argument("--residual-norm", choices=["l2", "dual"], default="l2", help="dual: each element's residual in the dual norm of its test space (robust VPINNs)")
     ap.add_argument("--gram-mass", type=float, default=0.0, help="weight of the L2 part of the dual norm's inner product")
+    ap.add_argument("--lbfgs", type=int, default=0, help="L-BFGS iterations after the Adam iterations")
     a = ap.parse_args(argv)
     if a.eps is None:
         a.eps = 0.1 if a.problem == "p-laplace" else 0.2
     run(setup(a.problem, lam=a.lam, nu=a.nu, eps=a.eps, width=a.width, hard_bc=a.hard_bc, p=a.p), n_iter=a.iters, validate_every=a.validate_every,
         adapt_every=a.adapt_every, max_elements=a.max_elements,
-        residual_norm="l2" if a.residual_norm == "l2" else dict(kind="dual", mass=a.gram_mass))
+        residual_norm="l2" if a.residual_norm == "l2" else dict(kind="dual", mass=a.gram_mass), lbfgs=a.lbfgs)
 
 
 if __name__ == "__main__":

@@ -136,8 +136,9 @@ def build_model(s, Net_layer, var_form=1, init_params=None, backend="auto", loss
 
 def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_x=5, N_test_y=5, N_quad=10,
         N_bound=80, N_residual=100, n_iter=10000 + 1, init_params=None, backend="auto", record_every=1, verbose=True,
-        validate_every=None, adapt_every=None, max_elements=None, neumann_sides=None, flux_weight=1.0):
-    """neumann_sides: a comma list out of left,right,bottom,top -- those sides carry the flux n . grad u of the exact solution
+        validate_every=None, adapt_every=None, max_elements=None, neumann_sides=None, flux_weight=1.0, lbfgs=0):
+    """lbfgs=N: an L-BFGS stage of N iterations after the Adam iterations (`train_lbfgs`; loss and error before and after are printed).
+    neumann_sides: a comma list out of left,right,bottom,top -- those sides carry the flux n . grad u of the exact solution
     (`set_flux_data`, weight flux_weight) instead of its value.  adapt_every=K: local hp-refinement (`train_adaptive`, right-hand side f_ext) after every K-th update, at most max_elements
     elements.  P2:279-288 hyper-parameters (reference defaults) -> trained model, prediction and L2 error.  validate_every=K trains
     through `train_validated` instead of `train`: the error on the test grid after every K-th update, reduced on the device."""
@@ -165,6 +166,8 @@ def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_
                 print("It: %d, adapted to %d elements, loss on the new mesh: %.3e" % (it, ne, loss))
     else:
         model.train(n_iter, record_every=record_every)           # P2:434
+    from . import lbfgs_stage
+    stage = lbfgs_stage(model, lbfgs, lambda: np.linalg.norm(s["u_test"] - model.predict(), 2) / np.linalg.norm(s["u_test"], 2), verbose=verbose)
     u_pred = model.predict()                                     # P2:435
     err = np.linalg.norm(s["u_test"] - u_pred, 2) / np.linalg.norm(s["u_test"], 2)
     if verbose:
@@ -172,6 +175,8 @@ def run(scheme="VPINNs", Net_layer=None, var_form=1, N_el_x=4, N_el_y=4, N_test_
     out = dict(model=model, u_pred=u_pred, rel_l2=err, loss_his=loss_his, setup=s)
     if curve is not None:
         out["error_curve"] = curve
+    if stage is not None:
+        out["lbfgs"] = stage
     return out
 
 
@@ -186,9 +191,10 @@ if __name__ == "__main__":
                     help="print the error on the test grid after every K-th update (device-side validation history)")
     ap.add_argument("--adapt-every", type=int, default=None, help="one local hp-refinement round after every K-th update")
     ap.add_argument("--max-elements", type=int, default=None, help="never refine beyond this many elements")
+    ap.add_argument("--lbfgs", type=int, default=0, help="L-BFGS iterations after the Adam iterations")
     ap.add_argument("--neumann-sides", default=None,
                     help="comma list out of left,right,bottom,top: sides that prescribe the flux n . grad u instead of u")
     a = ap.parse_args()
     run(n_iter=a.iters, N_el_x=a.elements, N_el_y=a.elements, var_form=a.var_form,
         Net_layer=[2] + [a.width] * 3 + [1], record_every=a.record_every, validate_every=a.validate_every,
-        adapt_every=a.adapt_every, max_elements=a.max_elements, neumann_sides=a.neumann_sides)
+        adapt_every=a.adapt_every, max_elements=a.max_elements, neumann_sides=a.neumann_sides, lbfgs=a.lbfgs)

@@ -604,6 +604,30 @@ class _VPINNBase:
         self._reducer.allreduce()
         return self.h.read_loss()
 
+    # -- L-BFGS stage after Adam (hpv_lbfgs_step) ------------------------------------------------------
+    def _record_lbfgs(self, losses):
+        """Append the losses after the accepted iterations to the class's history the way its `train` does (overridden per class;
+        VPINNAdvDiff keeps none -- its `train` returns its records -- and the caller has them in the returned dict)."""
+
+    def train_lbfgs(self, max_iter, history=20, lr=1.0, tolerance_grad=1e-7, tolerance_change=1e-9, max_eval=None):
+        """Up to `max_iter` L-BFGS iterations with a strong-Wolfe line search on ALL parameters (the network, epsilon, trainable
+        coefficients), device-resident; the options are those of torch.optim.LBFGS (`history` = history_size, at most 64;
+        max_eval None = max_iter * 5 // 4).  The loss after every accepted iteration goes to the class's loss history like the
+        losses of `train`.  Returns {"iters", "func_evals", "pairs_skipped", "reason", "loss"}: `loss` the (iters + 1, 3) array
+        {loss, lossb, lossv} from the starting point on, `reason` why it stopped (_lib.LBFGS_REASONS).  Adam's moments are left
+        alone -- a later `train` continues Adam from its own state at the new parameters -- and the curvature history survives
+        between calls until `lbfgs_reset`, `set_params` or `load_checkpoint`.  One GPU only."""
+        if self.world > 1 or self._coll or self._rccl or self._p2p:
+            raise RuntimeError("train_lbfgs runs on one GPU only (this model is one rank of several)")
+        hist, info = self.h.lbfgs_step(max_iter, history, lr, tolerance_grad, tolerance_change, max_eval)
+        self._record_lbfgs(hist[1:])
+        info["loss"] = hist
+        return info
+
+    def lbfgs_reset(self):
+        """Drop the curvature history of `train_lbfgs`: its next iteration steps along the negative gradient."""
+        self.h.lbfgs_reset()
+
     # -- flux term: Neumann / Robin conditions and derivative observations (hpv_set_flux_data) ------
     _flux = None      # (X, coef, g, weight) as handed to the library, kept for a handle that is rebuilt
 
@@ -969,6 +993,12 @@ class VPINN1D(_VPINNBase):
     def _train_n(self, n):
         self.train(n, 0.0)
 
+    def _record_lbfgs(self, losses):
+        self.total_record = self._history("total_record", self._total_record_arg, None)
+        it = int(self.total_record[-1][0]) + 1 if len(self.total_record) else 0
+        for k, l3 in enumerate(losses):
+            self.total_record.append(np.array([it + k, float(l3[0])]))
+
     def predict(self, x):                                   # P1:197-199
         return self._predict(x)
 
@@ -1073,6 +1103,10 @@ class VPINN2D(_VPINNBase):
 
     def _train_n(self, n):
         self.train(n)
+
+    def _record_lbfgs(self, losses):
+        self.loss_his = self._history("loss_his", self._loss_his_arg, None)
+        self.loss_his.extend(float(l3[0]) for l3 in losses)
 
     def predict(self, X=None):                              # P2:255-257 (stored test grid)
         return self._predict(self.X_test if X is None else X)
@@ -2056,6 +2090,9 @@ class VPINNLinear(_VPINNBase):
 
     def _train_n(self, n):
         self.train(n)
+
+    def _record_lbfgs(self, losses):
+        self.loss_his.extend(float(l3[0]) for l3 in losses)
 
     def predict(self, X):
         return self._predict(np.asarray(X, dtype=np.float64).reshape(-1, self.layers[0]))

@@ -449,6 +449,43 @@ int hpv_validation_read(hpv_handle h, int n, double* out);
  * hpv_step, and with its handling of an exchange timeout.  -1: every < 1, n_out too small, more samples than the history holds. */
 int hpv_step_validate(hpv_handle h, int n_iters, int every, double* out, size_t n_out);
 
+/* L-BFGS stage after Adam (an extension; no reference counterpart): up to max_iter quasi-Newton iterations on ALL num_params
+ * entries of theta -- the network, AdvDiff's epsilon, the trainable coefficients of a handle made with n_coef > 0 -- on every
+ * problem class and both schemes.  The optimiser's vectors (the iterate, the gradient, the direction, the rings of up to `history`
+ * pairs s, y) stay on the device; the line search runs on the host over scalars.  One function evaluation is one backward pass of
+ * the handle plus a read-back of 32 bytes; launches are eager (the captured iteration graphs of the Adam path are neither used nor
+ * dropped).  The algorithm and its decisions are those of torch.optim.LBFGS with line_search_fn = "strong_wolfe": two-loop
+ * recursion scaled by (y.s)/(y.y) of the newest pair, a pair kept only when y.s > 1e-10, strong-Wolfe search with c1 = 1e-4,
+ * c2 = 0.9 and at most 25 steps (and never more than the evaluations max_eval leaves), first step min(1, 1/|g|_1) lr and lr
+ * afterwards, exits on max|g| <= tolerance_grad, g.d > -tolerance_change, max|t d| <= tolerance_change and
+ * |f - f_prev| < tolerance_change.
+ *   opts: history 1 .. 64 (larger values are capped; torch's 100 is too large for here, the bindings default to 20); max_eval <= 0
+ *     means max_iter * 5 / 4; torch's defaults otherwise: lr 1, tolerance_grad 1e-7, tolerance_change 1e-9.
+ *   loss3_hist (may be NULL): [max_iter + 1][3] = {loss, lossb, lossv} at the starting point and after every accepted iteration
+ *     (iters + 1 rows are written); by the sufficient-decrease condition the first column never increases.
+ *   info (may be NULL): {iterations taken, function evaluations, pairs skipped by the curvature test, HPV_LBFGS_* reason}.
+ * A search that ends without an acceptable point -- 25 steps or the evaluation budget used up, a non-finite loss -- is not an
+ * error: the parameters are set back to the last accepted iterate bit for bit, the reason says which, the call returns 0.
+ * Adam's state is left alone: the moments m and v, the beta powers and the update count are what they were, and a later training
+ * call continues Adam from ITS state at the new parameters.  The history of pairs survives between calls (a second call goes on
+ * where the first stopped) and changes of the mesh, rule or data (theta keeps its meaning); it is dropped by the reset call below
+ * and whenever parameters are handed in (set_params, set_state), and it is not part of the checkpoint.
+ * -4 with a message: a handle with an exchange connected (hpv_exchange_in_use != 0) or holding a shard of the model (part of the
+ * elements or of the collocation points) -- one GPU only; history < 1.  Pass errors come back as they are. */
+typedef struct hpv_lbfgs_opts {
+    int history, max_iter, max_eval;
+    double lr, tolerance_grad, tolerance_change;
+} hpv_lbfgs_opts;
+enum { HPV_LBFGS_MAX_ITER = 0,        /* max_iter iterations were taken                                             */
+       HPV_LBFGS_MAX_EVAL = 1,        /* the evaluation budget ran out (inside a search: parameters set back)      */
+       HPV_LBFGS_TOL_GRAD = 2,        /* max|g| <= tolerance_grad                                                   */
+       HPV_LBFGS_TOL_CHANGE = 3,      /* step or decrease below tolerance_change, or the bracket closed on t = 0   */
+       HPV_LBFGS_TOL_DIRECTION = 4,   /* g.d > -tolerance_change: no descent left along the direction              */
+       HPV_LBFGS_MAX_LS = 5,          /* 25 search steps without a Wolfe point (parameters set back)               */
+       HPV_LBFGS_NONFINITE = 6 };     /* the loss is not finite (parameters set back)                              */
+int hpv_lbfgs_step(hpv_handle h, const hpv_lbfgs_opts* opts, double* loss3_hist, int* info);
+int hpv_lbfgs_reset(hpv_handle h);   /* drop the history of pairs; the next iteration steps along -g */
+
 /* Checkpoint / resume (the reference never saves weights): the packed state
  * [theta | Adam m | Adam v | beta1^t | beta2^t], 3*num_params+2 doubles; a resumed run continues bit-exactly. */
 int hpv_get_state(hpv_handle h, double* buf, size_t n);
